@@ -26,6 +26,19 @@ z-step QPs, PI + back-calculation dual update, residuals) plus propagation; the 
 loop never returns to the host inside the timed region.
 
   python bench.py [--gpus N --steps K --warmup W] [--config2 | --config5 | --strong [--split interleaved] | --crossing] [--natural]
+                  [--full] [--dump-outputs DIR]
+
+A plain run does what the headline needs and nothing else: set up, W warmup steps, K timed steps,
+one JSON line (``value``, ``ms_per_step``, the roofline / latency objects derived from this run's
+own launch time and the committed counter summaries under profiles/).  ``--full`` adds the
+measurements that take runs of their own: the CPU baselines (B-opt and the NumPy pool, timed before
+the GPU is touched; ``--no-cpu`` drops them), the natural-termination co-headline (``--no-natural``)
+and the cold first step on a fresh handle (``--no-cold``).
+
+``--dump-outputs DIR`` writes, after the timed steps, what the timed path computed in its last
+step as ``DIR/<name>.npy`` (float64): ``xt``, ``u``, ``iters``, ``global_resid``, ``global_iters``
+(--obca: ``out``, ``status``, ``iters``, ``qp_steps``).  The inputs are seeded, so two builds run
+with the same arguments can be compared output for output.
 
 N > 1: one process per GPU (torch.distributed.run).  Run directly with --gpus N and no
 WORLD_SIZE in the environment, this script starts ``torch.distributed.run --nproc-per-node N``
@@ -33,7 +46,8 @@ as a child process before anything touches the GPU and relays its output.  Each 
 whole components; the ranks join one RCCL communicator (the unique id travels over the gloo
 group, which otherwise only carries the harness's barrier and max-over-ranks timer).
 
-Prints ONE JSON line (rank 0) with roofline, latency and cpu_baseline objects.
+Prints ONE JSON line (rank 0) with roofline and latency objects (--full: and cpu_baseline,
+natural, cold_first_step).
 """
 from __future__ import annotations
 
@@ -189,11 +203,33 @@ def cpu_baseline(wl: dict, budget_s: float, K: int) -> dict:
     return bopt
 
 
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: all files of one rank together
+
+
+def dump_outputs(out_dir: str, arrays: dict, rank: int = 0) -> None:
+    """--dump-outputs: every array as float64 in out_dir/<name>.npy (ranks > 0: <name>_rank<r>.npy).
+    An array that would take the dump over DUMP_MAX_BYTES is cut to a fixed, seeded sample of its
+    flattened entries (in index order), the same from run to run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        keep = DUMP_MAX_BYTES / total * 0.99
+        rng = np.random.default_rng(0)
+        for k, a in arrays.items():
+            idx = np.sort(rng.choice(a.size, size=max(1, int(a.size * keep)), replace=False))
+            arrays[k] = a.reshape(-1)[idx]
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy" if rank == 0 else f"{k}_rank{rank}.npy"), a)
+
+
 def run(wl: dict, natural: bool, K: int, W: int, rank: int, world: int, local_rank: int, dist, split="components",
-        share: int = 0, precision: int = 0, cold: bool = False):
+        share: int = 0, precision: int = 0, cold: bool = False, dump: str | None = None):
     """Time K MPC steps of workload wl on this rank; returns (metrics, counters, solver info).
     share > 1 (strong scaling, one process): rank 0's share of a share-rank job alone on this GPU --
-    its agents (and, interleaved, its ghosts), every collective a no-op (SURVEY.md 8e readiness)."""
+    its agents (and, interleaved, its ghosts), every collective a no-op (SURVEY.md 8e readiness).
+    dump: a directory for the outputs of the last timed step (dump_outputs)."""
     import numpy as np
     from piadmm import config, scenario
     from piadmm import dist as pdist
@@ -265,6 +301,15 @@ def run(wl: dict, natural: bool, K: int, W: int, rank: int, world: int, local_ra
         # pairs across ranks (an X and a Z launch per outer iteration), or one component split over
         # workgroups (the same two launches, no exchange)
         xchg = (shard is not None and shard.n_slots > 0) or wl.get("kind") == "chain"
+        if dump:
+            # what a caller of the timed path holds after its last step (StepResult's xt, u, iters
+            # and the job's residual history; rows past the executed iterations, NaN in the
+            # library, are written as 0 so that two dumps compare entry for entry)
+            st = solver.state()
+            gres, giters = solver.global_resid()
+            gres[giters:] = 0.0
+            dump_outputs(dump, dict(xt=st["xt"], u=st["u"], iters=st["iters"], global_resid=gres,
+                                    global_iters=np.array([giters])), rank)
     finally:
         solver.close()
     # the cold first step: MPC step 0 on a FRESH handle, its per-scenario caches (the agents' P^-1,
@@ -367,7 +412,8 @@ def main_obca(args, world, rank, local_rank):
     from piadmm import obca
     n = args.obca_batch
     recs = obca.scenario_batch(n, seed=rank)
-    cpu = obca_cpu_baseline(recs, args.cpu_budget) if (rank == 0 and world == 1 and not args.no_cpu) else None
+    cpu = (obca_cpu_baseline(recs, args.cpu_budget)
+           if (args.full and rank == 0 and world == 1 and not args.no_cpu) else None)
     dist = None
     if world > 1:
         import torch.distributed as dist
@@ -388,6 +434,9 @@ def main_obca(args, world, rank, local_rank):
         res = b.download(n)
     finally:
         b.close()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(out=res.raw, status=res.status, iters=res.iters,
+                                             qp_steps=res.qp_steps), rank)
     if dist is not None:
         import torch
         tt = torch.tensor([wall, ev_ms], dtype=torch.float64)
@@ -432,10 +481,17 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--cpu-budget", type=float, default=20.0, help="seconds of CPU-baseline timing (rank 0, N=1)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-natural", action="store_true", help="skip the natural-termination co-headline")
-    ap.add_argument("--no-cold", action="store_true", help="skip the cold first step (a fresh handle's step 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements that take runs of their own: the CPU baselines, the "
+                         "natural-termination co-headline and the cold first step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float64)")
+    ap.add_argument("--cpu-budget", type=float, default=20.0,
+                    help="--full: seconds of CPU-baseline timing (rank 0, N=1)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-natural", action="store_true", help="--full without the natural-termination co-headline")
+    ap.add_argument("--no-cold", action="store_true",
+                    help="--full without the cold first step (a fresh handle's step 0)")
     ap.add_argument("--natural", action="store_true", help="natural termination as the headline itself")
     g = ap.add_mutually_exclusive_group()
     g.add_argument("--config2", action="store_true", help="BASELINE configs[1]: 64 agents x H20")
@@ -473,7 +529,7 @@ def main():
     # the CPU baseline first, on the host cores, before this process touches the GPU (its worker
     # pool is started with the spawn method)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         cpu = cpu_baseline(wl, args.cpu_budget, args.steps)
 
     from piadmm import _lib
@@ -488,7 +544,7 @@ def main():
     if args.share and (not args.strong or world != 1):
         raise SystemExit("bench.py: --share needs --strong on one GPU")
     m, cnt = run(wl, args.natural, K, W, rank, world, local_rank, dist, args.split, args.share, args.precision,
-                 cold=not args.no_cold)
+                 cold=args.full and not args.no_cold, dump=args.dump_outputs)
 
     # value = units all ranks processed / the max-over-ranks wall time.  Weak scaling: one unit =
     # one outer iteration of a rank's (256-agent) block, so all ranks processed world x job
@@ -601,7 +657,7 @@ def main():
                             "source": sq["_file"] + " (SQ_INSTS_VALU_{ADD,MUL,FMA}_F64 x 64 lanes; FMA = 2)"}
     line["latency"] = lat
 
-    if not args.natural and not args.no_natural:
+    if args.full and not args.natural and not args.no_natural:
         mn, cn = run(wl, True, K, W, rank, world, local_rank, dist, args.split, args.share, args.precision)
         line["natural"] = {
             "ms_per_step": mn["wall"] / K * 1e3,

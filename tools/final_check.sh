@@ -9,5 +9,5 @@ timeout -k 10 1200 python3 -u -m pytest -x -v --timeout 400 --timeout-method thr
 tail -2 $O/tests.log
 timeout -k 10 300 python3 -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 1; }
 tail -2 $O/smoke.log
-timeout -k 10 400 python3 -u bench.py > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+timeout -k 10 400 python3 -u bench.py --full > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
 tail -1 $O/bench.json | cut -c1-250

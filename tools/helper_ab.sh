@@ -11,7 +11,7 @@ tail -2 $O/tests.log
 for nh in 0 1; do
   for w in headline config2; do
     case $w in headline) a="";; *) a="--$w";; esac
-    PIADMM_NO_HELPER=$nh timeout -k 10 300 python3 -u bench.py --no-cpu --no-cold $a > $O/${w}_nh$nh.json 2> $O/${w}_nh$nh.err || { tail -5 $O/${w}_nh$nh.err; exit 1; }
+    PIADMM_NO_HELPER=$nh timeout -k 10 300 python3 -u bench.py --full --no-cpu --no-cold $a > $O/${w}_nh$nh.json 2> $O/${w}_nh$nh.err || { tail -5 $O/${w}_nh$nh.err; exit 1; }
     python3 -c "import json; d=json.loads(open('$O/${w}_nh$nh.json').read().strip().splitlines()[-1]); print('$w no_helper=$nh', d['ms_per_step'], d['natural']['ms_per_step'])"
   done
 done
