@@ -310,9 +310,9 @@ __device__ __forceinline__ bool chol(Ws& S) { return chol_n(S.Hm, NZ, 0.0); }
 
 // row c of the constraint matrix (C z >= din) dotted with v (28)
 __device__ double row_dot(const Ws& S, int c, const double* v) {
-  if (c >= ROWS_T * NT) {
-    int j = (c - ROWS_T * NT) >> 1;
-    return (c & 1) ? -v[j] : v[j];
+  if (c >= ROWS_T * NT) {            // control rows: u_j >= lo | -u_j >= -hi (ROWS_T * NT is odd)
+    int q = c - ROWS_T * NT, j = q >> 1;
+    return (q & 1) ? -v[j] : v[j];
   }
   int ti = c / ROWS_T, r = c % ROWS_T;
   if (r < 10) {                       // state rows: T_t only
@@ -336,8 +336,8 @@ __device__ double row_dot(const Ws& S, int c, const double* v) {
 }
 __device__ double row_elem(const Ws& S, int c, int k) {
   if (c >= ROWS_T * NT) {
-    int j = (c - ROWS_T * NT) >> 1;
-    return (k == j) ? ((c & 1) ? -1.0 : 1.0) : 0.0;
+    int q = c - ROWS_T * NT, j = q >> 1;
+    return (k == j) ? ((q & 1) ? -1.0 : 1.0) : 0.0;
   }
   int ti = c / ROWS_T, r = c % ROWS_T;
   if (r < 10) return (k < NUV) ? ((r & 1) ? -1.0 : 1.0) * S.T[ti][r >> 1][k] : 0.0;
@@ -892,10 +892,12 @@ __device__ __forceinline__ void sqp_one(Ws& S, int pb, const double* __restrict_
     for (int c = lane; c < NROW; c += 64) {
       double dv;
       if (c >= ROWS_T * NT) {
-        int j = (c - ROWS_T * NT) >> 1;
+        // the pair's first row is the lower bound (the order uin -> nyu below assumes): the parity
+        // is that of the row within the block, not of c
+        int q = c - ROWS_T * NT, j = q >> 1;
         double lo = (j & 1) ? -MAX_STEER_RATE : -MAX_ACC;
         double uj = (&S.U[0][0])[j];
-        dv = (c & 1) ? (uj + lo) : (lo - uj);      // lo - u  |  u - hi  (hi = -lo)
+        dv = (q & 1) ? (uj + lo) : (lo - uj);      // lo - u  |  u - hi  (hi = -lo)
       } else {
         int ti = c / ROWS_T, r = c % ROWS_T, t = ti + 1;
         if (r < 10) {
@@ -1233,7 +1235,8 @@ int check_recs(piadmm_obca_t h, const double* recs, int n) {
 
 // The schedule of the next launches: problems by decreasing work of the last solve of this batch
 // size (QP steps, then SQP iterations; the index breaks ties), or in index order when none ran
-// yet.  The work each problem does does not depend on the order (tests/test_gpu_obca.py).
+// yet.  The work each problem does and its answer do not depend on the order
+// (tests/test_gpu_obca.py: test_longest_first_schedule_keeps_answers).
 int schedule(piadmm_obca_t h) {
   const int n = h->n;
   h->order.resize(n);
