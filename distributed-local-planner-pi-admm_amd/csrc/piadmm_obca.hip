@@ -1173,22 +1173,7 @@ __global__ void __launch_bounds__(64) k_obca_sqp(const double* __restrict__ recs
 // ---------------------------------------------------------------------------------------------
 // C-ABI (include/piadmm.h)
 // ---------------------------------------------------------------------------------------------
-struct piadmm_obca_s {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  double* d_rec = nullptr;
-  double* d_out = nullptr;
-  int* d_ist = nullptr;
-  obca::WsG* d_qg = nullptr;   // per-problem linearisation blocks (HBM)
-  unsigned long long* d_stamps = nullptr;
-  int* d_order = nullptr;       // the launch's problem order (longest first; cap ints)
-  std::vector<int> order;       // host copy of the order
-  std::vector<int> cost;        // the last solve's status / SQP iterations / QP steps per problem
-  int cost_n = 0;               // batch size of the last solve (0: none yet)
-  int cap = 0, n = 0;
-  std::string err;
-};
+#include "piadmm_obca_handle.h"
 
 namespace {
 int fail(piadmm_obca_t h, int code, const std::string& msg) {
@@ -1259,7 +1244,7 @@ int schedule(piadmm_obca_t h) {
 
 int launch(piadmm_obca_t h) {
   hipLaunchKernelGGL(obca::k_obca_sqp, dim3(h->n), dim3(64), 0, h->stream, h->d_rec, h->n, h->d_out, h->d_ist,
-                     h->d_stamps, h->d_qg, h->d_order);
+                     h->d_stamps, static_cast<obca::WsG*>(h->d_qg), h->d_order);
   OHIP(h, hipGetLastError());
   return 0;
 }
@@ -1296,6 +1281,7 @@ int32_t piadmm_obca_destroy(piadmm_obca_t h) {
   if (h->d_rec) { (void)hipFree(h->d_rec); (void)hipFree(h->d_out); (void)hipFree(h->d_ist); (void)hipFree(h->d_qg); }
   if (h->d_stamps) (void)hipFree(h->d_stamps);
   if (h->d_order) (void)hipFree(h->d_order);
+  piadmm_obca_edge_free(h);
   if (h->e0) (void)hipEventDestroy(h->e0);
   if (h->e1) (void)hipEventDestroy(h->e1);
   if (h->stream) (void)hipStreamDestroy(h->stream);

@@ -1,0 +1,36 @@
+// piadmm_obca_handle.h -- the piadmm_obca_t handle, shared by the local batch
+// (csrc/piadmm_obca.hip) and the edge step (csrc/piadmm_obca_edge.hip).
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <vector>
+
+#include "piadmm.h"
+
+struct piadmm_obca_s {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  double* d_rec = nullptr;
+  double* d_out = nullptr;
+  int* d_ist = nullptr;
+  void* d_qg = nullptr;         // per-problem linearisation blocks (obca::WsG, HBM)
+  unsigned long long* d_stamps = nullptr;
+  int* d_order = nullptr;       // the launch's problem order (longest first; cap ints)
+  std::vector<int> order;       // host copy of the order
+  std::vector<int> cost;        // the last solve's status / SQP iterations / QP steps per problem
+  int cost_n = 0;               // batch size of the last solve (0: none yet)
+  int cap = 0, n = 0;
+  // the edge step's own buffers (csrc/piadmm_obca_edge.hip): an edge call never touches the
+  // resident local batch above or its longest-first history
+  double* e_rec = nullptr;
+  double* e_out = nullptr;
+  int* e_ist = nullptr;
+  int e_cap = 0;
+  std::string err;
+};
+
+// frees the edge buffers (piadmm_obca_destroy)
+void piadmm_obca_edge_free(piadmm_obca_t h);

@@ -98,6 +98,8 @@ SYMBOLS = [
     ("piadmm_obca_time", c_i32, [_H, c_i32, _P(ctypes.c_float)]),
     ("piadmm_obca_download", c_i32, [_H, _dp, _ip, c_i32]),
     ("piadmm_obca_debug_stamps", c_i32, [_H, _P(ctypes.c_uint64), c_i32]),
+    ("piadmm_obca_edge_solve", c_i32, [_H, _dp, c_i32, _dp, _ip]),
+    ("piadmm_obca_edge_time", c_i32, [_H, _dp, c_i32, c_i32, _P(ctypes.c_float)]),
 ]
 
 # piadmm_near_tie_t (include/piadmm.h, ABI 6) as a NumPy record

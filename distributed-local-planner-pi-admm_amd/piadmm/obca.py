@@ -238,6 +238,121 @@ def scenario_batch(n, prob=1, seed=0):
     return np.ascontiguousarray(np.stack(recs))
 
 
+# ---------------------------------------------------------------------------------------------
+# The coordinator (RSU) half of an ADMM iterate: the edge NLP on the consensus variable Z
+# (optimizer.py:239-328), lambda_update (:330-335) and check_converge (:225-235).
+#
+# Edge record (float64, ``EDGE_REC`` per vehicle pair):
+#   local_x 2x7x5 | lamb_ij 2x7x4 | lamb_bar 2x7x9 |
+#   rho, min_dis, prob, max_iter, round_decimals, start, x_bound, mu_max, g_max | pad
+# Edge output (float64, ``EDGE_OUT`` per pair): Z 2x7x9 (unrounded) | Z_bar 2x7x9 |
+#   lamb_bar_new 2x7x9 | y_eq 7x2 | y_in 7 | y_bnd 7x18 | cost 7 | dres 7 | pad;
+#   status / SQP iterations / QP steps per slot (int32, 7 x 3).
+# ---------------------------------------------------------------------------------------------
+EDGE_REC = 264
+EDGE_OUT = 544
+NE = 2 * (NX + NL)                   # variables of one slot problem: [s_0, mu_0, s_1, mu_1]
+_E_LX, _E_LIJ, _E_LB, _E_PAR = 0, 70, 126, 252
+_EO_Z, _EO_ZB, _EO_LBN, _EO_YEQ, _EO_YIN, _EO_YBND, _EO_COST, _EO_DRES = 0, 126, 252, 378, 392, 399, 525, 532
+EDGE_WRITES_ITERATE = (0, 1, 3)      # converged, max_iter, linesearch_fail (the last accepted iterate)
+
+
+def edge_record(bar, rho=1.0, min_dis=0.1, prob=1, max_iter=60, round_decimals=4, start=1, x_bound=1000.0,
+                mu_max=100000.0, g_max=1000.0):
+    """The record of one vehicle pair's edge NLP: what edge_generate_object (optimizer.py:297-307)
+    reads of bar_state, and the bounds of :282-295 as record fields.  start: 0 = the reference's
+    zeros (:249-250), 1 = w = [local_x, lamb_ij] clipped into the bounds."""
+    rec = np.zeros(EDGE_REC)
+    rec[_E_LX:_E_LX + 70] = np.asarray(bar["local_x"], np.float64)[:2].ravel()
+    rec[_E_LIJ:_E_LIJ + 56] = np.asarray(bar["lamb_ij"], np.float64)[:2].ravel()
+    rec[_E_LB:_E_LB + 126] = np.asarray(bar["lamb_bar"], np.float64)[:2].ravel()
+    rec[_E_PAR:_E_PAR + 9] = [rho, min_dis, float(prob), float(max_iter), float(round_decimals), float(start),
+                              x_bound, mu_max, g_max]
+    return rec
+
+
+def edge_unpack(rec):
+    """dict of an edge record's fields."""
+    rec = np.asarray(rec, np.float64)
+    par = rec[_E_PAR:_E_PAR + 9]
+    return dict(local_x=rec[_E_LX:_E_LX + 70].reshape(2, NT, NX).copy(),
+                lamb_ij=rec[_E_LIJ:_E_LIJ + 56].reshape(2, NT, NL).copy(),
+                lamb_bar=rec[_E_LB:_E_LB + 126].reshape(2, NT, 9).copy(),
+                rho=par[0], min_dis=par[1], prob=int(par[2]), max_iter=int(par[3]), round_decimals=int(par[4]),
+                start=int(par[5]), x_bound=par[6], mu_max=par[7], g_max=par[8])
+
+
+def local_z(bar):
+    """w = [local_x, lamb_ij] (num_veh x 7 x 9), the local side of the consensus (optimizer.py:303-304, :333)."""
+    return np.concatenate([bar["local_x"], bar["lamb_ij"]], axis=2)
+
+
+def lambda_update(bar, rho):
+    """`lambda_update` (optimizer.py:330-335): lamb_bar += rho (w - Z_bar).  Host form of the
+    update the edge kernel fuses behind its solve."""
+    out = {k: v.copy() for k, v in bar.items()}
+    out["lamb_bar"] = bar["lamb_bar"] + rho * (local_z(bar) - bar["Z_bar"])
+    return out
+
+
+def check_converge(bar, thres, min_dis):
+    """`check_converge` (optimizer.py:225-235): the coupled constraints at the exchanged
+    halfspaces and lamb_ij."""
+    eq = np.einsum("tij,ti->tj", bar["A"][0], bar["lamb_ij"][0]) + np.einsum("tij,ti->tj", bar["A"][1], bar["lamb_ij"][1])
+    ueq = -np.einsum("ti,ti->t", bar["b"][0], bar["lamb_ij"][0]) - np.einsum("ti,ti->t", bar["b"][1], bar["lamb_ij"][1])
+    return bool((np.abs(eq) <= thres).all() and (ueq >= min_dis).all())
+
+
+def seeded_bar_state(t_step, prob=1, alpha=0.9):
+    """A runnable initial bar_state at MPC step t_step: A, b, local_x from `executed_path`
+    (slots t_step + 1 .. t_step + 7), lamb_ij each vehicle's own `separating_duals` along the
+    direction to the other vehicle (so A_0' lamb_0 + A_1' lamb_1 = 0), Z_bar = [local_x, lamb_ij],
+    lamb_bar = 1e-3 (mid_state's value, optimizer.py:356).  The reference's mid_state (create_bar_state) is infeasible as written
+    (`as_written_problem`)."""
+    bar = create_bar_state()
+    for t in range(NT):
+        st = [executed_path(v, (t_step + t + 1) * DT) for v in (0, 1)]
+        for v in (0, 1):
+            A, b = halfspaces(st[v], prob)
+            dvec = st[1 - v][:2] - st[v][:2]
+            bar["A"][v, t], bar["b"][v, t] = A, b
+            bar["local_x"][v, t] = st[v]
+            bar["lamb_ij"][v, t] = separating_duals(A, dvec / np.linalg.norm(dvec), alpha)
+    bar["Z_bar"] = local_z(bar)
+    bar["lamb_bar"] = 1e-3 * np.ones((2, NT, 9))
+    return bar
+
+
+class OBCAEdgeResult:
+    """Decoded output of an edge batch (pairs x ...)."""
+
+    def __init__(self, out, ist):
+        n = out.shape[0]
+        self.raw = out
+        self.Z = out[:, _EO_Z:_EO_Z + 126].reshape(n, 2, NT, 9)
+        self.Z_bar = out[:, _EO_ZB:_EO_ZB + 126].reshape(n, 2, NT, 9)
+        self.lamb_bar = out[:, _EO_LBN:_EO_LBN + 126].reshape(n, 2, NT, 9)
+        self.y_eq = out[:, _EO_YEQ:_EO_YEQ + 14].reshape(n, NT, 2)
+        self.y_in = out[:, _EO_YIN:_EO_YIN + 7]
+        self.y_bnd = out[:, _EO_YBND:_EO_YBND + 126].reshape(n, NT, NE)
+        self.cost = out[:, _EO_COST:_EO_COST + 7]
+        self.dres = out[:, _EO_DRES:_EO_DRES + 7]
+        self.status = ist[:, :, 0]
+        self.iters = ist[:, :, 1]
+        self.qp_steps = ist[:, :, 2]
+
+    def z(self, k, t):
+        """The 18 variables [s_0, mu_0, s_1, mu_1] of pair k, slot t."""
+        return np.concatenate([self.Z[k, 0, t], self.Z[k, 1, t]])
+
+    def dual_residual(self):
+        """sum |lamb_bar_new - lamb_bar| per pair: the 7 slot partials added in index order."""
+        s = np.zeros(self.dres.shape[0])
+        for t in range(NT):
+            s = s + self.dres[:, t]
+        return s
+
+
 class OBCAResult:
     """Decoded output of a batch (fields as in the reference's local_solve, :183-201)."""
 
@@ -302,6 +417,27 @@ class OBCABatch:
         self._check(self._lib.piadmm_obca_solve(self._h, _lib.dptr(recs), n, _lib.dptr(out), _lib.iptr(ist)))
         return OBCAResult(out, ist)
 
+    def solve_edge(self, recs: np.ndarray) -> OBCAEdgeResult:
+        """One launch of the edge SQP (one wave per slot problem, 7 per pair) with the fused
+        lambda_update; separate device buffers from the local batch."""
+        from . import _lib
+        recs = np.ascontiguousarray(recs, np.float64)
+        n = recs.shape[0]
+        assert recs.shape == (n, EDGE_REC)
+        out = np.zeros((n, EDGE_OUT))
+        ist = np.zeros((n, NT, 3), np.int32)
+        self._check(self._lib.piadmm_obca_edge_solve(self._h, _lib.dptr(recs), n, _lib.dptr(out), _lib.iptr(ist)))
+        return OBCAEdgeResult(out, ist)
+
+    def time_edge(self, recs: np.ndarray, repeats: int) -> float:
+        """ms per edge launch over `repeats` launches of `recs` (HIP events)."""
+        from . import _lib
+        recs = np.ascontiguousarray(recs, np.float64)
+        ms = ctypes.c_float()
+        self._check(self._lib.piadmm_obca_edge_time(self._h, _lib.dptr(recs), recs.shape[0], int(repeats),
+                                                    ctypes.byref(ms)))
+        return ms.value
+
     def upload(self, recs: np.ndarray):
         from . import _lib
         recs = np.ascontiguousarray(recs, np.float64)
@@ -322,3 +458,140 @@ class OBCABatch:
         ist = np.zeros((n, 3), np.int32)
         self._check(self._lib.piadmm_obca_download(self._h, _lib.dptr(out), _lib.iptr(ist), n))
         return OBCAResult(out, ist)
+
+
+# ---------------------------------------------------------------------------------------------
+# The consensus loop (decentralized_overtaking_ADMM.py:31-102) for many scenarios at once
+# ---------------------------------------------------------------------------------------------
+class OBCARunRecord:
+    """state_record / iter_num_record / lambda_record as in the script (:18-20, :100-103), one
+    entry per MPC step, stacked over scenarios; status_record keeps, per ADMM iterate, the
+    scenarios submitted and every local / edge status (nothing is silent)."""
+
+    def __init__(self):
+        self.state_record = []
+        self.iter_num_record = []
+        self.lambda_record = []
+        self.status_record = []
+
+
+class OBCAPlanner:
+    """The OBCA-ADMM overtaking planner on the GPU.  Per ADMM iterate, in the script's order: one
+    local launch over all still-active scenarios x 2 vehicles (:49-63), bar_state_update (:66),
+    check_converge (:67), one edge launch with the fused lambda_update (:71-79), the residuals
+    (:82-85); a scenario stops at both residuals <= the thresholds or i_iter > max_admm_iter (:86)
+    and is not resubmitted.  Then the horizon shift -- of the PREVIOUS iterate's bar_state, as :87
+    is written -- and init_state = X[1] (:99).
+
+    prob, primal_thres, dual_thres: one value or one per scenario.  update_lamb_ij: 0 leaves lamb_ij untouched (the
+    commented-out :220), 1 takes each vehicle's local Lambda.  on_stage(name, inputs, outputs) sees
+    every stage: "local", "exchange", "converge", "edge", "residual", "shift"."""
+
+    def __init__(self, batch, n_scenarios, prob=1, t_step0=0, rho=1.0, min_dis=0.1, max_admm_iter=50,
+                 primal_thres=0.01, dual_thres=0.01, round_decimals=4, start=1, update_lamb_ij=0, max_iter=60,
+                 conv_thres=0.1, on_stage=None):
+        self.batch = batch
+        self.n = int(n_scenarios)
+        self.prob = [int(prob)] * self.n if np.isscalar(prob) else [int(p) for p in prob]
+        assert len(self.prob) == self.n
+        self.t_step = int(t_step0)
+        self.rho, self.min_dis = float(rho), float(min_dis)
+        self.max_admm_iter = int(max_admm_iter)
+        self.primal_thres = np.broadcast_to(np.asarray(primal_thres, np.float64), (self.n,)).copy()
+        self.dual_thres = np.broadcast_to(np.asarray(dual_thres, np.float64), (self.n,)).copy()
+        self.conv_thres = conv_thres
+        self.round_decimals, self.start, self.update_lamb_ij, self.max_iter = round_decimals, start, update_lamb_ij, max_iter
+        self.on_stage = on_stage or (lambda name, inputs, outputs: None)
+        self.ref_traj = ref_traj_gen()
+        self.bar_prev = [seeded_bar_state(self.t_step, p) for p in self.prob]
+        self.init_state = [np.stack([executed_path(v, self.t_step * DT) for v in (0, 1)]) for _ in range(self.n)]
+        self.record = OBCARunRecord()
+        self.record.state_record.append(np.stack(self.init_state))
+
+    @staticmethod
+    def _copy(bar):
+        return {k: v.copy() for k, v in bar.items()}
+
+    def step(self):
+        """One MPC step of every scenario."""
+        n = self.n
+        assert self.t_step + N_HORZ <= len(self.ref_traj[0]), "reference exhausted"
+        bar = [self._copy(b) for b in self.bar_prev]
+        bar_prev = [self._copy(b) for b in self.bar_prev]
+        ctrl_prev = [np.zeros((2, NT * NU)) for _ in range(n)]
+        X = [None] * n
+        iters = np.zeros(n, int)
+        shift_in = [None] * n
+        active = list(range(n))
+        i_iter = 0
+        while active:
+            i_iter += 1
+            # ---- vehicle side: one launch, scenarios x vehicles ----
+            recs = np.ascontiguousarray(np.stack([
+                local_record(bar[s], v, self.t_step, self.init_state[s][v], self.ref_traj, rho=self.rho,
+                             min_dis=self.min_dis, prob=self.prob[s], max_iter=self.max_iter)
+                for s in active for v in (0, 1)]))
+            res = self.batch.solve(recs)
+            self.on_stage("local", dict(recs=recs, scenarios=list(active), i_iter=i_iter, t_step=self.t_step),
+                          dict(result=res))
+            fullx = [[res.bar_fullx(2 * k + v) for v in (0, 1)] for k in range(len(active))]
+            ctrl = [np.stack([np.append(res.U[2 * k + v][:, 0], res.U[2 * k + v][:, 1]) for v in (0, 1)])
+                    for k in range(len(active))]
+            for k, s in enumerate(active):
+                X[s] = [res.X[2 * k].copy(), res.X[2 * k + 1].copy()]
+            # ---- information exchange ----
+            before = [bar[s] for s in active]
+            for k, s in enumerate(active):
+                bar[s] = bar_state_update(bar[s], fullx[k], prob=self.prob[s])
+                if self.update_lamb_ij:
+                    bar[s]["lamb_ij"] = np.stack([fullx[k][v][:, 5:] for v in (0, 1)])
+            self.on_stage("exchange", dict(bar=before, fullx=fullx, scenarios=list(active)),
+                          dict(bar=[self._copy(bar[s]) for s in active]))
+            conv = [check_converge(bar[s], self.conv_thres, self.min_dis) for s in active]
+            self.on_stage("converge", dict(bar=[self._copy(bar[s]) for s in active]), dict(if_converge=conv))
+            # ---- RSU side: one launch, the dual update fused ----
+            erecs = np.ascontiguousarray(np.stack([
+                edge_record(bar[s], rho=self.rho, min_dis=self.min_dis, prob=self.prob[s], max_iter=self.max_iter,
+                            round_decimals=self.round_decimals, start=self.start) for s in active]))
+            eres = self.batch.solve_edge(erecs)
+            self.on_stage("edge", dict(recs=erecs, scenarios=list(active)), dict(result=eres))
+            lamb_prev = [bar[s]["lamb_bar"].copy() for s in active]
+            for k, s in enumerate(active):
+                bar[s]["Z_bar"] = eres.Z_bar[k].copy()
+                bar[s]["lamb_bar"] = eres.lamb_bar[k].copy()
+            self.record.status_record.append(dict(t_step=self.t_step, i_iter=i_iter, scenarios=list(active),
+                                                  local_status=res.status.copy(), edge_status=eres.status.copy(),
+                                                  if_converge=conv))
+            # ---- residuals (:82-86) ----
+            primal = np.array([np.abs(ctrl[k] - ctrl_prev[s]).sum() for k, s in enumerate(active)])
+            dual = eres.dual_residual()
+            stop = ((primal <= self.primal_thres[active]) & (dual <= self.dual_thres[active])) \
+                | (i_iter > self.max_admm_iter)
+            self.on_stage("residual",
+                          dict(ctrl=ctrl, ctrl_prev=[ctrl_prev[s] for s in active],
+                               lamb_bar=[bar[s]["lamb_bar"] for s in active], lamb_bar_prev=lamb_prev, i_iter=i_iter,
+                               scenarios=list(active)),
+                          dict(primal=primal, dual=dual, stop=stop))
+            nxt = []
+            for k, s in enumerate(active):
+                if stop[k]:
+                    iters[s] = i_iter
+                    shift_in[s] = bar_prev[s]           # :87: the previous iterate's bar_state (B16)
+                else:
+                    bar_prev[s] = self._copy(bar[s])
+                    ctrl_prev[s] = ctrl[k]
+                    nxt.append(s)
+            active = nxt
+        # ---- next time step (:87, :99-103) ----
+        self.bar_prev = [iterate_next_state(shift_in[s]) for s in range(n)]
+        self.init_state = [np.stack([X[s][0][1], X[s][1][1]]) for s in range(n)]
+        self.on_stage("shift", dict(bar_prev=shift_in, X=X, iters=iters.copy()), dict(bar_next=self.bar_prev, init_state=self.init_state))
+        self.record.state_record.append(np.stack(self.init_state))
+        self.record.iter_num_record.append(iters)
+        self.record.lambda_record.append(np.stack([bar[s]["lamb_bar"] for s in range(n)]))
+        self.t_step += 1
+
+    def run(self, n_steps):
+        for _ in range(int(n_steps)):
+            self.step()
+        return self.record

@@ -359,6 +359,37 @@ int32_t piadmm_obca_download(piadmm_obca_t h, double* out, int32_t* status3, int
  * counts of the last launch (n = 16 x batch uint64); PIADMM_E_STATE otherwise. */
 int32_t piadmm_obca_debug_stamps(piadmm_obca_t h, uint64_t* out, int32_t n);
 
+/* ---- OBCA-ADMM edge (RSU) step -------------------------------------------------------------
+ * The coordinator half of an ADMM iterate: the edge NLP on the consensus variable Z
+ * (optimizer.py:239-328) and lambda_update (:330-335) fused behind it.  The NLP is separable over
+ * the 7 horizon slots: one vehicle pair is 7 slot problems in
+ * z = [s_0 (5), mu_0 (4), s_1 (5), mu_1 (4)],
+ *   min  -z.lamb_bar + rho/2 |w - z|^2,  w = [local_x, lamb_ij]
+ *   s.t. A(s_0)' mu_0 + A(s_1)' mu_1 = 0,  min_dis <= -b(s_0)' mu_0 - b(s_1)' mu_1 <= g_max,
+ *        |s| <= x_bound, 0 <= mu <= mu_max,
+ * one wavefront each, n_pairs x 7 per launch; the same wave then writes Z_bar (Z rounded to
+ * round_decimals, -1 = off), lamb_bar_new = lamb_bar + rho (w - Z_bar) and the slot's
+ * sum |lamb_bar_new - lamb_bar| partial (dres; the host adds the 7 in index order).  A slot whose
+ * status wrote no iterate (QP_INFEASIBLE, HESSIAN_FAIL) leaves lamb_bar unchanged, dres = 0.
+ *
+ * recs: n_pairs x PIADMM_OBCA_EDGE_REC fp64: local_x[2][7][5] | lamb_ij[2][7][4] | lamb_bar[2][7][9] |
+ *   rho, min_dis, prob, max_iter, round_decimals, start (0: zeros, 1: w clipped into the bounds),
+ *   x_bound, mu_max, g_max | pad.
+ * out: n_pairs x PIADMM_OBCA_EDGE_OUT fp64: Z[2][7][9] unrounded | Z_bar[2][7][9] |
+ *   lamb_bar_new[2][7][9] | y_eq[7][2] | y_in[7] | y_bnd[7][18] | cost[7] | dres[7] | pad.
+ * status3: n_pairs x 7 x 3 int32: PIADMM_OBCA_* status, SQP iterations, QP active-set steps.
+ * Records with rho <= 0, prob not 0/1, max_iter outside [1, 1000], start not 0/1, round_decimals
+ * outside [-1, 15], or x_bound or mu_max <= 0 are refused before any launch
+ * ("record k: bad parameters").  The edge buffers are the handle's own: a call between
+ * piadmm_obca_upload and piadmm_obca_download leaves the resident local batch as it was. */
+#define PIADMM_OBCA_EDGE_REC 264
+#define PIADMM_OBCA_EDGE_OUT 544
+int32_t piadmm_obca_edge_solve(piadmm_obca_t h, const double* recs, int32_t n_pairs, double* out,
+                               int32_t* status3);
+/* upload + `repeats` launches between two events; ms per launch */
+int32_t piadmm_obca_edge_time(piadmm_obca_t h, const double* recs, int32_t n_pairs, int32_t repeats,
+                              float* ms_per_launch);
+
 #ifdef __cplusplus
 }
 #endif

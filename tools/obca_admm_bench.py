@@ -1,0 +1,99 @@
+#!/usr/bin/env python3
+"""Times of the OBCA-ADMM edge step and of one full ADMM iterate on the GPU.
+
+  edge launch      ms per launch of the edge kernel at --pairs vehicle pairs (x 7 slot problems),
+                   HIP events around `repeats` launches, records resident
+  full iterate     wall-clock ms of one ADMM iterate of OBCAPlanner on --scenarios seeded
+                   scenarios: the local launch (scenarios x 2 problems), the host exchange
+                   (bar_state_update, check_converge, record packing), the edge launch
+
+There is no CPU baseline on an equal footing (the C++ port of the local solver has no edge step);
+the edge launch is reported next to the local launch so the reader sees its share of an iterate.
+Writes one JSON (default profiles/obca_admm_bench.json) and prints it.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "distributed-local-planner-pi-admm_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import numpy as np  # noqa: E402
+
+from piadmm import obca  # noqa: E402
+
+
+def edge_batch(n):
+    """n edge records cycling over (t_step 0..41, prob): the seeded states with vehicle 0 pulled
+    0.3 m towards vehicle 1, so the equality and the range row have work to do."""
+    base = []
+    for prob in (1, 0):
+        for ts in range(42):
+            bar = obca.seeded_bar_state(ts, prob)
+            d = bar["local_x"][1, :, :2] - bar["local_x"][0, :, :2]
+            bar["local_x"][0, :, :2] += 0.3 * d / np.linalg.norm(d, axis=1, keepdims=True)
+            bar["local_x"][0, :, 3] += 0.01
+            base.append(obca.edge_record(bar, prob=prob))
+    return np.ascontiguousarray(np.stack([base[k % len(base)] for k in range(n)]))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--pairs", type=int, default=4096)
+    ap.add_argument("--scenarios", type=int, default=2048)
+    ap.add_argument("--repeats", type=int, default=10)
+    ap.add_argument("--iterates", type=int, default=3)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "obca_admm_bench.json"))
+    a = ap.parse_args()
+    b = obca.OBCABatch(0)
+    recs = edge_batch(a.pairs)
+    b.time_edge(recs, 1)                                   # warm-up
+    edge_ms = [b.time_edge(recs, a.repeats) for _ in range(3)]
+    res = b.solve_edge(recs)
+    # the local launch at the same scenario count (pairs x 2 problems), for the share
+    lrecs = obca.scenario_batch(2 * a.pairs)
+    b.upload(lrecs)
+    b.time(1)
+    local_ms = [b.time(max(1, a.repeats // 2)) for _ in range(2)]
+    # full iterates
+    stamps = []
+    t_last = [time.perf_counter()]
+
+    def on_stage(name, inp, outp):
+        now = time.perf_counter()
+        stamps.append((name, (now - t_last[0]) * 1e3))
+        t_last[0] = now
+
+    pl = obca.OBCAPlanner(b, a.scenarios, prob=[k % 2 for k in range(a.scenarios)], t_step0=8,
+                          max_admm_iter=a.iterates - 1, on_stage=on_stage)
+    t0 = time.perf_counter()
+    t_last[0] = t0
+    pl.step()
+    total = (time.perf_counter() - t0) * 1e3
+    n_it = sum(1 for s in stamps if s[0] == "local")
+    by = {}
+    for name, ms in stamps:
+        by[name] = by.get(name, 0.0) + ms
+    out = dict(
+        pairs=a.pairs, slot_problems=a.pairs * obca.NT, repeats=a.repeats,
+        edge_ms_per_launch=min(edge_ms), edge_ms_runs=edge_ms,
+        edge_status_counts=np.bincount(res.status.ravel(), minlength=5).tolist(),
+        edge_sqp_iters_mean=float(res.iters.mean()),
+        local_problems=len(lrecs), local_ms_per_launch=min(local_ms),
+        scenarios=a.scenarios, admm_iterates=n_it, iterate_ms=total / max(n_it, 1),
+        stage_ms_per_iterate={k: v / max(n_it, 1) for k, v in by.items()},
+        baseline=None, note="no CPU baseline exists for the edge step",
+    )
+    b.close()
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
