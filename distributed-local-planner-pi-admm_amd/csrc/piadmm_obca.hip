@@ -1256,6 +1256,17 @@ int record_cost(piadmm_obca_t h) {
 }
 }  // namespace
 
+// the plan path (csrc/piadmm_obca_plan.hip): the buffers and one launch over the first n records
+int piadmm_obca_local_ensure(piadmm_obca_t h, int n) { return ensure(h, n); }
+
+int piadmm_obca_local_launch(piadmm_obca_t h, int n) {
+  if (n <= 0 || n > h->cap) return fail(h, PIADMM_E_STATE, "obca local launch: n outside the buffers");
+  hipLaunchKernelGGL(obca::k_obca_sqp, dim3(n), dim3(64), 0, h->stream, h->d_rec, n, h->d_out, h->d_ist,
+                     h->d_stamps, static_cast<obca::WsG*>(h->d_qg), h->d_order);
+  OHIP(h, hipGetLastError());
+  return 0;
+}
+
 extern "C" {
 
 int32_t piadmm_obca_create(int32_t device, piadmm_obca_t* out) {
@@ -1281,6 +1292,7 @@ int32_t piadmm_obca_destroy(piadmm_obca_t h) {
   if (h->d_rec) { (void)hipFree(h->d_rec); (void)hipFree(h->d_out); (void)hipFree(h->d_ist); (void)hipFree(h->d_qg); }
   if (h->d_stamps) (void)hipFree(h->d_stamps);
   if (h->d_order) (void)hipFree(h->d_order);
+  piadmm_obca_plan_free(h);
   piadmm_obca_edge_free(h);
   if (h->e0) (void)hipEventDestroy(h->e0);
   if (h->e1) (void)hipEventDestroy(h->e1);
@@ -1296,6 +1308,9 @@ int32_t piadmm_obca_upload(piadmm_obca_t h, const double* recs, int32_t n) {
   if (!recs || n <= 0) return fail(h, PIADMM_E_ARG, "obca_upload: recs / n");
   if (int rc = check_recs(h, recs, n)) return rc;
   OHIP(h, hipSetDevice(h->device));
+  // the buffers go back to the resident batch: an open plan ends here
+  piadmm_obca_plan_release(h);
+  h->plan_taken = false;
   // no batch until this upload succeeds: a failed reallocation or copy must not leave a batch size
   // that a later obca_run would launch on freed (null) buffers
   h->n = 0;
@@ -1337,6 +1352,7 @@ int32_t piadmm_obca_time(piadmm_obca_t h, int32_t repeats, float* ms) {
 
 int32_t piadmm_obca_download(piadmm_obca_t h, double* out, int32_t* status3, int32_t n) {
   if (!h) return PIADMM_E_ARG;
+  if (h->plan_taken) return fail(h, PIADMM_E_STATE, "obca_download: a plan took the buffers over (obca_upload first)");
   if (n != h->n || !out || !status3) return fail(h, PIADMM_E_ARG, "obca_download: n must equal the uploaded batch");
   OHIP(h, hipSetDevice(h->device));
   OHIP(h, hipMemcpyAsync(out, h->d_out, (size_t)n * obca::OUT * sizeof(double), hipMemcpyDeviceToHost, h->stream));

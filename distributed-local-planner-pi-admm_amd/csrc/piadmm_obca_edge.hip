@@ -681,6 +681,7 @@ int edge_upload(piadmm_obca_t h, const double* recs, int n) {
   if (!recs || n <= 0) return efail(h, PIADMM_E_ARG, "obca_edge: recs / n_pairs");
   if (int rc = edge_check(h, recs, n)) return rc;
   EHIP(h, hipSetDevice(h->device));
+  piadmm_obca_plan_release(h);       // the edge buffers are overwritten: an open plan ends here
   if (int rc = edge_ensure(h, n)) return rc;
   EHIP(h, hipMemcpyAsync(h->e_rec, recs, (size_t)n * obca_edge::REC * sizeof(double), hipMemcpyHostToDevice, h->stream));
   EHIP(h, hipMemsetAsync(h->e_out, 0, (size_t)n * obca_edge::OUT * sizeof(double), h->stream));
@@ -696,6 +697,14 @@ int edge_launch(piadmm_obca_t h, int n) {
   return 0;
 }
 }  // namespace
+
+// the plan path (csrc/piadmm_obca_plan.hip): the buffers and one launch over the first n pairs
+int piadmm_obca_edge_ensure(piadmm_obca_t h, int n) { return edge_ensure(h, n); }
+
+int piadmm_obca_edge_launch(piadmm_obca_t h, int n) {
+  if (n <= 0 || n > h->e_cap) return efail(h, PIADMM_E_STATE, "obca edge launch: n outside the buffers");
+  return edge_launch(h, n);
+}
 
 void piadmm_obca_edge_free(piadmm_obca_t h) {
   if (h->e_rec) (void)hipFree(h->e_rec);

@@ -1,5 +1,6 @@
 // piadmm_obca_handle.h -- the piadmm_obca_t handle, shared by the local batch
-// (csrc/piadmm_obca.hip) and the edge step (csrc/piadmm_obca_edge.hip).
+// (csrc/piadmm_obca.hip), the edge step (csrc/piadmm_obca_edge.hip) and the device-resident
+// consensus loop (csrc/piadmm_obca_plan.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -8,6 +9,8 @@
 #include <vector>
 
 #include "piadmm.h"
+
+struct piadmm_obca_plan_s;      // csrc/piadmm_obca_plan.hip
 
 struct piadmm_obca_s {
   int device = 0;
@@ -29,8 +32,26 @@ struct piadmm_obca_s {
   double* e_out = nullptr;
   int* e_ist = nullptr;
   int e_cap = 0;
+  // the consensus loop (csrc/piadmm_obca_plan.hip).  piadmm_obca_plan_begin takes the local and
+  // edge buffers over: plan_taken stays set (piadmm_obca_run / _time / _download: PIADMM_E_STATE)
+  // until the next piadmm_obca_upload, which also ends the plan.
+  piadmm_obca_plan_s* plan = nullptr;
+  bool plan_taken = false;
   std::string err;
 };
 
 // frees the edge buffers (piadmm_obca_destroy)
 void piadmm_obca_edge_free(piadmm_obca_t h);
+
+// The plan path's view of the two solves: grow the handle's buffers to n local problems / n pairs,
+// and enqueue one launch over the first n records already in d_rec (problem order d_order[0..n))
+// or e_rec on the handle's stream.  No copy, no synchronisation.
+int piadmm_obca_local_ensure(piadmm_obca_t h, int n);
+int piadmm_obca_local_launch(piadmm_obca_t h, int n);
+int piadmm_obca_edge_ensure(piadmm_obca_t h, int n);
+int piadmm_obca_edge_launch(piadmm_obca_t h, int n);
+
+// an upload into the handle's buffers ends an open plan (its records would be overwritten);
+// frees the plan's state (piadmm_obca_destroy)
+void piadmm_obca_plan_release(piadmm_obca_t h);
+void piadmm_obca_plan_free(piadmm_obca_t h);

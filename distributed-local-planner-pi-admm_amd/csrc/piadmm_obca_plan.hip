@@ -1,0 +1,585 @@
+// piadmm_obca_plan.hip -- the OBCA-ADMM consensus loop, device-resident (gfx950).
+//
+// The loop of decentralized_overtaking_ADMM.py:31-102 (piadmm.obca.OBCAPlanner.step is the same
+// statement on the host) for many scenarios at once, with the planner state kept on the device.
+// One ADMM iterate is a fixed sequence of short, bounded launches on the handle's stream:
+//   k_plan_pack_local   the local records of the active scenarios (pure copies of the state)
+//   k_obca_sqp          the local solves (csrc/piadmm_obca.hip, identity order)
+//   k_plan_exchange     bar_state_update + check_converge + the edge record
+//   k_obca_edge         the edge solves with the fused lambda_update (csrc/piadmm_obca_edge.hip)
+//   k_plan_residual     Z_bar / lamb_bar into the state, the residuals, the stop rule, B16's freeze
+//   k_plan_compact      the next active list, in ascending scenario order (one workgroup, a scan)
+// and the host reads back one int, the number of scenarios still active.  k_plan_shift closes an
+// MPC step.  No kernel here waits for another workgroup, keeps a queue or orders anything with
+// atomics: the record order of a launch is the ascending scenario order, the same on every run.
+//
+// Layout: one wavefront per item (a local record, a scenario), PW waves per workgroup; waves
+// never cooperate, and a wave past the end of its list exits whole at the top.
+
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "piadmm.h"
+#include "piadmm_obca_handle.h"
+
+namespace obca_plan {
+
+constexpr int NT = 7;
+constexpr int PW = 4;                          // waves per workgroup
+constexpr int STATE = PIADMM_OBCA_PLAN_STATE;
+constexpr int REC = PIADMM_OBCA_REC, OUT = PIADMM_OBCA_OUT;
+constexpr int EREC = PIADMM_OBCA_EDGE_REC, EOUT = PIADMM_OBCA_EDGE_OUT;
+// the state's fields (include/piadmm.h)
+constexpr int S_ZB = 0, S_A = 126, S_B = 238, S_LB = 294, S_LIJ = 420, S_LX = 476, S_INIT = 546;
+static_assert(S_INIT + 10 == STATE, "state layout");
+// local record / output (csrc/piadmm_obca.hip), edge record / output (csrc/piadmm_obca_edge.hip)
+constexpr int R_INIT = 0, R_REF = 5, R_AO = 45, R_BO = 101, R_LIJ = 129, R_LB = 157, R_ZB = 220, R_PAR = 283;
+constexpr int O_X = 0, O_U = 40, O_LAM = 54;
+constexpr int E_LX = 0, E_LIJ = 70, E_LB = 126, E_PAR = 252;
+constexpr int EO_ZB = 126, EO_LBN = 252, EO_DRES = 532;
+constexpr int NCTRL = 28, NX = 80;
+
+constexpr double LENGTH = 3.5, WIDTH = 2.0;
+constexpr double AVG_DELAY = 0.05, VAR_DELAY = 0.025;
+
+struct Par {
+  double rho, min_dis, conv_thres, max_x, max_y, r, q, x_bound, mu_max, g_max, sigd;
+  int max_admm_iter, round_decimals, start, update_lamb_ij, max_sqp_iter, n_ref;
+};
+
+// Record 2k + v = vehicle v of scenario active[k]: what local_record (piadmm/obca.py) packs.
+__global__ void __launch_bounds__(64 * PW) k_plan_pack_local(const int* __restrict__ active, int n_act,
+                                                             const double* __restrict__ bar,
+                                                             const int* __restrict__ prob,
+                                                             const double* __restrict__ ref, int t_step, Par P,
+                                                             double* __restrict__ recs) {
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * PW + (threadIdx.x >> 6);
+  if (r >= 2 * n_act) return;
+  const int k = r >> 1, v = r & 1, o = 1 - v;
+  const int s = active[k];
+  const double* B = bar + (size_t)s * STATE;
+  const double* rf = ref + ((size_t)v * P.n_ref + t_step) * 5;
+  double* rec = recs + (size_t)r * REC;
+  for (int i = lane; i < REC; i += 64) {
+    double val = 0.0;
+    if (i < R_REF) val = B[S_INIT + v * 5 + (i - R_INIT)];
+    else if (i < R_AO) val = rf[i - R_REF];
+    else if (i < R_BO) val = B[S_A + o * 56 + (i - R_AO)];
+    else if (i < R_LIJ) val = B[S_B + o * 28 + (i - R_BO)];
+    else if (i < R_LB) val = B[S_LIJ + o * 28 + (i - R_LIJ)];
+    else if (i < R_ZB) val = B[S_LB + v * 63 + (i - R_LB)];
+    else if (i < R_PAR) val = B[S_ZB + v * 63 + (i - R_ZB)];
+    else if (i < R_PAR + 8) {
+      const int j = i - R_PAR;
+      val = j == 0 ? P.rho : j == 1 ? P.min_dis : j == 2 ? P.max_x : j == 3 ? P.max_y : j == 4 ? P.r :
+            j == 5 ? P.q : j == 6 ? (double)prob[s] : (double)P.max_sqp_iter;
+    }
+    rec[i] = val;
+  }
+}
+
+// (A, b) of a vehicle at `st` -- halfspaces (piadmm/obca.py) in the host's order of operations,
+// products and sums kept apart (no contraction) so the two stay within rounding of each other.
+__device__ __forceinline__ void halfspaces(const double* st, int prob, double sigd, double A[4][2], double b[4]) {
+#pragma clang fp contract(off)
+  const double x = st[0], y = st[1], vel = st[2], th = st[3];
+  const double c = cos(th), s = sin(th);
+  double dx = 0.0, dy = 0.0;
+  A[0][0] = c;  A[0][1] = s;
+  A[2][0] = -c; A[2][1] = -s;
+  if (prob) {
+    A[1][0] = -s; A[1][1] = c;
+    A[3][0] = s;  A[3][1] = -c;
+    const double qx = VAR_DELAY * vel * c, qy = VAR_DELAY * vel * s;
+    dx = AVG_DELAY * vel * c + sigd * (qx * qx);
+    dy = AVG_DELAY * vel * s + sigd * (qy * qy);
+  } else {
+    A[1][0] = s;  A[1][1] = -c;
+    A[3][0] = -s; A[3][1] = c;
+  }
+  const double px = x + dx, py = y + dy;
+  const double b0[4] = {LENGTH / 2, WIDTH / 2, LENGTH / 2, WIDTH / 2};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) b[i] = b0[i] + (A[i][0] * px + A[i][1] * py);
+}
+
+// One wave per active scenario; lane < 14 owns the (vehicle, slot) item lane = v * 7 + t.
+__global__ void __launch_bounds__(64 * PW) k_plan_exchange(const int* __restrict__ active, int n_act,
+                                                           double* __restrict__ bar, const int* __restrict__ prob,
+                                                           const double* __restrict__ lout, Par P,
+                                                           double* __restrict__ ctrl, double* __restrict__ X,
+                                                           int* __restrict__ conv, double* __restrict__ erecs) {
+  const int lane = threadIdx.x & 63;
+  const int k = blockIdx.x * PW + (threadIdx.x >> 6);
+  if (k >= n_act) return;
+  const int s = active[k];
+  const int pr = prob[s];
+  double* B = bar + (size_t)s * STATE;
+  double* E = erecs + (size_t)k * EREC;
+  const double* o2 = lout + (size_t)(2 * k) * OUT;           // the pair's two local outputs
+  double pe0 = 0.0, pe1 = 0.0, pb = 0.0;
+  if (lane < 2 * NT) {
+    const int v = lane / NT, t = lane % NT, vt = lane;
+    const double* ov = o2 + (size_t)v * OUT;
+    const double* st = ov + O_X + (t + 1) * 5;
+    double A[4][2], b[4], l[4];
+    halfspaces(st, pr, P.sigd, A, b);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) l[i] = P.update_lamb_ij ? ov[O_LAM + t * 4 + i] : B[S_LIJ + vt * 4 + i];
+#pragma unroll
+    for (int j = 0; j < 5; ++j) { B[S_LX + vt * 5 + j] = st[j]; E[E_LX + vt * 5 + j] = st[j]; }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      B[S_A + vt * 8 + 2 * i] = A[i][0];
+      B[S_A + vt * 8 + 2 * i + 1] = A[i][1];
+      B[S_B + vt * 4 + i] = b[i];
+      if (P.update_lamb_ij) B[S_LIJ + vt * 4 + i] = l[i];
+      E[E_LIJ + vt * 4 + i] = l[i];
+      pe0 += A[i][0] * l[i];
+      pe1 += A[i][1] * l[i];
+      pb += b[i] * l[i];
+    }
+  }
+  // the rest of the edge record: this iterate's lamb_bar, the parameters, the pad
+  for (int i = lane; i < 126; i += 64) E[E_LB + i] = B[S_LB + i];
+  if (lane < EREC - E_PAR) {
+    const int j = lane;
+    E[E_PAR + j] = j == 0 ? P.rho : j == 1 ? P.min_dis : j == 2 ? (double)pr : j == 3 ? (double)P.max_sqp_iter :
+                   j == 4 ? (double)P.round_decimals : j == 5 ? (double)P.start : j == 6 ? P.x_bound :
+                   j == 7 ? P.mu_max : j == 8 ? P.g_max : 0.0;
+  }
+  // bar_ctrl = [U[:,0], U[:,1]] per vehicle, and X
+  if (lane < NCTRL) {
+    const int v = lane / 14, j = lane % 14;
+    ctrl[(size_t)s * NCTRL + lane] = o2[(size_t)v * OUT + O_U + (j < NT ? 2 * j : 2 * (j - NT) + 1)];
+  }
+  for (int i = lane; i < NX; i += 64) X[(size_t)s * NX + i] = o2[(size_t)(i / 40) * OUT + O_X + i % 40];
+  // check_converge: slot t = lanes t (vehicle 0) and t + 7 (vehicle 1)
+  const double e0 = pe0 + __shfl(pe0, (lane + NT) & 63, 64);
+  const double e1 = pe1 + __shfl(pe1, (lane + NT) & 63, 64);
+  const double ueq = -pb - __shfl(pb, (lane + NT) & 63, 64);
+  const bool ok = lane >= NT || (fabs(e0) <= P.conv_thres && fabs(e1) <= P.conv_thres && ueq >= P.min_dis);
+  const int all_ok = __all(ok);
+  if (lane == 0) conv[s] = all_ok ? 1 : 0;
+}
+
+// One wave per active scenario: the edge answer into the state, the residuals and the stop rule.
+__global__ void __launch_bounds__(64 * PW) k_plan_residual(const int* __restrict__ active, int n_act, int i_iter,
+                                                           double* __restrict__ bar, double* __restrict__ barp,
+                                                           const double* __restrict__ ctrl, double* __restrict__ ctrlp,
+                                                           const double* __restrict__ eout, const int* __restrict__ list,
+                                                           const int* __restrict__ eist,
+                                                           const double* __restrict__ pth, const double* __restrict__ dth,
+                                                           Par P, double* __restrict__ primal_o, double* __restrict__ dual_o,
+                                                           int* __restrict__ stop_o, int* __restrict__ iters,
+                                                           int* __restrict__ mask, int* __restrict__ keep) {
+  const int lane = threadIdx.x & 63;
+  const int k = blockIdx.x * PW + (threadIdx.x >> 6);
+  if (k >= n_act) return;
+  const int s = active[k];
+  double* B = bar + (size_t)s * STATE;
+  double* Bp = barp + (size_t)s * STATE;
+  const double* eo = eout + (size_t)k * EOUT;
+  // the 7 slot partials in index order, the 28 controls in index order (bit-repeatable)
+  double dual = 0.0;
+  for (int t = 0; t < NT; ++t) dual = dual + eo[EO_DRES + t];
+  const double d = lane < NCTRL ? fabs(ctrl[(size_t)s * NCTRL + lane] - ctrlp[(size_t)s * NCTRL + lane]) : 0.0;
+  double primal = 0.0;
+  for (int j = 0; j < NCTRL; ++j) primal = primal + __shfl(d, j, 64);
+  const bool stop = (primal <= pth[s] && dual <= dth[s]) || i_iter > P.max_admm_iter;
+  // every status of the iterate, as bits
+  int lm = lane < 2 ? 1 << (list[(size_t)(2 * k + lane) * 3] & 31) : 0;
+  int em = lane < NT ? 1 << (eist[((size_t)k * NT + lane) * 3] & 31) : 0;
+#pragma unroll
+  for (int o = 4; o > 0; o >>= 1) { lm |= __shfl_xor(lm, o, 64); em |= __shfl_xor(em, o, 64); }
+  // Z_bar and lamb_bar_new into the state; a continuing scenario's state becomes the previous
+  // iterate's, a stopped one's previous state stays frozen for the shift (:87, B16)
+  for (int i = lane; i < STATE; i += 64) {
+    const bool zb = i < S_ZB + 126, lb = i >= S_LB && i < S_LB + 126;
+    const double val = zb ? eo[EO_ZB + (i - S_ZB)] : lb ? eo[EO_LBN + (i - S_LB)] : B[i];
+    if (zb || lb) B[i] = val;
+    if (!stop) Bp[i] = val;
+  }
+  if (!stop && lane < NCTRL) ctrlp[(size_t)s * NCTRL + lane] = ctrl[(size_t)s * NCTRL + lane];
+  if (lane == 0) {
+    primal_o[s] = primal;
+    dual_o[s] = dual;
+    stop_o[s] = stop ? 1 : 0;
+    if (stop) iters[s] = i_iter;
+    mask[2 * s] |= lm;
+    mask[2 * s + 1] |= em;
+    keep[k] = stop ? 0 : 1;
+  }
+}
+
+// The next active list: the kept entries of `active` in their order (ascending scenarios).  One
+// workgroup scans the list tile by tile; nothing depends on the order workgroups run in.
+constexpr int CT = 256;
+__global__ void __launch_bounds__(CT) k_plan_compact(const int* __restrict__ active, const int* __restrict__ keep,
+                                                     int n_act, int* __restrict__ next, int* __restrict__ count) {
+  __shared__ int wtot[CT / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int base = 0;
+  for (int start = 0; start < n_act; start += CT) {
+    const int i = start + tid;
+    const int f = i < n_act ? keep[i] : 0;
+    const unsigned long long bal = __ballot(f);
+    const int before = __popcll(bal & ((1ull << lane) - 1ull));
+    if (lane == 0) wtot[wave] = __popcll(bal);
+    __syncthreads();
+    int off = base, tot = 0;
+    for (int w = 0; w < CT / 64; ++w) {
+      if (w < wave) off += wtot[w];
+      tot += wtot[w];
+    }
+    if (f) next[off + before] = active[i];
+    base += tot;
+    __syncthreads();
+  }
+  if (tid == 0) count[0] = base;
+}
+
+// One wave per scenario: iterate_next_state of the frozen previous state into both states,
+// init_state = X[:, 1], the step's last lamb_bar kept for the record, the step's bookkeeping reset.
+__global__ void __launch_bounds__(64) k_plan_shift(int n, double* __restrict__ bar, double* __restrict__ barp,
+                                                   const double* __restrict__ X, double* __restrict__ lamb,
+                                                   double* __restrict__ ctrlp, int* __restrict__ active) {
+  const int lane = threadIdx.x;
+  const int s = blockIdx.x;
+  if (s >= n) return;
+  double* B = bar + (size_t)s * STATE;
+  double* Bp = barp + (size_t)s * STATE;
+  constexpr int NV = (STATE + 63) / 64;
+  double val[NV], lam[2];
+  // every read first, then every write: the shift reads slot t + 1 of the array it overwrites
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    const int i = lane + 64 * j;
+    val[j] = 0.0;
+    if (i < S_INIT) {
+      const int base = i < S_A ? S_ZB : i < S_B ? S_A : i < S_LB ? S_B : i < S_LIJ ? S_LB : i < S_LX ? S_LIJ : S_LX;
+      const int w = i < S_A ? 9 : i < S_B ? 8 : i < S_LB ? 4 : i < S_LIJ ? 9 : i < S_LX ? 4 : 5;
+      const int f = i - base, v = f / (NT * w), t = (f % (NT * w)) / w, e = f % w;
+      const int tt = t + 1 < NT ? t + 1 : NT - 1;
+      val[j] = Bp[base + (v * NT + tt) * w + e];
+    } else if (i < STATE) {
+      const int f = i - S_INIT;
+      val[j] = X[(size_t)s * NX + (f / 5) * 40 + 5 + f % 5];
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int i = lane + 64 * j;
+    lam[j] = i < 126 ? B[S_LB + i] : 0.0;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    const int i = lane + 64 * j;
+    if (i < STATE) { B[i] = val[j]; Bp[i] = val[j]; }
+  }
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int i = lane + 64 * j;
+    if (i < 126) lamb[(size_t)s * 126 + i] = lam[j];
+  }
+  if (lane < NCTRL) ctrlp[(size_t)s * NCTRL + lane] = 0.0;
+  if (lane == 0) active[s] = s;
+}
+
+}  // namespace obca_plan
+
+// ---------------------------------------------------------------------------------------------
+// C-ABI (include/piadmm.h)
+// ---------------------------------------------------------------------------------------------
+struct piadmm_obca_plan_s {
+  piadmm_obca_plan_cfg_t cfg{};
+  obca_plan::Par par{};
+  bool open = false;
+  int n = 0, t_step = 0, i_iter = 0, n_act = 0, n_last = 0, cur = 0;
+  double *bar = nullptr, *barp = nullptr, *ctrl = nullptr, *ctrlp = nullptr, *X = nullptr, *primal = nullptr,
+         *dual = nullptr, *pth = nullptr, *dth = nullptr, *ref = nullptr, *lamb = nullptr;
+  int *iters = nullptr, *stop = nullptr, *conv = nullptr, *prob = nullptr, *act[2] = {nullptr, nullptr},
+      *keep = nullptr, *count = nullptr, *mask = nullptr;
+  int* h_count = nullptr;        // pinned: the 4 bytes read back per iterate
+};
+
+namespace {
+using obca_plan::PW;
+
+int pfail(piadmm_obca_t h, int code, const std::string& msg) {
+  if (h) h->err = msg;
+  return code;
+}
+#define PHIP(h, call)                                                                  \
+  do {                                                                                 \
+    hipError_t _e = (call);                                                            \
+    if (_e != hipSuccess) return pfail(h, PIADMM_E_HIP, std::string(#call ": ") + hipGetErrorString(_e)); \
+  } while (0)
+
+void plan_free_buffers(piadmm_obca_plan_s* p) {
+  void* d[] = {p->bar, p->barp, p->ctrl, p->ctrlp, p->X, p->primal, p->dual, p->pth, p->dth, p->ref, p->lamb,
+               p->iters, p->stop, p->conv, p->prob, p->act[0], p->act[1], p->keep, p->count, p->mask};
+  for (void* q : d)
+    if (q) (void)hipFree(q);
+  if (p->h_count) (void)hipHostFree(p->h_count);
+  p->bar = p->barp = p->ctrl = p->ctrlp = p->X = p->primal = p->dual = p->pth = p->dth = p->ref = p->lamb = nullptr;
+  p->iters = p->stop = p->conv = p->prob = p->act[0] = p->act[1] = p->keep = p->count = p->mask = nullptr;
+  p->h_count = nullptr;
+  p->open = false;
+}
+
+int plan_check(piadmm_obca_t h, const piadmm_obca_plan_cfg_t& c, const int32_t* prob) {
+  // the ranges check_recs (csrc/piadmm_obca.hip) and edge_check (csrc/piadmm_obca_edge.hip) enforce
+  // per record, on the configuration every record of the plan is packed from
+  if (!(c.rho > 0.0) || !(c.r > 0.0) || !(c.q > 0.0) || !(c.max_x > 0.0) || !(c.max_y > 0.0) ||
+      !(c.max_sqp_iter >= 1 && c.max_sqp_iter <= 1000) || (c.start != 0 && c.start != 1) ||
+      !(c.round_decimals >= -1 && c.round_decimals <= 15) || !(c.x_bound > 0.0) || !(c.mu_max > 0.0) ||
+      (c.update_lamb_ij != 0 && c.update_lamb_ij != 1))
+    return pfail(h, PIADMM_E_ARG, "obca_plan_begin: bad parameters (rho, r, q, max_x, max_y, x_bound, mu_max > 0; "
+                 "1 <= max_sqp_iter <= 1000; start, update_lamb_ij 0/1; -1 <= round_decimals <= 15)");
+  if (c.n_scenarios < 1) return pfail(h, PIADMM_E_ARG, "obca_plan_begin: n_scenarios >= 1");
+  if (c.n_scenarios > (1 << 20)) return pfail(h, PIADMM_E_ARG, "obca_plan_begin: n_scenarios <= 2^20");
+  if (c.max_admm_iter < 0) return pfail(h, PIADMM_E_ARG, "obca_plan_begin: max_admm_iter >= 0");
+  if (c.t_step0 < 0 || c.n_ref < 8 || c.t_step0 > c.n_ref - 8)
+    return pfail(h, PIADMM_E_ARG, "obca_plan_begin: t_step0 >= 0 and t_step0 + 8 <= n_ref");
+  for (int k = 0; k < c.n_scenarios; ++k)
+    if (prob[k] != 0 && prob[k] != 1)
+      return pfail(h, PIADMM_E_ARG, "obca_plan_begin: prob[" + std::to_string(k) + "] must be 0 or 1");
+  return 0;
+}
+
+template <typename T>
+int dalloc(piadmm_obca_t h, T** p, size_t count, bool zero) {
+  PHIP(h, hipMalloc(p, count * sizeof(T)));
+  if (zero) PHIP(h, hipMemset(*p, 0, count * sizeof(T)));
+  return 0;
+}
+
+int open_plan(piadmm_obca_t h, piadmm_obca_plan_s** out, const char* who) {
+  if (!h) return PIADMM_E_ARG;
+  if (!h->plan || !h->plan->open) return pfail(h, PIADMM_E_STATE, std::string(who) + ": no open plan (obca_plan_begin)");
+  *out = h->plan;
+  return 0;
+}
+
+int blocks_for(int waves) { return (waves + PW - 1) / PW; }
+}  // namespace
+
+void piadmm_obca_plan_release(piadmm_obca_t h) {
+  if (h->plan) h->plan->open = false;
+}
+
+void piadmm_obca_plan_free(piadmm_obca_t h) {
+  if (!h->plan) return;
+  plan_free_buffers(h->plan);
+  delete h->plan;
+  h->plan = nullptr;
+}
+
+extern "C" {
+
+int32_t piadmm_obca_plan_cfg_size(void) { return (int32_t)sizeof(piadmm_obca_plan_cfg_t); }
+
+int32_t piadmm_obca_plan_begin(piadmm_obca_t h, const piadmm_obca_plan_cfg_t* cfg, const int32_t* prob,
+                               const double* primal_thres, const double* dual_thres, const double* ref_traj,
+                               const double* state) {
+  using namespace obca_plan;
+  if (!h) return PIADMM_E_ARG;
+  if (!cfg || !prob || !primal_thres || !dual_thres || !ref_traj || !state)
+    return pfail(h, PIADMM_E_ARG, "obca_plan_begin: null argument");
+  if (int rc = plan_check(h, *cfg, prob)) return rc;
+  const int n = cfg->n_scenarios;
+  PHIP(h, hipSetDevice(h->device));
+  PHIP(h, hipStreamSynchronize(h->stream));
+  if (!h->plan) h->plan = new piadmm_obca_plan_s();
+  piadmm_obca_plan_s* p = h->plan;
+  plan_free_buffers(p);
+  // the takeover: the resident local batch and its longest-first history end here
+  h->n = 0;
+  h->cost_n = 0;
+  h->plan_taken = true;
+  if (int rc = piadmm_obca_local_ensure(h, 2 * n)) return rc;
+  if (int rc = piadmm_obca_edge_ensure(h, n)) return rc;
+  std::vector<int> ident((size_t)2 * n);
+  for (int i = 0; i < 2 * n; ++i) ident[i] = i;
+  PHIP(h, hipMemcpy(h->d_order, ident.data(), (size_t)2 * n * sizeof(int), hipMemcpyHostToDevice));
+
+  p->cfg = *cfg;
+  p->par = Par{cfg->rho, cfg->min_dis, cfg->conv_thres, cfg->max_x, cfg->max_y, cfg->r, cfg->q, cfg->x_bound,
+               cfg->mu_max, cfg->g_max, std::sqrt(0.95 / (1.0 - 0.95)),
+               cfg->max_admm_iter, cfg->round_decimals, cfg->start, cfg->update_lamb_ij, cfg->max_sqp_iter, cfg->n_ref};
+  p->n = n;
+  const size_t N = (size_t)n;
+  int rc = 0;
+  if ((rc = dalloc(h, &p->bar, N * STATE, false)) || (rc = dalloc(h, &p->barp, N * STATE, false)) ||
+      (rc = dalloc(h, &p->ctrl, N * NCTRL, true)) || (rc = dalloc(h, &p->ctrlp, N * NCTRL, true)) ||
+      (rc = dalloc(h, &p->X, N * NX, true)) || (rc = dalloc(h, &p->primal, N, true)) ||
+      (rc = dalloc(h, &p->dual, N, true)) || (rc = dalloc(h, &p->pth, N, false)) ||
+      (rc = dalloc(h, &p->dth, N, false)) || (rc = dalloc(h, &p->ref, (size_t)2 * cfg->n_ref * 5, false)) ||
+      (rc = dalloc(h, &p->lamb, N * 126, true)) || (rc = dalloc(h, &p->iters, N, true)) ||
+      (rc = dalloc(h, &p->stop, N, true)) || (rc = dalloc(h, &p->conv, N, true)) ||
+      (rc = dalloc(h, &p->prob, N, false)) || (rc = dalloc(h, &p->act[0], N, false)) ||
+      (rc = dalloc(h, &p->act[1], N, true)) || (rc = dalloc(h, &p->keep, N, true)) ||
+      (rc = dalloc(h, &p->count, (size_t)1, true)) || (rc = dalloc(h, &p->mask, 2 * N, true))) {
+    plan_free_buffers(p);
+    return rc;
+  }
+  PHIP(h, hipHostMalloc(reinterpret_cast<void**>(&p->h_count), sizeof(int)));
+  PHIP(h, hipMemcpy(p->bar, state, N * STATE * sizeof(double), hipMemcpyHostToDevice));
+  PHIP(h, hipMemcpy(p->barp, state, N * STATE * sizeof(double), hipMemcpyHostToDevice));
+  PHIP(h, hipMemcpy(p->pth, primal_thres, N * sizeof(double), hipMemcpyHostToDevice));
+  PHIP(h, hipMemcpy(p->dth, dual_thres, N * sizeof(double), hipMemcpyHostToDevice));
+  PHIP(h, hipMemcpy(p->ref, ref_traj, (size_t)2 * cfg->n_ref * 5 * sizeof(double), hipMemcpyHostToDevice));
+  PHIP(h, hipMemcpy(p->prob, prob, N * sizeof(int), hipMemcpyHostToDevice));
+  PHIP(h, hipMemcpy(p->act[0], ident.data(), N * sizeof(int), hipMemcpyHostToDevice));
+  p->t_step = cfg->t_step0;
+  p->i_iter = 0;
+  p->n_act = n;
+  p->n_last = 0;
+  p->cur = 0;
+  p->open = true;
+  return 0;
+}
+
+int32_t piadmm_obca_plan_iterate(piadmm_obca_t h, int32_t* n_active_after) {
+  using namespace obca_plan;
+  piadmm_obca_plan_s* p = nullptr;
+  if (int rc = open_plan(h, &p, "obca_plan_iterate")) return rc;
+  if (p->n_act <= 0) return pfail(h, PIADMM_E_STATE, "obca_plan_iterate: no active scenario (obca_plan_shift closes the step)");
+  if (p->t_step + 8 > p->cfg.n_ref) return pfail(h, PIADMM_E_STATE, "obca_plan_iterate: reference exhausted");
+  PHIP(h, hipSetDevice(h->device));
+  const int m = p->n_act;
+  if (2 * m > h->cap || m > h->e_cap) return pfail(h, PIADMM_E_STATE, "obca_plan_iterate: the handle's buffers shrank");
+  hipStream_t st = h->stream;
+  const int* act = p->act[p->cur];
+  int* nxt = p->act[1 - p->cur];
+  if (p->i_iter == 0) {
+    // a new MPC step: the stop iterates and the status bits are the step's own
+    PHIP(h, hipMemsetAsync(p->iters, 0, (size_t)p->n * sizeof(int), st));
+    PHIP(h, hipMemsetAsync(p->mask, 0, (size_t)2 * p->n * sizeof(int), st));
+  }
+  const int i_iter = p->i_iter + 1;
+  hipLaunchKernelGGL(k_plan_pack_local, dim3(blocks_for(2 * m)), dim3(64 * PW), 0, st, act, m, p->bar, p->prob, p->ref,
+                     p->t_step, p->par, h->d_rec);
+  PHIP(h, hipGetLastError());
+  if (int rc = piadmm_obca_local_launch(h, 2 * m)) return rc;
+  // the edge output starts from zeros, as in piadmm_obca_edge_solve
+  PHIP(h, hipMemsetAsync(h->e_out, 0, (size_t)m * EOUT * sizeof(double), st));
+  hipLaunchKernelGGL(k_plan_exchange, dim3(blocks_for(m)), dim3(64 * PW), 0, st, act, m, p->bar, p->prob, h->d_out,
+                     p->par, p->ctrl, p->X, p->conv, h->e_rec);
+  PHIP(h, hipGetLastError());
+  if (int rc = piadmm_obca_edge_launch(h, m)) return rc;
+  hipLaunchKernelGGL(k_plan_residual, dim3(blocks_for(m)), dim3(64 * PW), 0, st, act, m, i_iter, p->bar, p->barp,
+                     p->ctrl, p->ctrlp, h->e_out, h->d_ist, h->e_ist, p->pth, p->dth, p->par, p->primal, p->dual,
+                     p->stop, p->iters, p->mask, p->keep);
+  PHIP(h, hipGetLastError());
+  hipLaunchKernelGGL(k_plan_compact, dim3(1), dim3(CT), 0, st, act, p->keep, m, nxt, p->count);
+  PHIP(h, hipGetLastError());
+  PHIP(h, hipMemcpyAsync(p->h_count, p->count, sizeof(int), hipMemcpyDeviceToHost, st));
+  PHIP(h, hipStreamSynchronize(st));
+  const int left = *p->h_count;
+  if (left < 0 || left > m) return pfail(h, PIADMM_E_STATE, "obca_plan_iterate: active count out of range");
+  p->i_iter = i_iter;
+  p->n_last = m;
+  p->n_act = left;
+  p->cur = 1 - p->cur;
+  if (n_active_after) *n_active_after = left;
+  return 0;
+}
+
+int32_t piadmm_obca_plan_shift(piadmm_obca_t h) {
+  using namespace obca_plan;
+  piadmm_obca_plan_s* p = nullptr;
+  if (int rc = open_plan(h, &p, "obca_plan_shift")) return rc;
+  if (p->n_act > 0) return pfail(h, PIADMM_E_STATE, "obca_plan_shift: scenarios are still active");
+  if (p->i_iter == 0) return pfail(h, PIADMM_E_STATE, "obca_plan_shift: no iterate ran in this step");
+  PHIP(h, hipSetDevice(h->device));
+  // every scenario is active again: the list the next iterate reads is the identity
+  hipLaunchKernelGGL(k_plan_shift, dim3(p->n), dim3(64), 0, h->stream, p->n, p->bar, p->barp, p->X, p->lamb, p->ctrlp,
+                     p->act[p->cur]);
+  PHIP(h, hipGetLastError());
+  PHIP(h, hipStreamSynchronize(h->stream));
+  p->t_step += 1;
+  p->i_iter = 0;
+  p->n_act = p->n;
+  p->n_last = 0;
+  return 0;
+}
+
+int32_t piadmm_obca_plan_step(piadmm_obca_t h, int32_t* iters_out) {
+  piadmm_obca_plan_s* p = nullptr;
+  if (int rc = open_plan(h, &p, "obca_plan_step")) return rc;
+  if (p->t_step + 8 > p->cfg.n_ref) return pfail(h, PIADMM_E_STATE, "obca_plan_step: reference exhausted");
+  // i_iter > max_admm_iter stops every scenario: at most max_admm_iter + 1 iterates in a step
+  while (p->n_act > 0 && p->i_iter <= p->cfg.max_admm_iter) {
+    if (int rc = piadmm_obca_plan_iterate(h, nullptr)) return rc;
+  }
+  if (p->n_act > 0) return pfail(h, PIADMM_E_STATE, "obca_plan_step: scenarios active after max_admm_iter + 1 iterates");
+  if (iters_out) {
+    PHIP(h, hipMemcpyAsync(iters_out, p->iters, (size_t)p->n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    PHIP(h, hipStreamSynchronize(h->stream));
+  }
+  return piadmm_obca_plan_shift(h);
+}
+
+int32_t piadmm_obca_plan_get(piadmm_obca_t h, int32_t what, void* out, int64_t bytes) {
+  using namespace obca_plan;
+  piadmm_obca_plan_s* p = nullptr;
+  if (int rc = open_plan(h, &p, "obca_plan_get")) return rc;
+  const int64_t n = p->n, m = p->n_last, D = sizeof(double), I = sizeof(int32_t);
+  const void* src = nullptr;
+  int64_t want = -1;
+  int32_t counts[3] = {p->n_last, p->n_act, p->i_iter};
+  switch (what) {
+    case PIADMM_OBCA_PLAN_GET_STATE: src = p->bar; want = n * STATE * D; break;
+    case PIADMM_OBCA_PLAN_GET_STATE_PREV: src = p->barp; want = n * STATE * D; break;
+    case PIADMM_OBCA_PLAN_GET_CTRL: src = p->ctrl; want = n * NCTRL * D; break;
+    case PIADMM_OBCA_PLAN_GET_CTRL_PREV: src = p->ctrlp; want = n * NCTRL * D; break;
+    case PIADMM_OBCA_PLAN_GET_X: src = p->X; want = n * NX * D; break;
+    case PIADMM_OBCA_PLAN_GET_ITERS: src = p->iters; want = n * I; break;
+    case PIADMM_OBCA_PLAN_GET_ACTIVE: src = p->act[1 - p->cur]; want = m * I; break;
+    case PIADMM_OBCA_PLAN_GET_PRIMAL: src = p->primal; want = n * D; break;
+    case PIADMM_OBCA_PLAN_GET_DUAL: src = p->dual; want = n * D; break;
+    case PIADMM_OBCA_PLAN_GET_STOP: src = p->stop; want = n * I; break;
+    case PIADMM_OBCA_PLAN_GET_CONVERGE: src = p->conv; want = n * I; break;
+    case PIADMM_OBCA_PLAN_GET_LOCAL_REC: src = h->d_rec; want = 2 * m * REC * D; break;
+    case PIADMM_OBCA_PLAN_GET_LOCAL_OUT: src = h->d_out; want = 2 * m * OUT * D; break;
+    case PIADMM_OBCA_PLAN_GET_LOCAL_IST: src = h->d_ist; want = 2 * m * 3 * I; break;
+    case PIADMM_OBCA_PLAN_GET_EDGE_REC: src = h->e_rec; want = m * EREC * D; break;
+    case PIADMM_OBCA_PLAN_GET_EDGE_OUT: src = h->e_out; want = m * EOUT * D; break;
+    case PIADMM_OBCA_PLAN_GET_EDGE_IST: src = h->e_ist; want = m * NT * 3 * I; break;
+    case PIADMM_OBCA_PLAN_GET_LAMBDA: src = p->lamb; want = n * 126 * D; break;
+    case PIADMM_OBCA_PLAN_GET_STATUS_MASK: src = p->mask; want = 2 * n * I; break;
+    case PIADMM_OBCA_PLAN_GET_T_STEP: want = I; break;
+    case PIADMM_OBCA_PLAN_GET_COUNTS: want = 3 * I; break;
+    default: return pfail(h, PIADMM_E_ARG, "obca_plan_get: unknown item " + std::to_string(what));
+  }
+  if (bytes != want)
+    return pfail(h, PIADMM_E_ARG, "obca_plan_get: item " + std::to_string(what) + " is " + std::to_string(want) +
+                 " bytes, not " + std::to_string(bytes));
+  if (want == 0) return 0;
+  if (!out) return pfail(h, PIADMM_E_ARG, "obca_plan_get: out");
+  if (what == PIADMM_OBCA_PLAN_GET_T_STEP) { *static_cast<int32_t*>(out) = p->t_step; return 0; }
+  if (what == PIADMM_OBCA_PLAN_GET_COUNTS) { for (int i = 0; i < 3; ++i) static_cast<int32_t*>(out)[i] = counts[i]; return 0; }
+  PHIP(h, hipSetDevice(h->device));
+  PHIP(h, hipMemcpyAsync(out, src, (size_t)want, hipMemcpyDeviceToHost, h->stream));
+  PHIP(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int32_t piadmm_obca_plan_end(piadmm_obca_t h) {
+  if (!h) return PIADMM_E_ARG;
+  if (!h->plan) return 0;
+  (void)hipSetDevice(h->device);
+  if (h->stream) (void)hipStreamSynchronize(h->stream);
+  piadmm_obca_plan_free(h);
+  return 0;
+}
+
+}  // extern "C"

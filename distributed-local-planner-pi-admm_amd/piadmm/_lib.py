@@ -38,6 +38,16 @@ class PiadmmConfigC(ctypes.Structure):
     ]
 
 
+class ObcaPlanCfgC(ctypes.Structure):
+    """Byte-for-byte mirror of ``piadmm_obca_plan_cfg_t`` (``piadmm_obca_plan_cfg_size``)."""
+    _fields_ = [
+        ("n_scenarios", c_i32), ("t_step0", c_i32), ("max_admm_iter", c_i32), ("round_decimals", c_i32),
+        ("start", c_i32), ("update_lamb_ij", c_i32), ("max_sqp_iter", c_i32), ("n_ref", c_i32),
+        ("rho", c_dbl), ("min_dis", c_dbl), ("conv_thres", c_dbl), ("max_x", c_dbl), ("max_y", c_dbl),
+        ("r", c_dbl), ("q", c_dbl), ("x_bound", c_dbl), ("mu_max", c_dbl), ("g_max", c_dbl),
+    ]
+
+
 def to_c(cfg: PIADMMConfig, n_agents: int, device: int = 0) -> PiadmmConfigC:
     c = PiadmmConfigC()
     for name, _ in PiadmmConfigC._fields_:
@@ -100,7 +110,17 @@ SYMBOLS = [
     ("piadmm_obca_debug_stamps", c_i32, [_H, _P(ctypes.c_uint64), c_i32]),
     ("piadmm_obca_edge_solve", c_i32, [_H, _dp, c_i32, _dp, _ip]),
     ("piadmm_obca_edge_time", c_i32, [_H, _dp, c_i32, c_i32, _P(ctypes.c_float)]),
+    ("piadmm_obca_plan_cfg_size", c_i32, []),
+    ("piadmm_obca_plan_begin", c_i32, [_H, _P(ObcaPlanCfgC), _ip, _dp, _dp, _dp, _dp]),
+    ("piadmm_obca_plan_iterate", c_i32, [_H, _ip]),
+    ("piadmm_obca_plan_shift", c_i32, [_H]),
+    ("piadmm_obca_plan_step", c_i32, [_H, _ip]),
+    ("piadmm_obca_plan_get", c_i32, [_H, c_i32, ctypes.c_void_p, ctypes.c_int64]),
+    ("piadmm_obca_plan_end", c_i32, [_H]),
 ]
+
+# error codes of include/piadmm.h the OBCA bindings name
+E_ARG, E_HIP, E_STATE, E_NODEV = -1, -2, -3, -4
 
 # piadmm_near_tie_t (include/piadmm.h, ABI 6) as a NumPy record
 TIE_KINDS = ("round_u", "round_uhat", "round_seed", "collide", "stop", "dist")

@@ -595,3 +595,214 @@ class OBCAPlanner:
         for _ in range(int(n_steps)):
             self.step()
         return self.record
+
+
+# ---------------------------------------------------------------------------------------------
+# The same loop, device-resident (csrc/piadmm_obca_plan.hip behind piadmm_obca_plan_*)
+# ---------------------------------------------------------------------------------------------
+PLAN_STATE = 556
+# the state's fields in order (include/piadmm.h): name, shape
+PLAN_FIELDS = (("Z_bar", (2, NT, 9)), ("A", (2, NT, 4, 2)), ("b", (2, NT, 4)), ("lamb_bar", (2, NT, 9)),
+               ("lamb_ij", (2, NT, 4)), ("local_x", (2, NT, 5)), ("init_state", (2, 5)))
+# piadmm_obca_plan_get items: name -> (code, dtype)
+PLAN_GET = {"STATE": (0, np.float64), "STATE_PREV": (1, np.float64), "CTRL": (2, np.float64),
+            "CTRL_PREV": (3, np.float64), "X": (4, np.float64), "ITERS": (5, np.int32), "ACTIVE": (6, np.int32),
+            "PRIMAL": (7, np.float64), "DUAL": (8, np.float64), "STOP": (9, np.int32), "CONVERGE": (10, np.int32),
+            "LOCAL_REC": (11, np.float64), "LOCAL_OUT": (12, np.float64), "LOCAL_IST": (13, np.int32),
+            "EDGE_REC": (14, np.float64), "EDGE_OUT": (15, np.float64), "EDGE_IST": (16, np.int32),
+            "T_STEP": (17, np.int32), "LAMBDA": (18, np.float64), "COUNTS": (19, np.int32),
+            "STATUS_MASK": (20, np.int32)}
+
+
+def pack_state(bar, init_state):
+    """One scenario's resident state (PLAN_STATE doubles) from a bar_state and its 2 x 5 init_state."""
+    parts = dict(bar, init_state=init_state)
+    out = np.concatenate([np.asarray(parts[k], np.float64).reshape(-1) for k, _ in PLAN_FIELDS])
+    assert out.shape == (PLAN_STATE,)
+    return out
+
+
+def unpack_state(vec):
+    """(bar_state, init_state) of one scenario's resident state: copies, the inverse of `pack_state`."""
+    vec = np.asarray(vec, np.float64)
+    assert vec.shape == (PLAN_STATE,)
+    bar, o = {}, 0
+    for k, shp in PLAN_FIELDS:
+        n = int(np.prod(shp))
+        bar[k] = vec[o:o + n].reshape(shp).copy()
+        o += n
+    init = bar.pop("init_state")
+    return bar, init
+
+
+class OBCADevicePlanner:
+    """`OBCAPlanner` with the loop on the device: the planner state stays resident on the batch's
+    handle and one ADMM iterate is a fixed chain of launches (csrc/piadmm_obca_plan.hip); the host
+    reads back the number of scenarios still active.  Same constructor arguments, same seeding
+    (`seeded_bar_state`, `executed_path`) and the same OBCARunRecord fields as OBCAPlanner.
+
+    Without on_stage a step is one `piadmm_obca_plan_step`; status_record then keeps one entry per
+    MPC step: the iterate each scenario stopped at and, per scenario, the OR of (1 << status) over
+    its local and its edge solves (nothing is silent).  With on_stage the step goes iterate by
+    iterate, the callback sees the six stages of OBCAPlanner built from `get`, and status_record
+    keeps one entry per iterate as OBCAPlanner's does.
+
+    The planner takes the batch's device buffers over (include/piadmm.h): `batch.upload` / `solve`
+    / `solve_edge` on the same batch end the plan."""
+
+    def __init__(self, batch, n_scenarios, prob=1, t_step0=0, rho=1.0, min_dis=0.1, max_admm_iter=50,
+                 primal_thres=0.01, dual_thres=0.01, round_decimals=4, start=1, update_lamb_ij=0, max_iter=60,
+                 conv_thres=0.1, on_stage=None, max_x=150.0, max_y=20.0, r=1e4, q=1e5, x_bound=1000.0,
+                 mu_max=100000.0, g_max=1000.0, ref_traj=None, state=None):
+        from . import _lib
+        self.batch = batch
+        self._lib = batch._lib
+        self.n = int(n_scenarios)
+        self.prob = [int(prob)] * self.n if np.isscalar(prob) else [int(p) for p in prob]
+        assert len(self.prob) == self.n
+        self.t_step = int(t_step0)
+        self.rho, self.min_dis = float(rho), float(min_dis)
+        self.max_admm_iter = int(max_admm_iter)
+        self.primal_thres = np.broadcast_to(np.asarray(primal_thres, np.float64), (self.n,)).copy()
+        self.dual_thres = np.broadcast_to(np.asarray(dual_thres, np.float64), (self.n,)).copy()
+        self.conv_thres = conv_thres
+        self.round_decimals, self.start, self.update_lamb_ij, self.max_iter = round_decimals, start, update_lamb_ij, max_iter
+        self.on_stage = on_stage
+        self.ref_traj = ref_traj_gen() if ref_traj is None else ref_traj
+        ref = np.ascontiguousarray(np.stack([np.asarray(r_, np.float64) for r_ in self.ref_traj]))
+        assert ref.ndim == 3 and ref.shape[0] == 2 and ref.shape[2] == NX
+        self.n_ref = ref.shape[1]
+        self.init_state = [np.stack([executed_path(v, self.t_step * DT) for v in (0, 1)]) for _ in range(self.n)]
+        if state is None:
+            seeds = {p: pack_state(seeded_bar_state(self.t_step, p), self.init_state[0]) for p in set(self.prob)}
+            state = np.stack([seeds[p] for p in self.prob]) if self.n else np.zeros((0, PLAN_STATE))
+        state = np.ascontiguousarray(state, np.float64)
+        assert state.shape == (self.n, PLAN_STATE)
+        self.cfg = _lib.ObcaPlanCfgC(
+            n_scenarios=self.n, t_step0=self.t_step, max_admm_iter=self.max_admm_iter,
+            round_decimals=int(round_decimals), start=int(start), update_lamb_ij=int(update_lamb_ij),
+            max_sqp_iter=int(max_iter), n_ref=self.n_ref, rho=self.rho, min_dis=self.min_dis,
+            conv_thres=float(conv_thres), max_x=max_x, max_y=max_y, r=r, q=q, x_bound=x_bound, mu_max=mu_max,
+            g_max=g_max)
+        prob_a = np.ascontiguousarray(self.prob if self.n else [0], np.int32)
+        self._check(self._lib.piadmm_obca_plan_begin(batch._h, ctypes.byref(self.cfg), _lib.iptr(prob_a),
+                                                     _lib.dptr(self.primal_thres), _lib.dptr(self.dual_thres),
+                                                     _lib.dptr(ref), _lib.dptr(state)))
+        self.record = OBCARunRecord()
+        self.record.state_record.append(np.stack(self.init_state))
+
+    def _check(self, rc):
+        from . import _lib
+        if rc != 0:
+            msg = self._lib.piadmm_obca_last_error(self.batch._h)
+            err = _lib.PiadmmError(f"libpiadmm error {rc}: {msg.decode() if msg else ''}")
+            err.code = rc
+            raise err
+
+    def counts(self):
+        """(scenarios submitted to the last iterate, scenarios still active, iterates run in the open step)."""
+        c = np.zeros(3, np.int32)
+        self._check(self._lib.piadmm_obca_plan_get(self.batch._h, PLAN_GET["COUNTS"][0], c.ctypes.data, c.nbytes))
+        return int(c[0]), int(c[1]), int(c[2])
+
+    def get(self, what):
+        """One item of the resident plan (include/piadmm.h, piadmm_obca_plan_get), shaped."""
+        code, dt = PLAN_GET[what]
+        n, m = self.n, (self.counts()[0] if what != "COUNTS" else 0)
+        shape = {"STATE": (n, PLAN_STATE), "STATE_PREV": (n, PLAN_STATE), "CTRL": (n, 2, NT * NU),
+                 "CTRL_PREV": (n, 2, NT * NU), "X": (n, 2, N_HORZ, NX), "ITERS": (n,), "ACTIVE": (m,),
+                 "PRIMAL": (n,), "DUAL": (n,), "STOP": (n,), "CONVERGE": (n,), "LOCAL_REC": (2 * m, REC),
+                 "LOCAL_OUT": (2 * m, OUT), "LOCAL_IST": (2 * m, 3), "EDGE_REC": (m, EDGE_REC),
+                 "EDGE_OUT": (m, EDGE_OUT), "EDGE_IST": (m, NT, 3), "T_STEP": (1,), "LAMBDA": (n, 2, NT, 9),
+                 "COUNTS": (3,), "STATUS_MASK": (n, 2)}[what]
+        out = np.zeros(shape, dt)
+        self._check(self._lib.piadmm_obca_plan_get(self.batch._h, code, out.ctypes.data, out.nbytes))
+        return out
+
+    def iterate(self):
+        """One ADMM iterate of the open MPC step; the number of scenarios still active."""
+        left = ctypes.c_int32()
+        self._check(self._lib.piadmm_obca_plan_iterate(self.batch._h, ctypes.byref(left)))
+        return left.value
+
+    def shift(self):
+        self._check(self._lib.piadmm_obca_plan_shift(self.batch._h))
+
+    def close(self):
+        """End the plan (the batch stays usable after its next upload)."""
+        if self.batch._h:
+            self._lib.piadmm_obca_plan_end(self.batch._h)
+
+    def _close_step(self, iters, status):
+        X = self.get("X")
+        self.init_state = [X[s, :, 1].copy() for s in range(self.n)]
+        self.record.state_record.append(np.stack(self.init_state))
+        self.record.iter_num_record.append(np.asarray(iters, int))
+        self.record.lambda_record.append(self.get("LAMBDA"))
+        self.record.status_record.extend(status)
+        self.t_step += 1
+
+    def step(self):
+        """One MPC step of every scenario."""
+        from . import _lib
+        if self.on_stage is not None:
+            return self._step_staged()
+        iters = np.zeros(self.n, np.int32)
+        self._check(self._lib.piadmm_obca_plan_step(self.batch._h, _lib.iptr(iters)))
+        mask = self.get("STATUS_MASK")
+        self._close_step(iters, [dict(t_step=self.t_step, iters=iters.copy(), local_status_mask=mask[:, 0].copy(),
+                                      edge_status_mask=mask[:, 1].copy())])
+
+    def _step_staged(self):
+        n = self.n
+        status = []
+        left, i_iter = n, 0
+        while left:
+            i_iter += 1
+            before = self.get("STATE")
+            ctrl_prev = self.get("CTRL_PREV")
+            left = self.iterate()
+            active = [int(s) for s in self.get("ACTIVE")]
+            after = self.get("STATE")
+            recs = self.get("LOCAL_REC")
+            res = OBCAResult(self.get("LOCAL_OUT"), self.get("LOCAL_IST"))
+            self.on_stage("local", dict(recs=recs, scenarios=list(active), i_iter=i_iter, t_step=self.t_step),
+                          dict(result=res))
+            fullx = [[res.bar_fullx(2 * k + v) for v in (0, 1)] for k in range(len(active))]
+            bar_in = [unpack_state(before[s])[0] for s in active]
+            # the exchange leaves Z_bar and lamb_bar as they were; the edge answer replaces them later
+            bar_ex = []
+            for k, s in enumerate(active):
+                b = unpack_state(after[s])[0]
+                b["Z_bar"], b["lamb_bar"] = bar_in[k]["Z_bar"].copy(), bar_in[k]["lamb_bar"].copy()
+                bar_ex.append(b)
+            self.on_stage("exchange", dict(bar=bar_in, fullx=fullx, scenarios=list(active)), dict(bar=bar_ex))
+            conv = [bool(c) for c in self.get("CONVERGE")[active]]
+            self.on_stage("converge", dict(bar=bar_ex), dict(if_converge=conv))
+            erecs = self.get("EDGE_REC")
+            eres = OBCAEdgeResult(self.get("EDGE_OUT"), self.get("EDGE_IST"))
+            self.on_stage("edge", dict(recs=erecs, scenarios=list(active)), dict(result=eres))
+            status.append(dict(t_step=self.t_step, i_iter=i_iter, scenarios=list(active), local_status=res.status.copy(),
+                               edge_status=eres.status.copy(), if_converge=conv))
+            ctrl = self.get("CTRL")
+            self.on_stage("residual",
+                          dict(ctrl=[ctrl[s] for s in active], ctrl_prev=[ctrl_prev[s] for s in active],
+                               lamb_bar=[unpack_state(after[s])[0]["lamb_bar"] for s in active],
+                               lamb_bar_prev=[b["lamb_bar"] for b in bar_in], i_iter=i_iter, scenarios=list(active)),
+                          dict(primal=self.get("PRIMAL")[active], dual=self.get("DUAL")[active],
+                               stop=self.get("STOP")[active].astype(bool)))
+        iters = self.get("ITERS")
+        frozen = self.get("STATE_PREV")
+        X = self.get("X")
+        self.shift()
+        nxt = self.get("STATE")
+        self.on_stage("shift", dict(bar_prev=[unpack_state(frozen[s])[0] for s in range(n)],
+                                    X=[[X[s, 0], X[s, 1]] for s in range(n)], iters=iters.astype(int)),
+                      dict(bar_next=[unpack_state(nxt[s])[0] for s in range(n)],
+                           init_state=[unpack_state(nxt[s])[1] for s in range(n)]))
+        self._close_step(iters, status)
+
+    def run(self, n_steps):
+        for _ in range(int(n_steps)):
+            self.step()
+        return self.record

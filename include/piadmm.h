@@ -390,6 +390,91 @@ int32_t piadmm_obca_edge_solve(piadmm_obca_t h, const double* recs, int32_t n_pa
 int32_t piadmm_obca_edge_time(piadmm_obca_t h, const double* recs, int32_t n_pairs, int32_t repeats,
                               float* ms_per_launch);
 
+/* ---- OBCA-ADMM consensus loop, device-resident ---------------------------------------------
+ * The loop of decentralized_overtaking_ADMM.py:31-102 for n_scenarios vehicle pairs at once, the
+ * planner state resident on the device: per ADMM iterate one launch each of pack-local, the local
+ * SQP (scenarios x 2), exchange (bar_state_update, check_converge and the edge record), the edge
+ * SQP with the fused lambda_update, residual (the stop rule of :82-86) and an order-keeping
+ * compaction of the scenarios still active; the host reads back 4 bytes per iterate (their count).
+ * A stopped scenario is not resubmitted; on termination the horizon shift takes the PREVIOUS
+ * iterate's state (:87) and init_state = X[1] (:99).
+ *
+ * State of one scenario (PIADMM_OBCA_PLAN_STATE fp64):
+ *   Z_bar[2][7][9] | A[2][7][4][2] | b[2][7][4] | lamb_bar[2][7][9] | lamb_ij[2][7][4] |
+ *   local_x[2][7][5] | init_state[2][5]
+ *
+ * piadmm_obca_plan_begin checks the configuration before any launch (rho, r, q, max_x, max_y,
+ * x_bound, mu_max > 0; prob[k] 0/1; 1 <= max_sqp_iter <= 1000; start and update_lamb_ij 0/1;
+ * -1 <= round_decimals <= 15; n_scenarios >= 1; max_admm_iter >= 0; 0 <= t_step0 and
+ * t_step0 + 8 <= n_ref), copies prob, the thresholds (one per scenario), ref_traj and the state
+ * (which becomes both the current and the previous iterate's), and opens MPC step t_step0.
+ * It takes the handle's local and edge device buffers over: afterwards piadmm_obca_run, _time and
+ * _download return PIADMM_E_STATE until the next piadmm_obca_upload.  Any upload into those buffers
+ * (piadmm_obca_upload / _solve / _edge_solve / _edge_time) ends the plan as piadmm_obca_plan_end does.
+ *
+ * piadmm_obca_plan_iterate runs one ADMM iterate of the open MPC step on the scenarios still
+ * active and returns how many remain active; PIADMM_E_STATE without an open plan, with no active
+ * scenario left (call piadmm_obca_plan_shift) or when t_step + 8 > n_ref ("reference exhausted").
+ * piadmm_obca_plan_shift closes the step (iterate_next_state of the frozen previous state into both
+ * states, init_state = X[1], t_step += 1, every scenario active again); PIADMM_E_STATE while
+ * scenarios are active.  piadmm_obca_plan_step = iterate until none is active (at most
+ * max_admm_iter + 1 iterates), then shift; iters_out: the iterate each scenario stopped at.
+ *
+ * piadmm_obca_plan_get copies one item to the host; `bytes` must be the item's size exactly
+ * (PIADMM_E_ARG otherwise).  n = n_scenarios, m = the number of scenarios submitted to the last
+ * iterate (0 before the first iterate of a step):
+ *   STATE, STATE_PREV   n x 556 fp64     the current / the previous iterate's state
+ *   CTRL, CTRL_PREV     n x 2 x 14 fp64  [U[:,0], U[:,1]] per vehicle (CTRL_PREV: zeros at a step's start)
+ *   X                   n x 2 x 8 x 5 fp64   the last local solution of each scenario
+ *   ITERS               n int32          the iterate each scenario stopped at (0: still active)
+ *   ACTIVE              m int32          the scenarios submitted to the last iterate, ascending
+ *   PRIMAL, DUAL        n fp64           the residuals of each scenario's last iterate
+ *   STOP, CONVERGE      n int32          the stop decision / check_converge of its last iterate
+ *   LOCAL_REC / _OUT / _IST   2m x PIADMM_OBCA_REC / 2m x PIADMM_OBCA_OUT fp64 / 2m x 3 int32
+ *                       record 2k + v: vehicle v of scenario ACTIVE[k]
+ *   EDGE_REC / _OUT / _IST    m x PIADMM_OBCA_EDGE_REC / m x PIADMM_OBCA_EDGE_OUT fp64 / m x 7 x 3 int32
+ *   T_STEP              1 int32          the open MPC step
+ *   LAMBDA              n x 2 x 7 x 9 fp64   lamb_bar of each scenario's last iterate in the step
+ *                       closed last (what the script's lambda_record keeps, :103)
+ *   COUNTS              3 int32          m, the number still active, the iterates run in the open step
+ *   STATUS_MASK         n x 2 int32      OR of (1 << status) over the local / the edge solves of the
+ *                       scenario in the step closed last (in the open step before the shift) */
+#define PIADMM_OBCA_PLAN_STATE 556
+#define PIADMM_OBCA_PLAN_GET_STATE 0
+#define PIADMM_OBCA_PLAN_GET_STATE_PREV 1
+#define PIADMM_OBCA_PLAN_GET_CTRL 2
+#define PIADMM_OBCA_PLAN_GET_CTRL_PREV 3
+#define PIADMM_OBCA_PLAN_GET_X 4
+#define PIADMM_OBCA_PLAN_GET_ITERS 5
+#define PIADMM_OBCA_PLAN_GET_ACTIVE 6
+#define PIADMM_OBCA_PLAN_GET_PRIMAL 7
+#define PIADMM_OBCA_PLAN_GET_DUAL 8
+#define PIADMM_OBCA_PLAN_GET_STOP 9
+#define PIADMM_OBCA_PLAN_GET_CONVERGE 10
+#define PIADMM_OBCA_PLAN_GET_LOCAL_REC 11
+#define PIADMM_OBCA_PLAN_GET_LOCAL_OUT 12
+#define PIADMM_OBCA_PLAN_GET_LOCAL_IST 13
+#define PIADMM_OBCA_PLAN_GET_EDGE_REC 14
+#define PIADMM_OBCA_PLAN_GET_EDGE_OUT 15
+#define PIADMM_OBCA_PLAN_GET_EDGE_IST 16
+#define PIADMM_OBCA_PLAN_GET_T_STEP 17
+#define PIADMM_OBCA_PLAN_GET_LAMBDA 18
+#define PIADMM_OBCA_PLAN_GET_COUNTS 19
+#define PIADMM_OBCA_PLAN_GET_STATUS_MASK 20
+typedef struct {
+  int32_t n_scenarios, t_step0, max_admm_iter, round_decimals, start, update_lamb_ij, max_sqp_iter, n_ref;
+  double rho, min_dis, conv_thres, max_x, max_y, r, q, x_bound, mu_max, g_max;
+} piadmm_obca_plan_cfg_t;
+int32_t piadmm_obca_plan_cfg_size(void);
+int32_t piadmm_obca_plan_begin(piadmm_obca_t h, const piadmm_obca_plan_cfg_t* cfg, const int32_t* prob,
+                               const double* primal_thres, const double* dual_thres,
+                               const double* ref_traj /* 2 x n_ref x 5 */, const double* state /* n x 556 */);
+int32_t piadmm_obca_plan_iterate(piadmm_obca_t h, int32_t* n_active_after);
+int32_t piadmm_obca_plan_shift(piadmm_obca_t h);
+int32_t piadmm_obca_plan_step(piadmm_obca_t h, int32_t* iters_out /* n, may be NULL */);
+int32_t piadmm_obca_plan_get(piadmm_obca_t h, int32_t what, void* out, int64_t bytes);
+int32_t piadmm_obca_plan_end(piadmm_obca_t h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,6 +6,9 @@
   full iterate     wall-clock ms of one ADMM iterate of OBCAPlanner on --scenarios seeded
                    scenarios: the local launch (scenarios x 2 problems), the host exchange
                    (bar_state_update, check_converge, record packing), the edge launch
+  device iterate   the same MPC step of the same scenarios with the loop on the device
+                   (OBCADevicePlanner.step: one piadmm_obca_plan_step, then the record's downloads),
+                   wall-clock ms per ADMM iterate, and its ratio to the host iterate of this run
 
 There is no CPU baseline on an equal footing (the C++ port of the local solver has no edge step);
 the edge launch is reported next to the local launch so the reader sees its share of an iterate.
@@ -78,6 +81,20 @@ def main():
     by = {}
     for name, ms in stamps:
         by[name] = by.get(name, 0.0) + ms
+    # the same scenarios with the loop on the device (OBCADevicePlanner: one piadmm_obca_plan_step per
+    # MPC step): a warm-up step on its own plan, then the timed first step of a fresh plan, so both
+    # planners time the same MPC step from the same seeded state
+    kw = dict(prob=[k % 2 for k in range(a.scenarios)], t_step0=8, max_admm_iter=a.iterates - 1)
+    dp = obca.OBCADevicePlanner(b, a.scenarios, **kw)
+    dp.step()
+    dp.close()
+    dp = obca.OBCADevicePlanner(b, a.scenarios, **kw)
+    t0 = time.perf_counter()
+    dp.step()
+    dev_total = (time.perf_counter() - t0) * 1e3
+    dev_it = int(np.asarray(dp.record.iter_num_record[0]).max())
+    dev_iters_equal = bool(np.array_equal(dp.record.iter_num_record[0], pl.record.iter_num_record[0]))
+    dp.close()
     out = dict(
         pairs=a.pairs, slot_problems=a.pairs * obca.NT, repeats=a.repeats,
         edge_ms_per_launch=min(edge_ms), edge_ms_runs=edge_ms,
@@ -86,6 +103,10 @@ def main():
         local_problems=len(lrecs), local_ms_per_launch=min(local_ms),
         scenarios=a.scenarios, admm_iterates=n_it, iterate_ms=total / max(n_it, 1),
         stage_ms_per_iterate={k: v / max(n_it, 1) for k, v in by.items()},
+        device_admm_iterates=dev_it, device_step_ms=dev_total, device_iterate_ms=dev_total / max(dev_it, 1),
+        device_over_host_iterate=(dev_total / max(dev_it, 1)) / (total / max(n_it, 1)),
+        host_over_device_iterate=(total / max(n_it, 1)) / (dev_total / max(dev_it, 1)),
+        device_stop_iterates_equal_host=dev_iters_equal,
         baseline=None, note="no CPU baseline exists for the edge step",
     )
     b.close()
