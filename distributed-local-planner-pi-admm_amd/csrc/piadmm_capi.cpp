@@ -158,8 +158,18 @@ int check_cfg(piadmm_ctx* h, const piadmm_config_t& c) {
     return fail(h, PIADMM_E_ARG, "warm_duals and a nonzero dual_init are exclusive");
   if (!(c.dt > 0) || !(c.L > 0) || !(c.rho > 0) || !(c.Pcost > 0) || c.Pnorm < 0 || c.beta < 0)
     return fail(h, PIADMM_E_ARG, "dt, L, rho, Pcost must be > 0; Pnorm, beta >= 0");
+  // !(x > 0) also refuses NaN; a non-finite bound, distance or tolerance has no valid solve (an
+  // empty or unbounded box, a stop test that never or always fires)
+  if (!(c.u_max > 0) || !(c.du_max > 0) || !(c.dis_thres > 0) || !std::isfinite(c.u_max) ||
+      !std::isfinite(c.du_max) || !std::isfinite(c.dis_thres))
+    return fail(h, PIADMM_E_ARG, "u_max, du_max, dis_thres must be > 0 and finite");
+  if (!std::isfinite(c.eps_pri) || !std::isfinite(c.eps_dual))
+    return fail(h, PIADMM_E_ARG, "eps_pri, eps_dual must be finite");
+  if (c.windup && !(c.windup_sat > 0))
+    return fail(h, PIADMM_E_ARG, "windup needs windup_sat > 0 (the saturation +-windup_sat)");
   if (c.max_inner <= 0 || c.polish_every <= 0) return fail(h, PIADMM_E_ARG, "max_inner, polish_every must be > 0");
-  if (c.round_decimals > 12) return fail(h, PIADMM_E_ARG, "round_decimals must be <= 12");
+  if (c.round_decimals < -1 || c.round_decimals > 12)
+    return fail(h, PIADMM_E_ARG, "round_decimals must be in [-1, 12] (-1: no rounding)");
   if (c.tighten && !(c.tight_p > 0 && c.tight_p < 1)) return fail(h, PIADMM_E_ARG, "tight_p must be in (0, 1)");
   if (c.precision < 0 || c.precision > 2)
     return fail(h, PIADMM_E_ARG, "precision must be 0 (fp64), 1 (fp32 ADMM matrices) or 2 (fp32 x-step tables)");
@@ -240,19 +250,26 @@ const char* piadmm_last_error(piadmm_handle_t h) { return h ? h->err.c_str() : g
 int32_t piadmm_create(const piadmm_config_t* cfg, piadmm_handle_t* out) {
   if (!cfg || !out) return fail(nullptr, PIADMM_E_ARG, "null argument");
   *out = nullptr;
-  int nd = 0;
-  if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0) return fail(nullptr, PIADMM_E_NODEV, "no HIP device");
-  if (cfg->device < 0 || cfg->device >= nd) return fail(nullptr, PIADMM_E_ARG, "device ordinal out of range");
   piadmm_ctx* h = new piadmm_ctx();
   h->cfg = *cfg;
   if (h->cfg.admm_rho <= 0) h->cfg.admm_rho = 0.05;
   if (h->cfg.admm_sigma <= 0) h->cfg.admm_sigma = 1e-6;
   if (h->cfg.admm_alpha <= 0 || h->cfg.admm_alpha >= 2) h->cfg.admm_alpha = 1.6;
   if (h->cfg.qp_tol <= 0) h->cfg.qp_tol = 1e-9;
+  // the configuration is judged before any device call: a refusal needs no GPU
   if (int rc = check_cfg(h, h->cfg)) {
     g_err = h->err;
     delete h;
     return rc;
+  }
+  int nd = 0;
+  if (hipGetDeviceCount(&nd) != hipSuccess || nd == 0) {
+    delete h;
+    return fail(nullptr, PIADMM_E_NODEV, "no HIP device");
+  }
+  if (cfg->device < 0 || cfg->device >= nd) {
+    delete h;
+    return fail(nullptr, PIADMM_E_ARG, "device ordinal out of range");
   }
   hipError_t e = hipSetDevice(cfg->device);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);

@@ -123,7 +123,10 @@ const char* piadmm_build_info(void);           /* e.g. "gfx950 hip 7.2 ..." */
 int32_t piadmm_device_count(void);
 int32_t piadmm_config_size(void);              /* sizeof(piadmm_config_t), for binding checks */
 
-/* Create / destroy.  Replaces PI_ADMM_CASADI.__init__ (casadi/PI_ADMM_class.py:13-37). */
+/* Create / destroy.  Replaces PI_ADMM_CASADI.__init__ (casadi/PI_ADMM_class.py:13-37).
+ * The configuration is checked before any device call: one without a valid solve (u_max, du_max
+ * or dis_thres <= 0 or non-finite, non-finite eps_pri / eps_dual, windup with windup_sat <= 0,
+ * round_decimals outside [-1, 12], ...) is refused with PIADMM_E_ARG, with or without a GPU. */
 int32_t piadmm_create(const piadmm_config_t* cfg, piadmm_handle_t* out);
 int32_t piadmm_destroy(piadmm_handle_t h);
 const char* piadmm_last_error(piadmm_handle_t h);

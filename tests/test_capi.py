@@ -79,3 +79,46 @@ def test_header_enums_match_python():
     assert re.search(r"#define PIADMM_DUAL_PLAIN 0", src) and config.DUAL_PLAIN == 0
     assert re.search(r"#define PIADMM_DUAL_PI 1", src) and config.DUAL_PI == 1
     assert np.dtype(np.float64).itemsize == 8
+
+
+REFUSED = [
+    ("u_max", 0.0), ("u_max", -0.1), ("u_max", float("inf")), ("u_max", float("nan")),
+    ("du_max", 0.0), ("du_max", float("inf")), ("du_max", float("nan")),
+    ("dis_thres", 0.0), ("dis_thres", -2.0), ("dis_thres", float("inf")), ("dis_thres", float("nan")),
+    ("eps_pri", float("inf")), ("eps_pri", float("nan")), ("eps_dual", float("-inf")), ("eps_dual", float("nan")),
+    ("windup_sat", 0.0), ("windup_sat", -30.0), ("windup_sat", float("nan")),
+    ("round_decimals", -2), ("round_decimals", 13),
+]
+
+
+def _create(cfg):
+    lib = _lib.load()
+    c = _lib.to_c(cfg, n_agents=2)
+    h = ctypes.c_void_p()
+    rc = lib.piadmm_create(ctypes.byref(c), ctypes.byref(h))
+    msg = lib.piadmm_last_error(None).decode()
+    if h.value:
+        lib.piadmm_destroy(h)
+    return rc, msg
+
+
+@pytest.mark.parametrize("field,value", REFUSED, ids=[f"{f}={v}" for f, v in REFUSED])
+def test_create_refuses_configurations_without_a_valid_solve(field, value):
+    """An empty or unbounded steering box, a safety distance <= 0, a saturation at +-0 (windup on),
+    non-finite stop tolerances, a rounding below "off": PIADMM_E_ARG, judged before any device call
+    (so with or without a GPU), naming the field."""
+    rc, msg = _create(config.matlab_pi(H=8, **{field: value}))      # matlab_pi: windup = 1
+    assert rc == _lib.E_ARG, (rc, msg)
+    assert field in msg, msg
+
+
+def test_create_accepts_the_off_preset_values_the_suite_uses():
+    """The refusals do not reach valid configurations: every case of tests/_offpreset_cases.py, a
+    non-positive windup_sat with the saturation off, and round_decimals -1 pass check_cfg (without
+    a GPU the call then fails with PIADMM_E_NODEV, never PIADMM_E_ARG)."""
+    import _offpreset_cases as C
+    ok = (0, _lib.E_NODEV)
+    for cfg in [c.cfg for c in C.CASES] + [config.matlab_pi(H=8, windup=0, windup_sat=0.0),
+                                           config.casadi_default(H=8, round_decimals=-1)]:
+        rc, msg = _create(cfg)
+        assert rc in ok, (rc, msg, cfg)

@@ -12,12 +12,11 @@ propagated state after ``piadmm_step_finish`` must equal the oracle's step recor
 import numpy as np
 import pytest
 
+from _offpreset_cases import TOL, step_by_iterations      # the host-stepping helper, shared
 from oracle import piadmm_oracle as O
 from piadmm import _lib, config, scenario
 
 pytestmark = pytest.mark.gpu
-
-TOL = 1e-8
 
 
 @pytest.fixture(scope="module")
@@ -26,32 +25,6 @@ def Solver():
     if device_count() < 1:
         pytest.fail("no HIP device visible: the GPU tests need an MI355X")
     return PI_ADMM_MI355X
-
-
-def close(a, b, what, it, scale=1.0):
-    np.testing.assert_allclose(a, b, rtol=TOL, atol=TOL * scale, err_msg=f"{what} after outer iteration {it}")
-
-
-def step_by_iterations(s, orc, t, check_sd=True):
-    """Host-step MPC step t on the GPU and compare every iteration with the oracle's."""
-    states = []
-    rec = orc.mpc_step(on_iter=lambda it, st: states.append(st))
-    for it, ost in enumerate(states):
-        stop = s.outer_iter(it, t)
-        g = s.state()
-        close(g["pos_old"], ost["pos_old"], "pos_old", it)
-        close(g["hat"], ost["hat"], "hat", it)
-        close(g["lam"], ost["lam"], "lam", it)
-        if check_sd:
-            close(g["S"], ost["S"], "S", it)
-            # D = lam_sat - lam_raw with lam_raw = S + K_P e: a difference of O(|S|) quantities, so
-            # its absolute error scales with |S| (the integral grows over the step's iterations)
-            close(g["D"], ost["D"], "D", it, scale=max(1.0, float(np.max(np.abs(ost["S"])))))
-        assert stop == ost["stop"], f"stop flag at outer iteration {it}"
-    xt, u = s.step_finish()
-    np.testing.assert_allclose(xt, rec.xt, rtol=TOL, atol=TOL)
-    np.testing.assert_allclose(u, rec.u, rtol=TOL, atol=TOL)
-    return len(states), rec
 
 
 @pytest.mark.parametrize("preset,term_global,fixed", [("matlab_pi", 0, 0), ("matlab_pi", 1, 0), ("matlab_pi", 1, 1),
