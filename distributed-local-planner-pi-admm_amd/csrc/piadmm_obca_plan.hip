@@ -15,9 +15,18 @@
 //
 // Layout: one wavefront per item (a local record, a scenario), PW waves per workgroup; waves
 // never cooperate, and a wave past the end of its list exits whole at the top.
+//
+// Parameters and references are per scenario: the glue kernels read scenario s's parameter row
+// at tab + s * tab_stride (PIADMM_OBCA_FLEET_PAR doubles, include/piadmm.h) and its reference at
+// ref + s * ref_stride.  A plan opened by piadmm_obca_plan_begin is one row and one reference with
+// both strides 0; piadmm_obca_fleet_begin uploads n of each.  The scenario index is made provably
+// wave-uniform (first-lane broadcast), so what the whole wave needs of the row (conv_thres,
+// min_dis, max_admm_iter) is a uniform load; the record parameters are loaded by the few lanes
+// that store them.
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <string>
@@ -46,24 +55,33 @@ constexpr int NCTRL = 28, NX = 80;
 constexpr double LENGTH = 3.5, WIDTH = 2.0;
 constexpr double AVG_DELAY = 0.05, VAR_DELAY = 0.025;
 
-struct Par {
-  double rho, min_dis, conv_thres, max_x, max_y, r, q, x_bound, mu_max, g_max, sigd;
-  int max_admm_iter, round_decimals, start, update_lamb_ij, max_sqp_iter, n_ref;
-};
+// a parameter row (include/piadmm.h): the integers are stored as doubles, as the records do
+constexpr int TAB = PIADMM_OBCA_FLEET_PAR;
+constexpr int T_RHO = 0, T_MIN_DIS = 1, T_CONV = 2, T_MAX_X = 3, T_MAX_Y = 4, T_R = 5, T_Q = 6, T_XB = 7,
+              T_MU = 8, T_G = 9, T_ADMM = 10, T_SQP = 11, T_ROUND = 12, T_START = 13;
+// the row entry behind parameter j of a local / an edge record, one hex digit each (prob, local 6
+// and edge 2, comes from prob[])
+constexpr unsigned LOCAL_PAR_ROW = 0xB0654310u;            // rho, min_dis, max_x, max_y, r, q, -, max_sqp_iter
+constexpr unsigned long long EDGE_PAR_ROW = 0x987DCB010ull;  // rho, min_dis, -, max_sqp_iter, round_decimals, start,
+                                                             // x_bound, mu_max, g_max
+static_assert(T_START < TAB, "row layout");
 
 // Record 2k + v = vehicle v of scenario active[k]: what local_record (piadmm/obca.py) packs.
 __global__ void __launch_bounds__(64 * PW) k_plan_pack_local(const int* __restrict__ active, int n_act,
                                                              const double* __restrict__ bar,
                                                              const int* __restrict__ prob,
-                                                             const double* __restrict__ ref, int t_step, Par P,
+                                                             const double* __restrict__ ref, int ref_stride,
+                                                             int n_ref, int t_step,
+                                                             const double* __restrict__ tab, int tab_stride,
                                                              double* __restrict__ recs) {
   const int lane = threadIdx.x & 63;
-  const int r = blockIdx.x * PW + (threadIdx.x >> 6);
+  const int r = blockIdx.x * PW + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (r >= 2 * n_act) return;
   const int k = r >> 1, v = r & 1, o = 1 - v;
-  const int s = active[k];
+  const int s = __builtin_amdgcn_readfirstlane(active[k]);
   const double* B = bar + (size_t)s * STATE;
-  const double* rf = ref + ((size_t)v * P.n_ref + t_step) * 5;
+  const double* T = tab + (size_t)s * tab_stride;
+  const double* rf = ref + (size_t)s * ref_stride + ((size_t)v * n_ref + t_step) * 5;
   double* rec = recs + (size_t)r * REC;
   for (int i = lane; i < REC; i += 64) {
     double val = 0.0;
@@ -76,8 +94,7 @@ __global__ void __launch_bounds__(64 * PW) k_plan_pack_local(const int* __restri
     else if (i < R_PAR) val = B[S_ZB + v * 63 + (i - R_ZB)];
     else if (i < R_PAR + 8) {
       const int j = i - R_PAR;
-      val = j == 0 ? P.rho : j == 1 ? P.min_dis : j == 2 ? P.max_x : j == 3 ? P.max_y : j == 4 ? P.r :
-            j == 5 ? P.q : j == 6 ? (double)prob[s] : (double)P.max_sqp_iter;
+      val = j == 6 ? (double)prob[s] : T[(LOCAL_PAR_ROW >> (4 * j)) & 15u];
     }
     rec[i] = val;
   }
@@ -111,14 +128,18 @@ __device__ __forceinline__ void halfspaces(const double* st, int prob, double si
 // One wave per active scenario; lane < 14 owns the (vehicle, slot) item lane = v * 7 + t.
 __global__ void __launch_bounds__(64 * PW) k_plan_exchange(const int* __restrict__ active, int n_act,
                                                            double* __restrict__ bar, const int* __restrict__ prob,
-                                                           const double* __restrict__ lout, Par P,
+                                                           const double* __restrict__ lout,
+                                                           const double* __restrict__ tab, int tab_stride,
+                                                           double sigd, int update_lamb_ij,
                                                            double* __restrict__ ctrl, double* __restrict__ X,
                                                            int* __restrict__ conv, double* __restrict__ erecs) {
   const int lane = threadIdx.x & 63;
-  const int k = blockIdx.x * PW + (threadIdx.x >> 6);
+  const int k = blockIdx.x * PW + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (k >= n_act) return;
-  const int s = active[k];
+  const int s = __builtin_amdgcn_readfirstlane(active[k]);
   const int pr = prob[s];
+  const double* T = tab + (size_t)s * tab_stride;
+  const double conv_thres = T[T_CONV], min_dis = T[T_MIN_DIS];
   double* B = bar + (size_t)s * STATE;
   double* E = erecs + (size_t)k * EREC;
   const double* o2 = lout + (size_t)(2 * k) * OUT;           // the pair's two local outputs
@@ -128,9 +149,9 @@ __global__ void __launch_bounds__(64 * PW) k_plan_exchange(const int* __restrict
     const double* ov = o2 + (size_t)v * OUT;
     const double* st = ov + O_X + (t + 1) * 5;
     double A[4][2], b[4], l[4];
-    halfspaces(st, pr, P.sigd, A, b);
+    halfspaces(st, pr, sigd, A, b);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) l[i] = P.update_lamb_ij ? ov[O_LAM + t * 4 + i] : B[S_LIJ + vt * 4 + i];
+    for (int i = 0; i < 4; ++i) l[i] = update_lamb_ij ? ov[O_LAM + t * 4 + i] : B[S_LIJ + vt * 4 + i];
 #pragma unroll
     for (int j = 0; j < 5; ++j) { B[S_LX + vt * 5 + j] = st[j]; E[E_LX + vt * 5 + j] = st[j]; }
 #pragma unroll
@@ -138,7 +159,7 @@ __global__ void __launch_bounds__(64 * PW) k_plan_exchange(const int* __restrict
       B[S_A + vt * 8 + 2 * i] = A[i][0];
       B[S_A + vt * 8 + 2 * i + 1] = A[i][1];
       B[S_B + vt * 4 + i] = b[i];
-      if (P.update_lamb_ij) B[S_LIJ + vt * 4 + i] = l[i];
+      if (update_lamb_ij) B[S_LIJ + vt * 4 + i] = l[i];
       E[E_LIJ + vt * 4 + i] = l[i];
       pe0 += A[i][0] * l[i];
       pe1 += A[i][1] * l[i];
@@ -149,9 +170,7 @@ __global__ void __launch_bounds__(64 * PW) k_plan_exchange(const int* __restrict
   for (int i = lane; i < 126; i += 64) E[E_LB + i] = B[S_LB + i];
   if (lane < EREC - E_PAR) {
     const int j = lane;
-    E[E_PAR + j] = j == 0 ? P.rho : j == 1 ? P.min_dis : j == 2 ? (double)pr : j == 3 ? (double)P.max_sqp_iter :
-                   j == 4 ? (double)P.round_decimals : j == 5 ? (double)P.start : j == 6 ? P.x_bound :
-                   j == 7 ? P.mu_max : j == 8 ? P.g_max : 0.0;
+    E[E_PAR + j] = j == 2 ? (double)pr : j < 9 ? T[(int)(EDGE_PAR_ROW >> (4 * j)) & 15] : 0.0;
   }
   // bar_ctrl = [U[:,0], U[:,1]] per vehicle, and X
   if (lane < NCTRL) {
@@ -163,7 +182,7 @@ __global__ void __launch_bounds__(64 * PW) k_plan_exchange(const int* __restrict
   const double e0 = pe0 + __shfl(pe0, (lane + NT) & 63, 64);
   const double e1 = pe1 + __shfl(pe1, (lane + NT) & 63, 64);
   const double ueq = -pb - __shfl(pb, (lane + NT) & 63, 64);
-  const bool ok = lane >= NT || (fabs(e0) <= P.conv_thres && fabs(e1) <= P.conv_thres && ueq >= P.min_dis);
+  const bool ok = lane >= NT || (fabs(e0) <= conv_thres && fabs(e1) <= conv_thres && ueq >= min_dis);
   const int all_ok = __all(ok);
   if (lane == 0) conv[s] = all_ok ? 1 : 0;
 }
@@ -175,13 +194,15 @@ __global__ void __launch_bounds__(64 * PW) k_plan_residual(const int* __restrict
                                                            const double* __restrict__ eout, const int* __restrict__ list,
                                                            const int* __restrict__ eist,
                                                            const double* __restrict__ pth, const double* __restrict__ dth,
-                                                           Par P, double* __restrict__ primal_o, double* __restrict__ dual_o,
+                                                           const double* __restrict__ tab, int tab_stride,
+                                                           double* __restrict__ primal_o, double* __restrict__ dual_o,
                                                            int* __restrict__ stop_o, int* __restrict__ iters,
                                                            int* __restrict__ mask, int* __restrict__ keep) {
   const int lane = threadIdx.x & 63;
-  const int k = blockIdx.x * PW + (threadIdx.x >> 6);
+  const int k = blockIdx.x * PW + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (k >= n_act) return;
-  const int s = active[k];
+  const int s = __builtin_amdgcn_readfirstlane(active[k]);
+  const int max_admm_iter = (int)tab[(size_t)s * tab_stride + T_ADMM];
   double* B = bar + (size_t)s * STATE;
   double* Bp = barp + (size_t)s * STATE;
   const double* eo = eout + (size_t)k * EOUT;
@@ -191,7 +212,7 @@ __global__ void __launch_bounds__(64 * PW) k_plan_residual(const int* __restrict
   const double d = lane < NCTRL ? fabs(ctrl[(size_t)s * NCTRL + lane] - ctrlp[(size_t)s * NCTRL + lane]) : 0.0;
   double primal = 0.0;
   for (int j = 0; j < NCTRL; ++j) primal = primal + __shfl(d, j, 64);
-  const bool stop = (primal <= pth[s] && dual <= dth[s]) || i_iter > P.max_admm_iter;
+  const bool stop = (primal <= pth[s] && dual <= dth[s]) || i_iter > max_admm_iter;
   // every status of the iterate, as bits
   int lm = lane < 2 ? 1 << (list[(size_t)(2 * k + lane) * 3] & 31) : 0;
   int em = lane < NT ? 1 << (eist[((size_t)k * NT + lane) * 3] & 31) : 0;
@@ -299,11 +320,14 @@ __global__ void __launch_bounds__(64) k_plan_shift(int n, double* __restrict__ b
 // ---------------------------------------------------------------------------------------------
 struct piadmm_obca_plan_s {
   piadmm_obca_plan_cfg_t cfg{};
-  obca_plan::Par par{};
   bool open = false;
   int n = 0, t_step = 0, i_iter = 0, n_act = 0, n_last = 0, cur = 0;
+  // the parameter rows and the references: rows = 1 with stride 0 (piadmm_obca_plan_begin) or
+  // rows = n (piadmm_obca_fleet_begin); max_iter_all = the largest max_admm_iter of the rows
+  int tab_rows = 0, ref_rows = 0, tab_stride = 0, ref_stride = 0, max_iter_all = 0;
+  double sigd = 0.0;
   double *bar = nullptr, *barp = nullptr, *ctrl = nullptr, *ctrlp = nullptr, *X = nullptr, *primal = nullptr,
-         *dual = nullptr, *pth = nullptr, *dth = nullptr, *ref = nullptr, *lamb = nullptr;
+         *dual = nullptr, *pth = nullptr, *dth = nullptr, *ref = nullptr, *lamb = nullptr, *tab = nullptr;
   int *iters = nullptr, *stop = nullptr, *conv = nullptr, *prob = nullptr, *act[2] = {nullptr, nullptr},
       *keep = nullptr, *count = nullptr, *mask = nullptr;
   int* h_count = nullptr;        // pinned: the 4 bytes read back per iterate
@@ -324,33 +348,55 @@ int pfail(piadmm_obca_t h, int code, const std::string& msg) {
 
 void plan_free_buffers(piadmm_obca_plan_s* p) {
   void* d[] = {p->bar, p->barp, p->ctrl, p->ctrlp, p->X, p->primal, p->dual, p->pth, p->dth, p->ref, p->lamb,
-               p->iters, p->stop, p->conv, p->prob, p->act[0], p->act[1], p->keep, p->count, p->mask};
+               p->tab, p->iters, p->stop, p->conv, p->prob, p->act[0], p->act[1], p->keep, p->count, p->mask};
   for (void* q : d)
     if (q) (void)hipFree(q);
   if (p->h_count) (void)hipHostFree(p->h_count);
   p->bar = p->barp = p->ctrl = p->ctrlp = p->X = p->primal = p->dual = p->pth = p->dth = p->ref = p->lamb = nullptr;
+  p->tab = nullptr;
   p->iters = p->stop = p->conv = p->prob = p->act[0] = p->act[1] = p->keep = p->count = p->mask = nullptr;
   p->h_count = nullptr;
   p->open = false;
 }
 
-int plan_check(piadmm_obca_t h, const piadmm_obca_plan_cfg_t& c, const int32_t* prob) {
-  // the ranges check_recs (csrc/piadmm_obca.hip) and edge_check (csrc/piadmm_obca_edge.hip) enforce
-  // per record, on the configuration every record of the plan is packed from
-  if (!(c.rho > 0.0) || !(c.r > 0.0) || !(c.q > 0.0) || !(c.max_x > 0.0) || !(c.max_y > 0.0) ||
-      !(c.max_sqp_iter >= 1 && c.max_sqp_iter <= 1000) || (c.start != 0 && c.start != 1) ||
-      !(c.round_decimals >= -1 && c.round_decimals <= 15) || !(c.x_bound > 0.0) || !(c.mu_max > 0.0) ||
-      (c.update_lamb_ij != 0 && c.update_lamb_ij != 1))
-    return pfail(h, PIADMM_E_ARG, "obca_plan_begin: bad parameters (rho, r, q, max_x, max_y, x_bound, mu_max > 0; "
-                 "1 <= max_sqp_iter <= 1000; start, update_lamb_ij 0/1; -1 <= round_decimals <= 15)");
-  if (c.n_scenarios < 1) return pfail(h, PIADMM_E_ARG, "obca_plan_begin: n_scenarios >= 1");
-  if (c.n_scenarios > (1 << 20)) return pfail(h, PIADMM_E_ARG, "obca_plan_begin: n_scenarios <= 2^20");
-  if (c.max_admm_iter < 0) return pfail(h, PIADMM_E_ARG, "obca_plan_begin: max_admm_iter >= 0");
+// the parameter row of a configuration (the row a plan without a table runs every scenario on)
+void row_of_cfg(const piadmm_obca_plan_cfg_t& c, double* row) {
+  using namespace obca_plan;
+  for (int i = 0; i < TAB; ++i) row[i] = 0.0;
+  row[T_RHO] = c.rho;  row[T_MIN_DIS] = c.min_dis;  row[T_CONV] = c.conv_thres;
+  row[T_MAX_X] = c.max_x;  row[T_MAX_Y] = c.max_y;  row[T_R] = c.r;  row[T_Q] = c.q;
+  row[T_XB] = c.x_bound;  row[T_MU] = c.mu_max;  row[T_G] = c.g_max;
+  row[T_ADMM] = (double)c.max_admm_iter;  row[T_SQP] = (double)c.max_sqp_iter;
+  row[T_ROUND] = (double)c.round_decimals;  row[T_START] = (double)c.start;
+}
+
+// One parameter row: the ranges check_recs (csrc/piadmm_obca.hip) and edge_check
+// (csrc/piadmm_obca_edge.hip) enforce per record, on the row those records are packed from, and the
+// integers integral.  nullptr when the row is good, else what is wrong with it.
+const char* row_check(const double* row) {
+  using namespace obca_plan;
+  auto integral = [](double v, double lo, double hi) { return v >= lo && v <= hi && v == std::floor(v); };
+  if (!(row[T_RHO] > 0.0) || !(row[T_R] > 0.0) || !(row[T_Q] > 0.0) || !(row[T_MAX_X] > 0.0) ||
+      !(row[T_MAX_Y] > 0.0) || !(row[T_XB] > 0.0) || !(row[T_MU] > 0.0))
+    return "bad parameters (rho, r, q, max_x, max_y, x_bound, mu_max > 0)";
+  if (!integral(row[T_SQP], 1.0, 1000.0)) return "1 <= max_sqp_iter <= 1000, an integer";
+  if (!integral(row[T_START], 0.0, 1.0)) return "start 0 or 1";
+  if (!integral(row[T_ROUND], -1.0, 15.0)) return "-1 <= round_decimals <= 15, an integer";
+  if (!integral(row[T_ADMM], 0.0, 1073741824.0)) return "max_admm_iter >= 0 (at most 2^30), an integer";
+  return nullptr;
+}
+
+// what every scenario of a plan shares, and prob
+int shared_check(piadmm_obca_t h, const piadmm_obca_plan_cfg_t& c, const int32_t* prob, const std::string& who) {
+  if (c.update_lamb_ij != 0 && c.update_lamb_ij != 1) return pfail(h, PIADMM_E_ARG, who + ": update_lamb_ij 0 or 1");
+  if (c.n_scenarios < 1) return pfail(h, PIADMM_E_ARG, who + ": n_scenarios >= 1");
+  if (c.n_scenarios > (1 << 20)) return pfail(h, PIADMM_E_ARG, who + ": n_scenarios <= 2^20");
   if (c.t_step0 < 0 || c.n_ref < 8 || c.t_step0 > c.n_ref - 8)
-    return pfail(h, PIADMM_E_ARG, "obca_plan_begin: t_step0 >= 0 and t_step0 + 8 <= n_ref");
+    return pfail(h, PIADMM_E_ARG, who + ": t_step0 >= 0 and t_step0 + 8 <= n_ref");
+  if (c.n_ref > (1 << 20)) return pfail(h, PIADMM_E_ARG, who + ": n_ref <= 2^20");
   for (int k = 0; k < c.n_scenarios; ++k)
     if (prob[k] != 0 && prob[k] != 1)
-      return pfail(h, PIADMM_E_ARG, "obca_plan_begin: prob[" + std::to_string(k) + "] must be 0 or 1");
+      return pfail(h, PIADMM_E_ARG, who + ": prob[" + std::to_string(k) + "] must be 0 or 1");
   return 0;
 }
 
@@ -382,18 +428,14 @@ void piadmm_obca_plan_free(piadmm_obca_t h) {
   h->plan = nullptr;
 }
 
-extern "C" {
-
-int32_t piadmm_obca_plan_cfg_size(void) { return (int32_t)sizeof(piadmm_obca_plan_cfg_t); }
-
-int32_t piadmm_obca_plan_begin(piadmm_obca_t h, const piadmm_obca_plan_cfg_t* cfg, const int32_t* prob,
-                               const double* primal_thres, const double* dual_thres, const double* ref_traj,
-                               const double* state) {
+namespace {
+// Opens the plan both entry points share: `tab` holds tab_rows parameter rows (1: every scenario
+// reads row 0, stride 0; n: one each), ref_traj ref_rows references of 2 x n_ref x 5 likewise.
+// Everything was checked before; this is the first device call.
+int plan_open(piadmm_obca_t h, const piadmm_obca_plan_cfg_t* cfg, const int32_t* prob, const double* primal_thres,
+              const double* dual_thres, const double* ref_traj, int ref_rows, const std::vector<double>& tab,
+              int tab_rows, const double* state) {
   using namespace obca_plan;
-  if (!h) return PIADMM_E_ARG;
-  if (!cfg || !prob || !primal_thres || !dual_thres || !ref_traj || !state)
-    return pfail(h, PIADMM_E_ARG, "obca_plan_begin: null argument");
-  if (int rc = plan_check(h, *cfg, prob)) return rc;
   const int n = cfg->n_scenarios;
   PHIP(h, hipSetDevice(h->device));
   PHIP(h, hipStreamSynchronize(h->stream));
@@ -411,17 +453,23 @@ int32_t piadmm_obca_plan_begin(piadmm_obca_t h, const piadmm_obca_plan_cfg_t* cf
   PHIP(h, hipMemcpy(h->d_order, ident.data(), (size_t)2 * n * sizeof(int), hipMemcpyHostToDevice));
 
   p->cfg = *cfg;
-  p->par = Par{cfg->rho, cfg->min_dis, cfg->conv_thres, cfg->max_x, cfg->max_y, cfg->r, cfg->q, cfg->x_bound,
-               cfg->mu_max, cfg->g_max, std::sqrt(0.95 / (1.0 - 0.95)),
-               cfg->max_admm_iter, cfg->round_decimals, cfg->start, cfg->update_lamb_ij, cfg->max_sqp_iter, cfg->n_ref};
+  p->sigd = std::sqrt(0.95 / (1.0 - 0.95));
   p->n = n;
+  const size_t ref_one = (size_t)2 * cfg->n_ref * 5;
+  p->tab_rows = tab_rows;
+  p->ref_rows = ref_rows;
+  p->tab_stride = tab_rows > 1 ? TAB : 0;
+  p->ref_stride = ref_rows > 1 ? (int)ref_one : 0;
+  p->max_iter_all = 0;
+  for (int k = 0; k < tab_rows; ++k) p->max_iter_all = std::max(p->max_iter_all, (int)tab[(size_t)k * TAB + T_ADMM]);
   const size_t N = (size_t)n;
   int rc = 0;
   if ((rc = dalloc(h, &p->bar, N * STATE, false)) || (rc = dalloc(h, &p->barp, N * STATE, false)) ||
       (rc = dalloc(h, &p->ctrl, N * NCTRL, true)) || (rc = dalloc(h, &p->ctrlp, N * NCTRL, true)) ||
       (rc = dalloc(h, &p->X, N * NX, true)) || (rc = dalloc(h, &p->primal, N, true)) ||
       (rc = dalloc(h, &p->dual, N, true)) || (rc = dalloc(h, &p->pth, N, false)) ||
-      (rc = dalloc(h, &p->dth, N, false)) || (rc = dalloc(h, &p->ref, (size_t)2 * cfg->n_ref * 5, false)) ||
+      (rc = dalloc(h, &p->dth, N, false)) || (rc = dalloc(h, &p->ref, ref_one * ref_rows, false)) ||
+      (rc = dalloc(h, &p->tab, (size_t)tab_rows * TAB, false)) ||
       (rc = dalloc(h, &p->lamb, N * 126, true)) || (rc = dalloc(h, &p->iters, N, true)) ||
       (rc = dalloc(h, &p->stop, N, true)) || (rc = dalloc(h, &p->conv, N, true)) ||
       (rc = dalloc(h, &p->prob, N, false)) || (rc = dalloc(h, &p->act[0], N, false)) ||
@@ -435,7 +483,8 @@ int32_t piadmm_obca_plan_begin(piadmm_obca_t h, const piadmm_obca_plan_cfg_t* cf
   PHIP(h, hipMemcpy(p->barp, state, N * STATE * sizeof(double), hipMemcpyHostToDevice));
   PHIP(h, hipMemcpy(p->pth, primal_thres, N * sizeof(double), hipMemcpyHostToDevice));
   PHIP(h, hipMemcpy(p->dth, dual_thres, N * sizeof(double), hipMemcpyHostToDevice));
-  PHIP(h, hipMemcpy(p->ref, ref_traj, (size_t)2 * cfg->n_ref * 5 * sizeof(double), hipMemcpyHostToDevice));
+  PHIP(h, hipMemcpy(p->ref, ref_traj, ref_one * ref_rows * sizeof(double), hipMemcpyHostToDevice));
+  PHIP(h, hipMemcpy(p->tab, tab.data(), (size_t)tab_rows * TAB * sizeof(double), hipMemcpyHostToDevice));
   PHIP(h, hipMemcpy(p->prob, prob, N * sizeof(int), hipMemcpyHostToDevice));
   PHIP(h, hipMemcpy(p->act[0], ident.data(), N * sizeof(int), hipMemcpyHostToDevice));
   p->t_step = cfg->t_step0;
@@ -445,6 +494,48 @@ int32_t piadmm_obca_plan_begin(piadmm_obca_t h, const piadmm_obca_plan_cfg_t* cf
   p->cur = 0;
   p->open = true;
   return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int32_t piadmm_obca_plan_cfg_size(void) { return (int32_t)sizeof(piadmm_obca_plan_cfg_t); }
+
+int32_t piadmm_obca_plan_begin(piadmm_obca_t h, const piadmm_obca_plan_cfg_t* cfg, const int32_t* prob,
+                               const double* primal_thres, const double* dual_thres, const double* ref_traj,
+                               const double* state) {
+  if (!h) return PIADMM_E_ARG;
+  if (!cfg || !prob || !primal_thres || !dual_thres || !ref_traj || !state)
+    return pfail(h, PIADMM_E_ARG, "obca_plan_begin: null argument");
+  std::vector<double> row(obca_plan::TAB);
+  row_of_cfg(*cfg, row.data());
+  if (const char* why = row_check(row.data())) return pfail(h, PIADMM_E_ARG, std::string("obca_plan_begin: ") + why);
+  if (int rc = shared_check(h, *cfg, prob, "obca_plan_begin")) return rc;
+  return plan_open(h, cfg, prob, primal_thres, dual_thres, ref_traj, 1, row, 1, state);
+}
+
+int32_t piadmm_obca_fleet_begin(piadmm_obca_t h, const piadmm_obca_plan_cfg_t* cfg, const int32_t* prob,
+                                const double* primal_thres, const double* dual_thres, const double* ref_traj,
+                                const double* par, const double* state) {
+  using obca_plan::TAB;
+  if (!h) return PIADMM_E_ARG;
+  if (!cfg || !prob || !primal_thres || !dual_thres || !ref_traj || !state)
+    return pfail(h, PIADMM_E_ARG, "obca_fleet_begin: null argument");
+  if (int rc = shared_check(h, *cfg, prob, "obca_fleet_begin")) return rc;
+  const int n = cfg->n_scenarios;
+  // one row per scenario either way: without a table every row is the configuration's
+  std::vector<double> tab((size_t)n * TAB);
+  for (int k = 0; k < n; ++k) {
+    double* row = tab.data() + (size_t)k * TAB;
+    if (par) {
+      for (int i = 0; i < TAB; ++i) row[i] = par[(size_t)k * TAB + i];
+    } else {
+      row_of_cfg(*cfg, row);
+    }
+    if (const char* why = row_check(row))
+      return pfail(h, PIADMM_E_ARG, "obca_fleet_begin: row " + std::to_string(k) + ": " + why);
+  }
+  return plan_open(h, cfg, prob, primal_thres, dual_thres, ref_traj, n, tab, n, state);
 }
 
 int32_t piadmm_obca_plan_iterate(piadmm_obca_t h, int32_t* n_active_after) {
@@ -466,17 +557,18 @@ int32_t piadmm_obca_plan_iterate(piadmm_obca_t h, int32_t* n_active_after) {
   }
   const int i_iter = p->i_iter + 1;
   hipLaunchKernelGGL(k_plan_pack_local, dim3(blocks_for(2 * m)), dim3(64 * PW), 0, st, act, m, p->bar, p->prob, p->ref,
-                     p->t_step, p->par, h->d_rec);
+                     p->ref_stride, p->cfg.n_ref, p->t_step, p->tab, p->tab_stride, h->d_rec);
   PHIP(h, hipGetLastError());
   if (int rc = piadmm_obca_local_launch(h, 2 * m)) return rc;
   // the edge output starts from zeros, as in piadmm_obca_edge_solve
   PHIP(h, hipMemsetAsync(h->e_out, 0, (size_t)m * EOUT * sizeof(double), st));
   hipLaunchKernelGGL(k_plan_exchange, dim3(blocks_for(m)), dim3(64 * PW), 0, st, act, m, p->bar, p->prob, h->d_out,
-                     p->par, p->ctrl, p->X, p->conv, h->e_rec);
+                     p->tab, p->tab_stride, p->sigd, p->cfg.update_lamb_ij, p->ctrl, p->X, p->conv, h->e_rec);
   PHIP(h, hipGetLastError());
   if (int rc = piadmm_obca_edge_launch(h, m)) return rc;
   hipLaunchKernelGGL(k_plan_residual, dim3(blocks_for(m)), dim3(64 * PW), 0, st, act, m, i_iter, p->bar, p->barp,
-                     p->ctrl, p->ctrlp, h->e_out, h->d_ist, h->e_ist, p->pth, p->dth, p->par, p->primal, p->dual,
+                     p->ctrl, p->ctrlp, h->e_out, h->d_ist, h->e_ist, p->pth, p->dth, p->tab, p->tab_stride, p->primal,
+                     p->dual,
                      p->stop, p->iters, p->mask, p->keep);
   PHIP(h, hipGetLastError());
   hipLaunchKernelGGL(k_plan_compact, dim3(1), dim3(CT), 0, st, act, p->keep, m, nxt, p->count);
@@ -516,8 +608,8 @@ int32_t piadmm_obca_plan_step(piadmm_obca_t h, int32_t* iters_out) {
   piadmm_obca_plan_s* p = nullptr;
   if (int rc = open_plan(h, &p, "obca_plan_step")) return rc;
   if (p->t_step + 8 > p->cfg.n_ref) return pfail(h, PIADMM_E_STATE, "obca_plan_step: reference exhausted");
-  // i_iter > max_admm_iter stops every scenario: at most max_admm_iter + 1 iterates in a step
-  while (p->n_act > 0 && p->i_iter <= p->cfg.max_admm_iter) {
+  // i_iter > max_admm_iter stops a scenario: at most the largest max_admm_iter + 1 iterates in a step
+  while (p->n_act > 0 && p->i_iter <= p->max_iter_all) {
     if (int rc = piadmm_obca_plan_iterate(h, nullptr)) return rc;
   }
   if (p->n_act > 0) return pfail(h, PIADMM_E_STATE, "obca_plan_step: scenarios active after max_admm_iter + 1 iterates");
@@ -556,6 +648,8 @@ int32_t piadmm_obca_plan_get(piadmm_obca_t h, int32_t what, void* out, int64_t b
     case PIADMM_OBCA_PLAN_GET_EDGE_IST: src = h->e_ist; want = m * NT * 3 * I; break;
     case PIADMM_OBCA_PLAN_GET_LAMBDA: src = p->lamb; want = n * 126 * D; break;
     case PIADMM_OBCA_PLAN_GET_STATUS_MASK: src = p->mask; want = 2 * n * I; break;
+    case PIADMM_OBCA_PLAN_GET_REF: src = p->ref; want = (int64_t)p->ref_rows * 2 * p->cfg.n_ref * 5 * D; break;
+    case PIADMM_OBCA_PLAN_GET_PAR: src = p->tab; want = (int64_t)p->tab_rows * TAB * D; break;
     case PIADMM_OBCA_PLAN_GET_T_STEP: want = I; break;
     case PIADMM_OBCA_PLAN_GET_COUNTS: want = 3 * I; break;
     default: return pfail(h, PIADMM_E_ARG, "obca_plan_get: unknown item " + std::to_string(what));

@@ -117,7 +117,11 @@ SYMBOLS = [
     ("piadmm_obca_plan_step", c_i32, [_H, _ip]),
     ("piadmm_obca_plan_get", c_i32, [_H, c_i32, ctypes.c_void_p, ctypes.c_int64]),
     ("piadmm_obca_plan_end", c_i32, [_H]),
+    ("piadmm_obca_fleet_begin", c_i32, [_H, _P(ObcaPlanCfgC), _ip, _dp, _dp, _dp, _dp, _dp]),
 ]
+
+# PIADMM_OBCA_FLEET_PAR: doubles per parameter row of piadmm_obca_fleet_begin
+FLEET_PAR = 16
 
 # error codes of include/piadmm.h the OBCA bindings name
 E_ARG, E_HIP, E_STATE, E_NODEV = -1, -2, -3, -4

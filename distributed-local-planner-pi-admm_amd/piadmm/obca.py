@@ -18,6 +18,7 @@ Output (float64, ``OUT`` per problem): X 8x5 | U 7x2 | Lambda 7x4 | y_a 7 | y_b 
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 import math
 
 import numpy as np
@@ -36,11 +37,35 @@ DT, T_PERIOD = 0.1, 5.0
 AVG_DELAY, VAR_DELAY, DELAY_PROB = 0.05, 0.025, 0.95
 
 
-def ref_traj_gen():
+@dataclasses.dataclass(frozen=True)
+class OvertakeSpec:
+    """One overtaking manoeuvre: vehicle 0 at v0 m/s from x = 0, vehicle 1 at v1 m/s from x = gap;
+    vehicle 0 changes to y = +lane between t_out and t_out + ramp (s) and back between t_back and
+    t_back + ramp.  The defaults are the reference's scenario (veh_config.py:30-47) and the
+    manoeuvre `executed_path` always drove.  v0 above 20 (the vehicle's max_v) makes the local NLP
+    infeasible."""
+    v0: float = 20.0
+    v1: float = 10.0
+    gap: float = 20.0
+    lane: float = 4.0
+    t_out: float = 0.2
+    t_back: float = 3.0
+    ramp: float = 0.6
+
+
+def _spec(spec):
+    """`spec` with float fields; None is the default manoeuvre."""
+    if spec is None:
+        return OvertakeSpec()
+    return OvertakeSpec(*(float(getattr(spec, f.name)) for f in dataclasses.fields(OvertakeSpec)))
+
+
+def ref_traj_gen(spec=None):
     """The overtaking scenario's references (veh_config.py:30-47)."""
+    sp = _spec(spec)
     n = int(T_PERIOD / DT) + 1
     out = []
-    for v, x0 in ((20.0, 0.0), (10.0, 20.0)):
+    for v, x0 in ((sp.v0, 0.0), (sp.v1, sp.gap)):
         x = np.linspace(x0, x0 + v * T_PERIOD, n)
         out.append(np.vstack((x, np.zeros_like(x), v * np.ones_like(x), np.zeros_like(x), np.zeros_like(x))).T)
     return out
@@ -102,28 +127,29 @@ def unpack(rec):
                 max_iter=int(par[7]))
 
 
-def executed_path(veh, tau):
+def executed_path(veh, tau, spec=None):
     """Collision-free executed states of the overtaking manoeuvre at time tau (s): vehicle 1 on
     its reference (veh_config.py:41-45); vehicle 0 at 20 m/s changing to y = +lane between
     0.2 s and 0.8 s and back between 3.0 s and 3.6 s (smoothstep profiles, heading = path
-    tangent).  The reference's own references run vehicle 0 through vehicle 1; these are the
-    states a converged run would exchange."""
+    tangent) -- or the speeds, gap, lane and times of `spec`.  The reference's own references run
+    vehicle 0 through vehicle 1; these are the states a converged run would exchange."""
+    sp = _spec(spec)
     if veh == 1:
-        return np.array([20.0 + 10.0 * tau, 0.0, 10.0, 0.0, 0.0])
-    lane = 4.0
+        return np.array([sp.gap + sp.v1 * tau, 0.0, sp.v1, 0.0, 0.0])
+    lane = sp.lane
 
     def sstep(u):
         u = min(max(u, 0.0), 1.0)
         return u * u * (3 - 2 * u), 6 * u * (1 - u)
 
-    a, da = sstep((tau - 0.2) / 0.6)
-    b, db = sstep((tau - 3.0) / 0.6)
+    a, da = sstep((tau - sp.t_out) / sp.ramp)
+    b, db = sstep((tau - sp.t_back) / sp.ramp)
     y = lane * (a - b)
-    dy = lane * (da - db) / 0.6
-    return np.array([20.0 * tau, y, 20.0, math.atan2(dy, 20.0), 0.0])
+    dy = lane * (da - db) / sp.ramp
+    return np.array([sp.v0 * tau, y, sp.v0, math.atan2(dy, sp.v0), 0.0])
 
 
-def overtaking_problem(t_step, veh, variant="initial", prob=1, seed=0, alpha=0.9):
+def overtaking_problem(t_step, veh, variant="initial", prob=1, seed=0, alpha=0.9, spec=None):
     """One local problem of the two-vehicle overtaking scenario (decentralized_overtaking_ADMM.py:
     22-42: VehicleConfig references, N_horz 8, min_dis 0.1, max_x 150, max_y 20, rho 1).
 
@@ -137,16 +163,16 @@ def overtaking_problem(t_step, veh, variant="initial", prob=1, seed=0, alpha=0.9
       "perturbed" like consensus with a perturbed initial state.
     """
     rng = np.random.default_rng(seed * 7919 + t_step * 31 + veh)
-    refs = ref_traj_gen()
+    refs = ref_traj_gen(spec)
     o = 1 - veh
     ref = refs[veh][t_step:t_step + N_HORZ].copy()
-    init = executed_path(veh, t_step * DT)
+    init = executed_path(veh, t_step * DT, spec)
     A_o = np.zeros((NT, 4, 2))
     b_o = np.zeros((NT, 4))
     lij = np.zeros((NT, 4))
-    mine = np.stack([executed_path(veh, (t_step + t) * DT) for t in range(1, N_HORZ)])
+    mine = np.stack([executed_path(veh, (t_step + t) * DT, spec) for t in range(1, N_HORZ)])
     for t in range(1, N_HORZ):
-        so = executed_path(o, (t_step + t) * DT)
+        so = executed_path(o, (t_step + t) * DT, spec)
         A, b = halfspaces(so, prob)
         A_o[t - 1], b_o[t - 1] = A, b
         dvec = mine[t - 1][:2] - so[:2]
@@ -216,11 +242,11 @@ def local_record(bar, veh, t_step, init_state, ref_traj, rho=1.0, min_dis=0.1, p
                 q=q, prob=prob, max_iter=max_iter)
 
 
-def as_written_problem(t_step=0, veh=0, prob=1):
+def as_written_problem(t_step=0, veh=0, prob=1, spec=None):
     """The reference's first ADMM iterate as written: bar_state = mid_state (A = b = 0, the
     hard-coded lamb_ij, lamb_bar = 1e-3, Z_bar = 0; optimizer.py:351-373).  (5b) then forces
     A(X_t)' Lambda_t = 0, so (5a) reads -b0' Lambda >= 0.1 with Lambda >= 0: infeasible."""
-    refs = ref_traj_gen()
+    refs = ref_traj_gen(spec)
     return local_record(create_bar_state(), veh, t_step, refs[veh][t_step], refs, prob=prob)
 
 
@@ -303,7 +329,7 @@ def check_converge(bar, thres, min_dis):
     return bool((np.abs(eq) <= thres).all() and (ueq >= min_dis).all())
 
 
-def seeded_bar_state(t_step, prob=1, alpha=0.9):
+def seeded_bar_state(t_step, prob=1, alpha=0.9, spec=None):
     """A runnable initial bar_state at MPC step t_step: A, b, local_x from `executed_path`
     (slots t_step + 1 .. t_step + 7), lamb_ij each vehicle's own `separating_duals` along the
     direction to the other vehicle (so A_0' lamb_0 + A_1' lamb_1 = 0), Z_bar = [local_x, lamb_ij],
@@ -311,7 +337,7 @@ def seeded_bar_state(t_step, prob=1, alpha=0.9):
     (`as_written_problem`)."""
     bar = create_bar_state()
     for t in range(NT):
-        st = [executed_path(v, (t_step + t + 1) * DT) for v in (0, 1)]
+        st = [executed_path(v, (t_step + t + 1) * DT, spec) for v in (0, 1)]
         for v in (0, 1):
             A, b = halfspaces(st[v], prob)
             dvec = st[1 - v][:2] - st[v][:2]
@@ -321,6 +347,21 @@ def seeded_bar_state(t_step, prob=1, alpha=0.9):
     bar["Z_bar"] = local_z(bar)
     bar["lamb_bar"] = 1e-3 * np.ones((2, NT, 9))
     return bar
+
+
+def overtaking_fleet(n, seed=0):
+    """n different overtakes for one batch: (specs, params) with params = dict(rho=, min_dis=)
+    of length-n arrays, for `OBCAPlanner(batch, n, specs=specs, **params)` and OBCADevicePlanner
+    alike.  Uniform draws: v0 in [16, 20] (20 is the vehicle's max_v; above it the local NLP is
+    infeasible), v1 in [8, 12], gap in [12, 20], lane in [3, 4], rho in [0.5, 2], min_dis in
+    [0.05, 0.3].  The CPU restatement of both solves converges on these ranges while vehicle 0 is
+    behind or ahead (16 draws of seed 0 at MPC steps 5 and 8: 1 solve of 288 not CONVERGED); at the
+    steps where the vehicles are alongside (step 12) a draw with a lane below about 3.6 m can
+    end a solve on another status, which the planners record like every status."""
+    rng = np.random.default_rng(seed)
+    u = rng.uniform(size=(int(n), 6))
+    specs = [OvertakeSpec(v0=16.0 + 4.0 * a[0], v1=8.0 + 4.0 * a[1], gap=12.0 + 8.0 * a[2], lane=3.0 + a[3]) for a in u]
+    return specs, dict(rho=0.5 + 1.5 * u[:, 4], min_dis=0.05 + 0.25 * u[:, 5])
 
 
 class OBCAEdgeResult:
@@ -463,6 +504,58 @@ class OBCABatch:
 # ---------------------------------------------------------------------------------------------
 # The consensus loop (decentralized_overtaking_ADMM.py:31-102) for many scenarios at once
 # ---------------------------------------------------------------------------------------------
+# a parameter row of piadmm_obca_fleet_begin (include/piadmm.h), by constructor argument
+FLEET_ROW = ("rho", "min_dis", "conv_thres", "max_x", "max_y", "r", "q", "x_bound", "mu_max", "g_max",
+             "max_admm_iter", "max_iter", "round_decimals", "start")
+_FLEET_INTS = ("max_admm_iter", "max_iter", "round_decimals", "start")
+FLEET_PAR = 16                        # doubles per row (PIADMM_OBCA_FLEET_PAR); the rest is zero
+
+
+def _per_scenario(pl, n, **params):
+    """For each parameter: pl.<name>_s, its value per scenario, from a scalar or a length-n
+    sequence (an integer one stays float where a value is not integral, so that the library sees
+    it and refuses it).  True when any was a sequence."""
+    any_seq = False
+    for name, val in params.items():
+        arr = np.asarray(val, np.float64)
+        if arr.ndim:
+            any_seq = True
+            assert arr.shape == (n,), (name, arr.shape, n)
+        arr = np.broadcast_to(arr, (n,)).copy()
+        if name in _FLEET_INTS and np.all(np.isfinite(arr)) and np.all(arr == np.floor(arr)):
+            arr = arr.astype(np.int64)
+        setattr(pl, name + "_s", arr)
+    return any_seq
+
+
+def _scenario_refs(pl, specs, ref_traj):
+    """pl.specs, pl.ref_traj (the shared reference, None when each scenario has its own),
+    pl.ref_traj_s (n x 2 x n_ref x 5, a broadcast view of a shared one) and pl.n_ref; returns
+    (the references to upload, whether they are per scenario).  ref_traj: 2 x n_ref x 5 for all,
+    or n x 2 x n_ref x 5; without it the references of `specs`."""
+    n = pl.n
+    pl.specs = None if specs is None else [_spec(sp) for sp in specs]
+    assert pl.specs is None or len(pl.specs) == n
+    if ref_traj is None and pl.specs is not None:
+        ref = np.stack([np.stack(ref_traj_gen(sp)) for sp in pl.specs]) if n else np.zeros((0, 2, 51, NX))
+        pl.ref_traj = None
+    else:
+        pl.ref_traj = ref_traj_gen() if ref_traj is None else ref_traj
+        ref = np.stack([np.asarray(r_, np.float64) for r_ in pl.ref_traj])
+        if ref.ndim == 4:
+            pl.ref_traj = None
+    ref = np.ascontiguousarray(ref, np.float64)
+    each = ref.ndim == 4
+    assert ref.shape[-3] == 2 and ref.shape[-1] == NX and (not each or ref.shape[0] == n), ref.shape
+    pl.n_ref = ref.shape[-2]
+    pl.ref_traj_s = ref if each else np.broadcast_to(ref, (n,) + ref.shape)
+    return ref, each
+
+
+def _spec_of(pl, s):
+    return None if pl.specs is None else pl.specs[s]
+
+
 class OBCARunRecord:
     """state_record / iter_num_record / lambda_record as in the script (:18-20, :100-103), one
     entry per MPC step, stacked over scenarios; status_record keeps, per ADMM iterate, the
@@ -485,26 +578,39 @@ class OBCAPlanner:
 
     prob, primal_thres, dual_thres: one value or one per scenario.  update_lamb_ij: 0 leaves lamb_ij untouched (the
     commented-out :220), 1 takes each vehicle's local Lambda.  on_stage(name, inputs, outputs) sees
-    every stage: "local", "exchange", "converge", "edge", "residual", "shift"."""
+    every stage: "local", "exchange", "converge", "edge", "residual", "shift".
+
+    Every parameter of FLEET_ROW is one value or one per scenario (`rho_s`, `min_dis_s`, ... keep
+    the value of each scenario; the scalar attributes keep a scalar argument and are None for a
+    sequence).  specs: one OvertakeSpec per scenario, giving its reference, init_state and seeded
+    state; ref_traj: one reference (2 x n_ref x 5) or one per scenario (`ref_traj_s`)."""
 
     def __init__(self, batch, n_scenarios, prob=1, t_step0=0, rho=1.0, min_dis=0.1, max_admm_iter=50,
                  primal_thres=0.01, dual_thres=0.01, round_decimals=4, start=1, update_lamb_ij=0, max_iter=60,
-                 conv_thres=0.1, on_stage=None):
+                 conv_thres=0.1, on_stage=None, max_x=150.0, max_y=20.0, r=1e4, q=1e5, x_bound=1000.0,
+                 mu_max=100000.0, g_max=1000.0, ref_traj=None, specs=None):
         self.batch = batch
         self.n = int(n_scenarios)
         self.prob = [int(prob)] * self.n if np.isscalar(prob) else [int(p) for p in prob]
         assert len(self.prob) == self.n
         self.t_step = int(t_step0)
-        self.rho, self.min_dis = float(rho), float(min_dis)
-        self.max_admm_iter = int(max_admm_iter)
+        self.rho = float(rho) if np.ndim(rho) == 0 else None
+        self.min_dis = float(min_dis) if np.ndim(min_dis) == 0 else None
+        self.max_admm_iter = int(max_admm_iter) if np.ndim(max_admm_iter) == 0 else None
         self.primal_thres = np.broadcast_to(np.asarray(primal_thres, np.float64), (self.n,)).copy()
         self.dual_thres = np.broadcast_to(np.asarray(dual_thres, np.float64), (self.n,)).copy()
-        self.conv_thres = conv_thres
-        self.round_decimals, self.start, self.update_lamb_ij, self.max_iter = round_decimals, start, update_lamb_ij, max_iter
+        self.conv_thres = conv_thres if np.ndim(conv_thres) == 0 else None
+        self.round_decimals, self.start, self.max_iter = (v if np.ndim(v) == 0 else None
+                                                          for v in (round_decimals, start, max_iter))
+        self.update_lamb_ij = update_lamb_ij
+        _per_scenario(self, self.n, rho=rho, min_dis=min_dis, conv_thres=conv_thres, max_x=max_x, max_y=max_y, r=r,
+                      q=q, x_bound=x_bound, mu_max=mu_max, g_max=g_max, max_admm_iter=max_admm_iter,
+                      max_iter=max_iter, round_decimals=round_decimals, start=start)
         self.on_stage = on_stage or (lambda name, inputs, outputs: None)
-        self.ref_traj = ref_traj_gen()
-        self.bar_prev = [seeded_bar_state(self.t_step, p) for p in self.prob]
-        self.init_state = [np.stack([executed_path(v, self.t_step * DT) for v in (0, 1)]) for _ in range(self.n)]
+        _scenario_refs(self, specs, ref_traj)
+        self.bar_prev = [seeded_bar_state(self.t_step, p, spec=_spec_of(self, s)) for s, p in enumerate(self.prob)]
+        self.init_state = [np.stack([executed_path(v, self.t_step * DT, _spec_of(self, s)) for v in (0, 1)])
+                           for s in range(self.n)]
         self.record = OBCARunRecord()
         self.record.state_record.append(np.stack(self.init_state))
 
@@ -515,7 +621,7 @@ class OBCAPlanner:
     def step(self):
         """One MPC step of every scenario."""
         n = self.n
-        assert self.t_step + N_HORZ <= len(self.ref_traj[0]), "reference exhausted"
+        assert self.t_step + N_HORZ <= self.n_ref, "reference exhausted"
         bar = [self._copy(b) for b in self.bar_prev]
         bar_prev = [self._copy(b) for b in self.bar_prev]
         ctrl_prev = [np.zeros((2, NT * NU)) for _ in range(n)]
@@ -528,8 +634,9 @@ class OBCAPlanner:
             i_iter += 1
             # ---- vehicle side: one launch, scenarios x vehicles ----
             recs = np.ascontiguousarray(np.stack([
-                local_record(bar[s], v, self.t_step, self.init_state[s][v], self.ref_traj, rho=self.rho,
-                             min_dis=self.min_dis, prob=self.prob[s], max_iter=self.max_iter)
+                local_record(bar[s], v, self.t_step, self.init_state[s][v], self.ref_traj_s[s], rho=self.rho_s[s],
+                             min_dis=self.min_dis_s[s], prob=self.prob[s], max_x=self.max_x_s[s],
+                             max_y=self.max_y_s[s], r=self.r_s[s], q=self.q_s[s], max_iter=self.max_iter_s[s])
                 for s in active for v in (0, 1)]))
             res = self.batch.solve(recs)
             self.on_stage("local", dict(recs=recs, scenarios=list(active), i_iter=i_iter, t_step=self.t_step),
@@ -547,12 +654,14 @@ class OBCAPlanner:
                     bar[s]["lamb_ij"] = np.stack([fullx[k][v][:, 5:] for v in (0, 1)])
             self.on_stage("exchange", dict(bar=before, fullx=fullx, scenarios=list(active)),
                           dict(bar=[self._copy(bar[s]) for s in active]))
-            conv = [check_converge(bar[s], self.conv_thres, self.min_dis) for s in active]
+            conv = [check_converge(bar[s], self.conv_thres_s[s], self.min_dis_s[s]) for s in active]
             self.on_stage("converge", dict(bar=[self._copy(bar[s]) for s in active]), dict(if_converge=conv))
             # ---- RSU side: one launch, the dual update fused ----
             erecs = np.ascontiguousarray(np.stack([
-                edge_record(bar[s], rho=self.rho, min_dis=self.min_dis, prob=self.prob[s], max_iter=self.max_iter,
-                            round_decimals=self.round_decimals, start=self.start) for s in active]))
+                edge_record(bar[s], rho=self.rho_s[s], min_dis=self.min_dis_s[s], prob=self.prob[s],
+                            max_iter=self.max_iter_s[s], round_decimals=self.round_decimals_s[s],
+                            start=self.start_s[s], x_bound=self.x_bound_s[s], mu_max=self.mu_max_s[s],
+                            g_max=self.g_max_s[s]) for s in active]))
             eres = self.batch.solve_edge(erecs)
             self.on_stage("edge", dict(recs=erecs, scenarios=list(active)), dict(result=eres))
             lamb_prev = [bar[s]["lamb_bar"].copy() for s in active]
@@ -566,7 +675,7 @@ class OBCAPlanner:
             primal = np.array([np.abs(ctrl[k] - ctrl_prev[s]).sum() for k, s in enumerate(active)])
             dual = eres.dual_residual()
             stop = ((primal <= self.primal_thres[active]) & (dual <= self.dual_thres[active])) \
-                | (i_iter > self.max_admm_iter)
+                | (i_iter > self.max_admm_iter_s[active])
             self.on_stage("residual",
                           dict(ctrl=ctrl, ctrl_prev=[ctrl_prev[s] for s in active],
                                lamb_bar=[bar[s]["lamb_bar"] for s in active], lamb_bar_prev=lamb_prev, i_iter=i_iter,
@@ -611,7 +720,7 @@ PLAN_GET = {"STATE": (0, np.float64), "STATE_PREV": (1, np.float64), "CTRL": (2,
             "LOCAL_REC": (11, np.float64), "LOCAL_OUT": (12, np.float64), "LOCAL_IST": (13, np.int32),
             "EDGE_REC": (14, np.float64), "EDGE_OUT": (15, np.float64), "EDGE_IST": (16, np.int32),
             "T_STEP": (17, np.int32), "LAMBDA": (18, np.float64), "COUNTS": (19, np.int32),
-            "STATUS_MASK": (20, np.int32)}
+            "STATUS_MASK": (20, np.int32), "REF": (21, np.float64), "PAR": (22, np.float64)}
 
 
 def pack_state(bar, init_state):
@@ -648,12 +757,17 @@ class OBCADevicePlanner:
     keeps one entry per iterate as OBCAPlanner's does.
 
     The planner takes the batch's device buffers over (include/piadmm.h): `batch.upload` / `solve`
-    / `solve_edge` on the same batch end the plan."""
+    / `solve_edge` on the same batch end the plan.
+
+    With `specs`, a reference per scenario (ref_traj n x 2 x n_ref x 5) or a sequence for any
+    parameter of FLEET_ROW the plan is a fleet (`self.fleet`): it is opened by
+    piadmm_obca_fleet_begin with one reference and one parameter row (`par`) per scenario.
+    Otherwise it is opened by piadmm_obca_plan_begin, as ever."""
 
     def __init__(self, batch, n_scenarios, prob=1, t_step0=0, rho=1.0, min_dis=0.1, max_admm_iter=50,
                  primal_thres=0.01, dual_thres=0.01, round_decimals=4, start=1, update_lamb_ij=0, max_iter=60,
                  conv_thres=0.1, on_stage=None, max_x=150.0, max_y=20.0, r=1e4, q=1e5, x_bound=1000.0,
-                 mu_max=100000.0, g_max=1000.0, ref_traj=None, state=None):
+                 mu_max=100000.0, g_max=1000.0, ref_traj=None, state=None, specs=None):
         from . import _lib
         self.batch = batch
         self._lib = batch._lib
@@ -661,33 +775,58 @@ class OBCADevicePlanner:
         self.prob = [int(prob)] * self.n if np.isscalar(prob) else [int(p) for p in prob]
         assert len(self.prob) == self.n
         self.t_step = int(t_step0)
-        self.rho, self.min_dis = float(rho), float(min_dis)
-        self.max_admm_iter = int(max_admm_iter)
+        self.rho = float(rho) if np.ndim(rho) == 0 else None
+        self.min_dis = float(min_dis) if np.ndim(min_dis) == 0 else None
+        self.max_admm_iter = int(max_admm_iter) if np.ndim(max_admm_iter) == 0 else None
         self.primal_thres = np.broadcast_to(np.asarray(primal_thres, np.float64), (self.n,)).copy()
         self.dual_thres = np.broadcast_to(np.asarray(dual_thres, np.float64), (self.n,)).copy()
-        self.conv_thres = conv_thres
-        self.round_decimals, self.start, self.update_lamb_ij, self.max_iter = round_decimals, start, update_lamb_ij, max_iter
+        self.conv_thres = conv_thres if np.ndim(conv_thres) == 0 else None
+        self.round_decimals, self.start, self.max_iter = (v if np.ndim(v) == 0 else None
+                                                          for v in (round_decimals, start, max_iter))
+        self.update_lamb_ij = update_lamb_ij
+        any_seq = _per_scenario(self, self.n, rho=rho, min_dis=min_dis, conv_thres=conv_thres, max_x=max_x,
+                                max_y=max_y, r=r, q=q, x_bound=x_bound, mu_max=mu_max, g_max=g_max,
+                                max_admm_iter=max_admm_iter, max_iter=max_iter, round_decimals=round_decimals,
+                                start=start)
         self.on_stage = on_stage
-        self.ref_traj = ref_traj_gen() if ref_traj is None else ref_traj
-        ref = np.ascontiguousarray(np.stack([np.asarray(r_, np.float64) for r_ in self.ref_traj]))
-        assert ref.ndim == 3 and ref.shape[0] == 2 and ref.shape[2] == NX
-        self.n_ref = ref.shape[1]
-        self.init_state = [np.stack([executed_path(v, self.t_step * DT) for v in (0, 1)]) for _ in range(self.n)]
+        ref, ref_each = _scenario_refs(self, specs, ref_traj)
+        self.fleet = bool(any_seq or ref_each or self.specs is not None)
+        self.init_state = [np.stack([executed_path(v, self.t_step * DT, _spec_of(self, s)) for v in (0, 1)])
+                           for s in range(self.n)]
         if state is None:
-            seeds = {p: pack_state(seeded_bar_state(self.t_step, p), self.init_state[0]) for p in set(self.prob)}
-            state = np.stack([seeds[p] for p in self.prob]) if self.n else np.zeros((0, PLAN_STATE))
+            seeds = {}
+            for s, p in enumerate(self.prob):
+                key = (p, _spec_of(self, s))
+                if key not in seeds:
+                    seeds[key] = pack_state(seeded_bar_state(self.t_step, p, spec=key[1]), self.init_state[s])
+            state = (np.stack([seeds[(p, _spec_of(self, s))] for s, p in enumerate(self.prob)]) if self.n
+                     else np.zeros((0, PLAN_STATE)))
         state = np.ascontiguousarray(state, np.float64)
         assert state.shape == (self.n, PLAN_STATE)
-        self.cfg = _lib.ObcaPlanCfgC(
-            n_scenarios=self.n, t_step0=self.t_step, max_admm_iter=self.max_admm_iter,
-            round_decimals=int(round_decimals), start=int(start), update_lamb_ij=int(update_lamb_ij),
-            max_sqp_iter=int(max_iter), n_ref=self.n_ref, rho=self.rho, min_dis=self.min_dis,
-            conv_thres=float(conv_thres), max_x=max_x, max_y=max_y, r=r, q=q, x_bound=x_bound, mu_max=mu_max,
-            g_max=g_max)
         prob_a = np.ascontiguousarray(self.prob if self.n else [0], np.int32)
-        self._check(self._lib.piadmm_obca_plan_begin(batch._h, ctypes.byref(self.cfg), _lib.iptr(prob_a),
-                                                     _lib.dptr(self.primal_thres), _lib.dptr(self.dual_thres),
-                                                     _lib.dptr(ref), _lib.dptr(state)))
+        if not self.fleet:
+            self.par = None
+            self.cfg = _lib.ObcaPlanCfgC(
+                n_scenarios=self.n, t_step0=self.t_step, max_admm_iter=self.max_admm_iter,
+                round_decimals=int(round_decimals), start=int(start), update_lamb_ij=int(update_lamb_ij),
+                max_sqp_iter=int(max_iter), n_ref=self.n_ref, rho=self.rho, min_dis=self.min_dis,
+                conv_thres=float(conv_thres), max_x=max_x, max_y=max_y, r=r, q=q, x_bound=x_bound, mu_max=mu_max,
+                g_max=g_max)
+            self._check(self._lib.piadmm_obca_plan_begin(batch._h, ctypes.byref(self.cfg), _lib.iptr(prob_a),
+                                                         _lib.dptr(self.primal_thres), _lib.dptr(self.dual_thres),
+                                                         _lib.dptr(ref), _lib.dptr(state)))
+        else:
+            # cfg carries what stays shared; the rows carry the rest
+            self.par = np.zeros((self.n, FLEET_PAR))
+            for j, name in enumerate(FLEET_ROW):
+                self.par[:, j] = getattr(self, name + "_s")
+            if not ref_each:
+                ref = np.ascontiguousarray(self.ref_traj_s)
+            self.cfg = _lib.ObcaPlanCfgC(n_scenarios=self.n, t_step0=self.t_step, update_lamb_ij=int(update_lamb_ij),
+                                         n_ref=self.n_ref)
+            self._check(self._lib.piadmm_obca_fleet_begin(batch._h, ctypes.byref(self.cfg), _lib.iptr(prob_a),
+                                                          _lib.dptr(self.primal_thres), _lib.dptr(self.dual_thres),
+                                                          _lib.dptr(ref), _lib.dptr(self.par), _lib.dptr(state)))
         self.record = OBCARunRecord()
         self.record.state_record.append(np.stack(self.init_state))
 
@@ -709,12 +848,14 @@ class OBCADevicePlanner:
         """One item of the resident plan (include/piadmm.h, piadmm_obca_plan_get), shaped."""
         code, dt = PLAN_GET[what]
         n, m = self.n, (self.counts()[0] if what != "COUNTS" else 0)
+        rows = n if self.fleet else 1
         shape = {"STATE": (n, PLAN_STATE), "STATE_PREV": (n, PLAN_STATE), "CTRL": (n, 2, NT * NU),
                  "CTRL_PREV": (n, 2, NT * NU), "X": (n, 2, N_HORZ, NX), "ITERS": (n,), "ACTIVE": (m,),
                  "PRIMAL": (n,), "DUAL": (n,), "STOP": (n,), "CONVERGE": (n,), "LOCAL_REC": (2 * m, REC),
                  "LOCAL_OUT": (2 * m, OUT), "LOCAL_IST": (2 * m, 3), "EDGE_REC": (m, EDGE_REC),
                  "EDGE_OUT": (m, EDGE_OUT), "EDGE_IST": (m, NT, 3), "T_STEP": (1,), "LAMBDA": (n, 2, NT, 9),
-                 "COUNTS": (3,), "STATUS_MASK": (n, 2)}[what]
+                 "COUNTS": (3,), "STATUS_MASK": (n, 2), "REF": (rows, 2, self.n_ref, NX),
+                 "PAR": (rows, FLEET_PAR)}[what]
         out = np.zeros(shape, dt)
         self._check(self._lib.piadmm_obca_plan_get(self.batch._h, code, out.ctypes.data, out.nbytes))
         return out

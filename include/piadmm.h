@@ -441,7 +441,25 @@ int32_t piadmm_obca_edge_time(piadmm_obca_t h, const double* recs, int32_t n_pai
  *                       closed last (what the script's lambda_record keeps, :103)
  *   COUNTS              3 int32          m, the number still active, the iterates run in the open step
  *   STATUS_MASK         n x 2 int32      OR of (1 << status) over the local / the edge solves of the
- *                       scenario in the step closed last (in the open step before the shift) */
+ *                       scenario in the step closed last (in the open step before the shift)
+ *   REF                 rows x 2 x n_ref x 5 fp64   the references as uploaded
+ *   PAR                 rows x PIADMM_OBCA_FLEET_PAR fp64   the parameter rows as uploaded
+ *                       rows = 1 (the shared row) after piadmm_obca_plan_begin, n after piadmm_obca_fleet_begin
+ *
+ * piadmm_obca_fleet_begin opens the same plan with a reference and a parameter row per scenario
+ * (a fleet, a Monte-Carlo study over speeds and gaps, a sweep over rho and min_dis in one batch);
+ * piadmm_obca_plan_iterate / _shift / _step / _get / _end, the buffer takeover and the "an upload
+ * ends the plan" rule apply to it unchanged.  A row of `par` holds, in order,
+ *   rho, min_dis, conv_thres, max_x, max_y, r, q, x_bound, mu_max, g_max,
+ *   max_admm_iter, max_sqp_iter, round_decimals, start, 0, 0
+ * the integers stored as doubles, as the records store them.  cfg carries what stays shared
+ * (n_scenarios, t_step0, n_ref, update_lamb_ij); its other fields are the row of every scenario
+ * when par is NULL.  Every row passes the checks of piadmm_obca_plan_begin and its integers must be
+ * integral, before any device call: a bad row is PIADMM_E_ARG with "obca_fleet_begin: row k: ..."
+ * and an open plan stays as it was.  A scenario stops at i_iter > its own max_admm_iter;
+ * piadmm_obca_plan_step runs at most the largest max_admm_iter of the rows, plus one, iterates.
+ * The vehicle geometry and the delay statistics are constants of the solver kernels, n_ref and
+ * t_step are the plan's: none of them is per scenario. */
 #define PIADMM_OBCA_PLAN_STATE 556
 #define PIADMM_OBCA_PLAN_GET_STATE 0
 #define PIADMM_OBCA_PLAN_GET_STATE_PREV 1
@@ -464,6 +482,9 @@ int32_t piadmm_obca_edge_time(piadmm_obca_t h, const double* recs, int32_t n_pai
 #define PIADMM_OBCA_PLAN_GET_LAMBDA 18
 #define PIADMM_OBCA_PLAN_GET_COUNTS 19
 #define PIADMM_OBCA_PLAN_GET_STATUS_MASK 20
+#define PIADMM_OBCA_PLAN_GET_REF 21
+#define PIADMM_OBCA_PLAN_GET_PAR 22
+#define PIADMM_OBCA_FLEET_PAR 16
 typedef struct {
   int32_t n_scenarios, t_step0, max_admm_iter, round_decimals, start, update_lamb_ij, max_sqp_iter, n_ref;
   double rho, min_dis, conv_thres, max_x, max_y, r, q, x_bound, mu_max, g_max;
@@ -477,6 +498,11 @@ int32_t piadmm_obca_plan_shift(piadmm_obca_t h);
 int32_t piadmm_obca_plan_step(piadmm_obca_t h, int32_t* iters_out /* n, may be NULL */);
 int32_t piadmm_obca_plan_get(piadmm_obca_t h, int32_t what, void* out, int64_t bytes);
 int32_t piadmm_obca_plan_end(piadmm_obca_t h);
+int32_t piadmm_obca_fleet_begin(piadmm_obca_t h, const piadmm_obca_plan_cfg_t* cfg, const int32_t* prob,
+                                const double* primal_thres, const double* dual_thres,
+                                const double* ref_traj /* n x 2 x n_ref x 5 */,
+                                const double* par      /* n x PIADMM_OBCA_FLEET_PAR, may be NULL */,
+                                const double* state    /* n x 556 */);
 
 #ifdef __cplusplus
 }

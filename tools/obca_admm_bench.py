@@ -10,6 +10,17 @@
                    (OBCADevicePlanner.step: one piadmm_obca_plan_step, then the record's downloads),
                    wall-clock ms per ADMM iterate, and its ratio to the host iterate of this run
 
+  --fleet          instead of the above: --scenarios different overtakes (obca.overtaking_fleet: own
+                   speeds, gap, lane, rho and min_dis) through piadmm_obca_fleet_begin, and in the
+                   same run the shared plan (piadmm_obca_plan_begin) on as many copies of the
+                   default scenario from the same MPC step.  Per leg: wall-clock ms per ADMM
+                   iterate of one piadmm_obca_plan_step (a warm-up step on its own plan first), the
+                   mean local / edge SQP iterations and the status histogram over every solve of
+                   the timed step (taken afterwards from an untimed iterate-by-iterate rerun, which
+                   is bit-identical).  The two legs solve different problems: the SQP work tells
+                   the solves' share of a difference from the glue's.  Written under the keys
+                   "fleet" and "fleet_shared_leg" of the same JSON, the other keys kept.
+
 There is no CPU baseline on an equal footing (the C++ port of the local solver has no edge step);
 the edge launch is reported next to the local launch so the reader sees its share of an iterate.
 Writes one JSON (default profiles/obca_admm_bench.json) and prints it.
@@ -44,14 +55,75 @@ def edge_batch(n):
     return np.ascontiguousarray(np.stack([base[k % len(base)] for k in range(n)]))
 
 
+def plan_leg(b, n, kw):
+    """One MPC step of a device plan: timed as one piadmm_obca_plan_step, then rerun iterate by
+    iterate for the solves' statistics."""
+    dp = obca.OBCADevicePlanner(b, n, **kw)
+    dp.step()
+    dp.close()
+    dp = obca.OBCADevicePlanner(b, n, **kw)
+    fleet = dp.fleet
+    t0 = time.perf_counter()
+    dp.step()
+    ms = (time.perf_counter() - t0) * 1e3
+    iters = np.asarray(dp.record.iter_num_record[0])
+    dp.close()
+    dp = obca.OBCADevicePlanner(b, n, **kw)
+    loc_st, loc_it, edge_st, edge_it, submitted = np.zeros(5, int), 0, np.zeros(5, int), 0, []
+    left = n
+    while left:
+        left = dp.iterate()
+        li, ei = dp.get("LOCAL_IST"), dp.get("EDGE_IST")
+        submitted.append(len(ei))
+        loc_st += np.bincount(li[:, 0], minlength=5)[:5]
+        edge_st += np.bincount(ei[:, :, 0].ravel(), minlength=5)[:5]
+        loc_it += int(li[:, 1].sum())
+        edge_it += int(ei[:, :, 1].sum())
+    same = bool(np.array_equal(dp.get("ITERS"), iters))
+    dp.close()
+    n_it = int(iters.max())
+    return dict(entry="piadmm_obca_fleet_begin" if fleet else "piadmm_obca_plan_begin", scenarios=n,
+                admm_iterates=n_it, step_ms=ms, iterate_ms=ms / max(n_it, 1), scenarios_submitted=submitted,
+                stop_iterate_counts=np.bincount(iters, minlength=n_it + 1).tolist(),
+                local_sqp_iters_mean=loc_it / max(int(loc_st.sum()), 1),
+                edge_sqp_iters_mean=edge_it / max(int(edge_st.sum()), 1),
+                local_status_counts=loc_st.tolist(), edge_status_counts=edge_st.tolist(),
+                status_names=[obca.STATUS[k] for k in range(5)], rerun_stop_iterates_equal=same)
+
+
+def fleet_main(a):
+    b = obca.OBCABatch(0)
+    n = a.scenarios
+    common = dict(prob=[k % 2 for k in range(n)], t_step0=8, max_admm_iter=a.iterates - 1)
+    specs, par = obca.overtaking_fleet(n, seed=0)
+    shared = plan_leg(b, n, common)
+    fleet = plan_leg(b, n, dict(common, specs=specs, **par))
+    b.close()
+    out = {}
+    if os.path.exists(a.out):
+        with open(a.out) as f:
+            out = json.load(f)
+    out["fleet"] = fleet
+    out["fleet_shared_leg"] = shared
+    out["fleet_over_shared_iterate"] = fleet["iterate_ms"] / shared["iterate_ms"]
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+    print(json.dumps(dict(fleet=fleet, fleet_shared_leg=shared,
+                          fleet_over_shared_iterate=out["fleet_over_shared_iterate"])))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--fleet", action="store_true")
     ap.add_argument("--pairs", type=int, default=4096)
     ap.add_argument("--scenarios", type=int, default=2048)
     ap.add_argument("--repeats", type=int, default=10)
     ap.add_argument("--iterates", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "obca_admm_bench.json"))
     a = ap.parse_args()
+    if a.fleet:
+        return fleet_main(a)
     b = obca.OBCABatch(0)
     recs = edge_batch(a.pairs)
     b.time_edge(recs, 1)                                   # warm-up
