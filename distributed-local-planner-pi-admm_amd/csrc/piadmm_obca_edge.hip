@@ -660,9 +660,11 @@ int edge_check(piadmm_obca_t h, const double* recs, int n) {
   for (int i = 0; i < n; ++i) {
     const double* par = recs + (size_t)i * obca_edge::REC + obca_edge::O_PAR;
     if (!(par[0] > 0.0) || (par[2] != 0.0 && par[2] != 1.0) || !(par[3] >= 1.0 && par[3] <= 1000.0) ||
-        (par[5] != 0.0 && par[5] != 1.0) || !(par[4] >= -1.0 && par[4] <= 15.0) || !(par[6] > 0.0) || !(par[7] > 0.0))
+        (par[5] != 0.0 && par[5] != 1.0) || !(par[4] >= -1.0 && par[4] <= 15.0) || !(par[6] > 0.0) || !(par[7] > 0.0) ||
+        !std::isfinite(par[1]) || !std::isfinite(par[8]))
       return efail(h, PIADMM_E_ARG, "record " + std::to_string(i) + ": bad parameters (rho > 0; prob 0/1; "
-                   "1 <= max_iter <= 1000; start 0/1; -1 <= round_decimals <= 15; x_bound, mu_max > 0)");
+                   "1 <= max_iter <= 1000; start 0/1; -1 <= round_decimals <= 15; x_bound, mu_max > 0; "
+                   "min_dis, g_max finite)");
   }
   return 0;
 }

@@ -88,8 +88,13 @@ def violation(p, z):
     return v
 
 
-def solve_slot(p, opt=OPT):
-    """The edge SQP."""
+def solve_slot(p, opt=OPT, trace=None):
+    """The edge SQP.  `trace` (a list, optional) receives one dict per SQP
+    iteration that reached the QP or failed the modification: mod = ("none" | "sigma" | "tau" |
+    "fail", rung), n_prev (previously active rows that entered Ga), qst (the QP's status), active
+    (the inequality rows active at the QP's solution), drops / partial (rows the QP dropped, and
+    those of them after a partial step), halvings (of the line search; -1 = none was run).  The
+    trace is written only: the result is the same with and without it."""
     z = np.zeros(NE) if p.start == 0 else np.minimum(np.maximum(p.w, p.lo), p.hi)
     y_eq, y_in, y_bnd = np.zeros(2), 0.0, np.zeros(NE)
     mu = 0.0
@@ -112,7 +117,9 @@ def solve_slot(p, opt=OPT):
         # Hessian modification: sigma sum a a' over the equality rows and the rows active in the
         # previous QP (normalised), then tau diag(|H_ii|)
         Hm, gm = H, gf
+        mod, n_prev = ("none", 0), 0
         if not O._is_pd(Hm):
+            n_prev = len(prev_act) if prev_act is not None else 0
             rows = [Ceq[0], Ceq[1]] + ([Cin[k] for k in prev_act] if prev_act is not None else [])
             rhs = [deq[0], deq[1]] + ([din[k] for k in prev_act] if prev_act is not None else [])
             Ga, ga_ = np.zeros((NE, NE)), np.zeros(NE)
@@ -123,25 +130,34 @@ def solve_slot(p, opt=OPT):
                 ga_ += an * (b / nrm)
             hmax = float(np.max(np.abs(np.diag(H))))
             sig = 1e-4 * hmax
-            for _ in range(8):
+            for k in range(8):
                 Hm = H + sig * Ga
                 gm = gf - sig * ga_
+                mod = ("sigma", k)
                 if O._is_pd(Hm):
                     break
                 sig *= 10.0
         if not O._is_pd(Hm):
             Dg = np.diag(np.maximum(np.abs(np.diag(Hm)), 1e-12))
             H0, tau = Hm, 0.0
-            for _ in range(16):
+            for k in range(16):
                 tau = 1e-6 if tau == 0.0 else tau * 10.0
                 Hm = H0 + tau * Dg
+                mod = ("tau", k)
                 if O._is_pd(Hm):
                     break
             else:
                 status = HESSIAN_FAIL
+                if trace is not None:
+                    trace.append(dict(mod=("fail", 16), n_prev=n_prev, qst=-1, active=(), drops=0, partial=0, halvings=-1))
                 break
-        d, ueq, uin, qst, qsteps = O.gi_qp(Hm, gm, Ceq, deq, Cin, din)
+        count = {} if trace is not None else None
+        d, ueq, uin, qst, qsteps = O.gi_qp(Hm, gm, Ceq, deq, Cin, din, count=count)
         qp_total += qsteps
+        if trace is not None:
+            rec_ = dict(mod=mod, n_prev=n_prev, qst=qst, active=tuple(int(c) for c in np.nonzero(uin > 0)[0]) if qst == 0 else (),
+                        drops=count.get("drops", 0), partial=count.get("partial", 0), halvings=-1)
+            trace.append(rec_)
         prev_act = np.nonzero(uin > 0)[0] if qst == 0 else None
         if qst != 0:
             status = QP_INFEASIBLE if qst == 2 else MAX_ITER
@@ -161,9 +177,11 @@ def solve_slot(p, opt=OPT):
         phi0 = cost(p, z) + mu * viol
         D = float(gf @ d) - mu * viol
         alpha, ok = 1.0, False
-        for _ in range(opt.max_halvings + 1):
+        for k in range(opt.max_halvings + 1):
             zn = z + alpha * d
             phi = cost(p, zn) + mu * violation(p, zn)
+            if trace is not None:
+                rec_["halvings"] = k
             if phi <= phi0 + opt.armijo * alpha * D:
                 ok = True
                 break
@@ -181,11 +199,15 @@ def solve_slot(p, opt=OPT):
 @functools.lru_cache(maxsize=None)
 def _solve(raw, t):
     p = Slot(np.frombuffer(raw, np.float64), t)
-    return p, solve_slot(p)
+    tr = []
+    r = solve_slot(p, trace=tr)
+    r.trace = tr
+    return p, r
 
 
 def solve_record(rec):
-    """[(Slot, SlotResult)] x 7 of one edge record (each distinct record solved once per process)."""
+    """[(Slot, SlotResult)] x 7 of one edge record (each distinct record solved once per process);
+    SlotResult.trace is solve_slot's trace."""
     raw = np.ascontiguousarray(rec, np.float64).tobytes()
     return [_solve(raw, t) for t in range(obca.NT)]
 

@@ -1,10 +1,11 @@
 """GPU parity of the OBCA-ADMM edge step: csrc/piadmm_obca_edge.hip through the C-ABI
 (piadmm_obca_edge_solve) against the NumPy restatement tests/_obca_edge_ref.py on the case sets
-proved sound by tests/test_obca_edge_ref.py, and the planner loop (piadmm.obca.OBCAPlanner)
+proved sound by tests/test_obca_edge_ref.py and on the hard-branch sets of tests/_obca_edge_cases.py
+(proved by tests/test_obca_edge_cases.py), and the planner loop (piadmm.obca.OBCAPlanner)
 teacher-forced stage by stage.
 
-Bars (those of tests/test_gpu_obca.py): status and SQP iteration count equal the restatement's
-exactly; Z, multipliers and cost within ATOL 1e-7 / rtol 1e-9; the GPU's own answer, with the
+Bars (those of tests/test_gpu_obca.py): status, SQP iteration count and QP step count equal the
+restatement's exactly; Z, multipliers and cost within ATOL 1e-7 / rtol 1e-9; the GPU's own answer, with the
 GPU's multipliers, is a KKT point of the slot NLP -- stationarity <= 1e-9 of the gradient scale,
 feasibility and complementarity <= 1e-8.
 """
@@ -12,6 +13,7 @@ import numpy as np
 import pytest
 
 import _obca_cases as C
+import _obca_edge_cases as K
 import _obca_edge_ref as E
 from piadmm import _lib, obca
 
@@ -36,17 +38,22 @@ def batch():
     b.close()
 
 
-def _compare(res, recs, name="", kkt=True):
-    """An OBCAEdgeResult against the restatement, slot by slot."""
+def _compare(res, recs, name="", kkt=True, keep=None):
+    """An OBCAEdgeResult against the restatement, slot by slot (`keep`: the (record, slot) pairs
+    to compare, all by default)."""
     exempt = EXEMPT.get(name, ())
     assert len(exempt) <= 0.02 * len(recs) * obca.NT
     worst = dict(z=0.0, mult=0.0, cost=0.0, stat=0.0, feas=0.0, comp=0.0)
     for k, rec in enumerate(recs):
         for t, (p, r) in enumerate(E.solve_record(rec)):
+            if keep is not None and (k, t) not in keep:
+                continue
             same = res.status[k, t] == r.status and int(res.iters[k, t]) == r.iters
             if not same and (k, t) in exempt:
                 continue
             assert same, (name, k, t, int(res.status[k, t]), r.status, int(res.iters[k, t]), r.iters)
+            # the QP step count: a difference at equal status and iterations is a finding, not an exemption
+            assert int(res.qp_steps[k, t]) == r.qp_steps, (name, k, t, int(res.qp_steps[k, t]), r.qp_steps)
             if r.status not in E.WRITES_ITERATE:
                 continue
             z = res.z(k, t)
@@ -100,9 +107,9 @@ def test_rounding(batch):
     np.testing.assert_array_equal(r2.Z, res.Z)
 
 
-def test_fused_dual_update(batch):
-    recs = np.concatenate([E.case_set("exchanged"), E.case_set("zero_start")])
-    res = batch.solve_edge(recs)
+def _check_dual_update(res, recs):
+    """lamb_bar_new and the dual-residual partials against the host form on the GPU's own Z_bar;
+    returns the number of slots that wrote no iterate."""
     n_kept = 0
     for k, rec in enumerate(recs):
         d = obca.edge_unpack(rec)
@@ -118,7 +125,12 @@ def test_fused_dual_update(batch):
                 assert res.dres[k, t] == 0.0
             total += np.abs(res.lamb_bar[k, :, t] - d["lamb_bar"][:, t]).sum()
         assert abs(res.dual_residual()[k] - total) <= 1e-12 * max(1.0, total)
-    assert n_kept >= 1          # zero_start: slots that wrote no iterate
+    return n_kept
+
+
+def test_fused_dual_update(batch):
+    recs = np.concatenate([E.case_set("exchanged"), E.case_set("zero_start")])
+    assert _check_dual_update(batch.solve_edge(recs), recs) >= 1          # zero_start: slots that wrote no iterate
 
 
 @pytest.mark.parametrize("n_pairs", [1, 3, 65])
@@ -176,13 +188,98 @@ def test_edge_call_leaves_the_resident_local_batch_alone(batch):
 
 def test_errors_are_reported_before_any_launch(batch):
     rec = E.case_set("consistent")[:2]
-    for off, val in ((0, 0.0), (2, 2.0), (3, 0.0), (5, 2.0)):       # rho, prob, max_iter, start
+    # rho, prob, max_iter, start; min_dis and g_max not finite
+    for off, val in ((0, 0.0), (2, 2.0), (3, 0.0), (5, 2.0), (1, np.nan), (1, np.inf), (8, np.nan), (8, -np.inf)):
         bad = rec.copy()
         bad[1, obca._E_PAR + off] = val
         with pytest.raises(_lib.PiadmmError, match="record 1: bad parameters"):
             batch.solve_edge(bad)
     r = batch.solve_edge(rec)
     assert np.all(r.status == 0)
+
+
+# ---------------------------------------------------------------------------------------------
+# the hard branches (tests/_obca_edge_cases.py, proved on the CPU by tests/test_obca_edge_cases.py):
+# the Hessian modification with its two ladders, the QP's drops, the upper range row, solves from
+# zeros, rho / min_dis / round_decimals off their defaults -- on the slots the stability filter keeps
+# ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", K.SET_NAMES)
+def test_gpu_equals_restatement_on_the_hard_branches(batch, name):
+    recs = K.case_set(name)
+    res = batch.solve_edge(recs)
+    _compare(res, recs, name, keep=set(K.kept(name)))
+
+
+def test_rounding_at_other_decimals(batch):
+    recs = K.case_set("decimals")
+    res = batch.solve_edge(recs)
+    n, skipped, seen, keep = 0, 0, set(), set(K.kept("decimals"))
+    for k, rec in enumerate(recs):
+        for t, (p, r) in enumerate(E.solve_record(rec)):
+            if (k, t) not in keep:
+                continue
+            assert res.status[k, t] == r.status
+            d = p.round_decimals
+            seen.add(d)
+            x = r.z * 10.0 ** d
+            # within 1e-2 of the decimal's grid spacing of a rounding tie (test_rounding's window at d = 4)
+            tie = np.abs(np.abs(x - np.floor(x)) - 0.5) < 1e-2
+            want = np.round(r.z, d)
+            got = np.concatenate([res.Z_bar[k, 0, t], res.Z_bar[k, 1, t]])
+            n += x.size
+            skipped += int(tie.sum())
+            np.testing.assert_array_equal(got[~tie], want[~tie], err_msg=f"decimals {d}: record {k} slot {t}")
+    assert seen == set(K.DECIMALS)
+    print(f"rounding at {sorted(seen)} decimals: {skipped} of {n} values within 1e-2 grid steps of a tie")
+    assert skipped <= 0.05 * n
+    # the solve does not see the field
+    for j in range(0, len(recs), len(K.DECIMALS)):
+        for i in range(1, len(K.DECIMALS)):
+            np.testing.assert_array_equal(res.Z[j + i], res.Z[j])
+
+
+@pytest.mark.parametrize("name", ["soft_rho", "stiff_rho"])
+def test_fused_dual_update_off_unit_rho(batch, name):
+    recs = K.case_set(name)
+    assert np.all(recs[:, obca._E_PAR] != 1.0)
+    _check_dual_update(batch.solve_edge(recs), recs)
+
+
+def _long_and_short():
+    """soft_rho records with a slot that runs all 60 SQP iterations, consistent records (2 each)."""
+    long_ = [rec for rec in K.case_set("soft_rho") if any(r.iters == 60 for _, r in E.solve_record(rec))]
+    short = list(E.case_set("consistent")[:5])
+    assert len(long_) >= 3 and all(r.iters == 2 for rec in short for _, r in E.solve_record(rec))
+    recs, who = [], []
+    for k in range(36):
+        recs.append(long_[k % len(long_)])
+        who.append(("long", k % len(long_)))
+        if k % 3 != 2:          # irregular spacing: long and short solves share workgroups in every arrangement
+            recs.append(short[k % len(short)])
+            who.append(("short", k % len(short)))
+    return long_, short, np.ascontiguousarray(np.stack(recs)), who
+
+
+def test_long_and_short_solves_interleaved(batch):
+    long_, short, recs, who = _long_and_short()
+    alone = {("long", i): batch.solve_edge(np.ascontiguousarray(rec[None])) for i, rec in enumerate(long_)}
+    alone.update({("short", i): batch.solve_edge(np.ascontiguousarray(rec[None])) for i, rec in enumerate(short)})
+    assert all(alone["long", i].iters.max() == 60 for i in range(len(long_)))
+    assert all(alone["short", i].iters.max() == 2 for i in range(len(short)))
+    res = batch.solve_edge(recs)
+    for k, key in enumerate(who):
+        np.testing.assert_array_equal(res.raw[k], alone[key].raw[0], err_msg=f"{k} {key}")
+        np.testing.assert_array_equal(res.status[k], alone[key].status[0])
+        np.testing.assert_array_equal(res.iters[k], alone[key].iters[0])
+        np.testing.assert_array_equal(res.qp_steps[k], alone[key].qp_steps[0])
+
+
+def test_hard_branches_repeat_bit_for_bit(batch):
+    recs = np.concatenate([_long_and_short()[2], K.case_set("tight_mu"), K.case_set("cold_start")])
+    a, b = batch.solve_edge(recs), batch.solve_edge(recs)
+    np.testing.assert_array_equal(a.raw, b.raw)
+    for x, y in ((a.status, b.status), (a.iters, b.iters), (a.qp_steps, b.qp_steps)):
+        np.testing.assert_array_equal(x, y)
 
 
 # ---------------------------------------------------------------------------------------------
