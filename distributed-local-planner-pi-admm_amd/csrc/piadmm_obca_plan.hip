@@ -10,7 +10,8 @@
 //   k_plan_residual     Z_bar / lamb_bar into the state, the residuals, the stop rule, B16's freeze
 //   k_plan_compact      the next active list, in ascending scenario order (one workgroup, a scan)
 // and the host reads back one int, the number of scenarios still active.  k_plan_shift closes an
-// MPC step.  No kernel here waits for another workgroup, keeps a queue or orders anything with
+// MPC step; with a trace attached (piadmm_obca_trace_begin) k_plan_trace and k_plan_clearance then
+// append the step's row to the device-side run record.  No kernel here waits for another workgroup, keeps a queue or orders anything with
 // atomics: the record order of a launch is the ascending scenario order, the same on every run.
 //
 // Layout: one wavefront per item (a local record, a scenario), PW waves per workgroup; waves
@@ -32,6 +33,7 @@
 #include <string>
 #include <vector>
 
+#include "pd_common.h"
 #include "piadmm.h"
 #include "piadmm_obca_handle.h"
 
@@ -313,6 +315,125 @@ __global__ void __launch_bounds__(64) k_plan_shift(int n, double* __restrict__ b
   if (lane == 0) active[s] = s;
 }
 
+// ---------------------------------------------------------------------------------------------
+// The run record ("trace") of an open plan: k_plan_trace copies a closed step's row, and
+// k_plan_clearance measures how close the two vehicles are at the states the row holds.
+// ---------------------------------------------------------------------------------------------
+constexpr int TSUM = 4;     // summary per scenario: min plain clearance, its row, min tightened clearance, sum of iterates
+
+// One wave per scenario: row `row` of the record after k_plan_shift -- the new init_state and, for
+// row >= 1, what the step that was closed left behind (the stop iterate, both status masks, the
+// stopping iterate's residuals and, where kept, the step's lamb_bar).  Row 0 is the state the trace
+// was attached at and has no step.  Pure copies; lane 0 owns the scenario's sum of iterates.
+__global__ void __launch_bounds__(64 * PW) k_plan_trace(int n, int row, const double* __restrict__ bar,
+                                                        const int* __restrict__ iters, const int* __restrict__ mask,
+                                                        const double* __restrict__ primal,
+                                                        const double* __restrict__ dual,
+                                                        const double* __restrict__ lamb,
+                                                        double* __restrict__ t_states, int* __restrict__ t_iters,
+                                                        int* __restrict__ t_mask, double* __restrict__ t_primal,
+                                                        double* __restrict__ t_dual, double* __restrict__ t_lamb,
+                                                        double* __restrict__ summary) {
+  const int lane = threadIdx.x & 63;
+  const int s = blockIdx.x * PW + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (s >= n) return;
+  const size_t N = (size_t)n, S = (size_t)s;
+  if (lane < 10) t_states[((size_t)row * N + S) * 10 + lane] = bar[S * STATE + S_INIT + lane];
+  if (row == 0) {
+    if (lane == 0) summary[S * TSUM + 3] = 0.0;
+    return;
+  }
+  const size_t r = (size_t)(row - 1) * N + S;          // the step's index in the per-step arrays
+  if (lane < 2) t_mask[r * 2 + lane] = mask[2 * S + lane];
+  if (t_lamb)
+    for (int i = lane; i < 126; i += 64) t_lamb[r * 126 + i] = lamb[S * 126 + i];
+  if (lane == 0) {
+    const int it = iters[s];
+    t_iters[r] = it;
+    t_primal[r] = primal[s];
+    t_dual[r] = dual[s];
+    summary[S * TSUM + 3] = summary[S * TSUM + 3] + (double)it;
+  }
+}
+
+// One wave per scenario: the exact minimum distance between the two vehicles' rectangles
+// (generate_vehicle_vertices, util.py:34-42) at the state pair st[2][5] = states + s * stride, for
+// two box sets at once: the plain boxes (centre x, y) and the delay-tightened ones the planner
+// constrains (compute_square_halfspaces_ca_prob, util.py:70-101: each centre moved as halfspaces()
+// above moves it; prob = 0 moves nothing, so both outputs are the plain value).  The distance is 0
+// when no edge normal of either rectangle separates them (SAT over the 4 axes), else the minimum of
+// the 32 vertex-to-edge distances.  Lane = set * 32 + dir * 16 + vertex * 4 + edge: a vertex of
+// vehicle `dir` against an edge of the other vehicle, whose normal (edge & 1: the lateral one) is
+// the lane's SAT axis.  piadmm.obca.clearance is the same statements on the host; products and
+// sums are kept apart (no contraction).  With `summary`, lane 0 keeps the scenario's running
+// minima: row 0 starts them, a later row replaces the plain minimum only when it is smaller, so
+// the row kept is the first at which the minimum was reached.
+__global__ void __launch_bounds__(64 * PW) k_plan_clearance(int n, const double* __restrict__ states, int stride,
+                                                            const int* __restrict__ prob, double sigd, int row,
+                                                            double* __restrict__ out,
+                                                            double* __restrict__ summary) {
+#pragma clang fp contract(off)
+  const int lane = threadIdx.x & 63;
+  const int s = blockIdx.x * PW + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (s >= n) return;
+  const double* st = states + (size_t)s * stride;
+  const int pr = prob[s];
+  const int set = lane >> 5, dir = (lane >> 4) & 1, vi = (lane >> 2) & 3, ej = lane & 3;
+  constexpr double HL = LENGTH / 2, HW = WIDTH / 2;
+  // box a owns the lane's vertex, box o its edge
+  const double* sa = st + dir * 5;
+  const double* so = st + (1 - dir) * 5;
+  const double ca = cos(sa[3]), sna = sin(sa[3]), co = cos(so[3]), sno = sin(so[3]);
+  double ax = sa[0], ay = sa[1], ox = so[0], oy = so[1];
+  if (set == 1 && pr) {
+    const double va = sa[2], vo = so[2];
+    const double qax = VAR_DELAY * va * ca, qay = VAR_DELAY * va * sna;
+    const double qox = VAR_DELAY * vo * co, qoy = VAR_DELAY * vo * sno;
+    const double dax = AVG_DELAY * va * ca + sigd * (qax * qax), day = AVG_DELAY * va * sna + sigd * (qay * qay);
+    const double dox = AVG_DELAY * vo * co + sigd * (qox * qox), doy = AVG_DELAY * vo * sno + sigd * (qoy * qoy);
+    ax = ax + dax;  ay = ay + day;
+    ox = ox + dox;  oy = oy + doy;
+  }
+  // vertex i = centre + sl e + sw n: (+, +), (+, -), (-, -), (-, +)
+  const double pl = vi < 2 ? HL : -HL, pw = (vi == 0 || vi == 3) ? HW : -HW;
+  const double px = ax + pl * ca - pw * sna, py = ay + pl * sna + pw * ca;
+  const int e1 = (ej + 1) & 3;
+  const double al = ej < 2 ? HL : -HL, aw = (ej == 0 || ej == 3) ? HW : -HW;
+  const double bl = e1 < 2 ? HL : -HL, bw = (e1 == 0 || e1 == 3) ? HW : -HW;
+  const double e0x = ox + al * co - aw * sno, e0y = oy + al * sno + aw * co;
+  const double e1x = ox + bl * co - bw * sno, e1y = oy + bl * sno + bw * co;
+  const double abx = e1x - e0x, aby = e1y - e0y, apx = px - e0x, apy = py - e0y;
+  double t = (apx * abx + apy * aby) / (abx * abx + aby * aby);
+  t = fmin(fmax(t, 0.0), 1.0);
+  const double rx = apx - t * abx, ry = apy - t * aby;
+  const double dist = sqrt(rx * rx + ry * ry);
+  // SAT along the edge's normal: |centre distance| against the two half extents
+  const bool lateral = ej & 1;
+  const double ux = lateral ? -sno : co, uy = lateral ? co : sno;
+  const double cdx = ax - ox, cdy = ay - oy;
+  const double pc = fabs(cdx * ux + cdy * uy);
+  const double pe = fabs(ca * ux + sna * uy), pn = fabs(ca * uy - sna * ux);
+  const double gap = pc - ((lateral ? HW : HL) + (HL * pe + HW * pn));
+  // every lane is active here: the reductions are DPP scans over the whole wave
+  const double inf = __builtin_inf();
+  const double g0 = pd::wmax(set == 0 ? gap : -inf), g1 = pd::wmax(set == 1 ? gap : -inf);
+  const double d0 = pd::wmin(set == 0 ? dist : inf), d1 = pd::wmin(set == 1 ? dist : inf);
+  const double plain = g0 > 0.0 ? d0 : 0.0, tight = g1 > 0.0 ? d1 : 0.0;
+  if (lane == 0) {
+    out[(size_t)s * 2] = plain;
+    out[(size_t)s * 2 + 1] = tight;
+    if (summary) {
+      double* S = summary + (size_t)s * TSUM;
+      if (row == 0) {
+        S[0] = plain;  S[1] = 0.0;  S[2] = tight;
+      } else {
+        if (plain < S[0]) { S[0] = plain;  S[1] = (double)row; }
+        if (tight < S[2]) S[2] = tight;
+      }
+    }
+  }
+}
+
 }  // namespace obca_plan
 
 // ---------------------------------------------------------------------------------------------
@@ -331,6 +452,15 @@ struct piadmm_obca_plan_s {
   int *iters = nullptr, *stop = nullptr, *conv = nullptr, *prob = nullptr, *act[2] = {nullptr, nullptr},
       *keep = nullptr, *count = nullptr, *mask = nullptr;
   int* h_count = nullptr;        // pinned: the 4 bytes read back per iterate
+  // the run record (piadmm_obca_trace_begin): rows = MPC steps recorded, row-major over steps.
+  // states / clear hold cap + 1 rows (row 0: where the trace was attached), the rest cap.
+  struct trace_s {
+    bool on = false;
+    int cap = 0, rows = 0, flags = 0;
+    double *states = nullptr, *clear = nullptr, *primal = nullptr, *dual = nullptr, *lamb = nullptr,
+           *summary = nullptr;
+    int *iters = nullptr, *mask = nullptr;
+  } tr;
 };
 
 namespace {
@@ -346,7 +476,16 @@ int pfail(piadmm_obca_t h, int code, const std::string& msg) {
     if (_e != hipSuccess) return pfail(h, PIADMM_E_HIP, std::string(#call ": ") + hipGetErrorString(_e)); \
   } while (0)
 
+void trace_free(piadmm_obca_plan_s* p) {
+  void* d[] = {p->tr.states, p->tr.clear, p->tr.primal, p->tr.dual, p->tr.lamb, p->tr.summary, p->tr.iters,
+               p->tr.mask};
+  for (void* q : d)
+    if (q) (void)hipFree(q);
+  p->tr = piadmm_obca_plan_s::trace_s();
+}
+
 void plan_free_buffers(piadmm_obca_plan_s* p) {
+  trace_free(p);
   void* d[] = {p->bar, p->barp, p->ctrl, p->ctrlp, p->X, p->primal, p->dual, p->pth, p->dth, p->ref, p->lamb,
                p->tab, p->iters, p->stop, p->conv, p->prob, p->act[0], p->act[1], p->keep, p->count, p->mask};
   for (void* q : d)
@@ -418,7 +557,13 @@ int blocks_for(int waves) { return (waves + PW - 1) / PW; }
 }  // namespace
 
 void piadmm_obca_plan_release(piadmm_obca_t h) {
-  if (h->plan) h->plan->open = false;
+  if (!h->plan) return;
+  if (h->plan->tr.on) {
+    (void)hipSetDevice(h->device);
+    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    trace_free(h->plan);
+  }
+  h->plan->open = false;
 }
 
 void piadmm_obca_plan_free(piadmm_obca_t h) {
@@ -493,6 +638,30 @@ int plan_open(piadmm_obca_t h, const piadmm_obca_plan_cfg_t* cfg, const int32_t*
   p->n_last = 0;
   p->cur = 0;
   p->open = true;
+  return 0;
+}
+
+// Enqueues row `row` of the attached trace (0: the state it is attached at; rows + 1: the step
+// k_plan_shift has just closed, on the same stream): the copies, then the clearances of the row's
+// own states.  No synchronisation.
+int trace_append(piadmm_obca_t h, piadmm_obca_plan_s* p, int row) {
+  using namespace obca_plan;
+  auto& t = p->tr;
+  const size_t N = (size_t)p->n;
+  hipLaunchKernelGGL(k_plan_trace, dim3(blocks_for(p->n)), dim3(64 * PW), 0, h->stream, p->n, row, p->bar, p->iters,
+                     p->mask, p->primal, p->dual, p->lamb, t.states, t.iters, t.mask, t.primal, t.dual, t.lamb,
+                     t.summary);
+  PHIP(h, hipGetLastError());
+  hipLaunchKernelGGL(k_plan_clearance, dim3(blocks_for(p->n)), dim3(64 * PW), 0, h->stream, p->n,
+                     t.states + (size_t)row * N * 10, 10, p->prob, p->sigd, row, t.clear + (size_t)row * N * 2,
+                     t.summary);
+  PHIP(h, hipGetLastError());
+  return 0;
+}
+
+int open_trace(piadmm_obca_t h, piadmm_obca_plan_s** out, const char* who) {
+  if (int rc = open_plan(h, out, who)) return rc;
+  if (!(*out)->tr.on) return pfail(h, PIADMM_E_STATE, std::string(who) + ": no trace attached (obca_trace_begin)");
   return 0;
 }
 }  // namespace
@@ -591,12 +760,17 @@ int32_t piadmm_obca_plan_shift(piadmm_obca_t h) {
   if (int rc = open_plan(h, &p, "obca_plan_shift")) return rc;
   if (p->n_act > 0) return pfail(h, PIADMM_E_STATE, "obca_plan_shift: scenarios are still active");
   if (p->i_iter == 0) return pfail(h, PIADMM_E_STATE, "obca_plan_shift: no iterate ran in this step");
+  if (p->tr.on && p->tr.rows >= p->tr.cap) return pfail(h, PIADMM_E_STATE, "obca_plan_shift: trace full");
   PHIP(h, hipSetDevice(h->device));
   // every scenario is active again: the list the next iterate reads is the identity
   hipLaunchKernelGGL(k_plan_shift, dim3(p->n), dim3(64), 0, h->stream, p->n, p->bar, p->barp, p->X, p->lamb, p->ctrlp,
                      p->act[p->cur]);
   PHIP(h, hipGetLastError());
+  if (p->tr.on) {
+    if (int rc = trace_append(h, p, p->tr.rows + 1)) return rc;
+  }
   PHIP(h, hipStreamSynchronize(h->stream));
+  if (p->tr.on) p->tr.rows += 1;
   p->t_step += 1;
   p->i_iter = 0;
   p->n_act = p->n;
@@ -608,6 +782,7 @@ int32_t piadmm_obca_plan_step(piadmm_obca_t h, int32_t* iters_out) {
   piadmm_obca_plan_s* p = nullptr;
   if (int rc = open_plan(h, &p, "obca_plan_step")) return rc;
   if (p->t_step + 8 > p->cfg.n_ref) return pfail(h, PIADMM_E_STATE, "obca_plan_step: reference exhausted");
+  if (p->tr.on && p->tr.rows >= p->tr.cap) return pfail(h, PIADMM_E_STATE, "obca_plan_step: trace full");
   // i_iter > max_admm_iter stops a scenario: at most the largest max_admm_iter + 1 iterates in a step
   while (p->n_act > 0 && p->i_iter <= p->max_iter_all) {
     if (int rc = piadmm_obca_plan_iterate(h, nullptr)) return rc;
@@ -673,6 +848,139 @@ int32_t piadmm_obca_plan_end(piadmm_obca_t h) {
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   piadmm_obca_plan_free(h);
+  return 0;
+}
+
+int32_t piadmm_obca_clearance(piadmm_obca_t h, int32_t n, const double* states, const int32_t* prob, double* out) {
+  using namespace obca_plan;
+  if (!h) return PIADMM_E_ARG;
+  if (n < 1 || n > (1 << 20)) return pfail(h, PIADMM_E_ARG, "obca_clearance: 1 <= n <= 2^20");
+  if (!states || !prob || !out) return pfail(h, PIADMM_E_ARG, "obca_clearance: null argument");
+  for (int k = 0; k < n; ++k) {
+    if (prob[k] != 0 && prob[k] != 1)
+      return pfail(h, PIADMM_E_ARG, "obca_clearance: prob[" + std::to_string(k) + "] must be 0 or 1");
+    for (int i = 0; i < 10; ++i)
+      if (!std::isfinite(states[(size_t)k * 10 + i]))
+        return pfail(h, PIADMM_E_ARG, "obca_clearance: state pair " + std::to_string(k) + " is not finite");
+  }
+  PHIP(h, hipSetDevice(h->device));
+  // the call's own buffers: neither the handle's local and edge buffers nor an open plan is touched
+  double *d_st = nullptr, *d_out = nullptr;
+  int* d_pr = nullptr;
+  const size_t N = (size_t)n;
+  auto run = [&]() -> int {
+    if (int rc = dalloc(h, &d_st, N * 10, false)) return rc;
+    if (int rc = dalloc(h, &d_pr, N, false)) return rc;
+    if (int rc = dalloc(h, &d_out, N * 2, true)) return rc;
+    PHIP(h, hipMemcpyAsync(d_st, states, N * 10 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    PHIP(h, hipMemcpyAsync(d_pr, prob, N * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_plan_clearance, dim3(blocks_for(n)), dim3(64 * PW), 0, h->stream, n, d_st, 10, d_pr,
+                       std::sqrt(0.95 / (1.0 - 0.95)), 0, d_out, (double*)nullptr);
+    PHIP(h, hipGetLastError());
+    PHIP(h, hipMemcpyAsync(out, d_out, N * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    PHIP(h, hipStreamSynchronize(h->stream));
+    return 0;
+  };
+  const int rc = run();
+  if (rc) (void)hipStreamSynchronize(h->stream);
+  if (d_st) (void)hipFree(d_st);
+  if (d_pr) (void)hipFree(d_pr);
+  if (d_out) (void)hipFree(d_out);
+  return rc;
+}
+
+int32_t piadmm_obca_trace_begin(piadmm_obca_t h, int32_t cap_steps, int32_t flags) {
+  using namespace obca_plan;
+  piadmm_obca_plan_s* p = nullptr;
+  if (int rc = open_plan(h, &p, "obca_trace_begin")) return rc;
+  if (cap_steps < 1 || cap_steps > (1 << 20)) return pfail(h, PIADMM_E_ARG, "obca_trace_begin: 1 <= cap_steps <= 2^20");
+  if (flags & ~PIADMM_OBCA_TRACE_LAMBDA) return pfail(h, PIADMM_E_ARG, "obca_trace_begin: unknown flag bits");
+  if (p->i_iter != 0) return pfail(h, PIADMM_E_STATE, "obca_trace_begin: only at a step boundary (an MPC step is open)");
+  PHIP(h, hipSetDevice(h->device));
+  PHIP(h, hipStreamSynchronize(h->stream));
+  trace_free(p);
+  auto& t = p->tr;
+  const size_t N = (size_t)p->n, C = (size_t)cap_steps;
+  int rc = 0;
+  if ((rc = dalloc(h, &t.states, (C + 1) * N * 10, false)) || (rc = dalloc(h, &t.clear, (C + 1) * N * 2, false)) ||
+      (rc = dalloc(h, &t.iters, C * N, false)) || (rc = dalloc(h, &t.mask, C * N * 2, false)) ||
+      (rc = dalloc(h, &t.primal, C * N, false)) || (rc = dalloc(h, &t.dual, C * N, false)) ||
+      (rc = dalloc(h, &t.summary, N * TSUM, true)) ||
+      ((flags & PIADMM_OBCA_TRACE_LAMBDA) && (rc = dalloc(h, &t.lamb, C * N * 126, false)))) {
+    trace_free(p);
+    return rc;
+  }
+  t.cap = cap_steps;
+  t.rows = 0;
+  t.flags = flags;
+  if ((rc = trace_append(h, p, 0))) {
+    (void)hipStreamSynchronize(h->stream);
+    trace_free(p);
+    return rc;
+  }
+  PHIP(h, hipStreamSynchronize(h->stream));
+  t.on = true;
+  return 0;
+}
+
+int32_t piadmm_obca_trace_run(piadmm_obca_t h, int32_t n_steps, int32_t* steps_done) {
+  piadmm_obca_plan_s* p = nullptr;
+  if (steps_done) *steps_done = 0;
+  if (int rc = open_trace(h, &p, "obca_trace_run")) return rc;
+  if (n_steps < 1) return pfail(h, PIADMM_E_ARG, "obca_trace_run: n_steps >= 1");
+  if ((int64_t)p->tr.rows + n_steps > p->tr.cap)
+    return pfail(h, PIADMM_E_STATE, "obca_trace_run: " + std::to_string(n_steps) + " steps do not fit the trace (" +
+                 std::to_string(p->tr.rows) + " of " + std::to_string(p->tr.cap) + " rows used)");
+  if ((int64_t)p->t_step + n_steps - 1 + 8 > p->cfg.n_ref)
+    return pfail(h, PIADMM_E_STATE, "obca_trace_run: the reference ends before " + std::to_string(n_steps) + " steps");
+  // a host loop of the plan's bounded launches: every step ends in piadmm_obca_plan_shift, which appends its row
+  for (int k = 0; k < n_steps; ++k) {
+    if (int rc = piadmm_obca_plan_step(h, nullptr)) return rc;
+    if (steps_done) *steps_done = k + 1;
+  }
+  return 0;
+}
+
+int32_t piadmm_obca_trace_get(piadmm_obca_t h, int32_t what, void* out, int64_t bytes) {
+  using namespace obca_plan;
+  piadmm_obca_plan_s* p = nullptr;
+  if (int rc = open_trace(h, &p, "obca_trace_get")) return rc;
+  const auto& t = p->tr;
+  const int64_t n = p->n, R = t.rows, D = sizeof(double), I = sizeof(int32_t);
+  const void* src = nullptr;
+  int64_t want = -1;
+  switch (what) {
+    case PIADMM_OBCA_TRACE_GET_STATES: src = t.states; want = (R + 1) * n * 10 * D; break;
+    case PIADMM_OBCA_TRACE_GET_CLEARANCE: src = t.clear; want = (R + 1) * n * 2 * D; break;
+    case PIADMM_OBCA_TRACE_GET_ITERS: src = t.iters; want = R * n * I; break;
+    case PIADMM_OBCA_TRACE_GET_STATUS_MASK: src = t.mask; want = R * n * 2 * I; break;
+    case PIADMM_OBCA_TRACE_GET_PRIMAL: src = t.primal; want = R * n * D; break;
+    case PIADMM_OBCA_TRACE_GET_DUAL: src = t.dual; want = R * n * D; break;
+    case PIADMM_OBCA_TRACE_GET_LAMBDA:
+      if (!t.lamb) return pfail(h, PIADMM_E_STATE, "obca_trace_get: the trace keeps no lamb_bar (PIADMM_OBCA_TRACE_LAMBDA)");
+      src = t.lamb; want = R * n * 126 * D; break;
+    case PIADMM_OBCA_TRACE_GET_SUMMARY: src = t.summary; want = n * TSUM * D; break;
+    case PIADMM_OBCA_TRACE_GET_ROWS: want = I; break;
+    default: return pfail(h, PIADMM_E_ARG, "obca_trace_get: unknown item " + std::to_string(what));
+  }
+  if (bytes != want)
+    return pfail(h, PIADMM_E_ARG, "obca_trace_get: item " + std::to_string(what) + " is " + std::to_string(want) +
+                 " bytes, not " + std::to_string(bytes));
+  if (want == 0) return 0;
+  if (!out) return pfail(h, PIADMM_E_ARG, "obca_trace_get: out");
+  if (what == PIADMM_OBCA_TRACE_GET_ROWS) { *static_cast<int32_t*>(out) = t.rows; return 0; }
+  PHIP(h, hipSetDevice(h->device));
+  PHIP(h, hipMemcpyAsync(out, src, (size_t)want, hipMemcpyDeviceToHost, h->stream));
+  PHIP(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int32_t piadmm_obca_trace_end(piadmm_obca_t h) {
+  if (!h) return PIADMM_E_ARG;
+  if (!h->plan || !h->plan->tr.on) return 0;
+  (void)hipSetDevice(h->device);
+  if (h->stream) (void)hipStreamSynchronize(h->stream);
+  trace_free(h->plan);
   return 0;
 }
 

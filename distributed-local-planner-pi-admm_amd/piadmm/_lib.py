@@ -118,6 +118,11 @@ SYMBOLS = [
     ("piadmm_obca_plan_get", c_i32, [_H, c_i32, ctypes.c_void_p, ctypes.c_int64]),
     ("piadmm_obca_plan_end", c_i32, [_H]),
     ("piadmm_obca_fleet_begin", c_i32, [_H, _P(ObcaPlanCfgC), _ip, _dp, _dp, _dp, _dp, _dp]),
+    ("piadmm_obca_clearance", c_i32, [_H, c_i32, _dp, _ip, _dp]),
+    ("piadmm_obca_trace_begin", c_i32, [_H, c_i32, c_i32]),
+    ("piadmm_obca_trace_run", c_i32, [_H, c_i32, _ip]),
+    ("piadmm_obca_trace_get", c_i32, [_H, c_i32, ctypes.c_void_p, ctypes.c_int64]),
+    ("piadmm_obca_trace_end", c_i32, [_H]),
 ]
 
 # PIADMM_OBCA_FLEET_PAR: doubles per parameter row of piadmm_obca_fleet_begin

@@ -89,6 +89,70 @@ def halfspaces(state, prob):
     return A, b0 + A @ (np.array([x, y]) + d)
 
 
+def vehicle_box(state, prob=0, tight=False):
+    """(cx, cy, cos, sin) of a vehicle's rectangle at `state` (generate_vehicle_vertices,
+    util.py:34-42).  tight with prob: the centre moved as `halfspaces` moves it (the delay-tightened
+    box of compute_square_halfspaces_ca_prob, util.py:83-99); the products in the order
+    csrc/piadmm_obca_plan.hip forms them."""
+    x, y, v, th = float(state[0]), float(state[1]), float(state[2]), float(state[3])
+    c, s = math.cos(th), math.sin(th)
+    if tight and prob:
+        sig = math.sqrt(DELAY_PROB / (1.0 - DELAY_PROB))
+        qx, qy = VAR_DELAY * v * c, VAR_DELAY * v * s
+        dx = AVG_DELAY * v * c + sig * (qx * qx)
+        dy = AVG_DELAY * v * s + sig * (qy * qy)
+        x, y = x + dx, y + dy
+    return x, y, c, s
+
+
+def _box_vertex(box, i):
+    """Vertex i of a box: centre + sl e + sw n with the signs (+, +), (+, -), (-, -), (-, +)."""
+    cx, cy, c, s = box
+    sl = LENGTH / 2 if i < 2 else -(LENGTH / 2)
+    sw = WIDTH / 2 if i in (0, 3) else -(WIDTH / 2)
+    return cx + sl * c - sw * s, cy + sl * s + sw * c
+
+
+def box_clearance(box0, box1):
+    """(distance, gap) of two boxes of `vehicle_box`: gap is the largest separation along the 4
+    edge normals (SAT, exact for two rectangles); the distance is 0 when gap <= 0, else the minimum
+    of the 32 vertex-to-edge distances.  The statements of k_plan_clearance, one lane at a time."""
+    boxes = (box0, box1)
+    hl, hw = LENGTH / 2, WIDTH / 2
+    gap, dist = -math.inf, math.inf
+    for dr in (0, 1):
+        a, o = boxes[dr], boxes[1 - dr]
+        ax, ay, ca, sa = a
+        ox, oy, co, so = o
+        for vi in range(4):
+            px, py = _box_vertex(a, vi)
+            for ej in range(4):
+                e0x, e0y = _box_vertex(o, ej)
+                e1x, e1y = _box_vertex(o, (ej + 1) & 3)
+                abx, aby, apx, apy = e1x - e0x, e1y - e0y, px - e0x, py - e0y
+                t = (apx * abx + apy * aby) / (abx * abx + aby * aby)
+                t = min(max(t, 0.0), 1.0)
+                rx, ry = apx - t * abx, apy - t * aby
+                dist = min(dist, math.sqrt(rx * rx + ry * ry))
+                lateral = ej & 1
+                ux, uy = (-so, co) if lateral else (co, so)
+                cdx, cdy = ax - ox, ay - oy
+                pc = abs(cdx * ux + cdy * uy)
+                pe, pn = abs(ca * ux + sa * uy), abs(ca * uy - sa * ux)
+                gap = max(gap, pc - ((hw if lateral else hl) + (hl * pe + hw * pn)))
+    return (dist if gap > 0.0 else 0.0), gap
+
+
+def clearance(state_pair, prob):
+    """(plain, tight): the minimum distance between the two vehicles' rectangles at the state pair
+    (2 x 5), and between their delay-tightened boxes (prob = 0: the plain value twice).  Host
+    restatement of k_plan_clearance (csrc/piadmm_obca_plan.hip)."""
+    sp = np.asarray(state_pair, np.float64).reshape(2, NX)
+    plain = box_clearance(vehicle_box(sp[0]), vehicle_box(sp[1]))[0]
+    tight = box_clearance(vehicle_box(sp[0], prob, True), vehicle_box(sp[1], prob, True))[0]
+    return plain, tight
+
+
 def separating_duals(A_o, u, alpha):
     """lamb_ij of the other vehicle with A_o' lamb_ij = alpha * u (u a unit vector pointing from
     the other vehicle towards this one), the smallest such non-negative vector."""
@@ -470,6 +534,18 @@ class OBCABatch:
         self._check(self._lib.piadmm_obca_edge_solve(self._h, _lib.dptr(recs), n, _lib.dptr(out), _lib.iptr(ist)))
         return OBCAEdgeResult(out, ist)
 
+    def clearance(self, states, prob) -> np.ndarray:
+        """n x 2 (plain, tight) clearances of the state pairs `states` (n x 2 x 5), one launch of
+        k_plan_clearance on the call's own buffers; prob: one value or one per pair."""
+        from . import _lib
+        states = np.ascontiguousarray(states, np.float64)
+        n = states.shape[0] if states.ndim == 3 else 0
+        assert states.shape == (n, 2, NX), states.shape
+        prob = np.ascontiguousarray(np.broadcast_to(np.asarray(prob, np.int32), (n,)))
+        out = np.zeros((n, 2))
+        self._check(self._lib.piadmm_obca_clearance(self._h, n, _lib.dptr(states), _lib.iptr(prob), _lib.dptr(out)))
+        return out
+
     def time_edge(self, recs: np.ndarray, repeats: int) -> float:
         """ms per edge launch over `repeats` launches of `recs` (HIP events)."""
         from . import _lib
@@ -723,6 +799,33 @@ PLAN_GET = {"STATE": (0, np.float64), "STATE_PREV": (1, np.float64), "CTRL": (2,
             "STATUS_MASK": (20, np.int32), "REF": (21, np.float64), "PAR": (22, np.float64)}
 
 
+# piadmm_obca_trace_get items: name -> (code, dtype); piadmm_obca_trace_begin's flag
+TRACE_GET = {"STATES": (0, np.float64), "CLEARANCE": (1, np.float64), "ITERS": (2, np.int32),
+             "STATUS_MASK": (3, np.int32), "PRIMAL": (4, np.float64), "DUAL": (5, np.float64),
+             "LAMBDA": (6, np.float64), "SUMMARY": (7, np.float64), "ROWS": (8, np.int32)}
+TRACE_LAMBDA = 1
+
+
+@dataclasses.dataclass
+class OBCATrace:
+    """The device-side run record of R MPC steps of n scenarios (piadmm_obca_trace_get): states
+    (R + 1) x n x 2 x 5 and clearance (R + 1) x n x 2 (plain, tight) with row 0 where the trace was
+    attached; iters, primal, dual R x n and status_mask R x n x 2 per step; per scenario the
+    smallest plain clearance over the rows, the first row it was reached at and the smallest
+    tightened clearance; lamb R x n x 2 x 7 x 9, or None when it was not kept."""
+    states: np.ndarray
+    clearance: np.ndarray
+    iters: np.ndarray
+    status_mask: np.ndarray
+    primal: np.ndarray
+    dual: np.ndarray
+    min_clearance: np.ndarray
+    min_row: np.ndarray
+    min_clearance_tight: np.ndarray
+    iters_sum: np.ndarray
+    lamb: np.ndarray = None
+
+
 def pack_state(bar, init_state):
     """One scenario's resident state (PLAN_STATE doubles) from a bar_state and its 2 x 5 init_state."""
     parts = dict(bar, init_state=init_state)
@@ -947,3 +1050,67 @@ class OBCADevicePlanner:
         for _ in range(int(n_steps)):
             self.step()
         return self.record
+
+    def trace_begin(self, cap_steps, keep_lambda=True):
+        """Attach a device-side run record of capacity cap_steps to the plan (a step boundary only)."""
+        self._check(self._lib.piadmm_obca_trace_begin(self.batch._h, int(cap_steps),
+                                                      TRACE_LAMBDA if keep_lambda else 0))
+
+    def trace_run(self, n_steps):
+        """n_steps MPC steps on the device, recorded; the number completed."""
+        done = ctypes.c_int32()
+        self._check(self._lib.piadmm_obca_trace_run(self.batch._h, int(n_steps), ctypes.byref(done)))
+        return done.value
+
+    def trace_rows(self):
+        r = np.zeros(1, np.int32)
+        self._check(self._lib.piadmm_obca_trace_get(self.batch._h, TRACE_GET["ROWS"][0], r.ctypes.data, r.nbytes))
+        return int(r[0])
+
+    def trace_get(self, what):
+        """One item of the attached trace (include/piadmm.h, piadmm_obca_trace_get), shaped."""
+        code, dt = TRACE_GET[what]
+        n, R = self.n, (self.trace_rows() if what not in ("ROWS", "SUMMARY") else 0)
+        shape = {"STATES": (R + 1, n, 2, NX), "CLEARANCE": (R + 1, n, 2), "ITERS": (R, n), "STATUS_MASK": (R, n, 2),
+                 "PRIMAL": (R, n), "DUAL": (R, n), "LAMBDA": (R, n, 2, NT, 9), "SUMMARY": (n, 4), "ROWS": (1,)}[what]
+        out = np.zeros(shape, dt)
+        self._check(self._lib.piadmm_obca_trace_get(self.batch._h, code, out.ctypes.data, out.nbytes))
+        return out
+
+    def trace_end(self):
+        self._check(self._lib.piadmm_obca_trace_end(self.batch._h))
+
+    def trace(self, keep_lambda=True):
+        """The attached trace as an OBCATrace."""
+        summary = self.trace_get("SUMMARY")
+        return OBCATrace(states=self.trace_get("STATES"), clearance=self.trace_get("CLEARANCE"),
+                         iters=self.trace_get("ITERS"), status_mask=self.trace_get("STATUS_MASK"),
+                         primal=self.trace_get("PRIMAL"), dual=self.trace_get("DUAL"),
+                         min_clearance=summary[:, 0].copy(), min_row=summary[:, 1].astype(np.int64),
+                         min_clearance_tight=summary[:, 2].copy(), iters_sum=summary[:, 3].astype(np.int64),
+                         lamb=self.trace_get("LAMBDA") if keep_lambda else None)
+
+    def run_traced(self, n_steps, keep_lambda=True):
+        """`run` with the record kept on the device: one piadmm_obca_trace_begin, one
+        piadmm_obca_trace_run of n_steps MPC steps and the downloads at the end, instead of the
+        per-step downloads of `step`.  Fills `record` as `run` does (status_record with the per-step
+        entry of the un-staged `step`; lambda_record only with keep_lambda), advances t_step and
+        init_state, and returns the OBCATrace with the clearances.  Staged stepping stays on `run`."""
+        if self.on_stage is not None:
+            raise ValueError("run_traced does not stage: use run() with on_stage")
+        self.trace_begin(int(n_steps), keep_lambda)
+        self.trace_run(int(n_steps))
+        tr = self.trace(keep_lambda)
+        self.trace_end()
+        for k in range(tr.iters.shape[0]):
+            iters = tr.iters[k].copy()
+            self.init_state = [tr.states[k + 1, s].copy() for s in range(self.n)]
+            self.record.state_record.append(np.stack(self.init_state))
+            self.record.iter_num_record.append(np.asarray(iters, int))
+            if keep_lambda:
+                self.record.lambda_record.append(tr.lamb[k].copy())
+            self.record.status_record.append(dict(t_step=self.t_step, iters=iters.copy(),
+                                                  local_status_mask=tr.status_mask[k, :, 0].copy(),
+                                                  edge_status_mask=tr.status_mask[k, :, 1].copy()))
+            self.t_step += 1
+        return tr

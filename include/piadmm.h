@@ -504,6 +504,64 @@ int32_t piadmm_obca_fleet_begin(piadmm_obca_t h, const piadmm_obca_plan_cfg_t* c
                                 const double* par      /* n x PIADMM_OBCA_FLEET_PAR, may be NULL */,
                                 const double* state    /* n x 556 */);
 
+/* ---- the run record ("trace") of an open plan, and the clearance of a state pair -----------
+ * piadmm_obca_clearance: the exact minimum Euclidean distance between the two vehicles'
+ * rectangles (generate_vehicle_vertices, util.py:34-42: centre x, y, heading state[3], 3.5 x 2.0)
+ * at each of n state pairs, out[k] = {plain, tight}: `plain` for those rectangles, `tight` for the
+ * delay-tightened ones the planner constrains (compute_square_halfspaces_ca_prob, util.py:70-101:
+ * each centre moved by delta_avg + sqrt(p / (1 - p)) delta_var); prob[k] = 0 gives the plain value
+ * twice.  The distance is 0 when no edge normal of either rectangle separates them, else the
+ * minimum of the 32 vertex-to-edge distances.  The call has its own device buffers: the handle's
+ * local and edge buffers and an open plan stay as they are.  Before any device call: 1 <= n <= 2^20,
+ * non-null pointers, prob 0 or 1, every state finite (PIADMM_E_ARG otherwise).
+ *
+ * piadmm_obca_trace_begin attaches a record of capacity cap_steps MPC steps to the open plan
+ * (device arrays; a second call replaces the first) and writes its row 0: every scenario's current
+ * init_state and its clearances.  Only at a step boundary (no iterate of the open step has run):
+ * PIADMM_E_STATE otherwise; cap_steps < 1 (or > 2^20) or unknown flag bits are PIADMM_E_ARG.
+ * flags: PIADMM_OBCA_TRACE_LAMBDA also keeps each step's lamb_bar (126 fp64 per scenario and step).
+ * While a trace is attached piadmm_obca_plan_shift -- called directly, by piadmm_obca_plan_step or
+ * by piadmm_obca_trace_run -- appends one row for the step it closes, on the device: the new
+ * init_state and its clearances, the stop iterate, both status masks, the stopping iterate's
+ * residuals and, with the flag, the step's lamb_bar; each scenario's running minimum clearances are
+ * kept with the row the plain minimum was first reached at.  Nothing is read back for it.  With the
+ * trace full, piadmm_obca_plan_shift and piadmm_obca_plan_step return PIADMM_E_STATE ("trace
+ * full") before any launch and the plan stays as it was.  Without a trace the plan calls are as before.
+ *
+ * piadmm_obca_trace_run runs n_steps MPC steps (piadmm_obca_plan_step each; steps_done, may be
+ * NULL, counts the completed ones).  PIADMM_E_STATE with nothing run when the steps do not fit the
+ * trace (rows + n_steps > cap_steps) or the reference (t_step + n_steps - 1 + 8 > n_ref).
+ *
+ * piadmm_obca_trace_get copies one item; `bytes` must be exact.  R = the steps recorded, n = n_scenarios:
+ *   STATES        (R + 1) x n x 2 x 5 fp64   row 0: where the trace was attached; row r: init_state after step r
+ *   CLEARANCE     (R + 1) x n x 2 fp64       {plain, tight} of the same rows
+ *   ITERS         R x n int32                the iterate each scenario stopped at
+ *   STATUS_MASK   R x n x 2 int32            as PIADMM_OBCA_PLAN_GET_STATUS_MASK, per step
+ *   PRIMAL, DUAL  R x n fp64                 the residuals of each scenario's stopping iterate
+ *   LAMBDA        R x n x 2 x 7 x 9 fp64     as PIADMM_OBCA_PLAN_GET_LAMBDA, per step (PIADMM_E_STATE without the flag)
+ *   SUMMARY       n x 4 fp64                 min plain clearance over the rows, its row (the first such),
+ *                                            min tightened clearance, sum of the stop iterates
+ *   ROWS          1 int32                    R
+ * piadmm_obca_trace_end frees the trace alone; piadmm_obca_plan_end, a new piadmm_obca_plan_begin /
+ * _fleet_begin and any upload that ends the plan free it too.  Every trace call without an open plan
+ * or an attached trace is PIADMM_E_STATE (piadmm_obca_trace_end: 0). */
+#define PIADMM_OBCA_TRACE_LAMBDA 1
+#define PIADMM_OBCA_TRACE_GET_STATES 0
+#define PIADMM_OBCA_TRACE_GET_CLEARANCE 1
+#define PIADMM_OBCA_TRACE_GET_ITERS 2
+#define PIADMM_OBCA_TRACE_GET_STATUS_MASK 3
+#define PIADMM_OBCA_TRACE_GET_PRIMAL 4
+#define PIADMM_OBCA_TRACE_GET_DUAL 5
+#define PIADMM_OBCA_TRACE_GET_LAMBDA 6
+#define PIADMM_OBCA_TRACE_GET_SUMMARY 7
+#define PIADMM_OBCA_TRACE_GET_ROWS 8
+int32_t piadmm_obca_clearance(piadmm_obca_t h, int32_t n, const double* states /* n x 2 x 5 */,
+                              const int32_t* prob /* n */, double* out /* n x 2: plain, tight */);
+int32_t piadmm_obca_trace_begin(piadmm_obca_t h, int32_t cap_steps, int32_t flags);
+int32_t piadmm_obca_trace_run(piadmm_obca_t h, int32_t n_steps, int32_t* steps_done);
+int32_t piadmm_obca_trace_get(piadmm_obca_t h, int32_t what, void* out, int64_t bytes);
+int32_t piadmm_obca_trace_end(piadmm_obca_t h);
+
 #ifdef __cplusplus
 }
 #endif

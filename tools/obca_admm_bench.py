@@ -21,6 +21,13 @@
                    the solves' share of a difference from the glue's.  Written under the keys
                    "fleet" and "fleet_shared_leg" of the same JSON, the other keys kept.
 
+  --trace          instead of the above: the same --steps MPC steps of --scenarios scenarios twice in one
+                   process -- OBCADevicePlanner.run (a piadmm_obca_plan_step and the record's downloads
+                   per step) and run_traced (one piadmm_obca_trace_run, the record and the clearances
+                   kept on the device, downloaded once) -- wall-clock ms per step of each, whether
+                   the two records are equal, and the smallest clearances.  Written under the key
+                   "trace" of the same JSON, the other keys kept.
+
 There is no CPU baseline on an equal footing (the C++ port of the local solver has no edge step);
 the edge launch is reported next to the local launch so the reader sees its share of an iterate.
 Writes one JSON (default profiles/obca_admm_bench.json) and prints it.
@@ -113,9 +120,54 @@ def fleet_main(a):
                           fleet_over_shared_iterate=out["fleet_over_shared_iterate"])))
 
 
+def trace_main(a):
+    """The same --steps MPC steps of --scenarios scenarios twice in one process: OBCADevicePlanner.run
+    (one piadmm_obca_plan_step per step, then the record's downloads) and run_traced (one
+    piadmm_obca_trace_run, the record kept on the device and downloaded once at the end)."""
+    b = obca.OBCABatch(0)
+    n, K = a.scenarios, a.steps
+    kw = dict(prob=[k % 2 for k in range(n)], t_step0=8, max_admm_iter=a.iterates - 1)
+    warm = obca.OBCADevicePlanner(b, n, **kw)
+    warm.step()
+    warm.close()
+    legs, recs = {}, {}
+    for leg in ("run", "run_traced"):
+        dp = obca.OBCADevicePlanner(b, n, **kw)
+        t0 = time.perf_counter()
+        tr = dp.run(K) if leg == "run" else dp.run_traced(K)
+        ms = (time.perf_counter() - t0) * 1e3
+        rec = dp.record
+        dp.close()
+        recs[leg] = rec
+        iters = np.asarray(rec.iter_num_record)
+        legs[leg] = dict(total_ms=ms, step_ms=ms / K, admm_iterates=int(iters.max(axis=1).sum()),
+                         iterate_ms=ms / max(int(iters.max(axis=1).sum()), 1))
+        if leg == "run_traced":
+            legs[leg].update(min_clearance=float(tr.min_clearance.min()),
+                             min_clearance_tight=float(tr.min_clearance_tight.min()),
+                             scenarios_touching=int((tr.min_clearance == 0.0).sum()),
+                             min_row_histogram=np.bincount(tr.min_row, minlength=K + 1).tolist())
+    same = all(np.array_equal(np.asarray(getattr(recs["run"], k)), np.asarray(getattr(recs["run_traced"], k)))
+               for k in ("state_record", "iter_num_record", "lambda_record"))
+    res = dict(scenarios=n, steps=K, max_admm_iter=a.iterates - 1, run=legs["run"], run_traced=legs["run_traced"],
+               traced_over_run_step=legs["run_traced"]["step_ms"] / legs["run"]["step_ms"], records_equal=same)
+    b.close()
+    out = {}
+    if os.path.exists(a.out):
+        with open(a.out) as f:
+            out = json.load(f)
+    out["trace"] = res
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+    print(json.dumps(dict(trace=res)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--fleet", action="store_true")
+    ap.add_argument("--trace", action="store_true")
+    ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--pairs", type=int, default=4096)
     ap.add_argument("--scenarios", type=int, default=2048)
     ap.add_argument("--repeats", type=int, default=10)
@@ -124,6 +176,8 @@ def main():
     a = ap.parse_args()
     if a.fleet:
         return fleet_main(a)
+    if a.trace:
+        return trace_main(a)
     b = obca.OBCABatch(0)
     recs = edge_batch(a.pairs)
     b.time_edge(recs, 1)                                   # warm-up
