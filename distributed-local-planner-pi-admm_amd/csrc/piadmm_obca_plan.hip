@@ -11,7 +11,9 @@
 //   k_plan_compact      the next active list, in ascending scenario order (one workgroup, a scan)
 // and the host reads back one int, the number of scenarios still active.  k_plan_shift closes an
 // MPC step; with a trace attached (piadmm_obca_trace_begin) k_plan_trace and k_plan_clearance then
-// append the step's row to the device-side run record.  No kernel here waits for another workgroup, keeps a queue or orders anything with
+// append the step's row to the device-side run record.  With a dual law attached
+// (piadmm_obca_dual_plan) k_plan_dual_pi runs between k_obca_edge and k_plan_residual and
+// k_plan_dual_shift after k_plan_shift; without one neither is launched.  No kernel here waits for another workgroup, keeps a queue or orders anything with
 // atomics: the record order of a launch is the ascending scenario order, the same on every run.
 //
 // Layout: one wavefront per item (a local record, a scenario), PW waves per workgroup; waves
@@ -316,6 +318,126 @@ __global__ void __launch_bounds__(64) k_plan_shift(int n, double* __restrict__ b
 }
 
 // ---------------------------------------------------------------------------------------------
+// The PI anti-windup dual law (piadmm_obca_dual_plan): the per-edge PI of
+// ADMM_CVX_two_veh_intesection_PI_antiwindup.m:156-188 with a constant proportional gain, on the
+// consensus error of the plan.  Opt-in: without a law neither kernel is launched.
+// ---------------------------------------------------------------------------------------------
+// a gains row (include/piadmm.h)
+constexpr int DPAR = PIADMM_OBCA_DUAL_PAR;
+constexpr int G_KP = 0, G_KI = 1, G_SAT = 2, G_DGAIN = 3, G_WINDUP = 4;
+static_assert(G_WINDUP < DPAR, "gains row layout");
+
+// One wave per active scenario, between k_obca_edge and k_plan_residual: the edge output's
+// lamb_bar_new and its 7 dres partials are overwritten in place with the law's, so k_plan_residual
+// takes them into the state, the residual and the stop rule as it takes the fused update's.  Entry
+// i = lane + 64 j of [vehicle 2][slot 7][9] (two passes); of a slot whose edge solve wrote an answer
+//   e = w - Zb;  S' = S + kI e + d_gain D;  raw = S' + kP e;
+//   lam' = windup ? min(sat, max(raw, -sat)) : raw;  D' = windup ? lam' - raw : 0
+// with w = [local_x, lamb_ij] of the edge record and Zb the rounded Z of the edge output; every
+// other slot keeps lamb_bar, S and D and adds 0 to the residual.  S and D are first copied to
+// S_prev and D_prev: a scenario is only submitted while it has not stopped, so at its stopping
+// iterate the copies are the integrator of the frozen previous state (B16).  The scenario index is
+// wave-uniform, so the gains row and the 7 statuses are uniform loads.  Products and sums are kept
+// apart (no contraction): piadmm.obca.lambda_update_pi is the same statements on the host.
+__global__ void __launch_bounds__(64 * PW) k_plan_dual_pi(const int* __restrict__ active, int n_act,
+                                                          const double* __restrict__ erecs,
+                                                          double* __restrict__ eout, const int* __restrict__ eist,
+                                                          const double* __restrict__ gains, int g_stride,
+                                                          double* __restrict__ S, double* __restrict__ D,
+                                                          double* __restrict__ Sp, double* __restrict__ Dp) {
+#pragma clang fp contract(off)
+  const int lane = threadIdx.x & 63;
+  const int k = blockIdx.x * PW + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (k >= n_act) return;
+  const int s = __builtin_amdgcn_readfirstlane(active[k]);
+  const double* G = gains + (size_t)s * g_stride;
+  const double kP = G[G_KP], kI = G[G_KI], sat = G[G_SAT], d_gain = G[G_DGAIN];
+  const bool windup = G[G_WINDUP] != 0.0;
+  const double* E = erecs + (size_t)k * EREC;
+  double* eo = eout + (size_t)k * EOUT;
+  const int* st = eist + (size_t)k * NT * 3;
+  // the slots whose solve wrote an answer, as bits (the `wrote` rule of the edge kernel)
+  unsigned wrote = 0;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const int c = st[t * 3];
+    if (c == PIADMM_OBCA_CONVERGED || c == PIADMM_OBCA_MAX_ITER || c == PIADMM_OBCA_LINESEARCH_FAIL) wrote |= 1u << t;
+  }
+  double dr0 = 0.0, dr1 = 0.0;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int i = lane + 64 * j;
+    double dr = 0.0;
+    if (i < 126) {
+      const int vt = i / 9, li = i % 9, t = vt % NT;
+      const double w = li < 5 ? E[E_LX + vt * 5 + li] : E[E_LIJ + vt * 4 + (li - 5)];
+      const double zb = eo[EO_ZB + i], lam = E[E_LB + i];
+      const size_t q = (size_t)s * 126 + i;
+      const double S0 = S[q], D0 = D[q];
+      Sp[q] = S0;
+      Dp[q] = D0;
+      double lam1 = lam;
+      if ((wrote >> t) & 1u) {
+        const double e = w - zb;
+        const double S1 = S0 + kI * e + d_gain * D0;
+        const double raw = S1 + kP * e;
+        lam1 = windup ? fmin(sat, fmax(raw, -sat)) : raw;
+        const double D1 = windup ? lam1 - raw : 0.0;
+        S[q] = S1;
+        D[q] = D1;
+      }
+      eo[EO_LBN + i] = lam1;
+      dr = fabs(lam1 - lam);
+    }
+    if (j == 0) dr0 = dr; else dr1 = dr;
+  }
+  // every lane is here again.  Slot t's sum |delta lamb_bar| over its 18 entries in the edge kernel's
+  // lane order (vehicle 0's 9, then vehicle 1's 9): entry i sits in pass i / 64, lane i % 64
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    double dsum = 0.0;
+#pragma unroll
+    for (int c = 0; c < 18; ++c) {
+      const int i = (c / 9) * 63 + t * 9 + c % 9;
+      dsum += __shfl(i < 64 ? dr0 : dr1, i & 63, 64);
+    }
+    if (lane == 0) eo[EO_DRES + t] = dsum;
+  }
+}
+
+// One wave per scenario, after k_plan_shift: the horizon shift of the frozen integrator (S_prev,
+// D_prev: one slot on, the last slot repeated) into both copies, as k_plan_shift does to lamb_bar.
+__global__ void __launch_bounds__(64) k_plan_dual_shift(int n, double* __restrict__ S, double* __restrict__ D,
+                                                        double* __restrict__ Sp, double* __restrict__ Dp) {
+  const int lane = threadIdx.x;
+  const int s = blockIdx.x;
+  if (s >= n) return;
+  const size_t base = (size_t)s * 126;
+  double vs[2], vd[2];
+  // every read first, then every write: the shift reads slot t + 1 of the arrays it overwrites
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int i = lane + 64 * j;
+    vs[j] = vd[j] = 0.0;
+    if (i < 126) {
+      const int v = i / (NT * 9), t = (i % (NT * 9)) / 9, e = i % 9;
+      const int tt = t + 1 < NT ? t + 1 : NT - 1;
+      vs[j] = Sp[base + (v * NT + tt) * 9 + e];
+      vd[j] = Dp[base + (v * NT + tt) * 9 + e];
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int i = lane + 64 * j;
+    if (i < 126) {
+      S[base + i] = vs[j];  Sp[base + i] = vs[j];
+      D[base + i] = vd[j];  Dp[base + i] = vd[j];
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // The run record ("trace") of an open plan: k_plan_trace copies a closed step's row, and
 // k_plan_clearance measures how close the two vehicles are at the states the row holds.
 // ---------------------------------------------------------------------------------------------
@@ -461,6 +583,13 @@ struct piadmm_obca_plan_s {
            *summary = nullptr;
     int *iters = nullptr, *mask = nullptr;
   } tr;
+  // the PI anti-windup dual law (piadmm_obca_dual_plan): rows = 1 with stride 0 or n gains rows;
+  // the integrator S, D and the previous iterate's copy of each, n x 126
+  struct dual_s {
+    bool on = false;
+    int rows = 0, stride = 0;
+    double *par = nullptr, *S = nullptr, *D = nullptr, *Sp = nullptr, *Dp = nullptr;
+  } du;
 };
 
 namespace {
@@ -484,8 +613,16 @@ void trace_free(piadmm_obca_plan_s* p) {
   p->tr = piadmm_obca_plan_s::trace_s();
 }
 
+void dual_free(piadmm_obca_plan_s* p) {
+  void* d[] = {p->du.par, p->du.S, p->du.D, p->du.Sp, p->du.Dp};
+  for (void* q : d)
+    if (q) (void)hipFree(q);
+  p->du = piadmm_obca_plan_s::dual_s();
+}
+
 void plan_free_buffers(piadmm_obca_plan_s* p) {
   trace_free(p);
+  dual_free(p);
   void* d[] = {p->bar, p->barp, p->ctrl, p->ctrlp, p->X, p->primal, p->dual, p->pth, p->dth, p->ref, p->lamb,
                p->tab, p->iters, p->stop, p->conv, p->prob, p->act[0], p->act[1], p->keep, p->count, p->mask};
   for (void* q : d)
@@ -525,6 +662,26 @@ const char* row_check(const double* row) {
   return nullptr;
 }
 
+// One gains row of the dual law: nullptr when it is good, else what is wrong with it.
+const char* dual_row_check(const double* row) {
+  using namespace obca_plan;
+  for (int i = 0; i < DPAR; ++i)
+    if (!std::isfinite(row[i])) return "every entry finite";
+  if (row[G_WINDUP] != 0.0 && row[G_WINDUP] != 1.0) return "windup 0 or 1";
+  if (row[G_WINDUP] == 1.0 && !(row[G_SAT] > 0.0)) return "windup_sat > 0 with windup set";
+  for (int i = G_WINDUP + 1; i < DPAR; ++i)
+    if (row[i] != 0.0) return "the trailing entries must be 0";
+  return nullptr;
+}
+
+int dual_rows_check(piadmm_obca_t h, const double* gains, int rows, int n, const std::string& who) {
+  if (rows != 1 && rows != n) return pfail(h, PIADMM_E_ARG, who + ": rows must be 1 or n (" + std::to_string(n) + ")");
+  for (int k = 0; k < rows; ++k)
+    if (const char* why = dual_row_check(gains + (size_t)k * obca_plan::DPAR))
+      return pfail(h, PIADMM_E_ARG, who + ": row " + std::to_string(k) + ": " + why);
+  return 0;
+}
+
 // what every scenario of a plan shares, and prob
 int shared_check(piadmm_obca_t h, const piadmm_obca_plan_cfg_t& c, const int32_t* prob, const std::string& who) {
   if (c.update_lamb_ij != 0 && c.update_lamb_ij != 1) return pfail(h, PIADMM_E_ARG, who + ": update_lamb_ij 0 or 1");
@@ -558,10 +715,11 @@ int blocks_for(int waves) { return (waves + PW - 1) / PW; }
 
 void piadmm_obca_plan_release(piadmm_obca_t h) {
   if (!h->plan) return;
-  if (h->plan->tr.on) {
+  if (h->plan->tr.on || h->plan->du.on) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     trace_free(h->plan);
+    dual_free(h->plan);
   }
   h->plan->open = false;
 }
@@ -735,6 +893,12 @@ int32_t piadmm_obca_plan_iterate(piadmm_obca_t h, int32_t* n_active_after) {
                      p->tab, p->tab_stride, p->sigd, p->cfg.update_lamb_ij, p->ctrl, p->X, p->conv, h->e_rec);
   PHIP(h, hipGetLastError());
   if (int rc = piadmm_obca_edge_launch(h, m)) return rc;
+  if (p->du.on) {
+    // the law's lamb_bar_new and dres partials replace the fused update's in the edge output
+    hipLaunchKernelGGL(k_plan_dual_pi, dim3(blocks_for(m)), dim3(64 * PW), 0, st, act, m, h->e_rec, h->e_out, h->e_ist,
+                       p->du.par, p->du.stride, p->du.S, p->du.D, p->du.Sp, p->du.Dp);
+    PHIP(h, hipGetLastError());
+  }
   hipLaunchKernelGGL(k_plan_residual, dim3(blocks_for(m)), dim3(64 * PW), 0, st, act, m, i_iter, p->bar, p->barp,
                      p->ctrl, p->ctrlp, h->e_out, h->d_ist, h->e_ist, p->pth, p->dth, p->tab, p->tab_stride, p->primal,
                      p->dual,
@@ -766,6 +930,11 @@ int32_t piadmm_obca_plan_shift(piadmm_obca_t h) {
   hipLaunchKernelGGL(k_plan_shift, dim3(p->n), dim3(64), 0, h->stream, p->n, p->bar, p->barp, p->X, p->lamb, p->ctrlp,
                      p->act[p->cur]);
   PHIP(h, hipGetLastError());
+  if (p->du.on) {
+    hipLaunchKernelGGL(k_plan_dual_shift, dim3(p->n), dim3(64), 0, h->stream, p->n, p->du.S, p->du.D, p->du.Sp,
+                       p->du.Dp);
+    PHIP(h, hipGetLastError());
+  }
   if (p->tr.on) {
     if (int rc = trace_append(h, p, p->tr.rows + 1)) return rc;
   }
@@ -825,6 +994,13 @@ int32_t piadmm_obca_plan_get(piadmm_obca_t h, int32_t what, void* out, int64_t b
     case PIADMM_OBCA_PLAN_GET_STATUS_MASK: src = p->mask; want = 2 * n * I; break;
     case PIADMM_OBCA_PLAN_GET_REF: src = p->ref; want = (int64_t)p->ref_rows * 2 * p->cfg.n_ref * 5 * D; break;
     case PIADMM_OBCA_PLAN_GET_PAR: src = p->tab; want = (int64_t)p->tab_rows * TAB * D; break;
+    case PIADMM_OBCA_PLAN_GET_DUAL_S:
+    case PIADMM_OBCA_PLAN_GET_DUAL_D:
+    case PIADMM_OBCA_PLAN_GET_DUAL_PAR:
+      if (!p->du.on) return pfail(h, PIADMM_E_STATE, "obca_plan_get: no dual law attached (obca_dual_plan)");
+      if (what == PIADMM_OBCA_PLAN_GET_DUAL_PAR) { src = p->du.par; want = (int64_t)p->du.rows * DPAR * D; }
+      else { src = what == PIADMM_OBCA_PLAN_GET_DUAL_S ? p->du.S : p->du.D; want = n * 126 * D; }
+      break;
     case PIADMM_OBCA_PLAN_GET_T_STEP: want = I; break;
     case PIADMM_OBCA_PLAN_GET_COUNTS: want = 3 * I; break;
     default: return pfail(h, PIADMM_E_ARG, "obca_plan_get: unknown item " + std::to_string(what));
@@ -887,6 +1063,121 @@ int32_t piadmm_obca_clearance(piadmm_obca_t h, int32_t n, const double* states, 
   if (d_pr) (void)hipFree(d_pr);
   if (d_out) (void)hipFree(d_out);
   return rc;
+}
+
+int32_t piadmm_obca_dual_plan(piadmm_obca_t h, const double* gains, int32_t rows) {
+  using namespace obca_plan;
+  piadmm_obca_plan_s* p = nullptr;
+  if (int rc = open_plan(h, &p, "obca_dual_plan")) return rc;
+  const bool detach = !gains || rows == 0;
+  if (!detach)
+    if (int rc = dual_rows_check(h, gains, rows, p->n, "obca_dual_plan")) return rc;
+  if (p->i_iter != 0) return pfail(h, PIADMM_E_STATE, "obca_dual_plan: only at a step boundary (an MPC step is open)");
+  PHIP(h, hipSetDevice(h->device));
+  PHIP(h, hipStreamSynchronize(h->stream));
+  dual_free(p);
+  if (detach) return 0;
+  auto& d = p->du;
+  const size_t N = (size_t)p->n, L = 126 * sizeof(double);
+  int rc = 0;
+  if ((rc = dalloc(h, &d.par, (size_t)rows * DPAR, false)) || (rc = dalloc(h, &d.S, N * 126, false)) ||
+      (rc = dalloc(h, &d.Sp, N * 126, false)) || (rc = dalloc(h, &d.D, N * 126, true)) ||
+      (rc = dalloc(h, &d.Dp, N * 126, true))) {
+    dual_free(p);
+    return rc;
+  }
+  // S = lamb_bar of the current state (at a step boundary also the previous one's), D = 0: with
+  // kP = 0, kI = rho and no saturation the law is then the plain update
+  hipError_t e = hipMemcpy(d.par, gains, (size_t)rows * DPAR * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess)
+    e = hipMemcpy2DAsync(d.S, L, p->bar + S_LB, STATE * sizeof(double), L, N, hipMemcpyDeviceToDevice, h->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d.Sp, d.S, N * L, hipMemcpyDeviceToDevice, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(h->stream);
+    dual_free(p);
+    return pfail(h, PIADMM_E_HIP, std::string("obca_dual_plan: ") + hipGetErrorString(e));
+  }
+  d.rows = rows;
+  d.stride = rows > 1 ? DPAR : 0;
+  d.on = true;
+  return 0;
+}
+
+int32_t piadmm_obca_dual_pi(piadmm_obca_t h, int32_t n, const double* w, const double* zb, const double* lamb,
+                            const int32_t* status, const double* gains, int32_t rows, double* S, double* D,
+                            double* lamb_out, double* dres_out) {
+  using namespace obca_plan;
+  if (!h) return PIADMM_E_ARG;
+  if (n < 1 || n > (1 << 20)) return pfail(h, PIADMM_E_ARG, "obca_dual_pi: 1 <= n <= 2^20");
+  if (!w || !zb || !lamb || !status || !gains || !S || !D || !lamb_out || !dres_out)
+    return pfail(h, PIADMM_E_ARG, "obca_dual_pi: null argument");
+  if (int rc = dual_rows_check(h, gains, rows, n, "obca_dual_pi")) return rc;
+  const size_t N = (size_t)n;
+  const double* in[] = {w, zb, lamb, S, D};
+  const char* names[] = {"w", "zb", "lamb", "S", "D"};
+  for (int a = 0; a < 5; ++a)
+    for (size_t i = 0; i < N * 126; ++i)
+      if (!std::isfinite(in[a][i]))
+        return pfail(h, PIADMM_E_ARG, std::string("obca_dual_pi: ") + names[a] + " of scenario " +
+                     std::to_string(i / 126) + " is not finite");
+  // the kernel reads an edge record, an edge output and the slots' statuses: the caller's arrays in
+  // those layouts, scenario k of the identity list
+  std::vector<double> rec(N * EREC, 0.0), out(N * EOUT, 0.0);
+  std::vector<int> ist(N * NT * 3, 0), ident(N);
+  for (size_t k = 0; k < N; ++k) {
+    ident[k] = (int)k;
+    for (int i = 0; i < 126; ++i) {
+      const int vt = i / 9, li = i % 9;
+      rec[k * EREC + (li < 5 ? E_LX + vt * 5 + li : E_LIJ + vt * 4 + (li - 5))] = w[k * 126 + i];
+      rec[k * EREC + E_LB + i] = lamb[k * 126 + i];
+      out[k * EOUT + EO_ZB + i] = zb[k * 126 + i];
+    }
+    for (int t = 0; t < NT; ++t) ist[(k * NT + t) * 3] = status[k * NT + t];
+  }
+  PHIP(h, hipSetDevice(h->device));
+  // the call's own buffers: neither the handle's local and edge buffers nor an open plan is touched
+  double *d_rec = nullptr, *d_out = nullptr, *d_g = nullptr, *d_S = nullptr, *d_D = nullptr, *d_Sp = nullptr,
+         *d_Dp = nullptr;
+  int *d_ist = nullptr, *d_act = nullptr;
+  const size_t B = sizeof(double);
+  auto run = [&]() -> int {
+    if (int rc = dalloc(h, &d_rec, N * EREC, false)) return rc;
+    if (int rc = dalloc(h, &d_out, N * EOUT, false)) return rc;
+    if (int rc = dalloc(h, &d_g, (size_t)rows * DPAR, false)) return rc;
+    if (int rc = dalloc(h, &d_S, N * 126, false)) return rc;
+    if (int rc = dalloc(h, &d_D, N * 126, false)) return rc;
+    if (int rc = dalloc(h, &d_Sp, N * 126, true)) return rc;
+    if (int rc = dalloc(h, &d_Dp, N * 126, true)) return rc;
+    if (int rc = dalloc(h, &d_ist, N * NT * 3, false)) return rc;
+    if (int rc = dalloc(h, &d_act, N, false)) return rc;
+    PHIP(h, hipMemcpyAsync(d_rec, rec.data(), N * EREC * B, hipMemcpyHostToDevice, h->stream));
+    PHIP(h, hipMemcpyAsync(d_out, out.data(), N * EOUT * B, hipMemcpyHostToDevice, h->stream));
+    PHIP(h, hipMemcpyAsync(d_g, gains, (size_t)rows * DPAR * B, hipMemcpyHostToDevice, h->stream));
+    PHIP(h, hipMemcpyAsync(d_S, S, N * 126 * B, hipMemcpyHostToDevice, h->stream));
+    PHIP(h, hipMemcpyAsync(d_D, D, N * 126 * B, hipMemcpyHostToDevice, h->stream));
+    PHIP(h, hipMemcpyAsync(d_ist, ist.data(), N * NT * 3 * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    PHIP(h, hipMemcpyAsync(d_act, ident.data(), N * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_plan_dual_pi, dim3(blocks_for(n)), dim3(64 * PW), 0, h->stream, d_act, n, d_rec, d_out, d_ist,
+                       d_g, rows > 1 ? DPAR : 0, d_S, d_D, d_Sp, d_Dp);
+    PHIP(h, hipGetLastError());
+    PHIP(h, hipMemcpyAsync(out.data(), d_out, N * EOUT * B, hipMemcpyDeviceToHost, h->stream));
+    PHIP(h, hipMemcpyAsync(S, d_S, N * 126 * B, hipMemcpyDeviceToHost, h->stream));
+    PHIP(h, hipMemcpyAsync(D, d_D, N * 126 * B, hipMemcpyDeviceToHost, h->stream));
+    PHIP(h, hipStreamSynchronize(h->stream));
+    return 0;
+  };
+  const int rc = run();
+  if (rc) (void)hipStreamSynchronize(h->stream);
+  void* dev[] = {d_rec, d_out, d_g, d_S, d_D, d_Sp, d_Dp, d_ist, d_act};
+  for (void* q : dev)
+    if (q) (void)hipFree(q);
+  if (rc) return rc;
+  for (size_t k = 0; k < N; ++k) {
+    for (int i = 0; i < 126; ++i) lamb_out[k * 126 + i] = out[k * EOUT + EO_LBN + i];
+    for (int t = 0; t < NT; ++t) dres_out[k * NT + t] = out[k * EOUT + EO_DRES + t];
+  }
+  return 0;
 }
 
 int32_t piadmm_obca_trace_begin(piadmm_obca_t h, int32_t cap_steps, int32_t flags) {

@@ -123,10 +123,14 @@ SYMBOLS = [
     ("piadmm_obca_trace_run", c_i32, [_H, c_i32, _ip]),
     ("piadmm_obca_trace_get", c_i32, [_H, c_i32, ctypes.c_void_p, ctypes.c_int64]),
     ("piadmm_obca_trace_end", c_i32, [_H]),
+    ("piadmm_obca_dual_plan", c_i32, [_H, _dp, c_i32]),
+    ("piadmm_obca_dual_pi", c_i32, [_H, c_i32, _dp, _dp, _dp, _ip, _dp, c_i32, _dp, _dp, _dp, _dp]),
 ]
 
 # PIADMM_OBCA_FLEET_PAR: doubles per parameter row of piadmm_obca_fleet_begin
 FLEET_PAR = 16
+# PIADMM_OBCA_DUAL_PAR: doubles per gains row of piadmm_obca_dual_plan
+DUAL_PAR = 8
 
 # error codes of include/piadmm.h the OBCA bindings name
 E_ARG, E_HIP, E_STATE, E_NODEV = -1, -2, -3, -4

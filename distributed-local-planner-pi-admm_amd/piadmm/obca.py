@@ -385,6 +385,76 @@ def lambda_update(bar, rho):
     return out
 
 
+# a gains row of the PI anti-windup dual law (piadmm_obca_dual_plan, include/piadmm.h)
+DUAL_ROW = ("kP", "kI", "windup_sat", "d_gain", "windup")
+DUAL_PAR = 8                          # doubles per row (PIADMM_OBCA_DUAL_PAR); the rest is zero
+_DUAL_DEFAULT = dict(kP=0.0, kI=1.0, windup_sat=0.0, d_gain=0.0, windup=0)
+
+
+def dual_row(gains):
+    """One gains row (DUAL_PAR doubles) from a dict of DUAL_ROW names (absent: kP 0, kI 1,
+    windup_sat 0, d_gain 0, windup 0) or from a row."""
+    if isinstance(gains, dict):
+        assert set(gains) <= set(DUAL_ROW), set(gains) - set(DUAL_ROW)
+        row = np.zeros(DUAL_PAR)
+        row[:len(DUAL_ROW)] = [float(gains.get(k, _DUAL_DEFAULT[k])) for k in DUAL_ROW]
+        return row
+    row = np.asarray(gains, np.float64)
+    assert row.shape == (DUAL_PAR,), row.shape
+    return row
+
+
+def dual_rows(n, dual):
+    """The gains rows of a plan from dual = dict(kP=, kI=, windup_sat=, d_gain=, windup=), each a
+    scalar or a length-n sequence: one shared row, or n rows when any is a sequence."""
+    import types
+    assert set(dual) <= set(DUAL_ROW), set(dual) - set(DUAL_ROW)
+    ns = types.SimpleNamespace()
+    each = _per_scenario(ns, n, **{k: dual.get(k, _DUAL_DEFAULT[k]) for k in DUAL_ROW})
+    rows = np.zeros((n, DUAL_PAR))
+    for j, k in enumerate(DUAL_ROW):
+        rows[:, j] = getattr(ns, k + "_s")
+    return np.ascontiguousarray(rows if each else rows[:1])
+
+
+def lambda_update_pi(bar, S, D, gains, wrote):
+    """The PI anti-windup dual law on the consensus error, host restatement of k_plan_dual_pi
+    (csrc/piadmm_obca_plan.hip) with the same statements in the same order: for every entry of a
+    slot t with wrote[t]
+        e = w - Z_bar;  S' = S + kI e + d_gain D;  raw = S' + kP e;
+        lam' = windup ? min(sat, max(raw, -sat)) : raw;  D' = windup ? lam' - raw : 0
+    with w = [local_x, lamb_ij]; every other slot keeps lamb_bar, S and D.  bar holds the iterate's
+    local_x, lamb_ij, the new Z_bar and the old lamb_bar; gains is a dict of DUAL_ROW names or a
+    row; wrote 7 booleans.  Returns (bar with the new lamb_bar, S', D', dres): dres[t] = slot t's
+    sum |lam' - lam| over its 18 entries, vehicle 0's 9 and then vehicle 1's 9."""
+    g = dual_row(gains)
+    kP, kI, sat, d_gain, windup = g[0], g[1], g[2], g[3], g[4] != 0.0
+    S, D = np.asarray(S, np.float64), np.asarray(D, np.float64)
+    lam = np.asarray(bar["lamb_bar"], np.float64)
+    wrote = np.asarray(wrote, bool).reshape(NT)
+    e = local_z(bar)[:2] - bar["Z_bar"]
+    S1 = S + kI * e + d_gain * D
+    raw = S1 + kP * e
+    lam1 = np.minimum(sat, np.maximum(raw, -sat)) if windup else raw
+    D1 = lam1 - raw if windup else np.zeros_like(raw)
+    m = wrote[None, :, None]
+    lam1, S1, D1 = np.where(m, lam1, lam), np.where(m, S1, S), np.where(m, D1, D)
+    dr = np.abs(lam1 - lam)
+    dres = np.zeros(NT)
+    for v in (0, 1):
+        for li in range(9):
+            dres = dres + dr[v, :, li]
+    out = {k: v.copy() for k, v in bar.items()}
+    out["lamb_bar"] = lam1
+    return out, S1, D1, dres
+
+
+def shift_dual(S, D):
+    """The receding-horizon shift of the integrator: S and D drop slot 0 and repeat their last
+    slot, as `iterate_next_state` shifts lamb_bar."""
+    return tuple(np.concatenate((a[:, 1:], a[:, -1:]), axis=1) for a in (np.asarray(S), np.asarray(D)))
+
+
 def check_converge(bar, thres, min_dis):
     """`check_converge` (optimizer.py:225-235): the coupled constraints at the exchanged
     halfspaces and lamb_ij."""
@@ -546,6 +616,27 @@ class OBCABatch:
         self._check(self._lib.piadmm_obca_clearance(self._h, n, _lib.dptr(states), _lib.iptr(prob), _lib.dptr(out)))
         return out
 
+    def dual_pi(self, w, zb, lamb, status, gains, S, D):
+        """One launch of k_plan_dual_pi on the call's own buffers (piadmm_obca_dual_pi): w, zb, lamb,
+        S, D n x 2 x 7 x 9, status n x 7, gains one row or n rows of DUAL_PAR.  Returns
+        (lamb_out, S', D', dres n x 7); the arguments stay as they are."""
+        from . import _lib
+        w = np.ascontiguousarray(w, np.float64)
+        n = w.shape[0] if w.ndim == 4 else 0
+        shp = (n, 2, NT, 9)
+        zb, lamb = np.ascontiguousarray(zb, np.float64), np.ascontiguousarray(lamb, np.float64)
+        S, D = np.array(S, np.float64, order="C"), np.array(D, np.float64, order="C")
+        assert w.shape == zb.shape == lamb.shape == S.shape == D.shape == shp, (w.shape, zb.shape, S.shape)
+        status = np.ascontiguousarray(status, np.int32)
+        assert status.shape == (n, NT), status.shape
+        gains = np.ascontiguousarray(np.atleast_2d(np.asarray(gains, np.float64)))
+        assert gains.ndim == 2 and gains.shape[1] == DUAL_PAR, gains.shape
+        lamb_out, dres = np.zeros(shp), np.zeros((n, NT))
+        self._check(self._lib.piadmm_obca_dual_pi(self._h, n, _lib.dptr(w), _lib.dptr(zb), _lib.dptr(lamb),
+                                                  _lib.iptr(status), _lib.dptr(gains), gains.shape[0], _lib.dptr(S),
+                                                  _lib.dptr(D), _lib.dptr(lamb_out), _lib.dptr(dres)))
+        return lamb_out, S, D, dres
+
     def time_edge(self, recs: np.ndarray, repeats: int) -> float:
         """ms per edge launch over `repeats` launches of `recs` (HIP events)."""
         from . import _lib
@@ -659,12 +750,16 @@ class OBCAPlanner:
     Every parameter of FLEET_ROW is one value or one per scenario (`rho_s`, `min_dis_s`, ... keep
     the value of each scenario; the scalar attributes keep a scalar argument and are None for a
     sequence).  specs: one OvertakeSpec per scenario, giving its reference, init_state and seeded
-    state; ref_traj: one reference (2 x n_ref x 5) or one per scenario (`ref_traj_s`)."""
+    state; ref_traj: one reference (2 x n_ref x 5) or one per scenario (`ref_traj_s`).
+
+    dual: None keeps lambda_update; dict(kP=, kI=, windup_sat=, d_gain=, windup=), each one value or
+    one per scenario, replaces it by the PI anti-windup law (`lambda_update_pi`), the integrator
+    shifted with the state (`shift_dual`).  OBCADevicePlanner takes the same argument."""
 
     def __init__(self, batch, n_scenarios, prob=1, t_step0=0, rho=1.0, min_dis=0.1, max_admm_iter=50,
                  primal_thres=0.01, dual_thres=0.01, round_decimals=4, start=1, update_lamb_ij=0, max_iter=60,
                  conv_thres=0.1, on_stage=None, max_x=150.0, max_y=20.0, r=1e4, q=1e5, x_bound=1000.0,
-                 mu_max=100000.0, g_max=1000.0, ref_traj=None, specs=None):
+                 mu_max=100000.0, g_max=1000.0, ref_traj=None, specs=None, dual=None):
         self.batch = batch
         self.n = int(n_scenarios)
         self.prob = [int(prob)] * self.n if np.isscalar(prob) else [int(p) for p in prob]
@@ -687,6 +782,12 @@ class OBCAPlanner:
         self.bar_prev = [seeded_bar_state(self.t_step, p, spec=_spec_of(self, s)) for s, p in enumerate(self.prob)]
         self.init_state = [np.stack([executed_path(v, self.t_step * DT, _spec_of(self, s)) for v in (0, 1)])
                            for s in range(self.n)]
+        # the PI anti-windup dual law (dual=dict(kP=, kI=, windup_sat=, d_gain=, windup=), each one
+        # value or one per scenario): S = lamb_bar, D = 0, as piadmm_obca_dual_plan attaches it
+        self.dual_par = None if dual is None else dual_rows(self.n, dual)
+        if dual is not None:
+            self.dual_S = [b["lamb_bar"].copy() for b in self.bar_prev]
+            self.dual_D = [np.zeros((2, NT, 9)) for _ in range(self.n)]
         self.record = OBCARunRecord()
         self.record.state_record.append(np.stack(self.init_state))
 
@@ -741,15 +842,31 @@ class OBCAPlanner:
             eres = self.batch.solve_edge(erecs)
             self.on_stage("edge", dict(recs=erecs, scenarios=list(active)), dict(result=eres))
             lamb_prev = [bar[s]["lamb_bar"].copy() for s in active]
-            for k, s in enumerate(active):
-                bar[s]["Z_bar"] = eres.Z_bar[k].copy()
-                bar[s]["lamb_bar"] = eres.lamb_bar[k].copy()
+            if self.dual_par is None:
+                for k, s in enumerate(active):
+                    bar[s]["Z_bar"] = eres.Z_bar[k].copy()
+                    bar[s]["lamb_bar"] = eres.lamb_bar[k].copy()
+            else:
+                # the law instead of the fused update: the integrator before this iterate is the
+                # one the previous iterate's bar_state corresponds to (B16)
+                dual_before = {s: (self.dual_S[s], self.dual_D[s]) for s in active}
+                dres_pi = np.zeros((len(active), NT))
+                for k, s in enumerate(active):
+                    bar[s]["Z_bar"] = eres.Z_bar[k].copy()
+                    wrote = [int(c) in EDGE_WRITES_ITERATE for c in eres.status[k]]
+                    bar[s], self.dual_S[s], self.dual_D[s], dres_pi[k] = lambda_update_pi(
+                        bar[s], self.dual_S[s], self.dual_D[s], self.dual_par[s % len(self.dual_par)], wrote)
             self.record.status_record.append(dict(t_step=self.t_step, i_iter=i_iter, scenarios=list(active),
                                                   local_status=res.status.copy(), edge_status=eres.status.copy(),
                                                   if_converge=conv))
             # ---- residuals (:82-86) ----
             primal = np.array([np.abs(ctrl[k] - ctrl_prev[s]).sum() for k, s in enumerate(active)])
-            dual = eres.dual_residual()
+            if self.dual_par is None:
+                dual = eres.dual_residual()
+            else:
+                dual = np.zeros(len(active))
+                for t in range(NT):
+                    dual = dual + dres_pi[:, t]
             stop = ((primal <= self.primal_thres[active]) & (dual <= self.dual_thres[active])) \
                 | (i_iter > self.max_admm_iter_s[active])
             self.on_stage("residual",
@@ -762,6 +879,8 @@ class OBCAPlanner:
                 if stop[k]:
                     iters[s] = i_iter
                     shift_in[s] = bar_prev[s]           # :87: the previous iterate's bar_state (B16)
+                    if self.dual_par is not None:
+                        self.dual_S[s], self.dual_D[s] = dual_before[s]
                 else:
                     bar_prev[s] = self._copy(bar[s])
                     ctrl_prev[s] = ctrl[k]
@@ -769,6 +888,9 @@ class OBCAPlanner:
             active = nxt
         # ---- next time step (:87, :99-103) ----
         self.bar_prev = [iterate_next_state(shift_in[s]) for s in range(n)]
+        if self.dual_par is not None:
+            for s in range(n):
+                self.dual_S[s], self.dual_D[s] = shift_dual(self.dual_S[s], self.dual_D[s])
         self.init_state = [np.stack([X[s][0][1], X[s][1][1]]) for s in range(n)]
         self.on_stage("shift", dict(bar_prev=shift_in, X=X, iters=iters.copy()), dict(bar_next=self.bar_prev, init_state=self.init_state))
         self.record.state_record.append(np.stack(self.init_state))
@@ -796,7 +918,8 @@ PLAN_GET = {"STATE": (0, np.float64), "STATE_PREV": (1, np.float64), "CTRL": (2,
             "LOCAL_REC": (11, np.float64), "LOCAL_OUT": (12, np.float64), "LOCAL_IST": (13, np.int32),
             "EDGE_REC": (14, np.float64), "EDGE_OUT": (15, np.float64), "EDGE_IST": (16, np.int32),
             "T_STEP": (17, np.int32), "LAMBDA": (18, np.float64), "COUNTS": (19, np.int32),
-            "STATUS_MASK": (20, np.int32), "REF": (21, np.float64), "PAR": (22, np.float64)}
+            "STATUS_MASK": (20, np.int32), "REF": (21, np.float64), "PAR": (22, np.float64),
+            "DUAL_S": (23, np.float64), "DUAL_D": (24, np.float64), "DUAL_PAR": (25, np.float64)}
 
 
 # piadmm_obca_trace_get items: name -> (code, dtype); piadmm_obca_trace_begin's flag
@@ -870,7 +993,7 @@ class OBCADevicePlanner:
     def __init__(self, batch, n_scenarios, prob=1, t_step0=0, rho=1.0, min_dis=0.1, max_admm_iter=50,
                  primal_thres=0.01, dual_thres=0.01, round_decimals=4, start=1, update_lamb_ij=0, max_iter=60,
                  conv_thres=0.1, on_stage=None, max_x=150.0, max_y=20.0, r=1e4, q=1e5, x_bound=1000.0,
-                 mu_max=100000.0, g_max=1000.0, ref_traj=None, state=None, specs=None):
+                 mu_max=100000.0, g_max=1000.0, ref_traj=None, state=None, specs=None, dual=None):
         from . import _lib
         self.batch = batch
         self._lib = batch._lib
@@ -930,6 +1053,9 @@ class OBCADevicePlanner:
             self._check(self._lib.piadmm_obca_fleet_begin(batch._h, ctypes.byref(self.cfg), _lib.iptr(prob_a),
                                                           _lib.dptr(self.primal_thres), _lib.dptr(self.dual_thres),
                                                           _lib.dptr(ref), _lib.dptr(self.par), _lib.dptr(state)))
+        self.dual_par = None
+        if dual is not None:
+            self.set_dual(**dual)
         self.record = OBCARunRecord()
         self.record.state_record.append(np.stack(self.init_state))
 
@@ -940,6 +1066,19 @@ class OBCADevicePlanner:
             err = _lib.PiadmmError(f"libpiadmm error {rc}: {msg.decode() if msg else ''}")
             err.code = rc
             raise err
+
+    def set_dual(self, **dual):
+        """Attach the PI anti-windup dual law (piadmm_obca_dual_plan; a step boundary only): kP, kI,
+        windup_sat, d_gain, windup, each one value or one per scenario.  `dual_par` keeps the rows."""
+        from . import _lib
+        rows = dual_rows(self.n, dual)
+        self._check(self._lib.piadmm_obca_dual_plan(self.batch._h, _lib.dptr(rows), rows.shape[0]))
+        self.dual_par = rows
+
+    def clear_dual(self):
+        """Detach the law: the plan runs the plain lambda_update again (a step boundary only)."""
+        self._check(self._lib.piadmm_obca_dual_plan(self.batch._h, None, 0))
+        self.dual_par = None
 
     def counts(self):
         """(scenarios submitted to the last iterate, scenarios still active, iterates run in the open step)."""
@@ -958,7 +1097,8 @@ class OBCADevicePlanner:
                  "LOCAL_OUT": (2 * m, OUT), "LOCAL_IST": (2 * m, 3), "EDGE_REC": (m, EDGE_REC),
                  "EDGE_OUT": (m, EDGE_OUT), "EDGE_IST": (m, NT, 3), "T_STEP": (1,), "LAMBDA": (n, 2, NT, 9),
                  "COUNTS": (3,), "STATUS_MASK": (n, 2), "REF": (rows, 2, self.n_ref, NX),
-                 "PAR": (rows, FLEET_PAR)}[what]
+                 "PAR": (rows, FLEET_PAR), "DUAL_S": (n, 2, NT, 9), "DUAL_D": (n, 2, NT, 9),
+                 "DUAL_PAR": (1 if self.dual_par is None else len(self.dual_par), DUAL_PAR)}[what]
         out = np.zeros(shape, dt)
         self._check(self._lib.piadmm_obca_plan_get(self.batch._h, code, out.ctypes.data, out.nbytes))
         return out

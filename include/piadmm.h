@@ -484,6 +484,9 @@ int32_t piadmm_obca_edge_time(piadmm_obca_t h, const double* recs, int32_t n_pai
 #define PIADMM_OBCA_PLAN_GET_STATUS_MASK 20
 #define PIADMM_OBCA_PLAN_GET_REF 21
 #define PIADMM_OBCA_PLAN_GET_PAR 22
+#define PIADMM_OBCA_PLAN_GET_DUAL_S 23
+#define PIADMM_OBCA_PLAN_GET_DUAL_D 24
+#define PIADMM_OBCA_PLAN_GET_DUAL_PAR 25
 #define PIADMM_OBCA_FLEET_PAR 16
 typedef struct {
   int32_t n_scenarios, t_step0, max_admm_iter, round_decimals, start, update_lamb_ij, max_sqp_iter, n_ref;
@@ -561,6 +564,51 @@ int32_t piadmm_obca_trace_begin(piadmm_obca_t h, int32_t cap_steps, int32_t flag
 int32_t piadmm_obca_trace_run(piadmm_obca_t h, int32_t n_steps, int32_t* steps_done);
 int32_t piadmm_obca_trace_get(piadmm_obca_t h, int32_t what, void* out, int64_t bytes);
 int32_t piadmm_obca_trace_end(piadmm_obca_t h);
+
+/* ---- the PI anti-windup dual law of an open plan --------------------------------------------
+ * The plan's dual update is lamb_bar += rho (w - Z_bar) (optimizer.py:330-335), fused behind the
+ * edge solve.  piadmm_obca_dual_plan attaches a second law to the open plan, the per-edge PI with
+ * back-calculation of ADMM_CVX_two_veh_intesection_PI_antiwindup.m:156-188 with a constant
+ * proportional gain, on the plan's consensus error.  For every entry i of [vehicle 2][slot 7][9]
+ * in a slot whose edge solve wrote an answer (status CONVERGED, MAX_ITER or LINESEARCH_FAIL):
+ *   e    = w[i] - Zb[i]              w = [local_x, lamb_ij] of the edge record, Zb the rounded Z
+ *   S'   = S[i] + kI e + d_gain D[i]
+ *   raw  = S' + kP e
+ *   lam' = windup ? min(sat, max(raw, -sat)) : raw
+ *   D'   = windup ? lam' - raw : 0
+ * products and sums uncontracted; every other slot (any other status value) keeps lamb_bar, S and D
+ * and adds 0 to the dual residual, which is sum |lam' - lam| in the order of the plain path.
+ * A gains row is PIADMM_OBCA_DUAL_PAR doubles: kP, kI, windup_sat, d_gain, windup (0 / 1), 0, 0, 0.
+ * rows = 1 (every scenario reads the one row) or n (one row per scenario).  Checked before any
+ * device call: every entry finite, windup 0 or 1, windup_sat > 0 with windup set, the trailing
+ * entries 0; a bad row is PIADMM_E_ARG with "obca_dual_plan: row k: ..." and the plan, with a law
+ * attached before, stays as it was.  gains NULL or rows 0 detaches the law: the plan is plain again.
+ * Only at a step boundary (no iterate of the open step has run): PIADMM_E_STATE otherwise, as for
+ * piadmm_obca_trace_begin; for a plan of piadmm_obca_plan_begin or of piadmm_obca_fleet_begin alike.
+ * Attaching sets S = lamb_bar of the current state and D = 0, so kP = 0, kI = rho, windup = 0 is
+ * the plain update to rounding.  While attached, every iterate runs one more launch between the
+ * edge solve and the residual, which overwrites lamb_bar_new and the 7 dres partials of the edge
+ * output in place: PIADMM_OBCA_PLAN_GET_EDGE_OUT then shows the law's values in those two fields,
+ * and the state, the dual residual, the stop rule, LAMBDA and the trace follow them.  The horizon
+ * shift takes, as it does for the state (B16), the integrator of the iterate before the stopping
+ * one, one slot on with the last slot repeated.  piadmm_obca_plan_get gains
+ *   DUAL_S, DUAL_D      n x 2 x 7 x 9 fp64   the integrator and the back-calculation term
+ *   DUAL_PAR            rows x PIADMM_OBCA_DUAL_PAR fp64   the gains rows as uploaded
+ * (PIADMM_E_STATE without a law).  piadmm_obca_plan_end, a new piadmm_obca_plan_begin /
+ * _fleet_begin and any upload that ends the plan free the law.  Without a law the plan runs the
+ * launches it ran before.
+ *
+ * piadmm_obca_dual_pi applies the law once to the caller's arrays (w, zb, lamb, S, D and lamb_out
+ * n x 126 in the layout above, status and dres_out n x 7; S and D in / out), one launch of the same
+ * kernel on the call's own device buffers: the handle's buffers and an open plan stay as they are.
+ * Before any device call: 1 <= n <= 2^20, non-null pointers, rows 1 or n, the gains rows as above
+ * ("obca_dual_pi: row k: ..."), every input finite (PIADMM_E_ARG otherwise). */
+#define PIADMM_OBCA_DUAL_PAR 8
+int32_t piadmm_obca_dual_plan(piadmm_obca_t h, const double* gains /* rows x PIADMM_OBCA_DUAL_PAR, may be NULL */,
+                              int32_t rows);
+int32_t piadmm_obca_dual_pi(piadmm_obca_t h, int32_t n, const double* w, const double* zb, const double* lamb,
+                            const int32_t* status /* n x 7 */, const double* gains, int32_t rows,
+                            double* S, double* D, double* lamb_out, double* dres_out /* n x 7 */);
 
 #ifdef __cplusplus
 }

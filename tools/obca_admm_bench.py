@@ -28,6 +28,16 @@
                    the two records are equal, and the smallest clearances.  Written under the key
                    "trace" of the same JSON, the other keys kept.
 
+  --dual-pi        instead of the above, in one process on the shared plan of --scenarios scenarios:
+                   (a) the plain plan and (b) the PI anti-windup law with kP = 0, kI = rho, windup = 0
+                   (the same iterates to rounding, so the difference is the law's extra launch), each
+                   the first MPC step of --repeats fresh plans, wall-clock ms per ADMM iterate, their
+                   ratio and the spread of (a)'s own repeats; (c) one gain set (kP 0.5, kI = rho,
+                   windup_sat 0.5, d_gain 0.5) on obca.overtaking_fleet(--scenarios, seed=0) next to
+                   the plain fleet of the same run over --steps MPC steps: the histogram of stop
+                   iterates, the edge statuses and the smallest clearances.  Information only.
+                   Written under the key "dual_pi" of the same JSON, the other keys kept.
+
 There is no CPU baseline on an equal footing (the C++ port of the local solver has no edge step);
 the edge launch is reported next to the local launch so the reader sees its share of an iterate.
 Writes one JSON (default profiles/obca_admm_bench.json) and prints it.
@@ -163,8 +173,77 @@ def trace_main(a):
     print(json.dumps(dict(trace=res)))
 
 
+def dual_leg(b, n, kw, dual, repeats):
+    """`repeats` timed first MPC steps of fresh plans (a warm-up step first), with or without the
+    law: wall-clock ms per ADMM iterate of each, and the last step's iterates, duals and statuses."""
+    warm = obca.OBCADevicePlanner(b, n, dual=dual, **kw)
+    warm.step()
+    warm.close()
+    ms = []
+    for _ in range(repeats):
+        dp = obca.OBCADevicePlanner(b, n, dual=dual, **kw)
+        t0 = time.perf_counter()
+        dp.step()
+        step_ms = (time.perf_counter() - t0) * 1e3
+        iters = np.asarray(dp.record.iter_num_record[0])
+        lamb = np.asarray(dp.record.lambda_record[0])
+        mask = dp.record.status_record[0]["edge_status_mask"].copy()
+        dp.close()
+        ms.append(step_ms / max(int(iters.max()), 1))
+    return dict(iterate_ms=min(ms), iterate_ms_runs=ms, admm_iterates=int(iters.max()),
+                stop_iterate_counts=np.bincount(iters, minlength=int(iters.max()) + 1).tolist()), iters, lamb, mask
+
+
+def dual_pi_main(a):
+    """--dual-pi: (a) the plain shared plan, (b) the law with kP = 0, kI = rho, windup = 0 on it (the
+    same iterates to rounding: the difference is the extra launch), both timed --repeats times in
+    this process; (c) one gain set on overtaking_fleet(--scenarios, seed 0) next to the plain fleet
+    of this run: stop iterates, statuses and the smallest clearances over --steps MPC steps."""
+    b = obca.OBCABatch(0)
+    n = a.scenarios
+    kw = dict(prob=[k % 2 for k in range(n)], t_step0=8, max_admm_iter=a.iterates - 1)
+    plain, it_a, lam_a, _ = dual_leg(b, n, kw, None, a.repeats)
+    law, it_b, lam_b, _ = dual_leg(b, n, kw, dict(kP=0.0, kI=1.0, windup=0), a.repeats)
+    spread = max(plain["iterate_ms_runs"]) / min(plain["iterate_ms_runs"])
+    ratio = law["iterate_ms"] / plain["iterate_ms"]
+    res = dict(scenarios=n, repeats=a.repeats, max_admm_iter=a.iterates - 1, plain=plain, law_plain_gains=law,
+               law_over_plain_iterate=ratio, plain_spread_max_over_min=spread,
+               ratio_exceeds_plain_spread=bool(ratio > spread),
+               stop_iterates_equal=bool(np.array_equal(it_a, it_b)),
+               max_abs_lamb_bar_difference=float(np.abs(lam_a - lam_b).max()))
+    # (c) information only: one gain set on the fleet, next to the plain fleet of the same run
+    specs, par = obca.overtaking_fleet(n, seed=0)
+    gains = dict(kP=0.5, kI=list(par["rho"]), windup_sat=0.5, d_gain=0.5, windup=1)
+    fleet = {}
+    for name, dual in (("plain", None), ("law", gains)):
+        dp = obca.OBCADevicePlanner(b, n, specs=specs, dual=dual, **dict(kw, **par))
+        tr = dp.run_traced(a.steps, keep_lambda=False)
+        dp.close()
+        edge = np.zeros(5, int)
+        for bit in range(5):
+            edge[bit] = int(((tr.status_mask[:, :, 1] >> bit) & 1).sum())
+        fleet[name] = dict(stop_iterate_histogram=np.bincount(tr.iters.ravel(), minlength=a.iterates + 1).tolist(),
+                           iterates_sum=int(tr.iters_sum.sum()),
+                           steps_with_edge_status=edge.tolist(), status_names=[obca.STATUS[k] for k in range(5)],
+                           min_clearance=float(tr.min_clearance.min()),
+                           min_clearance_tight=float(tr.min_clearance_tight.min()),
+                           scenarios_touching=int((tr.min_clearance == 0.0).sum()))
+    res["fleet"] = dict(steps=a.steps, gains=dict(gains, kI="rho of each scenario"), **fleet)
+    b.close()
+    out = {}
+    if os.path.exists(a.out):
+        with open(a.out) as f:
+            out = json.load(f)
+    out["dual_pi"] = res
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+    print(json.dumps(dict(dual_pi=res)))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--dual-pi", action="store_true")
     ap.add_argument("--fleet", action="store_true")
     ap.add_argument("--trace", action="store_true")
     ap.add_argument("--steps", type=int, default=8)
@@ -174,6 +253,8 @@ def main():
     ap.add_argument("--iterates", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "obca_admm_bench.json"))
     a = ap.parse_args()
+    if a.dual_pi:
+        return dual_pi_main(a)
     if a.fleet:
         return fleet_main(a)
     if a.trace:
