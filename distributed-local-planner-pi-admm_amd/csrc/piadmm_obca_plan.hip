@@ -15,6 +15,10 @@
 // (piadmm_obca_dual_plan) k_plan_dual_pi runs between k_obca_edge and k_plan_residual and
 // k_plan_dual_shift after k_plan_shift; without one neither is launched.  No kernel here waits for another workgroup, keeps a queue or orders anything with
 // atomics: the record order of a launch is the ascending scenario order, the same on every run.
+// With the longest-first order attached (piadmm_obca_order_plan) k_plan_work runs after k_obca_edge
+// and k_plan_order after k_plan_compact and after k_plan_shift: the record order of a launch is then
+// the scenarios by the work of their last solves, a pure function of that record, the same on
+// every run; without it neither is launched.
 //
 // Layout: one wavefront per item (a local record, a scenario), PW waves per workgroup; waves
 // never cooperate, and a wave past the end of its list exits whole at the top.
@@ -556,6 +560,77 @@ __global__ void __launch_bounds__(64 * PW) k_plan_clearance(int n, const double*
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Longest-first scenario order (piadmm_obca_order_plan): k_plan_work keeps what every scenario's
+// solves cost when it last ran, k_plan_order sorts a list by it.  Both launches of an iterate run
+// one wave per problem in list order, so the list's order is the order both solves start in.
+// Opt-in: without it neither kernel is launched and every list is ascending.
+// ---------------------------------------------------------------------------------------------
+constexpr int ORDER_BITS = 21;                       // per key field; scenario indices stay below 2^21
+constexpr int ORDER_CLAMP = (1 << ORDER_BITS) - 1;
+
+// One wave per active scenario, after k_obca_edge (and k_plan_dual_pi, which leaves ist alone):
+// work[s] = (Q, I), the largest QP step count ist[.][2] and the largest SQP iteration count
+// ist[.][1] over the scenario's 2 local and 7 edge solves of this iterate.  Lanes 0-1 read the local
+// triples, lanes 2-8 the edge triples; the counts are non-negative, so the idle lanes' 0 is neutral.
+// A scenario that is not in the list keeps its pair.
+__global__ void __launch_bounds__(64 * PW) k_plan_work(const int* __restrict__ active, int n_act,
+                                                       const int* __restrict__ list, const int* __restrict__ eist,
+                                                       int* __restrict__ work) {
+  const int lane = threadIdx.x & 63;
+  const int k = blockIdx.x * PW + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (k >= n_act) return;
+  const int s = __builtin_amdgcn_readfirstlane(active[k]);
+  int q = 0, it = 0;
+  if (lane < 2 + NT) {
+    const int* t3 = lane < 2 ? list + (size_t)(2 * k + lane) * 3 : eist + ((size_t)k * NT + (lane - 2)) * 3;
+    it = t3[1];
+    q = t3[2];
+  }
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1) {
+    q = max(q, __shfl_xor(q, o, 64));
+    it = max(it, __shfl_xor(it, o, 64));
+  }
+  if (lane == 0) {
+    work[2 * (size_t)s] = q;
+    work[2 * (size_t)s + 1] = it;
+  }
+}
+
+// (Q, I, s) as one key: a greater key sorts earlier.  Q and I are clamped into their 21 bits and
+// the scenario enters as 2^21 - 1 - s, so the keys of distinct scenarios are distinct and equal
+// work is broken by the smaller index.
+__device__ __forceinline__ unsigned long long order_key(const int* __restrict__ work, int s) {
+  const int q = min(max(work[2 * (size_t)s], 0), ORDER_CLAMP), it = min(max(work[2 * (size_t)s + 1], 0), ORDER_CLAMP);
+  return ((unsigned long long)q << (2 * ORDER_BITS)) | ((unsigned long long)it << ORDER_BITS) |
+         (unsigned long long)(ORDER_CLAMP - s);
+}
+
+// list_out = the first c entries of list_in sorted by Q descending, then I descending, then
+// scenario ascending; c = count[0] clamped to [0, m] (read once), or m without a count.  One wave
+// per entry: its position is the number of entries with a greater key, counted by the lanes
+// striding over the list (ballot and popcount, so the position is wave-uniform).  Keys are distinct,
+// so the positions are a permutation of 0..c-1: every slot is written once, by one wave, whatever
+// the order of list_in or of the workgroups; no atomic, no wait.  list_out must not be list_in.
+__global__ void __launch_bounds__(64 * PW) k_plan_order(const int* __restrict__ list_in,
+                                                        const int* __restrict__ count, int m,
+                                                        const int* __restrict__ work, int* __restrict__ list_out) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * PW + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int c = count ? min(max(__builtin_amdgcn_readfirstlane(count[0]), 0), m) : m;
+  if (i >= c) return;
+  const int s = __builtin_amdgcn_readfirstlane(list_in[i]);
+  const unsigned long long mine = order_key(work, s);
+  int rank = 0;
+  for (int start = 0; start < c; start += 64) {
+    const int j = start + lane;
+    const bool greater = j < c && order_key(work, list_in[j]) > mine;
+    rank += __popcll(__ballot(greater));
+  }
+  if (lane == 0) list_out[rank] = s;
+}
+
 }  // namespace obca_plan
 
 // ---------------------------------------------------------------------------------------------
@@ -590,6 +665,12 @@ struct piadmm_obca_plan_s {
     int rows = 0, stride = 0;
     double *par = nullptr, *S = nullptr, *D = nullptr, *Sp = nullptr, *Dp = nullptr;
   } du;
+  // the longest-first order (piadmm_obca_order_plan): work = (Q, I) per scenario, n x 2; tmp = the
+  // unsorted list k_plan_compact / k_plan_shift write and k_plan_order reads, n ints
+  struct order_s {
+    bool on = false;
+    int *work = nullptr, *tmp = nullptr;
+  } ord;
 };
 
 namespace {
@@ -620,9 +701,16 @@ void dual_free(piadmm_obca_plan_s* p) {
   p->du = piadmm_obca_plan_s::dual_s();
 }
 
+void order_free(piadmm_obca_plan_s* p) {
+  if (p->ord.work) (void)hipFree(p->ord.work);
+  if (p->ord.tmp) (void)hipFree(p->ord.tmp);
+  p->ord = piadmm_obca_plan_s::order_s();
+}
+
 void plan_free_buffers(piadmm_obca_plan_s* p) {
   trace_free(p);
   dual_free(p);
+  order_free(p);
   void* d[] = {p->bar, p->barp, p->ctrl, p->ctrlp, p->X, p->primal, p->dual, p->pth, p->dth, p->ref, p->lamb,
                p->tab, p->iters, p->stop, p->conv, p->prob, p->act[0], p->act[1], p->keep, p->count, p->mask};
   for (void* q : d)
@@ -715,11 +803,12 @@ int blocks_for(int waves) { return (waves + PW - 1) / PW; }
 
 void piadmm_obca_plan_release(piadmm_obca_t h) {
   if (!h->plan) return;
-  if (h->plan->tr.on || h->plan->du.on) {
+  if (h->plan->tr.on || h->plan->du.on || h->plan->ord.on) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     trace_free(h->plan);
     dual_free(h->plan);
+    order_free(h->plan);
   }
   h->plan->open = false;
 }
@@ -899,13 +988,23 @@ int32_t piadmm_obca_plan_iterate(piadmm_obca_t h, int32_t* n_active_after) {
                        p->du.par, p->du.stride, p->du.S, p->du.D, p->du.Sp, p->du.Dp);
     PHIP(h, hipGetLastError());
   }
+  if (p->ord.on) {
+    hipLaunchKernelGGL(k_plan_work, dim3(blocks_for(m)), dim3(64 * PW), 0, st, act, m, h->d_ist, h->e_ist, p->ord.work);
+    PHIP(h, hipGetLastError());
+  }
   hipLaunchKernelGGL(k_plan_residual, dim3(blocks_for(m)), dim3(64 * PW), 0, st, act, m, i_iter, p->bar, p->barp,
                      p->ctrl, p->ctrlp, h->e_out, h->d_ist, h->e_ist, p->pth, p->dth, p->tab, p->tab_stride, p->primal,
                      p->dual,
                      p->stop, p->iters, p->mask, p->keep);
   PHIP(h, hipGetLastError());
-  hipLaunchKernelGGL(k_plan_compact, dim3(1), dim3(CT), 0, st, act, p->keep, m, nxt, p->count);
+  // with the order on, the kept entries go to the scratch list and are sorted into the next list
+  hipLaunchKernelGGL(k_plan_compact, dim3(1), dim3(CT), 0, st, act, p->keep, m, p->ord.on ? p->ord.tmp : nxt, p->count);
   PHIP(h, hipGetLastError());
+  if (p->ord.on) {
+    hipLaunchKernelGGL(k_plan_order, dim3(blocks_for(m)), dim3(64 * PW), 0, st, p->ord.tmp, p->count, m, p->ord.work,
+                       nxt);
+    PHIP(h, hipGetLastError());
+  }
   PHIP(h, hipMemcpyAsync(p->h_count, p->count, sizeof(int), hipMemcpyDeviceToHost, st));
   PHIP(h, hipStreamSynchronize(st));
   const int left = *p->h_count;
@@ -926,10 +1025,16 @@ int32_t piadmm_obca_plan_shift(piadmm_obca_t h) {
   if (p->i_iter == 0) return pfail(h, PIADMM_E_STATE, "obca_plan_shift: no iterate ran in this step");
   if (p->tr.on && p->tr.rows >= p->tr.cap) return pfail(h, PIADMM_E_STATE, "obca_plan_shift: trace full");
   PHIP(h, hipSetDevice(h->device));
-  // every scenario is active again: the list the next iterate reads is the identity
+  // every scenario is active again: the list the next iterate reads is the identity, or with the
+  // order on the identity sorted by the work of the step that closes
   hipLaunchKernelGGL(k_plan_shift, dim3(p->n), dim3(64), 0, h->stream, p->n, p->bar, p->barp, p->X, p->lamb, p->ctrlp,
-                     p->act[p->cur]);
+                     p->ord.on ? p->ord.tmp : p->act[p->cur]);
   PHIP(h, hipGetLastError());
+  if (p->ord.on) {
+    hipLaunchKernelGGL(k_plan_order, dim3(blocks_for(p->n)), dim3(64 * PW), 0, h->stream, p->ord.tmp,
+                       (const int*)nullptr, p->n, p->ord.work, p->act[p->cur]);
+    PHIP(h, hipGetLastError());
+  }
   if (p->du.on) {
     hipLaunchKernelGGL(k_plan_dual_shift, dim3(p->n), dim3(64), 0, h->stream, p->n, p->du.S, p->du.D, p->du.Sp,
                        p->du.Dp);
@@ -1001,6 +1106,9 @@ int32_t piadmm_obca_plan_get(piadmm_obca_t h, int32_t what, void* out, int64_t b
       if (what == PIADMM_OBCA_PLAN_GET_DUAL_PAR) { src = p->du.par; want = (int64_t)p->du.rows * DPAR * D; }
       else { src = what == PIADMM_OBCA_PLAN_GET_DUAL_S ? p->du.S : p->du.D; want = n * 126 * D; }
       break;
+    case PIADMM_OBCA_PLAN_GET_WORK:
+      if (!p->ord.on) return pfail(h, PIADMM_E_STATE, "obca_plan_get: no order attached (obca_order_plan)");
+      src = p->ord.work; want = n * 2 * I; break;
     case PIADMM_OBCA_PLAN_GET_T_STEP: want = I; break;
     case PIADMM_OBCA_PLAN_GET_COUNTS: want = 3 * I; break;
     default: return pfail(h, PIADMM_E_ARG, "obca_plan_get: unknown item " + std::to_string(what));
@@ -1178,6 +1286,99 @@ int32_t piadmm_obca_dual_pi(piadmm_obca_t h, int32_t n, const double* w, const d
     for (int t = 0; t < NT; ++t) dres_out[k * NT + t] = out[k * EOUT + EO_DRES + t];
   }
   return 0;
+}
+
+int32_t piadmm_obca_order_plan(piadmm_obca_t h, int32_t mode, const int32_t* work_init) {
+  using namespace obca_plan;
+  piadmm_obca_plan_s* p = nullptr;
+  if (int rc = open_plan(h, &p, "obca_order_plan")) return rc;
+  if (mode != 0 && mode != 1) return pfail(h, PIADMM_E_ARG, "obca_order_plan: mode 0 (detach) or 1 (attach)");
+  const int n = p->n;
+  if (mode == 1) {
+    if (n > ORDER_CLAMP) return pfail(h, PIADMM_E_ARG, "obca_order_plan: n_scenarios < 2^21");
+    if (work_init)
+      for (int k = 0; k < n; ++k)
+        if (work_init[2 * (size_t)k] < 0 || work_init[2 * (size_t)k + 1] < 0)
+          return pfail(h, PIADMM_E_ARG, "obca_order_plan: row " + std::to_string(k) + ": work_init >= 0");
+  }
+  if (p->i_iter != 0) return pfail(h, PIADMM_E_STATE, "obca_order_plan: only at a step boundary (an MPC step is open)");
+  PHIP(h, hipSetDevice(h->device));
+  PHIP(h, hipStreamSynchronize(h->stream));
+  // at a step boundary every scenario is active: the current list is all n of them
+  const size_t N = (size_t)n;
+  std::vector<int> ident(N);
+  for (int k = 0; k < n; ++k) ident[k] = k;
+  if (mode == 0) {
+    if (p->ord.on) PHIP(h, hipMemcpy(p->act[p->cur], ident.data(), N * sizeof(int), hipMemcpyHostToDevice));
+    order_free(p);
+    return 0;
+  }
+  int *work = nullptr, *tmp = nullptr;
+  hipError_t e = hipMalloc(&work, 2 * N * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc(&tmp, N * sizeof(int));
+  if (e == hipSuccess)
+    e = work_init ? hipMemcpy(work, work_init, 2 * N * sizeof(int), hipMemcpyHostToDevice)
+                  : hipMemset(work, 0, 2 * N * sizeof(int));
+  if (e == hipSuccess) e = hipMemcpy(tmp, ident.data(), N * sizeof(int), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    // the current list re-sorted at once (zero work: ascending, as it was)
+    hipLaunchKernelGGL(k_plan_order, dim3(blocks_for(n)), dim3(64 * PW), 0, h->stream, tmp, (const int*)nullptr, n, work,
+                       p->act[p->cur]);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(h->stream);
+    if (work) (void)hipFree(work);
+    if (tmp) (void)hipFree(tmp);
+    return pfail(h, PIADMM_E_HIP, std::string("obca_order_plan: ") + hipGetErrorString(e));
+  }
+  order_free(p);
+  p->ord.work = work;
+  p->ord.tmp = tmp;
+  p->ord.on = true;
+  return 0;
+}
+
+int32_t piadmm_obca_order(piadmm_obca_t h, const int32_t* list, int32_t m, const int32_t* work, int32_t n,
+                          int32_t* out) {
+  using namespace obca_plan;
+  if (!h) return PIADMM_E_ARG;
+  if (n < 1 || n > ORDER_CLAMP) return pfail(h, PIADMM_E_ARG, "obca_order: 1 <= n < 2^21");
+  if (m < 1 || m > n) return pfail(h, PIADMM_E_ARG, "obca_order: 1 <= m <= n");
+  if (!list || !work || !out) return pfail(h, PIADMM_E_ARG, "obca_order: null argument");
+  std::vector<char> seen((size_t)n, 0);
+  for (int k = 0; k < m; ++k) {
+    if (list[k] < 0 || list[k] >= n || seen[(size_t)list[k]])
+      return pfail(h, PIADMM_E_ARG, "obca_order: list[" + std::to_string(k) + "] must be a scenario below n, listed once");
+    seen[(size_t)list[k]] = 1;
+  }
+  for (int k = 0; k < n; ++k)
+    if (work[2 * (size_t)k] < 0 || work[2 * (size_t)k + 1] < 0)
+      return pfail(h, PIADMM_E_ARG, "obca_order: row " + std::to_string(k) + ": work >= 0");
+  PHIP(h, hipSetDevice(h->device));
+  // the call's own buffers: neither the handle's local and edge buffers nor an open plan is touched
+  int *d_in = nullptr, *d_work = nullptr, *d_out = nullptr;
+  const size_t M = (size_t)m, N = (size_t)n;
+  auto run = [&]() -> int {
+    if (int rc = dalloc(h, &d_in, M, false)) return rc;
+    if (int rc = dalloc(h, &d_work, 2 * N, false)) return rc;
+    if (int rc = dalloc(h, &d_out, M, true)) return rc;
+    PHIP(h, hipMemcpyAsync(d_in, list, M * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    PHIP(h, hipMemcpyAsync(d_work, work, 2 * N * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_plan_order, dim3(blocks_for(m)), dim3(64 * PW), 0, h->stream, d_in, (const int*)nullptr, m,
+                       d_work, d_out);
+    PHIP(h, hipGetLastError());
+    PHIP(h, hipMemcpyAsync(out, d_out, M * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    PHIP(h, hipStreamSynchronize(h->stream));
+    return 0;
+  };
+  const int rc = run();
+  if (rc) (void)hipStreamSynchronize(h->stream);
+  if (d_in) (void)hipFree(d_in);
+  if (d_work) (void)hipFree(d_work);
+  if (d_out) (void)hipFree(d_out);
+  return rc;
 }
 
 int32_t piadmm_obca_trace_begin(piadmm_obca_t h, int32_t cap_steps, int32_t flags) {

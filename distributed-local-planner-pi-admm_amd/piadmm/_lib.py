@@ -125,6 +125,8 @@ SYMBOLS = [
     ("piadmm_obca_trace_end", c_i32, [_H]),
     ("piadmm_obca_dual_plan", c_i32, [_H, _dp, c_i32]),
     ("piadmm_obca_dual_pi", c_i32, [_H, c_i32, _dp, _dp, _dp, _ip, _dp, c_i32, _dp, _dp, _dp, _dp]),
+    ("piadmm_obca_order_plan", c_i32, [_H, c_i32, _ip]),
+    ("piadmm_obca_order", c_i32, [_H, _ip, c_i32, _ip, c_i32, _ip]),
 ]
 
 # PIADMM_OBCA_FLEET_PAR: doubles per parameter row of piadmm_obca_fleet_begin

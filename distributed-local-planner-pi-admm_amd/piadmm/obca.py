@@ -455,6 +455,32 @@ def shift_dual(S, D):
     return tuple(np.concatenate((a[:, 1:], a[:, -1:]), axis=1) for a in (np.asarray(S), np.asarray(D)))
 
 
+# the longest-first order of a plan (piadmm_obca_order_plan, include/piadmm.h): Q and I are compared
+# after clamping to ORDER_CLAMP, the 21 bits each has in the device's key
+ORDER_CLAMP = (1 << 21) - 1
+
+
+def plan_order(lst, work):
+    """The order k_plan_order (csrc/piadmm_obca_plan.hip) puts a list of scenarios in: by
+    work[s] = (Q, I), Q descending, then I descending, then scenario ascending, Q and I clamped to
+    [0, ORDER_CLAMP].  A function of the set in `lst` and of `work` (n x 2) alone."""
+    lst = np.asarray(lst, np.int64).reshape(-1)
+    w = np.clip(np.asarray(work, np.int64).reshape(-1, 2), 0, ORDER_CLAMP)
+    idx = np.lexsort((lst, -w[lst, 1], -w[lst, 0]))
+    return lst[idx].astype(np.int32)
+
+
+def plan_work(local_ist, edge_ist):
+    """The work record k_plan_work keeps of one iterate: for the m scenarios submitted, (Q, I) =
+    (the largest QP step count ist[.][2], the largest SQP iteration count ist[.][1]) over the
+    scenario's 2 local (local_ist 2m x 3, record 2k + v) and 7 edge solves (edge_ist m x 7 x 3)."""
+    li, ei = np.asarray(local_ist, np.int32), np.asarray(edge_ist, np.int32)
+    m = ei.shape[0]
+    assert li.shape == (2 * m, 3) and ei.shape == (m, NT, 3), (li.shape, ei.shape)
+    both = np.concatenate((li.reshape(m, 2, 3), ei), axis=1)
+    return np.ascontiguousarray(np.stack((both[:, :, 2].max(axis=1), both[:, :, 1].max(axis=1)), axis=1), np.int32)
+
+
 def check_converge(bar, thres, min_dis):
     """`check_converge` (optimizer.py:225-235): the coupled constraints at the exchanged
     halfspaces and lamb_ij."""
@@ -636,6 +662,18 @@ class OBCABatch:
                                                   _lib.iptr(status), _lib.dptr(gains), gains.shape[0], _lib.dptr(S),
                                                   _lib.dptr(D), _lib.dptr(lamb_out), _lib.dptr(dres)))
         return lamb_out, S, D, dres
+
+    def order(self, lst, work) -> np.ndarray:
+        """One launch of k_plan_order on the call's own buffers (piadmm_obca_order): the m distinct
+        scenarios of `lst` sorted by `work` (n x 2), as `plan_order` states it."""
+        from . import _lib
+        lst = np.ascontiguousarray(lst, np.int32).reshape(-1)
+        work = np.ascontiguousarray(work, np.int32)
+        assert work.ndim == 2 and work.shape[1] == 2, work.shape
+        out = np.zeros(len(lst), np.int32)
+        self._check(self._lib.piadmm_obca_order(self._h, _lib.iptr(lst), len(lst), _lib.iptr(work), work.shape[0],
+                                                _lib.iptr(out)))
+        return out
 
     def time_edge(self, recs: np.ndarray, repeats: int) -> float:
         """ms per edge launch over `repeats` launches of `recs` (HIP events)."""
@@ -919,7 +957,8 @@ PLAN_GET = {"STATE": (0, np.float64), "STATE_PREV": (1, np.float64), "CTRL": (2,
             "EDGE_REC": (14, np.float64), "EDGE_OUT": (15, np.float64), "EDGE_IST": (16, np.int32),
             "T_STEP": (17, np.int32), "LAMBDA": (18, np.float64), "COUNTS": (19, np.int32),
             "STATUS_MASK": (20, np.int32), "REF": (21, np.float64), "PAR": (22, np.float64),
-            "DUAL_S": (23, np.float64), "DUAL_D": (24, np.float64), "DUAL_PAR": (25, np.float64)}
+            "DUAL_S": (23, np.float64), "DUAL_D": (24, np.float64), "DUAL_PAR": (25, np.float64),
+            "WORK": (26, np.int32)}
 
 
 # piadmm_obca_trace_get items: name -> (code, dtype); piadmm_obca_trace_begin's flag
@@ -988,12 +1027,18 @@ class OBCADevicePlanner:
     With `specs`, a reference per scenario (ref_traj n x 2 x n_ref x 5) or a sequence for any
     parameter of FLEET_ROW the plan is a fleet (`self.fleet`): it is opened by
     piadmm_obca_fleet_begin with one reference and one parameter row (`par`) per scenario.
-    Otherwise it is opened by piadmm_obca_plan_begin, as ever."""
+    Otherwise it is opened by piadmm_obca_plan_begin, as ever.
+
+    With order=True every active list is kept longest first by the work of each scenario's last
+    solves (piadmm_obca_order_plan; `work_init` n x 2 seeds the record, `work()` reads it): the
+    per-scenario results are the same bit for bit, ACTIVE and the LOCAL_ / EDGE_ items follow the
+    list's order."""
 
     def __init__(self, batch, n_scenarios, prob=1, t_step0=0, rho=1.0, min_dis=0.1, max_admm_iter=50,
                  primal_thres=0.01, dual_thres=0.01, round_decimals=4, start=1, update_lamb_ij=0, max_iter=60,
                  conv_thres=0.1, on_stage=None, max_x=150.0, max_y=20.0, r=1e4, q=1e5, x_bound=1000.0,
-                 mu_max=100000.0, g_max=1000.0, ref_traj=None, state=None, specs=None, dual=None):
+                 mu_max=100000.0, g_max=1000.0, ref_traj=None, state=None, specs=None, dual=None, order=False,
+                 work_init=None):
         from . import _lib
         self.batch = batch
         self._lib = batch._lib
@@ -1056,8 +1101,32 @@ class OBCADevicePlanner:
         self.dual_par = None
         if dual is not None:
             self.set_dual(**dual)
+        self.order = False
+        if order:
+            self.set_order(work_init)
+        else:
+            assert work_init is None, "work_init seeds the order's record: pass order=True"
         self.record = OBCARunRecord()
         self.record.state_record.append(np.stack(self.init_state))
+
+    def set_order(self, work_init=None):
+        """Attach the longest-first order (piadmm_obca_order_plan; a step boundary only), its record
+        zero or seeded with work_init (n x 2: Q, I per scenario)."""
+        from . import _lib
+        if work_init is not None:
+            work_init = np.ascontiguousarray(work_init, np.int32)
+            assert work_init.shape == (self.n, 2), work_init.shape
+        self._check(self._lib.piadmm_obca_order_plan(self.batch._h, 1, _lib.iptr(work_init)))
+        self.order = True
+
+    def clear_order(self):
+        """Detach the order: every list is ascending again (a step boundary only)."""
+        self._check(self._lib.piadmm_obca_order_plan(self.batch._h, 0, None))
+        self.order = False
+
+    def work(self):
+        """The order's record (Q, I) per scenario, n x 2 (PLAN_GET WORK)."""
+        return self.get("WORK")
 
     def _check(self, rc):
         from . import _lib
@@ -1098,7 +1167,7 @@ class OBCADevicePlanner:
                  "EDGE_OUT": (m, EDGE_OUT), "EDGE_IST": (m, NT, 3), "T_STEP": (1,), "LAMBDA": (n, 2, NT, 9),
                  "COUNTS": (3,), "STATUS_MASK": (n, 2), "REF": (rows, 2, self.n_ref, NX),
                  "PAR": (rows, FLEET_PAR), "DUAL_S": (n, 2, NT, 9), "DUAL_D": (n, 2, NT, 9),
-                 "DUAL_PAR": (1 if self.dual_par is None else len(self.dual_par), DUAL_PAR)}[what]
+                 "DUAL_PAR": (1 if self.dual_par is None else len(self.dual_par), DUAL_PAR), "WORK": (n, 2)}[what]
         out = np.zeros(shape, dt)
         self._check(self._lib.piadmm_obca_plan_get(self.batch._h, code, out.ctypes.data, out.nbytes))
         return out

@@ -431,6 +431,7 @@ int32_t piadmm_obca_edge_time(piadmm_obca_t h, const double* recs, int32_t n_pai
  *   X                   n x 2 x 8 x 5 fp64   the last local solution of each scenario
  *   ITERS               n int32          the iterate each scenario stopped at (0: still active)
  *   ACTIVE              m int32          the scenarios submitted to the last iterate, ascending
+ *                       (longest first with piadmm_obca_order_plan attached, below)
  *   PRIMAL, DUAL        n fp64           the residuals of each scenario's last iterate
  *   STOP, CONVERGE      n int32          the stop decision / check_converge of its last iterate
  *   LOCAL_REC / _OUT / _IST   2m x PIADMM_OBCA_REC / 2m x PIADMM_OBCA_OUT fp64 / 2m x 3 int32
@@ -487,6 +488,7 @@ int32_t piadmm_obca_edge_time(piadmm_obca_t h, const double* recs, int32_t n_pai
 #define PIADMM_OBCA_PLAN_GET_DUAL_S 23
 #define PIADMM_OBCA_PLAN_GET_DUAL_D 24
 #define PIADMM_OBCA_PLAN_GET_DUAL_PAR 25
+#define PIADMM_OBCA_PLAN_GET_WORK 26
 #define PIADMM_OBCA_FLEET_PAR 16
 typedef struct {
   int32_t n_scenarios, t_step0, max_admm_iter, round_decimals, start, update_lamb_ij, max_sqp_iter, n_ref;
@@ -609,6 +611,44 @@ int32_t piadmm_obca_dual_plan(piadmm_obca_t h, const double* gains /* rows x PIA
 int32_t piadmm_obca_dual_pi(piadmm_obca_t h, int32_t n, const double* w, const double* zb, const double* lamb,
                             const int32_t* status /* n x 7 */, const double* gains, int32_t rows,
                             double* S, double* D, double* lamb_out, double* dres_out /* n x 7 */);
+
+/* ---- longest-first scenario order inside an open plan ----------------------------------------
+ * Both solves of an iterate run one wavefront per problem in the order of the active list, and a
+ * launch lasts as long as its longest wave: a solve that runs to the SQP cap and starts last adds
+ * its whole length to the launch, started first it hides behind the rest.  Every scenario's answer
+ * is independent of its place in the list (bit for bit), so the list may be put in any order.
+ *
+ * piadmm_obca_order_plan, mode 1, attaches the order to the open plan: a record work[s] = (Q, I)
+ * per scenario, Q the largest QP step count and I the largest SQP iteration count (ist[.][2] and
+ * ist[.][1]) over the scenario's 2 local and 7 edge solves of the last iterate it was active in,
+ * kept on the device by one more launch per iterate; a scenario that did not run keeps its pair.
+ * The record starts at 0, or at work_init (n x 2: what an earlier run of the same fleet left in
+ * PIADMM_OBCA_PLAN_GET_WORK schedules the first step).  While attached, every active list -- the
+ * one the compaction leaves for the next iterate and the full one piadmm_obca_plan_shift leaves
+ * for the next step -- is sorted on the device by
+ *   Q descending, then I descending, then scenario ascending
+ * (Q and I compared after clamping to 2^21 - 1), a strict total order: the list is a function of
+ * the set of scenarios in it and of the record alone, the same on every run.  No position is
+ * decided by an atomic; no kernel waits for another workgroup.  PIADMM_OBCA_PLAN_GET_ACTIVE and
+ * the LOCAL_ / EDGE_ items then follow that order instead of the ascending one; every per-scenario
+ * item, the trace and the dual law are unchanged, bit for bit.  The 4 bytes read back per iterate
+ * stay the only ones.  Attaching sorts the current list at once (zero work: ascending, no change).
+ * mode 0 detaches: the list is ascending again, the record is freed and the plan runs the launches
+ * it ran before.  Checked before any device call: an open plan (PIADMM_E_STATE), mode 0 or 1,
+ * work_init >= 0 ("obca_order_plan: row k: ..."), n_scenarios < 2^21 (PIADMM_E_ARG), and a step
+ * boundary (no iterate of the open step has run: PIADMM_E_STATE); a refused call leaves the plan as
+ * it was.  piadmm_obca_plan_get gains
+ *   WORK                n x 2 int32      the record (Q, I) per scenario (PIADMM_E_STATE without the order)
+ * piadmm_obca_plan_end, a new piadmm_obca_plan_begin / _fleet_begin and any upload that ends the
+ * plan free the record.
+ *
+ * piadmm_obca_order sorts the caller's list (m distinct scenarios below n) by the caller's work
+ * (n x 2) into out (m), one launch of the same kernel on the call's own device buffers: the
+ * handle's buffers and an open plan stay as they are.  Before any device call: 1 <= m <= n < 2^21,
+ * non-null pointers, every list entry a scenario below n and listed once, work >= 0 (PIADMM_E_ARG). */
+int32_t piadmm_obca_order_plan(piadmm_obca_t h, int32_t mode, const int32_t* work_init /* n x 2, may be NULL */);
+int32_t piadmm_obca_order(piadmm_obca_t h, const int32_t* list /* m */, int32_t m, const int32_t* work /* n x 2 */,
+                          int32_t n, int32_t* out /* m */);
 
 #ifdef __cplusplus
 }

@@ -38,6 +38,18 @@
                    iterates, the edge statuses and the smallest clearances.  Information only.
                    Written under the key "dual_pi" of the same JSON, the other keys kept.
 
+  --order          instead of the above, in one process at --scenarios scenarios over --steps MPC steps
+                   from step 8 through run_traced, each leg the best of --repeats fresh plans after a
+                   warm-up step on its own plan: (a) obca.overtaking_fleet(--scenarios, seed=0) without
+                   the longest-first order (the yardstick: the launches of a plan that never heard of
+                   it), (b) the same fleet with order=True, (c) the shared plan, (d) the shared plan
+                   ordered (the overhead of the extra launches where there is nothing to gain), (e) a
+                   fleet whose rows all equal the shared configuration (the glue's share of the
+                   fleet's cost).  Per leg ms per iterate and per MPC step with the runs' range;
+                   whether the records of (a) and (b) and of (c) and (d) are equal; and from an
+                   untimed pass where the costliest scenarios sit in each iterate's list.  Written
+                   under the key "order" of the same JSON, the other keys kept.
+
 There is no CPU baseline on an equal footing (the C++ port of the local solver has no edge step);
 the edge launch is reported next to the local launch so the reader sees its share of an iterate.
 Writes one JSON (default profiles/obca_admm_bench.json) and prints it.
@@ -241,8 +253,104 @@ def dual_pi_main(a):
     print(json.dumps(dict(dual_pi=res)))
 
 
+def order_leg(b, n, kw, order, steps, repeats):
+    """Best of `repeats` fresh plans (a warm-up step on its own plan first), each --steps MPC steps
+    through run_traced, with or without the longest-first order; the last run's trace."""
+    warm = obca.OBCADevicePlanner(b, n, order=order, **kw)
+    state = warm.get("STATE")                     # the seeded state, so the later plans skip the host seeding
+    warm.step()
+    warm.close()
+    ms, tr = [], None
+    for _ in range(repeats):
+        dp = obca.OBCADevicePlanner(b, n, order=order, state=state, **kw)
+        t0 = time.perf_counter()
+        tr = dp.run_traced(steps, keep_lambda=False)
+        ms.append((time.perf_counter() - t0) * 1e3)
+        dp.close()
+    n_it = int(tr.iters.max(axis=1).sum())
+    best = min(ms)
+    return dict(order=bool(order), entry="piadmm_obca_fleet_begin" if dp.fleet else "piadmm_obca_plan_begin",
+                admm_iterates=n_it, step_ms=best / steps, iterate_ms=best / max(n_it, 1),
+                step_ms_runs=[v / steps for v in ms], iterate_ms_runs=[v / max(n_it, 1) for v in ms],
+                spread_max_over_min=max(ms) / best,
+                stop_iterate_histogram=np.bincount(tr.iters.ravel()).tolist()), tr
+
+
+def order_predictor(b, n, kw, order, steps):
+    """An untimed pass, iterate by iterate: where in each iterate's list the costliest scenarios sit.
+    Per iterate: the list position (as a fraction of m) of the scenario with the iterate's largest Q
+    (the first such in the list), and the share of the scenarios at or above the iterate's top-1 % Q
+    that sit in the first quarter of the list."""
+    dp = obca.OBCADevicePlanner(b, n, order=order, **kw)
+    rows = []
+    for step in range(steps):
+        left, i_iter = n, 0
+        while left:
+            i_iter += 1
+            left = dp.iterate()
+            q = obca.plan_work(dp.get("LOCAL_IST"), dp.get("EDGE_IST"))[:, 0]
+            m = len(q)
+            top = np.sort(q)[::-1][max(int(np.ceil(0.01 * m)), 1) - 1]
+            hot = np.flatnonzero(q >= top)
+            rows.append(dict(step=step, iterate=i_iter, m=m, q_max=int(q.max()), q_mean=float(q.mean()),
+                             argmax_position=float(int(np.argmax(q)) / m), top1pct_q=int(top), top1pct_count=int(len(hot)),
+                             top1pct_share_in_first_quarter=float((hot < (m + 3) // 4).mean())))
+        dp.shift()
+    dp.close()
+    return dict(order=bool(order), iterates=rows,
+                argmax_position_mean=float(np.mean([r["argmax_position"] for r in rows])),
+                top1pct_share_in_first_quarter_mean=float(np.mean([r["top1pct_share_in_first_quarter"] for r in rows])))
+
+
+def order_main(a):
+    """--order: five legs in one process at --scenarios scenarios over --steps MPC steps from step 8:
+    (a) overtaking_fleet(seed 0) unordered -- the yardstick, the launches of a plan without the order --
+    (b) the same fleet ordered, (c) the shared plan unordered, (d) the shared plan ordered, (e) a fleet
+    whose rows all equal the shared configuration, unordered."""
+    b = obca.OBCABatch(0)
+    n, K = a.scenarios, a.steps
+    common = dict(prob=[k % 2 for k in range(n)], t_step0=8, max_admm_iter=a.iterates - 1)
+    specs, par = obca.overtaking_fleet(n, seed=0)
+    fleet_kw = dict(common, specs=specs, **par)
+    same_kw = dict(common, ref_traj=np.ascontiguousarray(np.stack([np.stack(obca.ref_traj_gen())] * n)))
+    legs, traces = {}, {}
+    for name, kw, order in (("a_fleet", fleet_kw, False), ("b_fleet_ordered", fleet_kw, True),
+                            ("c_shared", common, False), ("d_shared_ordered", common, True),
+                            ("e_fleet_of_shared_rows", same_kw, False)):
+        legs[name], traces[name] = order_leg(b, n, kw, order, K, a.repeats)
+
+    def equal(x, y):
+        return all(np.array_equal(getattr(traces[x], f), getattr(traces[y], f))
+                   for f in ("states", "clearance", "iters", "status_mask", "primal", "dual", "min_clearance", "min_row",
+                             "min_clearance_tight", "iters_sum"))
+
+    res = dict(scenarios=n, steps=K, repeats=a.repeats, max_admm_iter=a.iterates - 1, legs=legs,
+               ordered_over_plain_fleet=legs["b_fleet_ordered"]["step_ms"] / legs["a_fleet"]["step_ms"],
+               fleet_spread_max_over_min=legs["a_fleet"]["spread_max_over_min"],
+               ordered_over_plain_shared=legs["d_shared_ordered"]["step_ms"] / legs["c_shared"]["step_ms"],
+               shared_spread_max_over_min=legs["c_shared"]["spread_max_over_min"],
+               fleet_over_shared=legs["a_fleet"]["step_ms"] / legs["c_shared"]["step_ms"],
+               fleet_of_shared_rows_over_shared=legs["e_fleet_of_shared_rows"]["step_ms"] / legs["c_shared"]["step_ms"],
+               records_equal_fleet=equal("a_fleet", "b_fleet_ordered"),
+               records_equal_shared=equal("c_shared", "d_shared_ordered"),
+               records_equal_shared_rows=equal("c_shared", "e_fleet_of_shared_rows"),
+               predictor=dict(ordered=order_predictor(b, n, fleet_kw, True, K),
+                              unordered=order_predictor(b, n, fleet_kw, False, K)))
+    b.close()
+    out = {}
+    if os.path.exists(a.out):
+        with open(a.out) as f:
+            out = json.load(f)
+    out["order"] = res
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+    print(json.dumps(dict(order=res)))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--order", action="store_true")
     ap.add_argument("--dual-pi", action="store_true")
     ap.add_argument("--fleet", action="store_true")
     ap.add_argument("--trace", action="store_true")
@@ -253,6 +361,8 @@ def main():
     ap.add_argument("--iterates", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "obca_admm_bench.json"))
     a = ap.parse_args()
+    if a.order:
+        return order_main(a)
     if a.dual_pi:
         return dual_pi_main(a)
     if a.fleet:
