@@ -19,6 +19,11 @@
 // and k_plan_order after k_plan_compact and after k_plan_shift: the record order of a launch is then
 // the scenarios by the work of their last solves, a pure function of that record, the same on
 // every run; without it neither is launched.
+// With per-scenario clocks attached (piadmm_obca_clock_plan) k_plan_pack_local reads each scenario's
+// own 8 reference rows from a window, piadmm_obca_plan_shift runs k_plan_shift_list /
+// k_plan_dual_shift_list on the scenarios the step ran and then k_plan_clock (their tick, the alive
+// flags, the windows) and k_plan_compact on the flags (the next list: the alive scenarios); without
+// them none of the three is launched and the plan issues the launches it issued before.
 //
 // Layout: one wavefront per item (a local record, a scenario), PW waves per workgroup; waves
 // never cooperate, and a wave past the end of its list exits whole at the top.
@@ -273,14 +278,12 @@ __global__ void __launch_bounds__(CT) k_plan_compact(const int* __restrict__ act
   if (tid == 0) count[0] = base;
 }
 
-// One wave per scenario: iterate_next_state of the frozen previous state into both states,
-// init_state = X[:, 1], the step's last lamb_bar kept for the record, the step's bookkeeping reset.
-__global__ void __launch_bounds__(64) k_plan_shift(int n, double* __restrict__ bar, double* __restrict__ barp,
-                                                   const double* __restrict__ X, double* __restrict__ lamb,
-                                                   double* __restrict__ ctrlp, int* __restrict__ active) {
-  const int lane = threadIdx.x;
-  const int s = blockIdx.x;
-  if (s >= n) return;
+// One wave (a workgroup of its own) on scenario s: iterate_next_state of the frozen previous state
+// into both states, init_state = X[:, 1], the step's last lamb_bar kept for the record, the step's
+// bookkeeping reset.  The body of k_plan_shift and of k_plan_shift_list.
+__device__ __forceinline__ void shift_scenario(int s, int lane, double* __restrict__ bar, double* __restrict__ barp,
+                                               const double* __restrict__ X, double* __restrict__ lamb,
+                                               double* __restrict__ ctrlp) {
   double* B = bar + (size_t)s * STATE;
   double* Bp = barp + (size_t)s * STATE;
   constexpr int NV = (STATE + 63) / 64;
@@ -318,7 +321,29 @@ __global__ void __launch_bounds__(64) k_plan_shift(int n, double* __restrict__ b
     if (i < 126) lamb[(size_t)s * 126 + i] = lam[j];
   }
   if (lane < NCTRL) ctrlp[(size_t)s * NCTRL + lane] = 0.0;
+}
+
+// One wave per scenario: every scenario is shifted and is active again.
+__global__ void __launch_bounds__(64) k_plan_shift(int n, double* __restrict__ bar, double* __restrict__ barp,
+                                                   const double* __restrict__ X, double* __restrict__ lamb,
+                                                   double* __restrict__ ctrlp, int* __restrict__ active) {
+  const int lane = threadIdx.x;
+  const int s = blockIdx.x;
+  if (s >= n) return;
+  shift_scenario(s, lane, bar, barp, X, lamb, ctrlp);
   if (lane == 0) active[s] = s;
+}
+
+// One wave per entry of `list` (the scenarios a clocked step ran, piadmm_obca_clock_plan): the same
+// shift for those alone; every other scenario stays as it is.  The next list is k_plan_clock's.
+__global__ void __launch_bounds__(64) k_plan_shift_list(const int* __restrict__ list, int m,
+                                                        double* __restrict__ bar, double* __restrict__ barp,
+                                                        const double* __restrict__ X, double* __restrict__ lamb,
+                                                        double* __restrict__ ctrlp) {
+  const int lane = threadIdx.x;
+  if ((int)blockIdx.x >= m) return;
+  const int s = __builtin_amdgcn_readfirstlane(list[blockIdx.x]);
+  shift_scenario(s, lane, bar, barp, X, lamb, ctrlp);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -409,13 +434,11 @@ __global__ void __launch_bounds__(64 * PW) k_plan_dual_pi(const int* __restrict_
   }
 }
 
-// One wave per scenario, after k_plan_shift: the horizon shift of the frozen integrator (S_prev,
-// D_prev: one slot on, the last slot repeated) into both copies, as k_plan_shift does to lamb_bar.
-__global__ void __launch_bounds__(64) k_plan_dual_shift(int n, double* __restrict__ S, double* __restrict__ D,
-                                                        double* __restrict__ Sp, double* __restrict__ Dp) {
-  const int lane = threadIdx.x;
-  const int s = blockIdx.x;
-  if (s >= n) return;
+// One wave (a workgroup of its own) on scenario s: the horizon shift of the frozen integrator
+// (S_prev, D_prev: one slot on, the last slot repeated) into both copies, as the state shift does to
+// lamb_bar.  The body of k_plan_dual_shift and of k_plan_dual_shift_list.
+__device__ __forceinline__ void dual_shift_scenario(int s, int lane, double* __restrict__ S, double* __restrict__ D,
+                                                    double* __restrict__ Sp, double* __restrict__ Dp) {
   const size_t base = (size_t)s * 126;
   double vs[2], vd[2];
   // every read first, then every write: the shift reads slot t + 1 of the arrays it overwrites
@@ -439,6 +462,26 @@ __global__ void __launch_bounds__(64) k_plan_dual_shift(int n, double* __restric
       D[base + i] = vd[j];  Dp[base + i] = vd[j];
     }
   }
+}
+
+// One wave per scenario, after k_plan_shift.
+__global__ void __launch_bounds__(64) k_plan_dual_shift(int n, double* __restrict__ S, double* __restrict__ D,
+                                                        double* __restrict__ Sp, double* __restrict__ Dp) {
+  const int lane = threadIdx.x;
+  const int s = blockIdx.x;
+  if (s >= n) return;
+  dual_shift_scenario(s, lane, S, D, Sp, Dp);
+}
+
+// One wave per entry of `list`, after k_plan_shift_list: the integrators of the scenarios a clocked
+// step ran; a retired scenario's stay frozen.
+__global__ void __launch_bounds__(64) k_plan_dual_shift_list(const int* __restrict__ list, int m,
+                                                             double* __restrict__ S, double* __restrict__ D,
+                                                             double* __restrict__ Sp, double* __restrict__ Dp) {
+  const int lane = threadIdx.x;
+  if ((int)blockIdx.x >= m) return;
+  const int s = __builtin_amdgcn_readfirstlane(list[blockIdx.x]);
+  dual_shift_scenario(s, lane, S, D, Sp, Dp);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -631,6 +674,44 @@ __global__ void __launch_bounds__(64 * PW) k_plan_order(const int* __restrict__ 
   if (lane == 0) list_out[rank] = s;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Per-scenario clocks (piadmm_obca_clock_plan): clk[s] = (c, len, alive), c the row of scenario s's
+// own reference that slot 0 of its horizon reads, len the valid rows of that reference.  Opt-in:
+// without a clock neither k_plan_clock nor the list-taking shifts are launched.
+// ---------------------------------------------------------------------------------------------
+constexpr int WIN = 2 * 8 * 5;       // a window: ref_s[v][c .. c + 7], the 80 doubles k_plan_pack_local reads
+
+// One wave per scenario, after the shifts of a clocked step: the tick c += ran[s] (ran: the scenarios
+// the step ran; nullptr ticks nobody and only rebuilds), alive = (c + 8 <= len), and of an alive
+// scenario the window copy, exact.  c and len are wave-uniform (first-lane broadcast), so the flag
+// is and a retired scenario's wave leaves whole.  The flag also asks 0 <= c and len <= n_ref, so the
+// copy stays inside the reference whatever the record holds.  `alive` is the flag list
+// k_plan_compact makes the next active list from, and the next tick's `ran`.
+__global__ void __launch_bounds__(64 * PW) k_plan_clock(int n, int* __restrict__ clk, const int* __restrict__ ran,
+                                                        const double* __restrict__ ref, int ref_stride, int n_ref,
+                                                        double* __restrict__ win, int* __restrict__ alive) {
+  const int lane = threadIdx.x & 63;
+  const int s = blockIdx.x * PW + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (s >= n) return;
+  int* K = clk + 3 * (size_t)s;
+  const int tick = ran ? (__builtin_amdgcn_readfirstlane(ran[s]) != 0 ? 1 : 0) : 0;
+  const int c = __builtin_amdgcn_readfirstlane(K[0]) + tick;
+  const int len = __builtin_amdgcn_readfirstlane(K[1]);
+  const int ok = (c >= 0 && len <= n_ref && c <= len - 8) ? 1 : 0;
+  if (lane == 0) {
+    K[0] = c;
+    K[2] = ok;
+    alive[s] = ok;
+  }
+  if (!ok) return;
+  const double* rf = ref + (size_t)s * ref_stride;
+  double* W = win + (size_t)s * WIN;
+  for (int i = lane; i < WIN; i += 64) {
+    const int v = i / 40, j = i % 40;
+    W[i] = rf[((size_t)v * n_ref + c) * 5 + j];
+  }
+}
+
 }  // namespace obca_plan
 
 // ---------------------------------------------------------------------------------------------
@@ -671,6 +752,19 @@ struct piadmm_obca_plan_s {
     bool on = false;
     int *work = nullptr, *tmp = nullptr;
   } ord;
+  // the per-scenario clocks (piadmm_obca_clock_plan): clk = (c, len, alive) per scenario, n x 3, and
+  // `host` its mirror; win = the reference windows, n x 80; flag[cur] = the alive flags (the next
+  // tick's `ran`), flag[1 - cur] the ones the next tick writes; list = the n_list scenarios alive
+  // when the open step opened, ascending (the active lists are overwritten as the step iterates);
+  // ident = 0 .. n - 1, the list k_plan_compact filters by the flags
+  struct clock_s {
+    bool on = false;
+    int cur = 0, n_list = 0;
+    int *clk = nullptr, *flag[2] = {nullptr, nullptr}, *list = nullptr, *ident = nullptr;
+    double* win = nullptr;
+    std::vector<int> host;
+  } ck;
+  std::vector<int> admm_rows;    // max_admm_iter of every parameter row (max_iter_all is their maximum)
 };
 
 namespace {
@@ -707,10 +801,20 @@ void order_free(piadmm_obca_plan_s* p) {
   p->ord = piadmm_obca_plan_s::order_s();
 }
 
+void clock_free_buffers(piadmm_obca_plan_s::clock_s& c) {
+  void* d[] = {c.clk, c.flag[0], c.flag[1], c.list, c.ident, c.win};
+  for (void* q : d)
+    if (q) (void)hipFree(q);
+  c = piadmm_obca_plan_s::clock_s();
+}
+
+void clock_free(piadmm_obca_plan_s* p) { clock_free_buffers(p->ck); }
+
 void plan_free_buffers(piadmm_obca_plan_s* p) {
   trace_free(p);
   dual_free(p);
   order_free(p);
+  clock_free(p);
   void* d[] = {p->bar, p->barp, p->ctrl, p->ctrlp, p->X, p->primal, p->dual, p->pth, p->dth, p->ref, p->lamb,
                p->tab, p->iters, p->stop, p->conv, p->prob, p->act[0], p->act[1], p->keep, p->count, p->mask};
   for (void* q : d)
@@ -803,12 +907,13 @@ int blocks_for(int waves) { return (waves + PW - 1) / PW; }
 
 void piadmm_obca_plan_release(piadmm_obca_t h) {
   if (!h->plan) return;
-  if (h->plan->tr.on || h->plan->du.on || h->plan->ord.on) {
+  if (h->plan->tr.on || h->plan->du.on || h->plan->ord.on || h->plan->ck.on) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     trace_free(h->plan);
     dual_free(h->plan);
     order_free(h->plan);
+    clock_free(h->plan);
   }
   h->plan->open = false;
 }
@@ -852,8 +957,9 @@ int plan_open(piadmm_obca_t h, const piadmm_obca_plan_cfg_t* cfg, const int32_t*
   p->ref_rows = ref_rows;
   p->tab_stride = tab_rows > 1 ? TAB : 0;
   p->ref_stride = ref_rows > 1 ? (int)ref_one : 0;
-  p->max_iter_all = 0;
-  for (int k = 0; k < tab_rows; ++k) p->max_iter_all = std::max(p->max_iter_all, (int)tab[(size_t)k * TAB + T_ADMM]);
+  p->admm_rows.resize((size_t)tab_rows);
+  for (int k = 0; k < tab_rows; ++k) p->admm_rows[(size_t)k] = (int)tab[(size_t)k * TAB + T_ADMM];
+  p->max_iter_all = std::max(0, *std::max_element(p->admm_rows.begin(), p->admm_rows.end()));
   const size_t N = (size_t)n;
   int rc = 0;
   if ((rc = dalloc(h, &p->bar, N * STATE, false)) || (rc = dalloc(h, &p->barp, N * STATE, false)) ||
@@ -903,6 +1009,76 @@ int trace_append(piadmm_obca_t h, piadmm_obca_plan_s* p, int row) {
                      t.states + (size_t)row * N * 10, 10, p->prob, p->sigd, row, t.clear + (size_t)row * N * 2,
                      t.summary);
   PHIP(h, hipGetLastError());
+  return 0;
+}
+
+// One clock row (c0, len) against the plan's n_ref: nullptr when it is good, else what is wrong.
+const char* clock_row_check(int c0, int len, int n_ref) {
+  if (c0 < 0) return "c0 >= 0";
+  if (len < 8 || len > n_ref) return "8 <= len <= n_ref";
+  if (c0 > len - 8) return "c0 + 8 <= len";
+  return nullptr;
+}
+
+// Enqueues what follows a change of the clocks: the tick of the scenarios flagged in `ran` (nullptr:
+// nobody, the record is only rebuilt), the alive flags into flag[dst], the windows of the alive
+// scenarios, their ascending list into ck.list and the list the next iterate reads (sorted, with
+// the order on).  n_alive is the mirror's count of the flags the tick writes.  No synchronisation.
+int clock_lists(piadmm_obca_t h, piadmm_obca_plan_s* p, const int* ran, int dst, int n_alive) {
+  using namespace obca_plan;
+  auto& c = p->ck;
+  hipLaunchKernelGGL(k_plan_clock, dim3(blocks_for(p->n)), dim3(64 * PW), 0, h->stream, p->n, c.clk, ran, p->ref,
+                     p->ref_stride, p->cfg.n_ref, c.win, c.flag[dst]);
+  PHIP(h, hipGetLastError());
+  hipLaunchKernelGGL(k_plan_compact, dim3(1), dim3(CT), 0, h->stream, c.ident, c.flag[dst], p->n, c.list, p->count);
+  PHIP(h, hipGetLastError());
+  if (n_alive <= 0) return 0;
+  if (p->ord.on) {
+    hipLaunchKernelGGL(k_plan_order, dim3(blocks_for(n_alive)), dim3(64 * PW), 0, h->stream, c.list,
+                       (const int*)nullptr, n_alive, p->ord.work, p->act[p->cur]);
+    PHIP(h, hipGetLastError());
+  } else {
+    PHIP(h, hipMemcpyAsync(p->act[p->cur], c.list, (size_t)n_alive * sizeof(int), hipMemcpyDeviceToDevice, h->stream));
+  }
+  return 0;
+}
+
+// piadmm_obca_plan_shift of a clocked plan: the step closes for the scenarios it ran (ck.list), their
+// clocks tick, and the next step's list is the scenarios still alive.
+int clock_shift(piadmm_obca_t h, piadmm_obca_plan_s* p) {
+  using namespace obca_plan;
+  auto& c = p->ck;
+  const int m = c.n_list;
+  hipLaunchKernelGGL(k_plan_shift_list, dim3(m), dim3(64), 0, h->stream, c.list, m, p->bar, p->barp, p->X, p->lamb,
+                     p->ctrlp);
+  PHIP(h, hipGetLastError());
+  if (p->du.on) {
+    hipLaunchKernelGGL(k_plan_dual_shift_list, dim3(m), dim3(64), 0, h->stream, c.list, m, p->du.S, p->du.D, p->du.Sp,
+                       p->du.Dp);
+    PHIP(h, hipGetLastError());
+  }
+  // the mirror: the tick is deterministic, nothing is read back for it
+  std::vector<int> next = c.host;
+  int n_alive = 0;
+  for (int s = 0; s < p->n; ++s) {
+    int* k = next.data() + 3 * (size_t)s;
+    if (k[2]) k[0] += 1;
+    k[2] = k[0] <= k[1] - 8 ? 1 : 0;
+    n_alive += k[2];
+  }
+  if (int rc = clock_lists(h, p, c.flag[c.cur], 1 - c.cur, n_alive)) return rc;
+  if (p->tr.on) {
+    if (int rc = trace_append(h, p, p->tr.rows + 1)) return rc;
+  }
+  PHIP(h, hipStreamSynchronize(h->stream));
+  c.host.swap(next);
+  c.cur = 1 - c.cur;
+  c.n_list = n_alive;
+  if (p->tr.on) p->tr.rows += 1;
+  p->t_step += 1;
+  p->i_iter = 0;
+  p->n_act = n_alive;
+  p->n_last = 0;
   return 0;
 }
 
@@ -958,8 +1134,9 @@ int32_t piadmm_obca_plan_iterate(piadmm_obca_t h, int32_t* n_active_after) {
   using namespace obca_plan;
   piadmm_obca_plan_s* p = nullptr;
   if (int rc = open_plan(h, &p, "obca_plan_iterate")) return rc;
+  if (p->ck.on && p->ck.n_list == 0) return pfail(h, PIADMM_E_STATE, "obca_plan_iterate: no scenario alive");
   if (p->n_act <= 0) return pfail(h, PIADMM_E_STATE, "obca_plan_iterate: no active scenario (obca_plan_shift closes the step)");
-  if (p->t_step + 8 > p->cfg.n_ref) return pfail(h, PIADMM_E_STATE, "obca_plan_iterate: reference exhausted");
+  if (!p->ck.on && p->t_step + 8 > p->cfg.n_ref) return pfail(h, PIADMM_E_STATE, "obca_plan_iterate: reference exhausted");
   PHIP(h, hipSetDevice(h->device));
   const int m = p->n_act;
   if (2 * m > h->cap || m > h->e_cap) return pfail(h, PIADMM_E_STATE, "obca_plan_iterate: the handle's buffers shrank");
@@ -972,8 +1149,14 @@ int32_t piadmm_obca_plan_iterate(piadmm_obca_t h, int32_t* n_active_after) {
     PHIP(h, hipMemsetAsync(p->mask, 0, (size_t)2 * p->n * sizeof(int), st));
   }
   const int i_iter = p->i_iter + 1;
-  hipLaunchKernelGGL(k_plan_pack_local, dim3(blocks_for(2 * m)), dim3(64 * PW), 0, st, act, m, p->bar, p->prob, p->ref,
-                     p->ref_stride, p->cfg.n_ref, p->t_step, p->tab, p->tab_stride, h->d_rec);
+  if (p->ck.on) {
+    // every scenario's own 8 reference rows: its window, read as a reference of 8 rows at step 0
+    hipLaunchKernelGGL(k_plan_pack_local, dim3(blocks_for(2 * m)), dim3(64 * PW), 0, st, act, m, p->bar, p->prob,
+                       p->ck.win, WIN, 8, 0, p->tab, p->tab_stride, h->d_rec);
+  } else {
+    hipLaunchKernelGGL(k_plan_pack_local, dim3(blocks_for(2 * m)), dim3(64 * PW), 0, st, act, m, p->bar, p->prob, p->ref,
+                       p->ref_stride, p->cfg.n_ref, p->t_step, p->tab, p->tab_stride, h->d_rec);
+  }
   PHIP(h, hipGetLastError());
   if (int rc = piadmm_obca_local_launch(h, 2 * m)) return rc;
   // the edge output starts from zeros, as in piadmm_obca_edge_solve
@@ -1025,6 +1208,7 @@ int32_t piadmm_obca_plan_shift(piadmm_obca_t h) {
   if (p->i_iter == 0) return pfail(h, PIADMM_E_STATE, "obca_plan_shift: no iterate ran in this step");
   if (p->tr.on && p->tr.rows >= p->tr.cap) return pfail(h, PIADMM_E_STATE, "obca_plan_shift: trace full");
   PHIP(h, hipSetDevice(h->device));
+  if (p->ck.on) return clock_shift(h, p);
   // every scenario is active again: the list the next iterate reads is the identity, or with the
   // order on the identity sorted by the work of the step that closes
   hipLaunchKernelGGL(k_plan_shift, dim3(p->n), dim3(64), 0, h->stream, p->n, p->bar, p->barp, p->X, p->lamb, p->ctrlp,
@@ -1055,7 +1239,8 @@ int32_t piadmm_obca_plan_shift(piadmm_obca_t h) {
 int32_t piadmm_obca_plan_step(piadmm_obca_t h, int32_t* iters_out) {
   piadmm_obca_plan_s* p = nullptr;
   if (int rc = open_plan(h, &p, "obca_plan_step")) return rc;
-  if (p->t_step + 8 > p->cfg.n_ref) return pfail(h, PIADMM_E_STATE, "obca_plan_step: reference exhausted");
+  if (p->ck.on && p->ck.n_list == 0) return pfail(h, PIADMM_E_STATE, "obca_plan_step: no scenario alive");
+  if (!p->ck.on && p->t_step + 8 > p->cfg.n_ref) return pfail(h, PIADMM_E_STATE, "obca_plan_step: reference exhausted");
   if (p->tr.on && p->tr.rows >= p->tr.cap) return pfail(h, PIADMM_E_STATE, "obca_plan_step: trace full");
   // i_iter > max_admm_iter stops a scenario: at most the largest max_admm_iter + 1 iterates in a step
   while (p->n_act > 0 && p->i_iter <= p->max_iter_all) {
@@ -1109,6 +1294,12 @@ int32_t piadmm_obca_plan_get(piadmm_obca_t h, int32_t what, void* out, int64_t b
     case PIADMM_OBCA_PLAN_GET_WORK:
       if (!p->ord.on) return pfail(h, PIADMM_E_STATE, "obca_plan_get: no order attached (obca_order_plan)");
       src = p->ord.work; want = n * 2 * I; break;
+    case PIADMM_OBCA_PLAN_GET_CLOCK:
+    case PIADMM_OBCA_PLAN_GET_WINDOW:
+      if (!p->ck.on) return pfail(h, PIADMM_E_STATE, "obca_plan_get: no clock attached (obca_clock_plan)");
+      if (what == PIADMM_OBCA_PLAN_GET_CLOCK) { src = p->ck.clk; want = n * 3 * I; }
+      else { src = p->ck.win; want = n * WIN * D; }
+      break;
     case PIADMM_OBCA_PLAN_GET_T_STEP: want = I; break;
     case PIADMM_OBCA_PLAN_GET_COUNTS: want = 3 * I; break;
     default: return pfail(h, PIADMM_E_ARG, "obca_plan_get: unknown item " + std::to_string(what));
@@ -1308,8 +1499,15 @@ int32_t piadmm_obca_order_plan(piadmm_obca_t h, int32_t mode, const int32_t* wor
   const size_t N = (size_t)n;
   std::vector<int> ident(N);
   for (int k = 0; k < n; ++k) ident[k] = k;
+  // with a clock the current list is the alive scenarios, ascending in ck.list
+  const int m_cur = p->ck.on ? p->ck.n_list : n;
   if (mode == 0) {
-    if (p->ord.on) PHIP(h, hipMemcpy(p->act[p->cur], ident.data(), N * sizeof(int), hipMemcpyHostToDevice));
+    if (p->ord.on && p->ck.on) {
+      if (m_cur > 0)
+        PHIP(h, hipMemcpy(p->act[p->cur], p->ck.list, (size_t)m_cur * sizeof(int), hipMemcpyDeviceToDevice));
+    } else if (p->ord.on) {
+      PHIP(h, hipMemcpy(p->act[p->cur], ident.data(), N * sizeof(int), hipMemcpyHostToDevice));
+    }
     order_free(p);
     return 0;
   }
@@ -1320,9 +1518,10 @@ int32_t piadmm_obca_order_plan(piadmm_obca_t h, int32_t mode, const int32_t* wor
     e = work_init ? hipMemcpy(work, work_init, 2 * N * sizeof(int), hipMemcpyHostToDevice)
                   : hipMemset(work, 0, 2 * N * sizeof(int));
   if (e == hipSuccess) e = hipMemcpy(tmp, ident.data(), N * sizeof(int), hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
+  if (e == hipSuccess && m_cur > 0) {
     // the current list re-sorted at once (zero work: ascending, as it was)
-    hipLaunchKernelGGL(k_plan_order, dim3(blocks_for(n)), dim3(64 * PW), 0, h->stream, tmp, (const int*)nullptr, n, work,
+    hipLaunchKernelGGL(k_plan_order, dim3(blocks_for(m_cur)), dim3(64 * PW), 0, h->stream,
+                       p->ck.on ? (const int*)p->ck.list : (const int*)tmp, (const int*)nullptr, m_cur, work,
                        p->act[p->cur]);
     e = hipGetLastError();
   }
@@ -1381,6 +1580,212 @@ int32_t piadmm_obca_order(piadmm_obca_t h, const int32_t* list, int32_t m, const
   return rc;
 }
 
+int32_t piadmm_obca_clock_plan(piadmm_obca_t h, int32_t mode, const int32_t* clock_init) {
+  using namespace obca_plan;
+  piadmm_obca_plan_s* p = nullptr;
+  if (int rc = open_plan(h, &p, "obca_clock_plan")) return rc;
+  if (mode != 0 && mode != 1) return pfail(h, PIADMM_E_ARG, "obca_clock_plan: mode 0 (detach) or 1 (attach)");
+  const int n = p->n, n_ref = p->cfg.n_ref;
+  const size_t N = (size_t)n;
+  std::vector<int> rec(3 * N);
+  if (mode == 1) {
+    for (int k = 0; k < n; ++k) {
+      const int c0 = clock_init ? clock_init[2 * (size_t)k] : p->t_step;
+      const int len = clock_init ? clock_init[2 * (size_t)k + 1] : n_ref;
+      if (const char* why = clock_row_check(c0, len, n_ref))
+        return pfail(h, PIADMM_E_ARG, "obca_clock_plan: row " + std::to_string(k) + ": " + why);
+      rec[3 * (size_t)k] = c0;
+      rec[3 * (size_t)k + 1] = len;
+      rec[3 * (size_t)k + 2] = 1;
+    }
+  }
+  if (p->i_iter != 0) return pfail(h, PIADMM_E_STATE, "obca_clock_plan: only at a step boundary (an MPC step is open)");
+  if (mode == 0) {
+    if (!p->ck.on) return 0;
+    const std::vector<int>& k = p->ck.host;
+    for (int s = 0; s < n; ++s)
+      if (!k[3 * (size_t)s + 2] || k[3 * (size_t)s] != k[0] || k[3 * (size_t)s + 1] != n_ref)
+        return pfail(h, PIADMM_E_STATE, "obca_clock_plan: detaching needs every scenario alive, on one c and with len = n_ref (scenario " +
+                     std::to_string(s) + ")");
+    PHIP(h, hipSetDevice(h->device));
+    PHIP(h, hipStreamSynchronize(h->stream));
+    // every scenario is alive: the current list already holds all n, in the plan's order
+    p->t_step = k[0];
+    clock_free(p);
+    return 0;
+  }
+  PHIP(h, hipSetDevice(h->device));
+  PHIP(h, hipStreamSynchronize(h->stream));
+  piadmm_obca_plan_s::clock_s nk;
+  std::vector<int> ident(N);
+  for (int k = 0; k < n; ++k) ident[(size_t)k] = k;
+  hipError_t e = hipMalloc(&nk.clk, 3 * N * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc(&nk.flag[0], N * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc(&nk.flag[1], N * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc(&nk.list, N * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc(&nk.ident, N * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc(&nk.win, N * WIN * sizeof(double));
+  if (e == hipSuccess) e = hipMemcpy(nk.clk, rec.data(), 3 * N * sizeof(int), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(nk.ident, ident.data(), N * sizeof(int), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(nk.flag[0], 0, N * sizeof(int));
+  if (e == hipSuccess) e = hipMemset(nk.flag[1], 0, N * sizeof(int));
+  if (e == hipSuccess) e = hipMemset(nk.list, 0, N * sizeof(int));
+  if (e == hipSuccess) e = hipMemset(nk.win, 0, N * WIN * sizeof(double));
+  if (e != hipSuccess) {
+    clock_free_buffers(nk);
+    return pfail(h, PIADMM_E_HIP, std::string("obca_clock_plan: ") + hipGetErrorString(e));
+  }
+  clock_free(p);
+  p->ck = nk;
+  p->ck.host = rec;
+  p->ck.cur = 0;
+  p->ck.n_list = n;
+  p->ck.on = true;
+  // every row is alive: the windows, the flags and the list of all n (sorted, with the order on)
+  if (int rc = clock_lists(h, p, nullptr, 0, n)) {
+    (void)hipStreamSynchronize(h->stream);
+    return rc;
+  }
+  PHIP(h, hipStreamSynchronize(h->stream));
+  p->n_act = n;
+  return 0;
+}
+
+int32_t piadmm_obca_clock_admit(piadmm_obca_t h, int32_t m, const int32_t* slots, const int32_t* clock,
+                                const double* state, const double* ref, const double* par, const int32_t* prob,
+                                const double* primal_thres, const double* dual_thres) {
+  using namespace obca_plan;
+  piadmm_obca_plan_s* p = nullptr;
+  if (int rc = open_plan(h, &p, "obca_clock_admit")) return rc;
+  const int n = p->n, n_ref = p->cfg.n_ref;
+  if (m < 1 || m > n) return pfail(h, PIADMM_E_ARG, "obca_clock_admit: 1 <= m <= n_scenarios");
+  if (!slots || !clock) return pfail(h, PIADMM_E_ARG, "obca_clock_admit: null argument (slots, clock)");
+  std::vector<char> seen((size_t)n, 0);
+  for (int k = 0; k < m; ++k) {
+    if (slots[k] < 0 || slots[k] >= n || seen[(size_t)slots[k]])
+      return pfail(h, PIADMM_E_ARG, "obca_clock_admit: slots[" + std::to_string(k) + "] must be a scenario below n, listed once");
+    seen[(size_t)slots[k]] = 1;
+  }
+  for (int k = 0; k < m; ++k) {
+    const std::string row = "obca_clock_admit: row " + std::to_string(k) + ": ";
+    if (const char* why = clock_row_check(clock[2 * (size_t)k], clock[2 * (size_t)k + 1], n_ref))
+      return pfail(h, PIADMM_E_ARG, row + why);
+    if (par)
+      if (const char* why = row_check(par + (size_t)k * TAB)) return pfail(h, PIADMM_E_ARG, row + why);
+    if (prob && prob[k] != 0 && prob[k] != 1) return pfail(h, PIADMM_E_ARG, row + "prob must be 0 or 1");
+  }
+  if (!p->ck.on) return pfail(h, PIADMM_E_STATE, "obca_clock_admit: no clock attached (obca_clock_plan)");
+  if (p->tr.on) return pfail(h, PIADMM_E_STATE, "obca_clock_admit: a trace is attached (its minima would mix two tenants)");
+  if (p->i_iter != 0) return pfail(h, PIADMM_E_STATE, "obca_clock_admit: only at a step boundary (an MPC step is open)");
+  if (ref && p->ref_rows != n) return pfail(h, PIADMM_E_STATE, "obca_clock_admit: ref needs a plan with a reference per scenario (obca_fleet_begin)");
+  if (par && p->tab_rows != n) return pfail(h, PIADMM_E_STATE, "obca_clock_admit: par needs a plan with a parameter row per scenario (obca_fleet_begin)");
+  PHIP(h, hipSetDevice(h->device));
+  PHIP(h, hipStreamSynchronize(h->stream));
+  const size_t D = sizeof(double), ref_one = (size_t)2 * n_ref * 5;
+  for (int k = 0; k < m; ++k) {
+    const size_t s = (size_t)slots[k], K = (size_t)k;
+    if (state) {
+      PHIP(h, hipMemcpy(p->bar + s * STATE, state + K * STATE, STATE * D, hipMemcpyHostToDevice));
+      PHIP(h, hipMemcpy(p->barp + s * STATE, state + K * STATE, STATE * D, hipMemcpyHostToDevice));
+    }
+    if (ref) PHIP(h, hipMemcpy(p->ref + s * ref_one, ref + K * ref_one, ref_one * D, hipMemcpyHostToDevice));
+    if (par) {
+      PHIP(h, hipMemcpy(p->tab + s * TAB, par + K * TAB, TAB * D, hipMemcpyHostToDevice));
+      p->admm_rows[s] = (int)par[K * TAB + T_ADMM];
+    }
+    if (prob) PHIP(h, hipMemcpy(p->prob + s, prob + K, sizeof(int), hipMemcpyHostToDevice));
+    if (primal_thres) PHIP(h, hipMemcpy(p->pth + s, primal_thres + K, D, hipMemcpyHostToDevice));
+    if (dual_thres) PHIP(h, hipMemcpy(p->dth + s, dual_thres + K, D, hipMemcpyHostToDevice));
+    // the slot starts as a scenario of a fresh plan does
+    PHIP(h, hipMemset(p->ctrl + s * NCTRL, 0, NCTRL * D));
+    PHIP(h, hipMemset(p->ctrlp + s * NCTRL, 0, NCTRL * D));
+    PHIP(h, hipMemset(p->X + s * NX, 0, NX * D));
+    PHIP(h, hipMemset(p->lamb + s * 126, 0, 126 * D));
+    PHIP(h, hipMemset(p->iters + s, 0, sizeof(int)));
+    PHIP(h, hipMemset(p->mask + 2 * s, 0, 2 * sizeof(int)));
+    if (p->du.on) {
+      PHIP(h, hipMemcpy(p->du.S + s * 126, p->bar + s * STATE + S_LB, 126 * D, hipMemcpyDeviceToDevice));
+      PHIP(h, hipMemcpy(p->du.Sp + s * 126, p->bar + s * STATE + S_LB, 126 * D, hipMemcpyDeviceToDevice));
+      PHIP(h, hipMemset(p->du.D + s * 126, 0, 126 * D));
+      PHIP(h, hipMemset(p->du.Dp + s * 126, 0, 126 * D));
+    }
+    if (p->ord.on) PHIP(h, hipMemset(p->ord.work + 2 * s, 0, 2 * sizeof(int)));
+    int* k3 = p->ck.host.data() + 3 * s;
+    k3[0] = clock[2 * K];
+    k3[1] = clock[2 * K + 1];
+    k3[2] = 1;
+    PHIP(h, hipMemcpy(p->ck.clk + 3 * s, k3, 3 * sizeof(int), hipMemcpyHostToDevice));
+  }
+  p->max_iter_all = std::max(0, *std::max_element(p->admm_rows.begin(), p->admm_rows.end()));
+  int n_alive = 0;
+  for (int s = 0; s < n; ++s) n_alive += p->ck.host[3 * (size_t)s + 2];
+  // the windows, the flags and the list again, over all n (the order, when attached, re-sorts it)
+  if (int rc = clock_lists(h, p, nullptr, p->ck.cur, n_alive)) {
+    (void)hipStreamSynchronize(h->stream);
+    return rc;
+  }
+  PHIP(h, hipStreamSynchronize(h->stream));
+  p->ck.n_list = n_alive;
+  p->n_act = n_alive;
+  return 0;
+}
+
+int32_t piadmm_obca_clock_tick(piadmm_obca_t h, int32_t n, const int32_t* clock_in, const int32_t* ran,
+                               const double* ref, int32_t ref_rows, int32_t n_ref, int32_t* clock_out,
+                               double* window_out, int32_t* list_out, int32_t* count_out) {
+  using namespace obca_plan;
+  if (!h) return PIADMM_E_ARG;
+  if (n < 1 || n > (1 << 20)) return pfail(h, PIADMM_E_ARG, "obca_clock_tick: 1 <= n <= 2^20");
+  if (!clock_in || !ran || !ref || !clock_out || !window_out || !list_out || !count_out)
+    return pfail(h, PIADMM_E_ARG, "obca_clock_tick: null argument");
+  if (ref_rows != 1 && ref_rows != n) return pfail(h, PIADMM_E_ARG, "obca_clock_tick: ref_rows must be 1 or n");
+  if (n_ref < 8 || n_ref > (1 << 20)) return pfail(h, PIADMM_E_ARG, "obca_clock_tick: 8 <= n_ref <= 2^20");
+  for (int k = 0; k < n; ++k) {
+    const int c = clock_in[3 * (size_t)k], len = clock_in[3 * (size_t)k + 1];
+    const char* why = c < 0 || c > (1 << 30) ? "0 <= c <= 2^30" : len < 8 || len > n_ref ? "8 <= len <= n_ref"
+                      : ran[k] != 0 && ran[k] != 1 ? "ran 0 or 1" : nullptr;
+    if (why) return pfail(h, PIADMM_E_ARG, "obca_clock_tick: row " + std::to_string(k) + ": " + why);
+  }
+  PHIP(h, hipSetDevice(h->device));
+  // the call's own buffers: neither the handle's local and edge buffers nor an open plan is touched
+  int *d_clk = nullptr, *d_ran = nullptr, *d_alive = nullptr, *d_ident = nullptr, *d_list = nullptr, *d_count = nullptr;
+  double *d_ref = nullptr, *d_win = nullptr;
+  const size_t N = (size_t)n, ref_one = (size_t)2 * n_ref * 5, R = ref_one * (size_t)ref_rows;
+  std::vector<int> ident(N);
+  for (int k = 0; k < n; ++k) ident[(size_t)k] = k;
+  auto run = [&]() -> int {
+    if (int rc = dalloc(h, &d_clk, 3 * N, false)) return rc;
+    if (int rc = dalloc(h, &d_ran, N, false)) return rc;
+    if (int rc = dalloc(h, &d_alive, N, true)) return rc;
+    if (int rc = dalloc(h, &d_ident, N, false)) return rc;
+    if (int rc = dalloc(h, &d_list, N, true)) return rc;
+    if (int rc = dalloc(h, &d_count, (size_t)1, true)) return rc;
+    if (int rc = dalloc(h, &d_ref, R, false)) return rc;
+    if (int rc = dalloc(h, &d_win, N * WIN, true)) return rc;
+    PHIP(h, hipMemcpyAsync(d_clk, clock_in, 3 * N * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    PHIP(h, hipMemcpyAsync(d_ran, ran, N * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    PHIP(h, hipMemcpyAsync(d_ident, ident.data(), N * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    PHIP(h, hipMemcpyAsync(d_ref, ref, R * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(k_plan_clock, dim3(blocks_for(n)), dim3(64 * PW), 0, h->stream, n, d_clk, d_ran, d_ref,
+                       ref_rows > 1 ? (int)ref_one : 0, n_ref, d_win, d_alive);
+    PHIP(h, hipGetLastError());
+    hipLaunchKernelGGL(k_plan_compact, dim3(1), dim3(CT), 0, h->stream, d_ident, d_alive, n, d_list, d_count);
+    PHIP(h, hipGetLastError());
+    PHIP(h, hipMemcpyAsync(clock_out, d_clk, 3 * N * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    PHIP(h, hipMemcpyAsync(window_out, d_win, N * WIN * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    PHIP(h, hipMemcpyAsync(list_out, d_list, N * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    PHIP(h, hipMemcpyAsync(count_out, d_count, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    PHIP(h, hipStreamSynchronize(h->stream));
+    return 0;
+  };
+  const int rc = run();
+  if (rc) (void)hipStreamSynchronize(h->stream);
+  void* dev[] = {d_clk, d_ran, d_alive, d_ident, d_list, d_count, d_ref, d_win};
+  for (void* q : dev)
+    if (q) (void)hipFree(q);
+  return rc;
+}
+
 int32_t piadmm_obca_trace_begin(piadmm_obca_t h, int32_t cap_steps, int32_t flags) {
   using namespace obca_plan;
   piadmm_obca_plan_s* p = nullptr;
@@ -1423,7 +1828,17 @@ int32_t piadmm_obca_trace_run(piadmm_obca_t h, int32_t n_steps, int32_t* steps_d
   if ((int64_t)p->tr.rows + n_steps > p->tr.cap)
     return pfail(h, PIADMM_E_STATE, "obca_trace_run: " + std::to_string(n_steps) + " steps do not fit the trace (" +
                  std::to_string(p->tr.rows) + " of " + std::to_string(p->tr.cap) + " rows used)");
-  if ((int64_t)p->t_step + n_steps - 1 + 8 > p->cfg.n_ref)
+  if (p->ck.on) {
+    // the steps the longest-lived scenario has left
+    int left = 0;
+    for (int s = 0; s < p->n; ++s)
+      if (p->ck.host[3 * (size_t)s + 2])
+        left = std::max(left, p->ck.host[3 * (size_t)s + 1] - 8 - p->ck.host[3 * (size_t)s] + 1);
+    if (left == 0) return pfail(h, PIADMM_E_STATE, "obca_trace_run: no scenario alive");
+    if (n_steps > left)
+      return pfail(h, PIADMM_E_STATE, "obca_trace_run: every reference ends before " + std::to_string(n_steps) +
+                   " steps (" + std::to_string(left) + " left)");
+  } else if ((int64_t)p->t_step + n_steps - 1 + 8 > p->cfg.n_ref)
     return pfail(h, PIADMM_E_STATE, "obca_trace_run: the reference ends before " + std::to_string(n_steps) + " steps");
   // a host loop of the plan's bounded launches: every step ends in piadmm_obca_plan_shift, which appends its row
   for (int k = 0; k < n_steps; ++k) {

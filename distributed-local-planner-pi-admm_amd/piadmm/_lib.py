@@ -127,6 +127,9 @@ SYMBOLS = [
     ("piadmm_obca_dual_pi", c_i32, [_H, c_i32, _dp, _dp, _dp, _ip, _dp, c_i32, _dp, _dp, _dp, _dp]),
     ("piadmm_obca_order_plan", c_i32, [_H, c_i32, _ip]),
     ("piadmm_obca_order", c_i32, [_H, _ip, c_i32, _ip, c_i32, _ip]),
+    ("piadmm_obca_clock_plan", c_i32, [_H, c_i32, _ip]),
+    ("piadmm_obca_clock_admit", c_i32, [_H, c_i32, _ip, _ip, _dp, _dp, _dp, _ip, _dp, _dp]),
+    ("piadmm_obca_clock_tick", c_i32, [_H, c_i32, _ip, _ip, _dp, c_i32, c_i32, _ip, _dp, _ip, _ip]),
 ]
 
 # PIADMM_OBCA_FLEET_PAR: doubles per parameter row of piadmm_obca_fleet_begin

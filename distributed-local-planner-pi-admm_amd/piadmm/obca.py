@@ -481,6 +481,43 @@ def plan_work(local_ist, edge_ist):
     return np.ascontiguousarray(np.stack((both[:, :, 2].max(axis=1), both[:, :, 1].max(axis=1)), axis=1), np.int32)
 
 
+def clock_tick(clock, ran):
+    """The tick of k_plan_clock (csrc/piadmm_obca_plan.hip) on the record clock[s] = (c, len, alive),
+    n x 3: c += 1 for the scenarios flagged in `ran` (n, 0 / 1: the ones the step ran), then
+    alive = (c + 8 <= len).  Returns the new record (int32); the argument stays."""
+    out = np.array(clock, np.int32).reshape(-1, 3)
+    ran = np.asarray(ran).reshape(-1)
+    assert ran.shape == (out.shape[0],), (ran.shape, out.shape)
+    out[:, 0] += (ran != 0).astype(np.int32)
+    out[:, 2] = out[:, 0] + N_HORZ <= out[:, 1]
+    return out
+
+
+def clock_window(ref, clock):
+    """The reference windows k_plan_clock copies: window[s] = ref_s[v][c : c + 8] (n x 2 x 8 x 5)
+    of every scenario with clock[s] = (c, len, alive) alive, zeros for the others.  ref: one
+    reference for all (2 x n_ref x 5) or one per scenario (n x 2 x n_ref x 5)."""
+    clock = np.asarray(clock, np.int32).reshape(-1, 3)
+    ref = np.asarray(ref, np.float64)
+    n = clock.shape[0]
+    ref = np.broadcast_to(ref, (n,) + ref.shape[-3:])
+    out = np.zeros((n, 2, N_HORZ, NX))
+    for s, (c, _, alive) in enumerate(clock):
+        if alive:
+            out[s] = ref[s, :, c:c + N_HORZ]
+    return out
+
+
+def clock_rows(n, clock, t_step, n_ref):
+    """The n x 2 (c0, len) rows of a planner's clock argument: True is everyone at the plan's step
+    over the whole reference (what a NULL clock_init attaches), else the rows themselves."""
+    if clock is True:
+        return np.tile(np.array([[t_step, n_ref]], np.int32), (n, 1))
+    rows = np.ascontiguousarray(clock, np.int32)
+    assert rows.shape == (n, 2), rows.shape
+    return rows
+
+
 def check_converge(bar, thres, min_dis):
     """`check_converge` (optimizer.py:225-235): the coupled constraints at the exchanged
     halfspaces and lamb_ij."""
@@ -675,6 +712,27 @@ class OBCABatch:
                                                 _lib.iptr(out)))
         return out
 
+    def clock_tick(self, clock, ran, ref):
+        """One launch each of k_plan_clock and k_plan_compact on the call's own buffers
+        (piadmm_obca_clock_tick): clock n x 3, ran n, ref 2 x n_ref x 5 or n x 2 x n_ref x 5.
+        Returns (clock_out, window n x 2 x 8 x 5, the alive scenarios ascending), as `clock_tick` /
+        `clock_window` state them."""
+        from . import _lib
+        clock = np.ascontiguousarray(clock, np.int32)
+        n = clock.shape[0]
+        assert clock.shape == (n, 3), clock.shape
+        ran = np.ascontiguousarray(ran, np.int32)
+        ref = np.ascontiguousarray(ref, np.float64)
+        assert ran.shape == (n,) and ref.shape[-3] == 2 and ref.shape[-1] == NX, (ran.shape, ref.shape)
+        rows = ref.shape[0] if ref.ndim == 4 else 1
+        out, win = np.zeros((n, 3), np.int32), np.zeros((n, 2, N_HORZ, NX))
+        lst, count = np.zeros(n, np.int32), np.zeros(1, np.int32)
+        self._check(self._lib.piadmm_obca_clock_tick(self._h, n, _lib.iptr(clock), _lib.iptr(ran), _lib.dptr(ref), rows,
+                                                     ref.shape[-2], _lib.iptr(out), _lib.dptr(win), _lib.iptr(lst),
+                                                     _lib.iptr(count)))
+        assert 0 <= count[0] <= n and not lst[count[0]:].any()
+        return out, win, lst[:count[0]].copy()
+
     def time_edge(self, recs: np.ndarray, repeats: int) -> float:
         """ms per edge launch over `repeats` launches of `recs` (HIP events)."""
         from . import _lib
@@ -792,12 +850,17 @@ class OBCAPlanner:
 
     dual: None keeps lambda_update; dict(kP=, kI=, windup_sat=, d_gain=, windup=), each one value or
     one per scenario, replaces it by the PI anti-windup law (`lambda_update_pi`), the integrator
-    shifted with the state (`shift_dual`).  OBCADevicePlanner takes the same argument."""
+    shifted with the state (`shift_dual`).  OBCADevicePlanner takes the same argument.
+
+    clock: None keeps the one step of all scenarios; n x 2 rows (c0, len), or True for everyone at
+    t_step0 over the whole reference, gives every scenario its own step (`clock`, n x 3: c, len,
+    alive, ticked by `clock_tick`): it is seeded at c0, reads its reference at c, and once
+    c + 8 > len it is retired -- skipped by every later step, its state frozen, its stop iterate 0."""
 
     def __init__(self, batch, n_scenarios, prob=1, t_step0=0, rho=1.0, min_dis=0.1, max_admm_iter=50,
                  primal_thres=0.01, dual_thres=0.01, round_decimals=4, start=1, update_lamb_ij=0, max_iter=60,
                  conv_thres=0.1, on_stage=None, max_x=150.0, max_y=20.0, r=1e4, q=1e5, x_bound=1000.0,
-                 mu_max=100000.0, g_max=1000.0, ref_traj=None, specs=None, dual=None):
+                 mu_max=100000.0, g_max=1000.0, ref_traj=None, specs=None, dual=None, clock=None):
         self.batch = batch
         self.n = int(n_scenarios)
         self.prob = [int(prob)] * self.n if np.isscalar(prob) else [int(p) for p in prob]
@@ -817,9 +880,17 @@ class OBCAPlanner:
                       max_iter=max_iter, round_decimals=round_decimals, start=start)
         self.on_stage = on_stage or (lambda name, inputs, outputs: None)
         _scenario_refs(self, specs, ref_traj)
-        self.bar_prev = [seeded_bar_state(self.t_step, p, spec=_spec_of(self, s)) for s, p in enumerate(self.prob)]
-        self.init_state = [np.stack([executed_path(v, self.t_step * DT, _spec_of(self, s)) for v in (0, 1)])
+        self.clock = None
+        if clock is not None:
+            rows = clock_rows(self.n, clock, self.t_step, self.n_ref)
+            assert (rows[:, 0] >= 0).all() and (rows[:, 1] <= self.n_ref).all() \
+                and (rows[:, 0] + N_HORZ <= rows[:, 1]).all(), rows
+            self.clock = np.concatenate((rows, np.ones((self.n, 1), np.int32)), axis=1)
+        t0 = [self.t_step] * self.n if self.clock is None else [int(c) for c in self.clock[:, 0]]
+        self.bar_prev = [seeded_bar_state(t0[s], p, spec=_spec_of(self, s)) for s, p in enumerate(self.prob)]
+        self.init_state = [np.stack([executed_path(v, t0[s] * DT, _spec_of(self, s)) for v in (0, 1)])
                            for s in range(self.n)]
+        self.lamb_last = [np.zeros((2, NT, 9)) for _ in range(self.n)]
         # the PI anti-windup dual law (dual=dict(kP=, kI=, windup_sat=, d_gain=, windup=), each one
         # value or one per scenario): S = lamb_bar, D = 0, as piadmm_obca_dual_plan attaches it
         self.dual_par = None if dual is None else dual_rows(self.n, dual)
@@ -836,20 +907,28 @@ class OBCAPlanner:
     def step(self):
         """One MPC step of every scenario."""
         n = self.n
-        assert self.t_step + N_HORZ <= self.n_ref, "reference exhausted"
+        if self.clock is None:
+            assert self.t_step + N_HORZ <= self.n_ref, "reference exhausted"
+            ran = list(range(n))
+            t_of = [self.t_step] * n
+        else:
+            # every scenario at its own step; the retired ones are skipped
+            ran = [s for s in range(n) if self.clock[s, 2]]
+            assert ran, "no scenario alive"
+            t_of = [int(c) for c in self.clock[:, 0]]
         bar = [self._copy(b) for b in self.bar_prev]
         bar_prev = [self._copy(b) for b in self.bar_prev]
         ctrl_prev = [np.zeros((2, NT * NU)) for _ in range(n)]
         X = [None] * n
         iters = np.zeros(n, int)
         shift_in = [None] * n
-        active = list(range(n))
+        active = list(ran)
         i_iter = 0
         while active:
             i_iter += 1
             # ---- vehicle side: one launch, scenarios x vehicles ----
             recs = np.ascontiguousarray(np.stack([
-                local_record(bar[s], v, self.t_step, self.init_state[s][v], self.ref_traj_s[s], rho=self.rho_s[s],
+                local_record(bar[s], v, t_of[s], self.init_state[s][v], self.ref_traj_s[s], rho=self.rho_s[s],
                              min_dis=self.min_dis_s[s], prob=self.prob[s], max_x=self.max_x_s[s],
                              max_y=self.max_y_s[s], r=self.r_s[s], q=self.q_s[s], max_iter=self.max_iter_s[s])
                 for s in active for v in (0, 1)]))
@@ -924,20 +1003,26 @@ class OBCAPlanner:
                     ctrl_prev[s] = ctrl[k]
                     nxt.append(s)
             active = nxt
-        # ---- next time step (:87, :99-103) ----
-        self.bar_prev = [iterate_next_state(shift_in[s]) for s in range(n)]
-        if self.dual_par is not None:
-            for s in range(n):
+        # ---- next time step (:87, :99-103): of the scenarios this step ran ----
+        self.bar_prev, self.init_state = list(self.bar_prev), list(self.init_state)
+        for s in ran:
+            self.bar_prev[s] = iterate_next_state(shift_in[s])
+            if self.dual_par is not None:
                 self.dual_S[s], self.dual_D[s] = shift_dual(self.dual_S[s], self.dual_D[s])
-        self.init_state = [np.stack([X[s][0][1], X[s][1][1]]) for s in range(n)]
+            self.init_state[s] = np.stack([X[s][0][1], X[s][1][1]])
+            self.lamb_last[s] = bar[s]["lamb_bar"]
         self.on_stage("shift", dict(bar_prev=shift_in, X=X, iters=iters.copy()), dict(bar_next=self.bar_prev, init_state=self.init_state))
         self.record.state_record.append(np.stack(self.init_state))
         self.record.iter_num_record.append(iters)
-        self.record.lambda_record.append(np.stack([bar[s]["lamb_bar"] for s in range(n)]))
+        self.record.lambda_record.append(np.stack(self.lamb_last))
+        if self.clock is not None:
+            self.clock = clock_tick(self.clock, self.clock[:, 2])
         self.t_step += 1
 
     def run(self, n_steps):
         for _ in range(int(n_steps)):
+            if self.clock is not None and not self.clock[:, 2].any():
+                break
             self.step()
         return self.record
 
@@ -958,7 +1043,7 @@ PLAN_GET = {"STATE": (0, np.float64), "STATE_PREV": (1, np.float64), "CTRL": (2,
             "T_STEP": (17, np.int32), "LAMBDA": (18, np.float64), "COUNTS": (19, np.int32),
             "STATUS_MASK": (20, np.int32), "REF": (21, np.float64), "PAR": (22, np.float64),
             "DUAL_S": (23, np.float64), "DUAL_D": (24, np.float64), "DUAL_PAR": (25, np.float64),
-            "WORK": (26, np.int32)}
+            "WORK": (26, np.int32), "CLOCK": (27, np.int32), "WINDOW": (28, np.float64)}
 
 
 # piadmm_obca_trace_get items: name -> (code, dtype); piadmm_obca_trace_begin's flag
@@ -1032,13 +1117,20 @@ class OBCADevicePlanner:
     With order=True every active list is kept longest first by the work of each scenario's last
     solves (piadmm_obca_order_plan; `work_init` n x 2 seeds the record, `work()` reads it): the
     per-scenario results are the same bit for bit, ACTIVE and the LOCAL_ / EDGE_ items follow the
-    list's order."""
+    list's order.
+
+    With clock= every scenario has its own MPC step and reference length (piadmm_obca_clock_plan):
+    clock is n x 2 rows (c0, len), or True for everyone at t_step0 over the whole reference.
+    Scenario s is seeded at its own c0 and reads its reference at its own step; once c + 8 > len it
+    is retired and frozen while the others go on.  `clock()` reads the record, `admit` puts new
+    tenants into slots, `run` / `run_traced` stop when nothing is alive.  t_step counts the plan's
+    steps."""
 
     def __init__(self, batch, n_scenarios, prob=1, t_step0=0, rho=1.0, min_dis=0.1, max_admm_iter=50,
                  primal_thres=0.01, dual_thres=0.01, round_decimals=4, start=1, update_lamb_ij=0, max_iter=60,
                  conv_thres=0.1, on_stage=None, max_x=150.0, max_y=20.0, r=1e4, q=1e5, x_bound=1000.0,
                  mu_max=100000.0, g_max=1000.0, ref_traj=None, state=None, specs=None, dual=None, order=False,
-                 work_init=None):
+                 work_init=None, clock=None):
         from . import _lib
         self.batch = batch
         self._lib = batch._lib
@@ -1062,15 +1154,18 @@ class OBCADevicePlanner:
         self.on_stage = on_stage
         ref, ref_each = _scenario_refs(self, specs, ref_traj)
         self.fleet = bool(any_seq or ref_each or self.specs is not None)
-        self.init_state = [np.stack([executed_path(v, self.t_step * DT, _spec_of(self, s)) for v in (0, 1)])
+        # every scenario is seeded at the step it starts at: its own c0 with a clock
+        rows = None if clock is None else clock_rows(self.n, clock, self.t_step, self.n_ref)
+        t0 = [self.t_step] * self.n if rows is None else [int(c) for c in rows[:, 0]]
+        self.init_state = [np.stack([executed_path(v, t0[s] * DT, _spec_of(self, s)) for v in (0, 1)])
                            for s in range(self.n)]
         if state is None:
             seeds = {}
             for s, p in enumerate(self.prob):
-                key = (p, _spec_of(self, s))
+                key = (p, _spec_of(self, s), t0[s])
                 if key not in seeds:
-                    seeds[key] = pack_state(seeded_bar_state(self.t_step, p, spec=key[1]), self.init_state[s])
-            state = (np.stack([seeds[(p, _spec_of(self, s))] for s, p in enumerate(self.prob)]) if self.n
+                    seeds[key] = pack_state(seeded_bar_state(t0[s], p, spec=key[1]), self.init_state[s])
+            state = (np.stack([seeds[(p, _spec_of(self, s), t0[s])] for s, p in enumerate(self.prob)]) if self.n
                      else np.zeros((0, PLAN_STATE)))
         state = np.ascontiguousarray(state, np.float64)
         assert state.shape == (self.n, PLAN_STATE)
@@ -1106,8 +1201,98 @@ class OBCADevicePlanner:
             self.set_order(work_init)
         else:
             assert work_init is None, "work_init seeds the order's record: pass order=True"
+        self._clock = None
+        if clock is not None:
+            self.set_clock(None if clock is True else rows)
         self.record = OBCARunRecord()
         self.record.state_record.append(np.stack(self.init_state))
+
+    def set_clock(self, clock_init=None):
+        """Attach the per-scenario clocks (piadmm_obca_clock_plan; a step boundary only): clock_init
+        n x 2 rows (c0, len), or None for everyone at the plan's step over the whole reference."""
+        from . import _lib
+        t_plan = int(self.get("T_STEP")[0])
+        rows = clock_rows(self.n, True if clock_init is None else clock_init, t_plan, self.n_ref)
+        self._check(self._lib.piadmm_obca_clock_plan(self.batch._h, 1, None if clock_init is None else _lib.iptr(rows)))
+        self._clock = np.concatenate((rows, np.ones((self.n, 1), np.int32)), axis=1)
+
+    def clear_clock(self):
+        """Detach the clocks (a step boundary only; every scenario alive, on one step, over the whole
+        reference): the plan is plain again at that step."""
+        self._check(self._lib.piadmm_obca_clock_plan(self.batch._h, 0, None))
+        if self._clock is not None:
+            self.t_step = int(self._clock[0, 0])
+        self._clock = None
+
+    def clock(self):
+        """The record (c, len, alive) per scenario, n x 3 (PLAN_GET CLOCK)."""
+        return self.get("CLOCK")
+
+    def alive(self):
+        """The scenarios the next step runs: every one without a clock, else the alive ones."""
+        return np.ones(self.n, bool) if self._clock is None else self._clock[:, 2].astype(bool)
+
+    def admit(self, slots, clock, state=None, ref=None, par=None, prob=None, primal_thres=None, dual_thres=None,
+              specs=None):
+        """New tenants into `slots` of the clocked plan (piadmm_obca_clock_admit; a step boundary, no
+        trace): clock m x 2 rows (c0, len); state m x 556, ref m x 2 x n_ref x 5, par m x FLEET_PAR,
+        prob, primal_thres, dual_thres m each -- None keeps what the slot has.  With specs= (one
+        OvertakeSpec per tenant) a missing ref is the spec's reference and a missing state the
+        state seeded at the tenant's c0, as the constructor seeds it."""
+        from . import _lib
+        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        m = len(slots)
+        clock = np.ascontiguousarray(clock, np.int32)
+        assert clock.shape == (m, 2), clock.shape
+        if prob is not None:
+            prob = np.ascontiguousarray(np.broadcast_to(np.asarray(prob, np.int32), (m,)))
+        if specs is not None:
+            specs = [_spec(sp) for sp in specs]
+            assert len(specs) == m
+            if ref is None:
+                ref = np.stack([np.stack(ref_traj_gen(sp)) for sp in specs])
+            if state is None:
+                pr = [self.prob[s] for s in slots] if prob is None else prob
+                state = np.stack([pack_state(seeded_bar_state(int(c), int(p_), spec=sp),
+                                             np.stack([executed_path(v, int(c) * DT, sp) for v in (0, 1)]))
+                                  for sp, c, p_ in zip(specs, clock[:, 0], pr)])
+
+        def arr(a, shape):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, np.float64)
+            assert a.shape == shape, (a.shape, shape)
+            return a
+        state, ref = arr(state, (m, PLAN_STATE)), arr(ref, (m, 2, self.n_ref, NX))
+        par = arr(par, (m, FLEET_PAR))
+        primal_thres, dual_thres = arr(primal_thres, (m,)), arr(dual_thres, (m,))
+        self._check(self._lib.piadmm_obca_clock_admit(self.batch._h, m, _lib.iptr(slots), _lib.iptr(clock),
+                                                      _lib.dptr(state), _lib.dptr(ref), _lib.dptr(par), _lib.iptr(prob),
+                                                      _lib.dptr(primal_thres), _lib.dptr(dual_thres)))
+        # the host's copies of what the slots now hold
+        self._clock[slots, :2] = clock
+        self._clock[slots, 2] = 1
+        if ref is not None:
+            self.ref_traj_s = np.array(self.ref_traj_s)
+            self.ref_traj_s[slots] = ref
+            self.ref_traj = None
+        for k, s in enumerate(slots):
+            if state is not None:
+                self.init_state[s] = unpack_state(state[k])[1]
+            if prob is not None:
+                self.prob[s] = int(prob[k])
+            if primal_thres is not None:
+                self.primal_thres[s] = primal_thres[k]
+            if dual_thres is not None:
+                self.dual_thres[s] = dual_thres[k]
+            if par is not None:
+                self.par[s] = par[k]
+                for j, name in enumerate(FLEET_ROW):
+                    col = getattr(self, name + "_s").astype(np.float64)
+                    col[s] = par[k, j]
+                    setattr(self, name + "_s", col)
+            if specs is not None and self.specs is not None:
+                self.specs[s] = specs[k]
 
     def set_order(self, work_init=None):
         """Attach the longest-first order (piadmm_obca_order_plan; a step boundary only), its record
@@ -1167,7 +1352,8 @@ class OBCADevicePlanner:
                  "EDGE_OUT": (m, EDGE_OUT), "EDGE_IST": (m, NT, 3), "T_STEP": (1,), "LAMBDA": (n, 2, NT, 9),
                  "COUNTS": (3,), "STATUS_MASK": (n, 2), "REF": (rows, 2, self.n_ref, NX),
                  "PAR": (rows, FLEET_PAR), "DUAL_S": (n, 2, NT, 9), "DUAL_D": (n, 2, NT, 9),
-                 "DUAL_PAR": (1 if self.dual_par is None else len(self.dual_par), DUAL_PAR), "WORK": (n, 2)}[what]
+                 "DUAL_PAR": (1 if self.dual_par is None else len(self.dual_par), DUAL_PAR), "WORK": (n, 2),
+                 "CLOCK": (n, 3), "WINDOW": (n, 2, N_HORZ, NX)}[what]
         out = np.zeros(shape, dt)
         self._check(self._lib.piadmm_obca_plan_get(self.batch._h, code, out.ctypes.data, out.nbytes))
         return out
@@ -1178,8 +1364,14 @@ class OBCADevicePlanner:
         self._check(self._lib.piadmm_obca_plan_iterate(self.batch._h, ctypes.byref(left)))
         return left.value
 
+    def _tick(self, steps=1):
+        """The host's copy of the clocks after `steps` closed steps (the record is deterministic)."""
+        for _ in range(steps if self._clock is not None else 0):
+            self._clock = clock_tick(self._clock, self._clock[:, 2])
+
     def shift(self):
         self._check(self._lib.piadmm_obca_plan_shift(self.batch._h))
+        self._tick()
 
     def close(self):
         """End the plan (the batch stays usable after its next upload)."""
@@ -1187,8 +1379,13 @@ class OBCADevicePlanner:
             self._lib.piadmm_obca_plan_end(self.batch._h)
 
     def _close_step(self, iters, status):
-        X = self.get("X")
-        self.init_state = [X[s, :, 1].copy() for s in range(self.n)]
+        if self._clock is None:
+            X = self.get("X")
+            self.init_state = [X[s, :, 1].copy() for s in range(self.n)]
+        else:
+            # a retired scenario's init_state is frozen, an admitted one's X is zero until it runs
+            st = self.get("STATE")
+            self.init_state = [unpack_state(st[s])[1] for s in range(self.n)]
         self.record.state_record.append(np.stack(self.init_state))
         self.record.iter_num_record.append(np.asarray(iters, int))
         self.record.lambda_record.append(self.get("LAMBDA"))
@@ -1202,6 +1399,7 @@ class OBCADevicePlanner:
             return self._step_staged()
         iters = np.zeros(self.n, np.int32)
         self._check(self._lib.piadmm_obca_plan_step(self.batch._h, _lib.iptr(iters)))
+        self._tick()
         mask = self.get("STATUS_MASK")
         self._close_step(iters, [dict(t_step=self.t_step, iters=iters.copy(), local_status_mask=mask[:, 0].copy(),
                                       edge_status_mask=mask[:, 1].copy())])
@@ -1209,7 +1407,7 @@ class OBCADevicePlanner:
     def _step_staged(self):
         n = self.n
         status = []
-        left, i_iter = n, 0
+        left, i_iter = int(self.alive().sum()), 0
         while left:
             i_iter += 1
             before = self.get("STATE")
@@ -1257,8 +1455,18 @@ class OBCADevicePlanner:
 
     def run(self, n_steps):
         for _ in range(int(n_steps)):
+            if not self.alive().any():
+                break
             self.step()
         return self.record
+
+    def steps_left(self):
+        """The steps the longest-lived scenario has left (None without a clock: the plan's reference
+        decides)."""
+        if self._clock is None:
+            return None
+        c = self._clock[self._clock[:, 2] != 0]
+        return int((c[:, 1] - N_HORZ - c[:, 0] + 1).max()) if len(c) else 0
 
     def trace_begin(self, cap_steps, keep_lambda=True):
         """Attach a device-side run record of capacity cap_steps to the plan (a step boundary only)."""
@@ -1268,7 +1476,9 @@ class OBCADevicePlanner:
     def trace_run(self, n_steps):
         """n_steps MPC steps on the device, recorded; the number completed."""
         done = ctypes.c_int32()
-        self._check(self._lib.piadmm_obca_trace_run(self.batch._h, int(n_steps), ctypes.byref(done)))
+        rc = self._lib.piadmm_obca_trace_run(self.batch._h, int(n_steps), ctypes.byref(done))
+        self._tick(done.value)
+        self._check(rc)
         return done.value
 
     def trace_rows(self):
@@ -1307,8 +1517,12 @@ class OBCADevicePlanner:
         init_state, and returns the OBCATrace with the clearances.  Staged stepping stays on `run`."""
         if self.on_stage is not None:
             raise ValueError("run_traced does not stage: use run() with on_stage")
-        self.trace_begin(int(n_steps), keep_lambda)
-        self.trace_run(int(n_steps))
+        n_steps = int(n_steps)
+        if self._clock is not None:
+            n_steps = min(n_steps, self.steps_left())      # with nothing alive: an empty trace
+        self.trace_begin(max(n_steps, 1), keep_lambda)
+        if n_steps:
+            self.trace_run(n_steps)
         tr = self.trace(keep_lambda)
         self.trace_end()
         for k in range(tr.iters.shape[0]):

@@ -459,8 +459,10 @@ int32_t piadmm_obca_edge_time(piadmm_obca_t h, const double* recs, int32_t n_pai
  * integral, before any device call: a bad row is PIADMM_E_ARG with "obca_fleet_begin: row k: ..."
  * and an open plan stays as it was.  A scenario stops at i_iter > its own max_admm_iter;
  * piadmm_obca_plan_step runs at most the largest max_admm_iter of the rows, plus one, iterates.
- * The vehicle geometry and the delay statistics are constants of the solver kernels, n_ref and
- * t_step are the plan's: none of them is per scenario. */
+ * The vehicle geometry and the delay statistics are constants of the solver kernels and n_ref is
+ * the plan's: none of them is per scenario.  t_step is the plan's too unless a clock is attached
+ * (piadmm_obca_clock_plan, below): then every scenario reads its reference at its own step and
+ * over its own length. */
 #define PIADMM_OBCA_PLAN_STATE 556
 #define PIADMM_OBCA_PLAN_GET_STATE 0
 #define PIADMM_OBCA_PLAN_GET_STATE_PREV 1
@@ -489,6 +491,8 @@ int32_t piadmm_obca_edge_time(piadmm_obca_t h, const double* recs, int32_t n_pai
 #define PIADMM_OBCA_PLAN_GET_DUAL_D 24
 #define PIADMM_OBCA_PLAN_GET_DUAL_PAR 25
 #define PIADMM_OBCA_PLAN_GET_WORK 26
+#define PIADMM_OBCA_PLAN_GET_CLOCK 27
+#define PIADMM_OBCA_PLAN_GET_WINDOW 28
 #define PIADMM_OBCA_FLEET_PAR 16
 typedef struct {
   int32_t n_scenarios, t_step0, max_admm_iter, round_decimals, start, update_lamb_ij, max_sqp_iter, n_ref;
@@ -649,6 +653,80 @@ int32_t piadmm_obca_dual_pi(piadmm_obca_t h, int32_t n, const double* w, const d
 int32_t piadmm_obca_order_plan(piadmm_obca_t h, int32_t mode, const int32_t* work_init /* n x 2, may be NULL */);
 int32_t piadmm_obca_order(piadmm_obca_t h, const int32_t* list /* m */, int32_t m, const int32_t* work /* n x 2 */,
                           int32_t n, int32_t* out /* m */);
+
+/* ---- per-scenario clocks inside an open plan: mixed phases, retiring, admission ---------------
+ * A plan has one clock: every scenario reads its reference at the plan's t_step, and the plan ends
+ * for all of them when t_step + 8 > n_ref.  piadmm_obca_clock_plan, mode 1, attaches a record
+ *   clock[s] = (c, len, alive), three int32
+ * per scenario: c the row of its own reference that slot 0 of its horizon reads (its own MPC step),
+ * len the number of valid rows of its reference (8 <= len <= n_ref), alive = (c + 8 <= len).
+ * clock_init holds (c0, len) per scenario; NULL is c0 = t_step, len = n_ref for everyone, and the
+ * plan then computes what it computed without the clock, bit for bit.  Rows are checked before any
+ * device call (c0 >= 0, 8 <= len <= n_ref, c0 + 8 <= len): a bad row is PIADMM_E_ARG with
+ * "obca_clock_plan: row k: ...".  Only at a step boundary (PIADMM_E_STATE otherwise, as for
+ * piadmm_obca_trace_begin); for a plan of piadmm_obca_plan_begin (one shared reference read at
+ * different phases) or of piadmm_obca_fleet_begin alike; a second attach replaces the record.
+ * mode 0 detaches, only while every scenario is alive, all c are equal and every len == n_ref
+ * (PIADMM_E_STATE otherwise): the plan's t_step becomes that common c and the plan is plain again,
+ * running the launches it ran before.  A refused call leaves the plan as it was.
+ *
+ * While attached the device keeps a window ref_s[v][c .. c + 7] per scenario (n x 2 x 8 x 5 fp64,
+ * exact copies) and the local records are packed from it, so they are bit-equal to what the plain
+ * plan packs at t_step = c.  A step runs the scenarios that were alive when it opened;
+ * piadmm_obca_plan_shift closes it for exactly those (the state shift, init_state = X[1], the
+ * CTRL_PREV reset, LAMBDA and, with a dual law, the integrator shift), then c += 1 for them, alive
+ * is recomputed, the windows of the alive scenarios are refreshed and the next list is the alive
+ * scenarios ascending (longest first with piadmm_obca_order_plan attached).  The record evolves
+ * deterministically and the host keeps a mirror of it: nothing more is read back per iterate or per
+ * step.  A retired scenario (alive = 0) is frozen: its STATE, STATE_PREV, X, CTRL, LAMBDA, DUAL_S,
+ * DUAL_D, WORK and WINDOW stay as its last shift left them, its ITERS and STATUS_MASK are 0 in
+ * every later step, and its PRIMAL / DUAL (and STOP / CONVERGE) keep the values of its last iterate.
+ * With no scenario alive piadmm_obca_plan_iterate, piadmm_obca_plan_step and piadmm_obca_trace_run
+ * return PIADMM_E_STATE ("no scenario alive") before any launch; this replaces "reference
+ * exhausted".  T_STEP keeps counting the plan's steps and may pass n_ref - 8.  A trace keeps one row
+ * per plan step for all n: a retired scenario's row repeats its frozen init_state and clearance, has
+ * iterate 0 and masks 0 (its PRIMAL / DUAL / LAMBDA entries repeat the frozen values), adds 0 to the
+ * summary's sum and cannot move the running minimum's row (the comparison is strict).
+ * piadmm_obca_trace_run refuses n_steps larger than the steps the longest-lived scenario has left,
+ * max over the alive of len - 8 - c + 1.  piadmm_obca_plan_get gains
+ *   CLOCK               n x 3 int32          (c, len, alive) per scenario
+ *   WINDOW              n x 2 x 8 x 5 fp64   the reference window of each scenario (a retired one's: its last)
+ * (PIADMM_E_STATE without a clock).  piadmm_obca_plan_end, a new piadmm_obca_plan_begin /
+ * _fleet_begin and any upload that ends the plan free the record.
+ *
+ * piadmm_obca_clock_admit puts m new tenants into the slots `slots` (distinct, below n; a slot need
+ * not be retired) of the open plan.  Only at a step boundary, with a clock and without a trace
+ * attached (a trace's running minima would mix two tenants): PIADMM_E_STATE otherwise.  clock holds
+ * (c0, len) per tenant and is required; every other array may be NULL, which keeps what the slot
+ * has.  A non-NULL ref or par needs a plan with n rows of that kind (piadmm_obca_fleet_begin):
+ * PIADMM_E_STATE otherwise.  Before any device call the par rows pass the checks of
+ * piadmm_obca_fleet_begin, prob is 0 or 1 and the clock rows pass the checks above: a bad row is
+ * PIADMM_E_ARG with "obca_clock_admit: row k: ..." and the plan is unchanged.  Of every admitted
+ * slot both state copies are set to `state`, CTRL, CTRL_PREV, X, LAMBDA, ITERS and STATUS_MASK are
+ * zeroed, with a dual law S = S_prev = lamb_bar of the slot's state and D = D_prev = 0, with the
+ * order WORK = (0, 0); then the largest max_admm_iter is taken over the current rows and the
+ * windows, the alive flags and the active list are rebuilt.  The admitted tenant then computes what
+ * a fresh plan opened at t_step0 = c0 on the same state, reference and row computes.
+ *
+ * piadmm_obca_clock_tick runs the tick, window and compaction kernels alone on the call's own
+ * device buffers (the handle's buffers and an open plan stay as they are): clock_out[s] =
+ * (c + ran[s], len, alive), window_out[s] = ref_s[v][c' .. c' + 7] of an alive scenario (zeros
+ * otherwise), list_out = the alive scenarios ascending (count_out[0] of them, zeros behind).
+ * ref_rows = 1 (one reference for all) or n.  Before any device call: 1 <= n <= 2^20, non-null
+ * pointers, ref_rows 1 or n, 8 <= n_ref <= 2^20, 0 <= c <= 2^30, 8 <= len <= n_ref, ran 0 or 1
+ * ("obca_clock_tick: row k: ...", PIADMM_E_ARG). */
+int32_t piadmm_obca_clock_plan(piadmm_obca_t h, int32_t mode, const int32_t* clock_init /* n x 2: c0, len; may be NULL */);
+int32_t piadmm_obca_clock_admit(piadmm_obca_t h, int32_t m, const int32_t* slots /* m */,
+                                const int32_t* clock /* m x 2: c0, len */,
+                                const double* state /* m x 556 or NULL */,
+                                const double* ref /* m x 2 x n_ref x 5 or NULL */,
+                                const double* par /* m x PIADMM_OBCA_FLEET_PAR or NULL */,
+                                const int32_t* prob /* m or NULL */, const double* primal_thres /* m or NULL */,
+                                const double* dual_thres /* m or NULL */);
+int32_t piadmm_obca_clock_tick(piadmm_obca_t h, int32_t n, const int32_t* clock_in /* n x 3 */,
+                               const int32_t* ran /* n, 0 / 1 */, const double* ref, int32_t ref_rows /* 1 or n */,
+                               int32_t n_ref, int32_t* clock_out /* n x 3 */, double* window_out /* n x 2 x 8 x 5 */,
+                               int32_t* list_out /* n */, int32_t* count_out /* 1 */);
 
 #ifdef __cplusplus
 }

@@ -50,6 +50,17 @@
                    untimed pass where the costliest scenarios sit in each iterate's list.  Written
                    under the key "order" of the same JSON, the other keys kept.
 
+  --clock          instead of the above, in one process at --scenarios scenarios over --steps MPC steps
+                   from step 8 through run_traced, the repeats of the legs alternating after a warm-up
+                   step of each on its own plan: (a) obca.overtaking_fleet(--scenarios, seed=0) without a
+                   clock (the yardstick: the launches of a plan that never heard of it), (b) the same
+                   fleet with clock_init = NULL (everyone at step 8 over the whole reference: the same
+                   results, the difference is the window, the list-taking shifts and the tick), and,
+                   for information, (c) the fleet staggered, c0 drawn uniformly over the manoeuvre
+                   (0 .. n_ref - 8), so scenarios retire while the others go on.  (b)/(a) is reported
+                   next to the max/min spread of (a)'s own repeats; no ratio is fixed in advance.
+                   Written under the key "clock" of the same JSON, the other keys kept.
+
 There is no CPU baseline on an equal footing (the C++ port of the local solver has no edge step);
 the edge launch is reported next to the local launch so the reader sees its share of an iterate.
 Writes one JSON (default profiles/obca_admm_bench.json) and prints it.
@@ -348,8 +359,68 @@ def order_main(a):
     print(json.dumps(dict(order=res)))
 
 
+def clock_main(a):
+    """--clock: (a) the plain fleet, (b) the same fleet with clock_init = NULL, (c) the fleet staggered
+    over the manoeuvre; --steps MPC steps from step 8 through run_traced, the repeats alternating."""
+    b = obca.OBCABatch(0)
+    n, K = a.scenarios, a.steps
+    specs, par = obca.overtaking_fleet(n, seed=0)
+    kw = dict(prob=[k % 2 for k in range(n)], t_step0=8, max_admm_iter=a.iterates - 1, specs=specs, **par)
+    n_ref = 51
+    c0 = np.random.default_rng(0).integers(0, n_ref - 8 + 1, n)
+    stagger = np.ascontiguousarray(np.stack((c0, np.full(n, n_ref)), axis=1), np.int32)
+    clocks = dict(a_fleet=None, b_fleet_null_clock=True, c_fleet_staggered=stagger)
+    states, ms, traces, planners = {}, {k: [] for k in clocks}, {}, {}
+    for name, clock in clocks.items():
+        warm = obca.OBCADevicePlanner(b, n, clock=clock, **kw)
+        assert warm.n_ref == n_ref
+        states[name] = warm.get("STATE")              # the seeded state, so the later plans skip the host seeding
+        warm.step()
+        warm.close()
+    for _ in range(a.repeats):
+        for name, clock in clocks.items():
+            dp = obca.OBCADevicePlanner(b, n, clock=clock, state=states[name], **kw)
+            t0 = time.perf_counter()
+            traces[name] = dp.run_traced(K, keep_lambda=False)
+            ms[name].append((time.perf_counter() - t0) * 1e3)
+            planners[name] = dp
+            dp.close()
+    legs = {}
+    for name in clocks:
+        tr = traces[name]
+        n_it, best = int(tr.iters.max(axis=1).sum()), min(ms[name])
+        legs[name] = dict(steps_run=int(tr.iters.shape[0]), admm_iterates=n_it, step_ms=best / max(tr.iters.shape[0], 1),
+                          iterate_ms=best / max(n_it, 1), total_ms_runs=ms[name], spread_max_over_min=max(ms[name]) / best,
+                          scenario_steps_run=int((tr.iters > 0).sum()),
+                          stop_iterate_histogram=np.bincount(tr.iters.ravel()).tolist())
+    alive_end = planners["c_fleet_staggered"].alive()
+    legs["c_fleet_staggered"].update(alive_per_step=(traces["c_fleet_staggered"].iters > 0).sum(axis=1).tolist(),
+                                     alive_at_end=int(alive_end.sum()))
+    same = all(np.array_equal(getattr(traces["a_fleet"], f), getattr(traces["b_fleet_null_clock"], f))
+               for f in ("states", "clearance", "iters", "status_mask", "primal", "dual", "min_clearance", "min_row",
+                         "min_clearance_tight", "iters_sum"))
+    ratio = min(ms["b_fleet_null_clock"]) / min(ms["a_fleet"])
+    res = dict(scenarios=n, steps=K, repeats=a.repeats, max_admm_iter=a.iterates - 1, legs=legs,
+               null_clock_over_plain=ratio, plain_spread_max_over_min=legs["a_fleet"]["spread_max_over_min"],
+               ratio_exceeds_plain_spread=bool(ratio > legs["a_fleet"]["spread_max_over_min"]),
+               records_equal_null_clock=same,
+               staggered_ms_per_scenario_step=min(ms["c_fleet_staggered"]) / max(legs["c_fleet_staggered"]["scenario_steps_run"], 1),
+               plain_ms_per_scenario_step=min(ms["a_fleet"]) / max(legs["a_fleet"]["scenario_steps_run"], 1))
+    b.close()
+    out = {}
+    if os.path.exists(a.out):
+        with open(a.out) as f:
+            out = json.load(f)
+    out["clock"] = res
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+    print(json.dumps(dict(clock=res)))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--clock", action="store_true")
     ap.add_argument("--order", action="store_true")
     ap.add_argument("--dual-pi", action="store_true")
     ap.add_argument("--fleet", action="store_true")
@@ -361,6 +432,8 @@ def main():
     ap.add_argument("--iterates", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "obca_admm_bench.json"))
     a = ap.parse_args()
+    if a.clock:
+        return clock_main(a)
     if a.order:
         return order_main(a)
     if a.dual_pi:
