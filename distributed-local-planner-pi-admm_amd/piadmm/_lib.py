@@ -130,6 +130,9 @@ SYMBOLS = [
     ("piadmm_obca_clock_plan", c_i32, [_H, c_i32, _ip]),
     ("piadmm_obca_clock_admit", c_i32, [_H, c_i32, _ip, _ip, _dp, _dp, _dp, _ip, _dp, _dp]),
     ("piadmm_obca_clock_tick", c_i32, [_H, c_i32, _ip, _ip, _dp, c_i32, c_i32, _ip, _dp, _ip, _ip]),
+    ("piadmm_obca_tenant_export_bytes", c_i32, [_H, c_i32, _P(ctypes.c_int64)]),
+    ("piadmm_obca_tenant_export", c_i32, [_H, c_i32, _ip, ctypes.c_void_p, ctypes.c_int64]),
+    ("piadmm_obca_tenant_import", c_i32, [_H, c_i32, _ip, ctypes.c_void_p, ctypes.c_int64]),
 ]
 
 # PIADMM_OBCA_FLEET_PAR: doubles per parameter row of piadmm_obca_fleet_begin

@@ -142,6 +142,42 @@ def load_checkpoint(path: str, cfg=None, scn=None) -> dict:
     return st
 
 
+PLAN_ATTACHMENTS = ("fleet", "clock", "law", "order", "trace")
+
+
+def save_plan_checkpoint(path: str, tenants, t_step: int, plan_cfg: dict, attached: dict, dual_par=None) -> str:
+    """Checkpoint of a device-resident OBCA plan between two MPC steps
+    (``OBCADevicePlanner.save``): the blob of all its tenants as ``piadmm_obca_tenant_export`` wrote
+    it (``piadmm.obca.tenant_unpack`` reads it), the plan's ``T_STEP``, its cfg struct as JSON,
+    which of ``PLAN_ATTACHMENTS`` were on, and the gains row the plan shared, if it shared one.  A
+    trace is never part of the file; ``attached["trace"]`` only says that one was on."""
+    base = path[:-4] if path.endswith(".npz") else path
+    arrs = {"tenants": np.frombuffer(bytes(tenants), np.uint8), "t_step": np.array(int(t_step), np.int64),
+            "plan_cfg_json": np.array(json.dumps(plan_cfg, sort_keys=True)),
+            "attached": np.array([int(bool(attached.get(k, False))) for k in PLAN_ATTACHMENTS], np.int32)}
+    if dual_par is not None:
+        arrs["dual_par"] = np.asarray(dual_par, np.float64).reshape(-1)
+    np.savez_compressed(base + ".npz", **arrs)
+    return base + ".npz"
+
+
+def load_plan_checkpoint(path: str) -> dict:
+    """What :func:`save_plan_checkpoint` wrote (NumPy only, no pickles): ``tenants`` (a uint8 array),
+    ``t_step``, ``plan_cfg``, ``attached`` (name -> bool) and ``dual_par`` (the shared gains row or
+    None).  The blob is parsed once, so a truncated or corrupted one is refused here."""
+    from . import obca
+    base = path[:-4] if path.endswith(".npz") else path
+    d = np.load(base + ".npz", allow_pickle=False)
+    for k in ("tenants", "t_step", "plan_cfg_json", "attached"):
+        if k not in d.files:
+            raise ValueError(f"not a plan checkpoint: no {k}")
+    tenants = np.ascontiguousarray(d["tenants"], np.uint8)
+    obca.tenant_unpack(tenants)
+    return {"tenants": tenants, "t_step": int(d["t_step"]), "plan_cfg": json.loads(str(d["plan_cfg_json"])),
+            "attached": {k: bool(v) for k, v in zip(PLAN_ATTACHMENTS, d["attached"])},
+            "dual_par": d["dual_par"].copy() if "dual_par" in d.files else None}
+
+
 def plot_run(rec: RunRecord, path: str, agents=None) -> str:
     """The reference's figure (``casadi/main.py:206-220``): one scatter per vehicle of its
     positions over the run; more than two agents get one colour each."""

@@ -1043,7 +1043,9 @@ PLAN_GET = {"STATE": (0, np.float64), "STATE_PREV": (1, np.float64), "CTRL": (2,
             "T_STEP": (17, np.int32), "LAMBDA": (18, np.float64), "COUNTS": (19, np.int32),
             "STATUS_MASK": (20, np.int32), "REF": (21, np.float64), "PAR": (22, np.float64),
             "DUAL_S": (23, np.float64), "DUAL_D": (24, np.float64), "DUAL_PAR": (25, np.float64),
-            "WORK": (26, np.int32), "CLOCK": (27, np.int32), "WINDOW": (28, np.float64)}
+            "WORK": (26, np.int32), "CLOCK": (27, np.int32), "WINDOW": (28, np.float64),
+            "PRIMAL_THRES": (29, np.float64), "DUAL_THRES": (30, np.float64), "PROB": (31, np.int32),
+            "DUAL_S_PREV": (32, np.float64), "DUAL_D_PREV": (33, np.float64)}
 
 
 # piadmm_obca_trace_get items: name -> (code, dtype); piadmm_obca_trace_begin's flag
@@ -1094,6 +1096,147 @@ def unpack_state(vec):
     return bar, init
 
 
+# ---------------------------------------------------------------------------------------------
+# The tenant record of piadmm_obca_tenant_export / _import (include/piadmm.h), in NumPy
+# ---------------------------------------------------------------------------------------------
+TENANT_MAGIC = 0x314E5454
+TENANT_ABI = 7
+TENANT_HEADER = 64                    # bytes: sixteen int32
+TENANT_INTS = 12                      # int32 words behind the fp64 section of a record
+TENANT_F64 = 1474                     # fp64 words of a record, + 10 n_ref, + TENANT_F64_LAW with a law
+TENANT_F64_LAW = 512
+# the int32 section: name -> (first word, words)
+TENANT_INT_FIELDS = {"ITERS": (0, 1), "STOP": (1, 1), "CONVERGE": (2, 1), "PROB": (3, 1), "STATUS_MASK": (4, 2),
+                     "WORK": (6, 2), "CLOCK": (8, 3)}
+_TENANT_SHAPES = {"STATE": (PLAN_STATE,), "STATE_PREV": (PLAN_STATE,), "CTRL": (2, NT * NU), "CTRL_PREV": (2, NT * NU),
+                  "X": (2, N_HORZ, NX), "LAMBDA": (2, NT, 9), "PRIMAL": (), "DUAL": (), "PRIMAL_THRES": (),
+                  "DUAL_THRES": (), "PAR": (FLEET_PAR,), "WINDOW": (2, N_HORZ, NX), "DUAL_S": (2, NT, 9),
+                  "DUAL_D": (2, NT, 9), "DUAL_S_PREV": (2, NT, 9), "DUAL_D_PREV": (2, NT, 9), "DUAL_PAR": (DUAL_PAR,),
+                  "ITERS": (), "STOP": (), "CONVERGE": (), "PROB": (), "STATUS_MASK": (2,), "WORK": (2,), "CLOCK": (3,)}
+
+
+def tenant_layout(n_ref, law=False):
+    """The layout of one tenant record: dict(f64={name: (first fp64 word, words)}, F=the fp64 words,
+    ints=TENANT_INT_FIELDS, record_bytes=8 F + 48), as the table of include/piadmm.h has it."""
+    fields = [("STATE", PLAN_STATE), ("STATE_PREV", PLAN_STATE), ("CTRL", 28), ("CTRL_PREV", 28), ("X", 80),
+              ("LAMBDA", 126), ("PRIMAL", 1), ("DUAL", 1), ("PRIMAL_THRES", 1), ("DUAL_THRES", 1), ("PAR", FLEET_PAR),
+              ("REF", 10 * int(n_ref)), ("WINDOW", 80)]
+    if law:
+        fields += [("DUAL_S", 126), ("DUAL_D", 126), ("DUAL_S_PREV", 126), ("DUAL_D_PREV", 126), ("DUAL_PAR", DUAL_PAR)]
+    f64, o = {}, 0
+    for name, words in fields:
+        f64[name] = (o, words)
+        o += words
+    assert o == TENANT_F64 + 10 * int(n_ref) + (TENANT_F64_LAW if law else 0)
+    return dict(f64=f64, F=o, ints=dict(TENANT_INT_FIELDS), record_bytes=8 * o + 4 * TENANT_INTS)
+
+
+def _tenant_row_check(par):
+    """What the library's row check refuses of a parameter row (None: the row is good)."""
+    rho, _, _, max_x, max_y, r, q, x_bound, mu_max, _, admm, sqp, rnd, start = (float(v) for v in par[:14])
+
+    def integral(v, lo, hi):
+        return lo <= v <= hi and v == np.floor(v)
+    if not (rho > 0 and r > 0 and q > 0 and max_x > 0 and max_y > 0 and x_bound > 0 and mu_max > 0):
+        return "bad parameters (rho, r, q, max_x, max_y, x_bound, mu_max > 0)"
+    if not integral(sqp, 1, 1000):
+        return "1 <= max_sqp_iter <= 1000, an integer"
+    if not integral(start, 0, 1):
+        return "start 0 or 1"
+    if not integral(rnd, -1, 15):
+        return "-1 <= round_decimals <= 15, an integer"
+    if not integral(admm, 0, 2 ** 30):
+        return "max_admm_iter >= 0 (at most 2^30), an integer"
+    return None
+
+
+def tenant_pack(items, slots, n_ref, update_lamb_ij=0, t_step=0):
+    """The blob piadmm_obca_tenant_export writes for the scenarios `slots`, from the plan's
+    piadmm_obca_plan_get items (name -> array over all n scenarios): STATE, STATE_PREV, CTRL,
+    CTRL_PREV, X, LAMBDA, PRIMAL, DUAL, PRIMAL_THRES, DUAL_THRES, PAR, REF, ITERS, STOP, CONVERGE, PROB,
+    STATUS_MASK; with a law DUAL_S, DUAL_D, DUAL_S_PREV, DUAL_D_PREV and DUAL_PAR; with the order WORK;
+    with a clock CLOCK and WINDOW.  PAR, REF and DUAL_PAR of one row are shared: the row goes into
+    every record.  Without CLOCK the record's clock is (t_step, n_ref, 1) and its window the 8
+    reference rows at t_step (zeros past the end).  Returns a uint8 array."""
+    slots = [int(s) for s in np.asarray(slots).reshape(-1)]
+    m, n_ref = len(slots), int(n_ref)
+    law, order, clocked = "DUAL_S" in items, "WORK" in items, "CLOCK" in items
+    lay = tenant_layout(n_ref, law)
+    n = np.asarray(items["STATE"]).reshape(-1, PLAN_STATE).shape[0]
+    f64 = np.zeros((m, lay["F"]))
+    ints = np.zeros((m, TENANT_INTS), np.int32)
+    for name, (o, words) in lay["f64"].items():
+        if name == "WINDOW" and not clocked:
+            ref = np.ascontiguousarray(items["REF"], np.float64).reshape(-1, 2, n_ref, NX)
+            for k, s in enumerate(slots):
+                if 0 <= t_step and t_step + N_HORZ <= n_ref:
+                    f64[k, o:o + words] = ref[s if len(ref) > 1 else 0][:, t_step:t_step + N_HORZ].reshape(-1)
+            continue
+        a = np.ascontiguousarray(items[name], np.float64).reshape(-1, words)
+        assert len(a) in (1, n), (name, a.shape)
+        for k, s in enumerate(slots):
+            f64[k, o:o + words] = a[s if len(a) > 1 else 0]
+    for name, (o, words) in lay["ints"].items():
+        if name == "WORK" and not order:
+            continue
+        if name == "CLOCK" and not clocked:
+            ints[:, o:o + 3] = (int(t_step), n_ref, 1)
+            continue
+        a = np.ascontiguousarray(items[name], np.int32).reshape(n, words)
+        for k, s in enumerate(slots):
+            ints[k, o:o + words] = a[s]
+    hdr = np.zeros(TENANT_HEADER // 4, np.int32)
+    hdr[:11] = (TENANT_MAGIC, TENANT_ABI, m, n_ref, int(update_lamb_ij), int(law), int(order), lay["F"], TENANT_INTS,
+                lay["record_bytes"], TENANT_HEADER)
+    body = np.concatenate((f64.view(np.uint8).reshape(m, -1), ints.view(np.uint8).reshape(m, -1)), axis=1)
+    return np.concatenate((hdr.view(np.uint8), body.reshape(-1)))
+
+
+def tenant_unpack(blob):
+    """The tenants of a blob: dict(m, n_ref, update_lamb_ij, law, order, and per field of the record an
+    array over the m tenants -- copies).  ValueError for what piadmm_obca_tenant_import refuses of the
+    blob alone: a short or corrupted header, a size that does not follow from it, and per record
+    ("row k: ...") a bad parameter row, prob not 0 / 1, a clock with c < 0 or len outside [8, n_ref]."""
+    raw = np.frombuffer(blob, np.uint8) if isinstance(blob, (bytes, bytearray, memoryview)) else np.asarray(blob, np.uint8)
+    raw = raw.reshape(-1)
+    if raw.size < TENANT_HEADER:
+        raise ValueError("tenant blob: shorter than its header")
+    hdr = raw[:TENANT_HEADER].copy().view(np.int32)
+    magic, abi, m, n_ref, ulij, law, order, F, n_int, rec_bytes, hdr_bytes = (int(v) for v in hdr[:11])
+    if magic != TENANT_MAGIC:
+        raise ValueError("tenant blob: bad magic")
+    if abi != TENANT_ABI:
+        raise ValueError(f"tenant blob: ABI {abi}, not {TENANT_ABI}")
+    if m < 1 or n_ref < N_HORZ or ulij not in (0, 1) or law not in (0, 1) or order not in (0, 1) or hdr[11:].any():
+        raise ValueError("tenant blob: bad header (counts or flags)")
+    lay = tenant_layout(n_ref, bool(law))
+    if (F, n_int, rec_bytes, hdr_bytes) != (lay["F"], TENANT_INTS, lay["record_bytes"], TENANT_HEADER):
+        raise ValueError("tenant blob: bad header (section sizes)")
+    if raw.size != TENANT_HEADER + m * rec_bytes:
+        raise ValueError(f"tenant blob: {raw.size} bytes, not the {TENANT_HEADER + m * rec_bytes} of its header (truncated?)")
+    body = raw[TENANT_HEADER:].reshape(m, rec_bytes)
+    f64 = np.ascontiguousarray(body[:, :8 * F]).view(np.float64).reshape(m, F)
+    ints = np.ascontiguousarray(body[:, 8 * F:]).view(np.int32).reshape(m, TENANT_INTS)
+    out = dict(m=m, n_ref=n_ref, update_lamb_ij=ulij, law=bool(law), order=bool(order))
+    for name, (o, words) in lay["f64"].items():
+        shape = (2, n_ref, NX) if name == "REF" else _TENANT_SHAPES[name]
+        out[name] = f64[:, o:o + words].reshape((m,) + shape).copy()
+    for name, (o, words) in lay["ints"].items():
+        out[name] = ints[:, o:o + words].reshape((m,) + _TENANT_SHAPES[name]).copy()
+    for k in range(m):
+        why = _tenant_row_check(out["PAR"][k])
+        if why is None and out["PROB"][k] not in (0, 1):
+            why = "prob must be 0 or 1"
+        c, length = int(out["CLOCK"][k, 0]), int(out["CLOCK"][k, 1])
+        if why is None and c < 0:
+            why = "c >= 0"
+        if why is None and not N_HORZ <= length <= n_ref:
+            why = "8 <= len <= n_ref"
+        if why is not None:
+            raise ValueError(f"tenant blob: row {k}: {why}")
+    return out
+
+
 class OBCADevicePlanner:
     """`OBCAPlanner` with the loop on the device: the planner state stays resident on the batch's
     handle and one ADMM iterate is a fixed chain of launches (csrc/piadmm_obca_plan.hip); the host
@@ -1124,7 +1267,12 @@ class OBCADevicePlanner:
     Scenario s is seeded at its own c0 and reads its reference at its own step; once c + 8 > len it
     is retired and frozen while the others go on.  `clock()` reads the record, `admit` puts new
     tenants into slots, `run` / `run_traced` stop when nothing is alive.  t_step counts the plan's
-    steps."""
+    steps.
+
+    Running tenants move as records (piadmm_obca_tenant_export / _import): `export_tenants` of any
+    plan, `import_tenants` into a clocked fleet plan, `compact()` for a new planner with the alive
+    tenants only, `save` / `load` for a checkpoint of the whole plan; a moved tenant continues bit
+    for bit."""
 
     def __init__(self, batch, n_scenarios, prob=1, t_step0=0, rho=1.0, min_dis=0.1, max_admm_iter=50,
                  primal_thres=0.01, dual_thres=0.01, round_decimals=4, start=1, update_lamb_ij=0, max_iter=60,
@@ -1294,6 +1442,144 @@ class OBCADevicePlanner:
             if specs is not None and self.specs is not None:
                 self.specs[s] = specs[k]
 
+    # -- running tenants: export, import, compaction, checkpoints (piadmm_obca_tenant_export / _import) --
+    TENANT_ITEMS = ("STATE", "STATE_PREV", "CTRL", "CTRL_PREV", "X", "LAMBDA", "PRIMAL", "DUAL", "PRIMAL_THRES",
+                    "DUAL_THRES", "PAR", "REF", "ITERS", "STOP", "CONVERGE", "PROB", "STATUS_MASK")
+
+    def tenant_items(self):
+        """Every piadmm_obca_plan_get item a tenant record holds, by name: what `tenant_pack` takes."""
+        names = self.TENANT_ITEMS
+        if self.dual_par is not None:
+            names += ("DUAL_S", "DUAL_D", "DUAL_S_PREV", "DUAL_D_PREV", "DUAL_PAR")
+        if self.order:
+            names += ("WORK",)
+        if self._clock is not None:
+            names += ("CLOCK", "WINDOW")
+        return {k: self.get(k) for k in names}
+
+    def export_tenants(self, slots) -> bytes:
+        """The running tenants in `slots` as one blob (piadmm_obca_tenant_export; a step boundary only):
+        `tenant_unpack` reads it, `import_tenants` of any clocked fleet plan with the same n_ref,
+        update_lamb_ij, law and order continues them bit for bit.  The plan is not changed."""
+        from . import _lib
+        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        size = ctypes.c_int64()
+        self._check(self._lib.piadmm_obca_tenant_export_bytes(self.batch._h, len(slots), ctypes.byref(size)))
+        blob = np.zeros(size.value, np.uint8)
+        self._check(self._lib.piadmm_obca_tenant_export(self.batch._h, len(slots), _lib.iptr(slots), blob.ctypes.data,
+                                                      blob.nbytes))
+        return blob.tobytes()
+
+    def import_tenants(self, slots, tenants):
+        """The tenants of a blob of `export_tenants` into `slots` (piadmm_obca_tenant_import; a clocked
+        fleet plan at a step boundary, without a trace).  Nothing is zeroed: a slot holds what the
+        tenant had, a retired tenant stays retired."""
+        from . import _lib
+        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        blob = np.frombuffer(tenants, np.uint8) if isinstance(tenants, (bytes, bytearray, memoryview)) \
+            else np.ascontiguousarray(tenants, np.uint8)
+        self._check(self._lib.piadmm_obca_tenant_import(self.batch._h, len(slots), _lib.iptr(slots), blob.ctypes.data,
+                                                      blob.nbytes))
+        # the host's copies of what the slots now hold
+        t = tenant_unpack(blob)
+        self._clock[slots, :2] = t["CLOCK"][:, :2]
+        self._clock[slots, 2] = t["CLOCK"][:, 0] + N_HORZ <= t["CLOCK"][:, 1]
+        self.ref_traj_s = np.array(self.ref_traj_s)
+        self.ref_traj_s[slots] = t["REF"]
+        self.ref_traj = None
+        self.par[slots] = t["PAR"]
+        for j, name in enumerate(FLEET_ROW):
+            col = getattr(self, name + "_s").astype(np.float64)
+            col[slots] = t["PAR"][:, j]
+            setattr(self, name + "_s", col)
+        self.primal_thres[slots] = t["PRIMAL_THRES"]
+        self.dual_thres[slots] = t["DUAL_THRES"]
+        if self.dual_par is not None and len(self.dual_par) == self.n:
+            self.dual_par[slots] = t["DUAL_PAR"]
+        for k, s in enumerate(slots):
+            self.prob[s] = int(t["PROB"][k])
+            self.init_state[s] = unpack_state(t["STATE"][k])[1]
+            if self.specs is not None:
+                self.specs[s] = None              # the tenant's reference is its own, not a spec's
+
+    @classmethod
+    def from_tenants(cls, batch, tenants, t_step=0, dual_par=None, on_stage=None):
+        """A new clocked fleet plan on `batch` that holds exactly the tenants of a blob, in its order:
+        opened through piadmm_obca_fleet_begin on the tenants' own rows and references, the clock
+        attached, then the law and the order when the blob carries them, then the import.  dual_par:
+        the one gains row the plan shares (None: a row per tenant, the blob's).  The plan counts its
+        steps from t_step; the library opens it at min(t_step, n_ref - 8), which a clocked plan
+        only shows in T_STEP."""
+        t = tenant_unpack(tenants)
+        m, par = t["m"], t["PAR"]
+        kw = {name: par[:, j] for j, name in enumerate(FLEET_ROW)}
+        pl = cls(batch, m, prob=[int(p) for p in t["PROB"]], t_step0=min(int(t_step), t["n_ref"] - N_HORZ),
+                 primal_thres=t["PRIMAL_THRES"], dual_thres=t["DUAL_THRES"], update_lamb_ij=t["update_lamb_ij"],
+                 ref_traj=t["REF"], state=t["STATE"], clock=True, on_stage=on_stage, **kw)
+        if t["law"]:
+            pl._set_dual_rows(t["DUAL_PAR"] if dual_par is None else np.asarray(dual_par, np.float64).reshape(1, DUAL_PAR))
+        if t["order"]:
+            pl.set_order()
+        pl.import_tenants(np.arange(m), tenants)
+        pl.t_step = int(t_step)
+        pl.record.state_record[0] = np.stack(pl.init_state)
+        return pl
+
+    def _shared_gains(self):
+        """The one gains row a plan of more than one scenario shares, else None."""
+        shared = self.dual_par is not None and len(self.dual_par) == 1 and self.n > 1
+        return self.dual_par[0].copy() if shared else None
+
+    def compact(self):
+        """A new planner on the same batch that holds only the alive tenants, in ascending order of
+        their slots (`compact_slots` on the result: where each was).  The batch holds one plan, so
+        this planner ends as the new one opens; the tenants continue bit for bit."""
+        alive = np.flatnonzero(self.alive())
+        if not len(alive):
+            raise ValueError("compact: no tenant alive")
+        blob = self.export_tenants(alive)
+        pl = type(self).from_tenants(self.batch, blob, t_step=int(self.get("T_STEP")[0]), dual_par=self._shared_gains(),
+                                     on_stage=self.on_stage)
+        pl.compact_slots = alive
+        return pl
+
+    def _trace_attached(self):
+        try:
+            self.trace_rows()
+            return True
+        except Exception:
+            return False
+
+    def save(self, path):
+        """Checkpoint of the whole plan at a step boundary (piadmm.io.save_plan_checkpoint, one
+        .npz): the blob of all n tenants, the plan cfg, T_STEP, which attachments were on and the
+        shared gains row if any.  A trace is not saved (the file says one was attached; it stays
+        readable here)."""
+        from . import io
+        cfg = {f: getattr(self.cfg, f) for f, _ in self.cfg._fields_}
+        return io.save_plan_checkpoint(path, self.export_tenants(np.arange(self.n)), int(self.get("T_STEP")[0]), cfg,
+                                       dict(fleet=self.fleet, clock=self._clock is not None,
+                                            law=self.dual_par is not None, order=bool(self.order),
+                                            trace=self._trace_attached()), self._shared_gains())
+
+    @classmethod
+    def load(cls, batch, path, on_stage=None):
+        """The plan `save` wrote, reopened on `batch` (`from_tenants` at the saved T_STEP) so that its
+        next steps are the uninterrupted run's, bit for bit.  It is a fleet plan whatever the saved
+        one was; a plan saved without a clock gets its clock detached again."""
+        from . import io
+        ck = io.load_plan_checkpoint(path)
+        pl = cls.from_tenants(batch, ck["tenants"], t_step=ck["t_step"], dual_par=ck["dual_par"], on_stage=on_stage)
+        if not ck["attached"]["clock"] and pl.alive().all():
+            pl.clear_clock()
+        return pl
+
+    def _set_dual_rows(self, rows):
+        from . import _lib
+        rows = np.ascontiguousarray(rows, np.float64).reshape(-1, DUAL_PAR)
+        self._check(self._lib.piadmm_obca_dual_plan(self.batch._h, _lib.dptr(rows), rows.shape[0]))
+        self.dual_par = rows
+
     def set_order(self, work_init=None):
         """Attach the longest-first order (piadmm_obca_order_plan; a step boundary only), its record
         zero or seeded with work_init (n x 2: Q, I per scenario)."""
@@ -1353,7 +1639,8 @@ class OBCADevicePlanner:
                  "COUNTS": (3,), "STATUS_MASK": (n, 2), "REF": (rows, 2, self.n_ref, NX),
                  "PAR": (rows, FLEET_PAR), "DUAL_S": (n, 2, NT, 9), "DUAL_D": (n, 2, NT, 9),
                  "DUAL_PAR": (1 if self.dual_par is None else len(self.dual_par), DUAL_PAR), "WORK": (n, 2),
-                 "CLOCK": (n, 3), "WINDOW": (n, 2, N_HORZ, NX)}[what]
+                 "CLOCK": (n, 3), "WINDOW": (n, 2, N_HORZ, NX), "PRIMAL_THRES": (n,), "DUAL_THRES": (n,),
+                 "PROB": (n,), "DUAL_S_PREV": (n, 2, NT, 9), "DUAL_D_PREV": (n, 2, NT, 9)}[what]
         out = np.zeros(shape, dt)
         self._check(self._lib.piadmm_obca_plan_get(self.batch._h, code, out.ctypes.data, out.nbytes))
         return out

@@ -728,6 +728,77 @@ int32_t piadmm_obca_clock_tick(piadmm_obca_t h, int32_t n, const int32_t* clock_
                                int32_t n_ref, int32_t* clock_out /* n x 3 */, double* window_out /* n x 2 x 8 x 5 */,
                                int32_t* list_out /* n */, int32_t* count_out /* 1 */);
 
+/* ---- export and import of running tenants: checkpoint, migration, compaction ------------------
+ * piadmm_obca_clock_admit starts a fresh tenant.  A RUNNING tenant leaves a plan, or enters one,
+ * as a record that holds every per-scenario array of the plan; a scenario's answers do not depend
+ * on its place in a batch, so a tenant exported at a step boundary and imported into any slot of any
+ * plan continues bit for bit.  A blob is a header followed by m records, little endian as the
+ * device writes them.
+ *
+ * Header, PIADMM_OBCA_TENANT_HEADER = 64 bytes, sixteen int32:
+ *   0 magic PIADMM_OBCA_TENANT_MAGIC | 1 PIADMM_ABI_VERSION | 2 m | 3 n_ref | 4 update_lamb_ij |
+ *   5 law present (0 / 1) | 6 order present (0 / 1) | 7 F, the fp64 words of a record |
+ *   8 PIADMM_OBCA_TENANT_INTS, its int32 words | 9 the bytes of a record, 8 F + 48 |
+ *   10 the bytes of the header | 11-15 zero
+ * Record k starts at byte 64 + k (8 F + 48).  Its fp64 section, offsets in doubles (R = 10 n_ref):
+ *   0 STATE 556 | 556 STATE_PREV 556 | 1112 CTRL 28 | 1140 CTRL_PREV 28 | 1168 X 80 |
+ *   1248 LAMBDA 126 | 1374 PRIMAL | 1375 DUAL | 1376 primal_thres | 1377 dual_thres |
+ *   1378 the parameter row 16 | 1394 the tenant's reference 2 x n_ref x 5 |
+ *   1394 + R WINDOW 80 (with a clock the window the plan holds; without one the 8 rows at t_step,
+ *   zeros when t_step + 8 > n_ref)
+ * and, only with a law, from L = 1474 + R:
+ *   L S 126 | L + 126 D 126 | L + 252 S_prev 126 | L + 378 D_prev 126 | L + 504 the gains row 8
+ * so F = 1474 + R without a law and 1986 + R with one.  Every segment but the four scalars starts
+ * on an even word and has an even length, and a record is a multiple of 16 bytes.  Its int32
+ * section, at byte 8 F of the record:
+ *   0 ITERS | 1 STOP | 2 CONVERGE | 3 prob | 4-5 STATUS_MASK | 6-7 WORK (zeros without the order) |
+ *   8-10 CLOCK (c, len, alive; (t_step, n_ref, 1) without a clock) | 11 zero
+ * piadmm.obca.tenant_pack / tenant_unpack are the same statement in NumPy.
+ *
+ * piadmm_obca_tenant_export_bytes returns the size of a blob of m tenants of the open plan.
+ * piadmm_obca_tenant_export writes the tenants in `slots` (m distinct scenarios below n, any order;
+ * record k is scenario slots[k]) of any open plan -- shared or fleet, with or without clock, law,
+ * order or trace; a shared plan writes its one row, its one reference and its one gains row into
+ * every record; a retired tenant exports like any other.  `bytes` must be exact (PIADMM_E_ARG); only
+ * at a step boundary (PIADMM_E_STATE).  The plan is not changed.  The m slot numbers go to the device,
+ * one launch of k_plan_export (one wave per tenant) fills a staging buffer there, and one copy
+ * brings the records to the host.
+ *
+ * piadmm_obca_tenant_import puts the m tenants of a blob into `slots` of the open plan; nothing is
+ * zeroed, the slot holds what the tenant had.  Checked before any device call, PIADMM_E_ARG: the
+ * slots; the header (magic, ABI, m, the section sizes against its own n_ref and flags, `bytes`);
+ * n_ref and update_lamb_ij equal to the plan's; then per record, "obca_tenant_import: row k: ...":
+ * the parameter row as piadmm_obca_fleet_begin checks it, prob 0 or 1, the clock c >= 0 and
+ * 8 <= len <= n_ref.  Then, PIADMM_E_STATE: a clock is attached, no trace is, the plan is at a step
+ * boundary, it has n references and n parameter rows (piadmm_obca_fleet_begin), and the law and the
+ * order are attached exactly when the blob carries them.  A plan with one shared gains row takes
+ * only tenants whose gains row equals it bit for bit (PIADMM_E_ARG; the row is read back for this);
+ * with n gains rows the row travels.  A refused call leaves every piadmm_obca_plan_get item as it
+ * was.  One copy of the records to the device (and the m slot numbers) and one launch of
+ * k_plan_import; alive is recomputed
+ * as c + 8 <= len, so a retired tenant stays retired and frozen; then, as an admission does, the
+ * largest max_admm_iter is taken over the current rows and the windows of the alive, the alive flags
+ * and the active list are rebuilt (re-sorted, with the order attached).
+ *
+ * piadmm_obca_plan_get gains, for the arrays a record holds and no item showed,
+ *   PRIMAL_THRES, DUAL_THRES   n fp64    the stop thresholds as uploaded
+ *   PROB                       n int32
+ *   DUAL_S_PREV, DUAL_D_PREV   n x 2 x 7 x 9 fp64   the previous iterate's integrator (PIADMM_E_STATE without a law) */
+#define PIADMM_OBCA_TENANT_MAGIC 0x314E5454 /* "TTN1" */
+#define PIADMM_OBCA_TENANT_HEADER 64
+#define PIADMM_OBCA_TENANT_INTS 12
+#define PIADMM_OBCA_TENANT_F64 1474       /* + 10 n_ref, + PIADMM_OBCA_TENANT_F64_LAW with a law */
+#define PIADMM_OBCA_TENANT_F64_LAW 512
+#define PIADMM_OBCA_PLAN_GET_PRIMAL_THRES 29
+#define PIADMM_OBCA_PLAN_GET_DUAL_THRES 30
+#define PIADMM_OBCA_PLAN_GET_PROB 31
+#define PIADMM_OBCA_PLAN_GET_DUAL_S_PREV 32
+#define PIADMM_OBCA_PLAN_GET_DUAL_D_PREV 33
+int32_t piadmm_obca_tenant_export_bytes(piadmm_obca_t h, int32_t m, int64_t* bytes);
+int32_t piadmm_obca_tenant_export(piadmm_obca_t h, int32_t m, const int32_t* slots /* m */, void* blob, int64_t bytes);
+int32_t piadmm_obca_tenant_import(piadmm_obca_t h, int32_t m, const int32_t* slots /* m */, const void* blob,
+                                int64_t bytes);
+
 #ifdef __cplusplus
 }
 #endif

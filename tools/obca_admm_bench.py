@@ -61,6 +61,20 @@
                    next to the max/min spread of (a)'s own repeats; no ratio is fixed in advance.
                    Written under the key "clock" of the same JSON, the other keys kept.
 
+  --migrate        instead of the above, in one process: all --scenarios tenants of
+                   obca.overtaking_fleet(--scenarios, seed=0) (clocked, at step 8) move from one plan
+                   into another on a second handle, two ways, the legs alternating over --repeats
+                   repeats after one untimed repeat: (a) piadmm_obca_tenant_export + piadmm_obca_tenant_import
+                   (one launch and one copy of the records each way), (b) the per-slot path there was
+                   before: piadmm_obca_plan_get of STATE, REF, PAR, PROB and both thresholds, then one
+                   piadmm_obca_clock_admit with every array (about fifteen synchronous copies or memsets
+                   per slot).  (b) does less: an admission does not carry the running state, so this
+                   compares upload mechanics only.  After each leg one MPC step of the destination is
+                   timed next to the first step of a plan that never saw an import (the same work: the
+                   source stands at its seeded state); that ratio is reported next to the fresh leg's
+                   own spread.  No ratio is fixed in advance.  Written under the key "migrate" of the
+                   same JSON, the other keys kept.
+
 There is no CPU baseline on an equal footing (the C++ port of the local solver has no edge step);
 the edge launch is reported next to the local launch so the reader sees its share of an iterate.
 Writes one JSON (default profiles/obca_admm_bench.json) and prints it.
@@ -418,8 +432,95 @@ def clock_main(a):
     print(json.dumps(dict(clock=res)))
 
 
+def migrate_main(a):
+    """--migrate: every tenant of a clocked fleet from one plan into another, through export + import and
+    through plan_get + clock_admit, the legs alternating; then one MPC step of the destination against
+    the first step of a plan that never saw an import."""
+    import ctypes
+
+    from piadmm import _lib
+    n = a.scenarios
+    specs, par = obca.overtaking_fleet(n, seed=0)
+    kw = dict(prob=[k % 2 for k in range(n)], t_step0=8, max_admm_iter=a.iterates - 1, specs=specs, clock=True, **par)
+    ha, hb, hc = (obca.OBCABatch(0) for _ in range(3))
+    lib = ha._lib
+    src = obca.OBCADevicePlanner(ha, n, **kw)
+    seeds = src.get("STATE")                           # the seeded state, so the later plans skip the host seeding
+    dst = obca.OBCADevicePlanner(hb, n, state=seeds, **kw)
+    slots = np.arange(n, dtype=np.int32)
+    size = ctypes.c_int64()
+    src._check(lib.piadmm_obca_tenant_export_bytes(ha._h, n, ctypes.byref(size)))
+    blob = np.zeros(size.value, np.uint8)
+    clock2 = np.ascontiguousarray(src.clock()[:, :2])
+    iters = {k: np.zeros(n, np.int32) for k in ("import", "admit", "fresh")}
+
+    def step_ms(pl, key):
+        t0 = time.perf_counter()
+        pl._check(lib.piadmm_obca_plan_step(pl.batch._h, _lib.iptr(iters[key])))
+        return (time.perf_counter() - t0) * 1e3
+
+    def leg_export_import():
+        t0 = time.perf_counter()
+        src._check(lib.piadmm_obca_tenant_export(ha._h, n, _lib.iptr(slots), blob.ctypes.data, blob.nbytes))
+        t1 = time.perf_counter()
+        dst._check(lib.piadmm_obca_tenant_import(hb._h, n, _lib.iptr(slots), blob.ctypes.data, blob.nbytes))
+        t2 = time.perf_counter()
+        return (t1 - t0) * 1e3, (t2 - t1) * 1e3
+
+    def leg_get_admit():
+        t0 = time.perf_counter()
+        got = {k: src.get(k) for k in ("STATE", "REF", "PAR", "PROB", "PRIMAL_THRES", "DUAL_THRES")}
+        t1 = time.perf_counter()
+        dst._check(lib.piadmm_obca_clock_admit(hb._h, n, _lib.iptr(slots), _lib.iptr(clock2), _lib.dptr(got["STATE"]),
+                                               _lib.dptr(got["REF"]), _lib.dptr(got["PAR"]), _lib.iptr(got["PROB"]),
+                                               _lib.dptr(got["PRIMAL_THRES"]), _lib.dptr(got["DUAL_THRES"])))
+        t2 = time.perf_counter()
+        return (t1 - t0) * 1e3, (t2 - t1) * 1e3
+
+    ms = {k: [] for k in ("export", "import", "export_import", "get", "admit", "get_admit", "step_after_import",
+                          "step_after_admit", "step_fresh")}
+    same_iters = True
+    for rep in range(a.repeats + 1):                    # repeat 0 is the warm-up
+        e, i = leg_export_import()
+        s_imp = step_ms(dst, "import")
+        g, ad = leg_get_admit()
+        s_adm = step_ms(dst, "admit")
+        fresh = obca.OBCADevicePlanner(hc, n, state=seeds, **kw)
+        s_fresh = step_ms(fresh, "fresh")
+        fresh.close()
+        same_iters = same_iters and np.array_equal(iters["import"], iters["fresh"]) and np.array_equal(iters["admit"], iters["fresh"])
+        if rep == 0:
+            continue
+        for k, v in (("export", e), ("import", i), ("export_import", e + i), ("get", g), ("admit", ad), ("get_admit", g + ad),
+                     ("step_after_import", s_imp), ("step_after_admit", s_adm), ("step_fresh", s_fresh)):
+            ms[k].append(v)
+    legs = {k: dict(best_ms=min(v), runs_ms=v, spread_max_over_min=max(v) / min(v)) for k, v in ms.items()}
+    res = dict(scenarios=n, repeats=a.repeats, max_admm_iter=a.iterates - 1, blob_bytes=int(size.value),
+               record_bytes=(int(size.value) - obca.TENANT_HEADER) // n, legs=legs,
+               get_admit_over_export_import=legs["get_admit"]["best_ms"] / legs["export_import"]["best_ms"],
+               step_after_import_over_fresh=legs["step_after_import"]["best_ms"] / legs["step_fresh"]["best_ms"],
+               step_after_admit_over_fresh=legs["step_after_admit"]["best_ms"] / legs["step_fresh"]["best_ms"],
+               fresh_step_spread_max_over_min=legs["step_fresh"]["spread_max_over_min"],
+               stop_iterates_equal=bool(same_iters),
+               note="the admission leg does less (it does not carry the running state): upload mechanics only")
+    src.close()
+    dst.close()
+    for h in (ha, hb, hc):
+        h.close()
+    out = {}
+    if os.path.exists(a.out):
+        with open(a.out) as f:
+            out = json.load(f)
+    out["migrate"] = res
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+    print(json.dumps(dict(migrate=res)))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--migrate", action="store_true")
     ap.add_argument("--clock", action="store_true")
     ap.add_argument("--order", action="store_true")
     ap.add_argument("--dual-pi", action="store_true")
@@ -432,6 +533,8 @@ def main():
     ap.add_argument("--iterates", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "obca_admm_bench.json"))
     a = ap.parse_args()
+    if a.migrate:
+        return migrate_main(a)
     if a.clock:
         return clock_main(a)
     if a.order:
