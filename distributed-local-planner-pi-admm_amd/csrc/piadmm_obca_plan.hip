@@ -24,6 +24,10 @@
 // k_plan_dual_shift_list on the scenarios the step ran and then k_plan_clock (their tick, the alive
 // flags, the windows) and k_plan_compact on the flags (the next list: the alive scenarios); without
 // them none of the three is launched and the plan issues the launches it issued before.
+// With the feedback attached (piadmm_obca_feedback_plan) piadmm_obca_plan_shift runs k_plan_propagate
+// before k_plan_shift (the plant step from the closing step's init_state and first control) and
+// k_plan_set_init after it (the state the vehicle reached over init_state of both copies); without
+// it neither is launched.  These two run one lane per vehicle, not one wave per item.
 //
 // Layout: one wavefront per item (a local record, a scenario), PW waves per workgroup; waves
 // never cooperate, and a wave past the end of its list exits whole at the top.
@@ -852,6 +856,126 @@ __global__ void __launch_bounds__(64 * PW) k_plan_import(const int* __restrict__
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Closed-loop feedback (piadmm_obca_feedback_plan / _measure, piadmm_obca_propagate): the plant step
+// between two MPC steps and the scatter of states over init_state.  Opt-in: without the attachment
+// neither kernel is launched by piadmm_obca_plan_shift.
+// ---------------------------------------------------------------------------------------------
+// a plant row (include/piadmm.h): 8 doubles per vehicle, vehicle 0 first
+constexpr int FPAR = PIADMM_OBCA_FEEDBACK_PAR, FV = FPAR / 2;
+constexpr int F_METHOD = 0, F_NSUB = 1, F_LR = 2, F_LF = 3, F_GA = 4, F_GW = 5, F_AMAX = 6, F_WMAX = 7;
+constexpr int F_NSUB_MAX = 64;
+constexpr double PLANT_DT = 0.1, MAX_STEER = 0.6;
+static_assert(F_WMAX + 1 == FV && FV % 2 == 0, "plant row layout");
+
+// One plant step of one vehicle, all in registers: x (5) <- F(x, (a, om)) under the vehicle's row P
+// (8), without the disturbance.  n_sub substeps of DT / n_sub; a substep is 1 stage (Euler) or 4
+// (classical RK4) of the one right-hand side below, the stage loop kept rolled so that the libm
+// calls are inlined once; then delta is clipped.  n_sub is clamped to its range, so the loop is
+// bounded whatever the row holds.  piadmm.obca.propagate is the same statements on the host;
+// products and sums are kept apart (no contraction).  The body of both entry points of
+// k_plan_propagate: the stand-alone call and the in-plan step give the same bits.
+__device__ __forceinline__ void plant_step(double x[5], double a, double om, const double P[FV]) {
+#pragma clang fp contract(off)
+  const double lr = P[F_LR], lf = P[F_LF];
+  const double a_eff = fmin(P[F_AMAX], fmax(P[F_GA] * a, -P[F_AMAX]));
+  const double w_eff = fmin(P[F_WMAX], fmax(P[F_GW] * om, -P[F_WMAX]));
+  const int n_sub = min(max((int)P[F_NSUB], 1), F_NSUB_MAX);
+  const int n_stage = P[F_METHOD] != 0.0 ? 4 : 1;
+  const double hs = PLANT_DT / (double)n_sub;
+  const double scale = n_stage == 4 ? hs / 6.0 : hs;
+#pragma unroll 1
+  for (int sub = 0; sub < n_sub; ++sub) {
+    double xs[5], acc[5];
+#pragma unroll
+    for (int i = 0; i < 5; ++i) { xs[i] = x[i]; acc[i] = 0.0; }
+#pragma unroll 1
+    for (int st = 0; st < n_stage; ++st) {
+      const double beta = atan(lr * tan(xs[4]) / (lr + lf));
+      const double ph = xs[3] + beta;
+      const double f[5] = {xs[2] * cos(ph), xs[2] * sin(ph), a_eff, xs[2] / lr * sin(beta), w_eff};
+      const double wgt = (st == 1 || st == 2) ? 2.0 : 1.0;
+      const double c = st < 2 ? 0.5 * hs : hs;          // the next stage's point: x + c f
+#pragma unroll
+      for (int i = 0; i < 5; ++i) {
+        acc[i] = st == 0 ? f[i] : acc[i] + wgt * f[i];
+        xs[i] = x[i] + c * f[i];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 5; ++i) x[i] = x[i] + scale * acc[i];
+    x[4] = fmin(MAX_STEER, fmax(x[4], -MAX_STEER));
+  }
+}
+
+// where the arrays of one k_plan_propagate launch sit, all indexed by scenario: the strides in
+// doubles per scenario; the vehicle's state row at + v * 5, its controls a and omega at
+// ctrl + v * ctrl_v and + ctrl_w behind it, its plant row at + v * 8 (par_s = 0: one shared row),
+// its disturbance row at + v * 5 (w = nullptr: none), its result at out + s * 10 + v * 5
+struct plant_io {
+  const double *x0, *ctrl, *par, *w;
+  double* out;
+  long long x0_s, w_s;
+  int ctrl_s, ctrl_v, ctrl_w, par_s;
+};
+
+// One lane per vehicle: lane g of the grid = vehicle g & 1 of entry g >> 1 of `list` (nullptr: of
+// scenario g >> 1), 2 m lanes.  No LDS; the state, the stage point and the RK4 sum stay in
+// registers over the runtime substep loop.  The plant row is 64 bytes on a 64-byte boundary (the
+// base comes from hipMalloc): four 16-byte loads.  The 5-wide rows (state, disturbance, result) are
+// 40 bytes, only 8-byte aligned for the odd vehicle and inside the plan's state: five 8-byte
+// accesses each; neighbouring lanes hold neighbouring rows, so a wave's accesses fall into the
+// same few cache lines.
+__global__ void __launch_bounds__(64 * PW) k_plan_propagate(const int* __restrict__ list, int m, plant_io io) {
+  const int g = blockIdx.x * (64 * PW) + threadIdx.x;
+  if (g >= 2 * m) return;
+  const int v = g & 1;
+  const size_t s = (size_t)(list ? list[g >> 1] : (g >> 1));
+  const double2* P2 = reinterpret_cast<const double2*>(io.par + s * io.par_s + v * FV);
+  double P[FV];
+#pragma unroll
+  for (int i = 0; i < FV / 2; ++i) {
+    const double2 q = P2[i];
+    P[2 * i] = q.x;
+    P[2 * i + 1] = q.y;
+  }
+  const double* xin = io.x0 + s * io.x0_s + v * 5;
+  const double* cu = io.ctrl + s * io.ctrl_s + v * io.ctrl_v;
+  double x[5];
+#pragma unroll
+  for (int i = 0; i < 5; ++i) x[i] = xin[i];
+  plant_step(x, cu[0], cu[io.ctrl_w], P);
+  double* o = io.out + s * 10 + v * 5;
+  if (io.w) {
+#pragma clang fp contract(off)
+    const double* wr = io.w + s * io.w_s + v * 5;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) o[i] = x[i] + wr[i];
+  } else {
+#pragma unroll
+    for (int i = 0; i < 5; ++i) o[i] = x[i];
+  }
+}
+
+// One lane per vehicle, 2 m lanes: init_state of both state copies of scenario list[k] (nullptr: of
+// scenario k) = states[k] (m x 2 x 5).  Pure copies; nothing else of the state is written.
+__global__ void __launch_bounds__(64 * PW) k_plan_set_init(const int* __restrict__ list, int m,
+                                                           const double* __restrict__ states,
+                                                           double* __restrict__ bar, double* __restrict__ barp) {
+  const int g = blockIdx.x * (64 * PW) + threadIdx.x;
+  if (g >= 2 * m) return;
+  const int k = g >> 1, v = g & 1;
+  const size_t s = (size_t)(list ? list[k] : k);
+  const double* src = states + (size_t)k * 10 + v * 5;
+  const size_t at = s * STATE + S_INIT + v * 5;
+#pragma unroll
+  for (int i = 0; i < 5; ++i) {
+    const double val = src[i];
+    bar[at + i] = val;
+    barp[at + i] = val;
+  }
+}
+
 }  // namespace obca_plan
 
 // ---------------------------------------------------------------------------------------------
@@ -905,6 +1029,14 @@ struct piadmm_obca_plan_s {
     std::vector<int> host;
   } ck;
   std::vector<int> admm_rows;    // max_admm_iter of every parameter row (max_iter_all is their maximum)
+  // the closed-loop feedback (piadmm_obca_feedback_plan): rows = 1 with stride 0 or n plant rows; tape
+  // = cap disturbance rows per scenario (nullptr: none), n x cap x 10; steps = the shifts since the
+  // attachment (the tape row the next shift adds); next = the states the plant reached, n x 10
+  struct feedback_s {
+    bool on = false;
+    int rows = 0, stride = 0, cap = 0, steps = 0;
+    double *par = nullptr, *tape = nullptr, *next = nullptr;
+  } fb;
   // the staging buffer of piadmm_obca_tenant_export / _import: the records, then the slot list; grown on demand
   struct stage_s {
     char* buf = nullptr;
@@ -955,6 +1087,15 @@ void clock_free_buffers(piadmm_obca_plan_s::clock_s& c) {
 
 void clock_free(piadmm_obca_plan_s* p) { clock_free_buffers(p->ck); }
 
+void feedback_free_buffers(piadmm_obca_plan_s::feedback_s& f) {
+  void* d[] = {f.par, f.tape, f.next};
+  for (void* q : d)
+    if (q) (void)hipFree(q);
+  f = piadmm_obca_plan_s::feedback_s();
+}
+
+void feedback_free(piadmm_obca_plan_s* p) { feedback_free_buffers(p->fb); }
+
 void stage_free(piadmm_obca_plan_s* p) {
   if (p->stg.buf) (void)hipFree(p->stg.buf);
   p->stg = piadmm_obca_plan_s::stage_s();
@@ -965,6 +1106,7 @@ void plan_free_buffers(piadmm_obca_plan_s* p) {
   dual_free(p);
   order_free(p);
   clock_free(p);
+  feedback_free(p);
   stage_free(p);
   void* d[] = {p->bar, p->barp, p->ctrl, p->ctrlp, p->X, p->primal, p->dual, p->pth, p->dth, p->ref, p->lamb,
                p->tab, p->iters, p->stop, p->conv, p->prob, p->act[0], p->act[1], p->keep, p->count, p->mask};
@@ -1025,6 +1167,39 @@ int dual_rows_check(piadmm_obca_t h, const double* gains, int rows, int n, const
   return 0;
 }
 
+// One plant row of the feedback (both vehicles): nullptr when it is good, else what is wrong with it.
+const char* feedback_row_check(const double* row) {
+  using namespace obca_plan;
+  for (int i = 0; i < FPAR; ++i)
+    if (!std::isfinite(row[i])) return "every entry finite";
+  for (int v = 0; v < 2; ++v) {
+    const double* P = row + v * FV;
+    if (P[F_METHOD] != 0.0 && P[F_METHOD] != 1.0) return "method 0 (Euler) or 1 (RK4)";
+    if (!(P[F_NSUB] >= 1.0 && P[F_NSUB] <= (double)F_NSUB_MAX && P[F_NSUB] == std::floor(P[F_NSUB])))
+      return "1 <= n_sub <= 64, an integer";
+    if (!(P[F_LR] > 0.0) || !(P[F_LF] > 0.0)) return "lr, lf > 0";
+    if (!(P[F_AMAX] > 0.0) || !(P[F_WMAX] > 0.0)) return "a_max, w_max > 0";
+  }
+  return nullptr;
+}
+
+// the nominal plant: the NLP's own transition
+void feedback_row_nominal(double* row) {
+  using namespace obca_plan;
+  for (int v = 0; v < 2; ++v) {
+    double* P = row + v * FV;
+    P[F_METHOD] = 0.0;  P[F_NSUB] = 1.0;  P[F_LR] = 1.0;  P[F_LF] = 1.5;
+    P[F_GA] = 1.0;  P[F_GW] = 1.0;  P[F_AMAX] = 5.0;  P[F_WMAX] = 20.0;
+  }
+}
+
+// the first entry of a[0 .. count) that is not finite, or -1
+int64_t first_not_finite(const double* a, size_t count) {
+  for (size_t i = 0; i < count; ++i)
+    if (!std::isfinite(a[i])) return (int64_t)i;
+  return -1;
+}
+
 // what every scenario of a plan shares, and prob
 int shared_check(piadmm_obca_t h, const piadmm_obca_plan_cfg_t& c, const int32_t* prob, const std::string& who) {
   if (c.update_lamb_ij != 0 && c.update_lamb_ij != 1) return pfail(h, PIADMM_E_ARG, who + ": update_lamb_ij 0 or 1");
@@ -1054,17 +1229,24 @@ int open_plan(piadmm_obca_t h, piadmm_obca_plan_s** out, const char* who) {
 }
 
 int blocks_for(int waves) { return (waves + PW - 1) / PW; }
+// workgroups of 64 * PW lanes for a kernel that runs one lane per item
+int lane_blocks(int lanes) { return (lanes + 64 * PW - 1) / (64 * PW); }
+// true when the attached feedback has a tape and the next `steps` shifts do not fit what is left of it
+bool feedback_exhausted(const piadmm_obca_plan_s* p, int64_t steps) {
+  return p->fb.on && p->fb.tape && (int64_t)p->fb.steps + steps > p->fb.cap;
+}
 }  // namespace
 
 void piadmm_obca_plan_release(piadmm_obca_t h) {
   if (!h->plan) return;
-  if (h->plan->tr.on || h->plan->du.on || h->plan->ord.on || h->plan->ck.on) {
+  if (h->plan->tr.on || h->plan->du.on || h->plan->ord.on || h->plan->ck.on || h->plan->fb.on) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     trace_free(h->plan);
     dual_free(h->plan);
     order_free(h->plan);
     clock_free(h->plan);
+    feedback_free(h->plan);
   }
   h->plan->open = false;
 }
@@ -1358,8 +1540,22 @@ int32_t piadmm_obca_plan_shift(piadmm_obca_t h) {
   if (p->n_act > 0) return pfail(h, PIADMM_E_STATE, "obca_plan_shift: scenarios are still active");
   if (p->i_iter == 0) return pfail(h, PIADMM_E_STATE, "obca_plan_shift: no iterate ran in this step");
   if (p->tr.on && p->tr.rows >= p->tr.cap) return pfail(h, PIADMM_E_STATE, "obca_plan_shift: trace full");
+  if (feedback_exhausted(p, 1)) return pfail(h, PIADMM_E_STATE, "obca_plan_shift: disturbance tape exhausted");
   PHIP(h, hipSetDevice(h->device));
   if (p->ck.on) return clock_shift(h, p);
+  if (p->fb.on) {
+    // the plant step first: it reads the closing step's init_state and the stopping solution's first
+    // control (k_plan_exchange wrote ctrl and X from the same local output), which the shift overwrites
+    plant_io io{};
+    io.x0 = p->bar + S_INIT;  io.x0_s = STATE;
+    io.ctrl = p->ctrl;  io.ctrl_s = NCTRL;  io.ctrl_v = NCTRL / 2;  io.ctrl_w = NT;
+    io.par = p->fb.par;  io.par_s = p->fb.stride;
+    io.w = p->fb.tape ? p->fb.tape + (size_t)p->fb.steps * 10 : nullptr;  io.w_s = (long long)p->fb.cap * 10;
+    io.out = p->fb.next;
+    hipLaunchKernelGGL(k_plan_propagate, dim3(lane_blocks(2 * p->n)), dim3(64 * PW), 0, h->stream, (const int*)nullptr,
+                       p->n, io);
+    PHIP(h, hipGetLastError());
+  }
   // every scenario is active again: the list the next iterate reads is the identity, or with the
   // order on the identity sorted by the work of the step that closes
   hipLaunchKernelGGL(k_plan_shift, dim3(p->n), dim3(64), 0, h->stream, p->n, p->bar, p->barp, p->X, p->lamb, p->ctrlp,
@@ -1375,11 +1571,18 @@ int32_t piadmm_obca_plan_shift(piadmm_obca_t h) {
                        p->du.Dp);
     PHIP(h, hipGetLastError());
   }
+  if (p->fb.on) {
+    // the state the vehicle reached over init_state of both copies, before the trace reads it
+    hipLaunchKernelGGL(k_plan_set_init, dim3(lane_blocks(2 * p->n)), dim3(64 * PW), 0, h->stream, (const int*)nullptr,
+                       p->n, p->fb.next, p->bar, p->barp);
+    PHIP(h, hipGetLastError());
+  }
   if (p->tr.on) {
     if (int rc = trace_append(h, p, p->tr.rows + 1)) return rc;
   }
   PHIP(h, hipStreamSynchronize(h->stream));
   if (p->tr.on) p->tr.rows += 1;
+  if (p->fb.on) p->fb.steps += 1;
   p->t_step += 1;
   p->i_iter = 0;
   p->n_act = p->n;
@@ -1393,6 +1596,7 @@ int32_t piadmm_obca_plan_step(piadmm_obca_t h, int32_t* iters_out) {
   if (p->ck.on && p->ck.n_list == 0) return pfail(h, PIADMM_E_STATE, "obca_plan_step: no scenario alive");
   if (!p->ck.on && p->t_step + 8 > p->cfg.n_ref) return pfail(h, PIADMM_E_STATE, "obca_plan_step: reference exhausted");
   if (p->tr.on && p->tr.rows >= p->tr.cap) return pfail(h, PIADMM_E_STATE, "obca_plan_step: trace full");
+  if (feedback_exhausted(p, 1)) return pfail(h, PIADMM_E_STATE, "obca_plan_step: disturbance tape exhausted");
   // i_iter > max_admm_iter stops a scenario: at most the largest max_admm_iter + 1 iterates in a step
   while (p->n_act > 0 && p->i_iter <= p->max_iter_all) {
     if (int rc = piadmm_obca_plan_iterate(h, nullptr)) return rc;
@@ -1458,6 +1662,12 @@ int32_t piadmm_obca_plan_get(piadmm_obca_t h, int32_t what, void* out, int64_t b
       if (what == PIADMM_OBCA_PLAN_GET_CLOCK) { src = p->ck.clk; want = n * 3 * I; }
       else { src = p->ck.win; want = n * WIN * D; }
       break;
+    case PIADMM_OBCA_PLAN_GET_FEEDBACK_PAR:
+    case PIADMM_OBCA_PLAN_GET_FEEDBACK_STEPS:
+      if (!p->fb.on) return pfail(h, PIADMM_E_STATE, "obca_plan_get: no feedback attached (obca_feedback_plan)");
+      if (what == PIADMM_OBCA_PLAN_GET_FEEDBACK_PAR) { src = p->fb.par; want = (int64_t)p->fb.rows * FPAR * D; }
+      else want = I;
+      break;
     case PIADMM_OBCA_PLAN_GET_T_STEP: want = I; break;
     case PIADMM_OBCA_PLAN_GET_COUNTS: want = 3 * I; break;
     default: return pfail(h, PIADMM_E_ARG, "obca_plan_get: unknown item " + std::to_string(what));
@@ -1468,6 +1678,7 @@ int32_t piadmm_obca_plan_get(piadmm_obca_t h, int32_t what, void* out, int64_t b
   if (want == 0) return 0;
   if (!out) return pfail(h, PIADMM_E_ARG, "obca_plan_get: out");
   if (what == PIADMM_OBCA_PLAN_GET_T_STEP) { *static_cast<int32_t*>(out) = p->t_step; return 0; }
+  if (what == PIADMM_OBCA_PLAN_GET_FEEDBACK_STEPS) { *static_cast<int32_t*>(out) = p->fb.steps; return 0; }
   if (what == PIADMM_OBCA_PLAN_GET_COUNTS) { for (int i = 0; i < 3; ++i) static_cast<int32_t*>(out)[i] = counts[i]; return 0; }
   PHIP(h, hipSetDevice(h->device));
   PHIP(h, hipMemcpyAsync(out, src, (size_t)want, hipMemcpyDeviceToHost, h->stream));
@@ -1757,6 +1968,8 @@ int32_t piadmm_obca_clock_plan(piadmm_obca_t h, int32_t mode, const int32_t* clo
       rec[3 * (size_t)k + 2] = 1;
     }
   }
+  if (mode == 1 && p->fb.on)
+    return pfail(h, PIADMM_E_STATE, "obca_clock_plan: feedback is attached (obca_feedback_plan: the tape has no per-scenario clocks)");
   if (p->i_iter != 0) return pfail(h, PIADMM_E_STATE, "obca_clock_plan: only at a step boundary (an MPC step is open)");
   if (mode == 0) {
     if (!p->ck.on) return 0;
@@ -1986,6 +2199,9 @@ int32_t piadmm_obca_trace_run(piadmm_obca_t h, int32_t n_steps, int32_t* steps_d
   if ((int64_t)p->tr.rows + n_steps > p->tr.cap)
     return pfail(h, PIADMM_E_STATE, "obca_trace_run: " + std::to_string(n_steps) + " steps do not fit the trace (" +
                  std::to_string(p->tr.rows) + " of " + std::to_string(p->tr.cap) + " rows used)");
+  if (feedback_exhausted(p, n_steps))
+    return pfail(h, PIADMM_E_STATE, "obca_trace_run: disturbance tape exhausted before " + std::to_string(n_steps) +
+                 " steps (" + std::to_string(p->fb.steps) + " of " + std::to_string(p->fb.cap) + " rows used)");
   if (p->ck.on) {
     // the steps the longest-lived scenario has left
     int left = 0;
@@ -2123,6 +2339,7 @@ int32_t piadmm_obca_tenant_export(piadmm_obca_t h, int32_t m, const int32_t* slo
   if (bytes != PIADMM_OBCA_TENANT_HEADER + body)
     return pfail(h, PIADMM_E_ARG, "obca_tenant_export: the blob is " + std::to_string(PIADMM_OBCA_TENANT_HEADER + body) +
                  " bytes, not " + std::to_string(bytes));
+  if (p->fb.on) return pfail(h, PIADMM_E_STATE, "obca_tenant_export: feedback is attached (the tenant record has no room for the tape)");
   if (p->i_iter != 0) return pfail(h, PIADMM_E_STATE, "obca_tenant_export: only at a step boundary (an MPC step is open)");
   PHIP(h, hipSetDevice(h->device));
   if (int rc = stage_ensure(h, p, (size_t)body, m)) return rc;
@@ -2196,6 +2413,7 @@ int32_t piadmm_obca_tenant_import(piadmm_obca_t h, int32_t m, const int32_t* slo
     }
   }
   // the destination
+  if (p->fb.on) return pfail(h, PIADMM_E_STATE, "obca_tenant_import: feedback is attached (the tenant record has no room for the tape)");
   if (!p->ck.on) return pfail(h, PIADMM_E_STATE, "obca_tenant_import: no clock attached (obca_clock_plan)");
   if (p->tr.on) return pfail(h, PIADMM_E_STATE, "obca_tenant_import: a trace is attached (its minima would mix two tenants)");
   if (p->i_iter != 0) return pfail(h, PIADMM_E_STATE, "obca_tenant_import: only at a step boundary (an MPC step is open)");
@@ -2250,6 +2468,162 @@ int32_t piadmm_obca_tenant_import(piadmm_obca_t h, int32_t m, const int32_t* slo
   PHIP(h, hipStreamSynchronize(h->stream));
   p->ck.n_list = n_alive;
   p->n_act = n_alive;
+  return 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// Closed-loop feedback (include/piadmm.h)
+// ---------------------------------------------------------------------------------------------
+extern "C" {
+
+int32_t piadmm_obca_propagate(piadmm_obca_t h, int32_t n, const double* states, const double* ctrl, const double* par,
+                              const double* w, double* out) {
+  using namespace obca_plan;
+  if (!h) return PIADMM_E_ARG;
+  if (n < 1 || n > (1 << 20)) return pfail(h, PIADMM_E_ARG, "obca_propagate: 1 <= n <= 2^20");
+  if (!states || !ctrl || !par || !out) return pfail(h, PIADMM_E_ARG, "obca_propagate: null argument");
+  const size_t N = (size_t)n;
+  int64_t bad = -1;
+  if ((bad = first_not_finite(states, N * 10)) >= 0)
+    return pfail(h, PIADMM_E_ARG, "obca_propagate: state pair " + std::to_string(bad / 10) + " is not finite");
+  if ((bad = first_not_finite(ctrl, N * 4)) >= 0)
+    return pfail(h, PIADMM_E_ARG, "obca_propagate: ctrl of scenario " + std::to_string(bad / 4) + " is not finite");
+  if (w && (bad = first_not_finite(w, N * 10)) >= 0)
+    return pfail(h, PIADMM_E_ARG, "obca_propagate: w of scenario " + std::to_string(bad / 10) + " is not finite");
+  for (int k = 0; k < n; ++k)
+    if (const char* why = feedback_row_check(par + (size_t)k * FPAR))
+      return pfail(h, PIADMM_E_ARG, "obca_propagate: row " + std::to_string(k) + ": " + why);
+  PHIP(h, hipSetDevice(h->device));
+  // the call's own buffers: neither the handle's local and edge buffers nor an open plan is touched
+  double *d_st = nullptr, *d_ct = nullptr, *d_par = nullptr, *d_w = nullptr, *d_out = nullptr;
+  const size_t B = sizeof(double);
+  auto run = [&]() -> int {
+    if (int rc = dalloc(h, &d_st, N * 10, false)) return rc;
+    if (int rc = dalloc(h, &d_ct, N * 4, false)) return rc;
+    if (int rc = dalloc(h, &d_par, N * FPAR, false)) return rc;
+    if (w)
+      if (int rc = dalloc(h, &d_w, N * 10, false)) return rc;
+    if (int rc = dalloc(h, &d_out, N * 10, true)) return rc;
+    PHIP(h, hipMemcpyAsync(d_st, states, N * 10 * B, hipMemcpyHostToDevice, h->stream));
+    PHIP(h, hipMemcpyAsync(d_ct, ctrl, N * 4 * B, hipMemcpyHostToDevice, h->stream));
+    PHIP(h, hipMemcpyAsync(d_par, par, N * FPAR * B, hipMemcpyHostToDevice, h->stream));
+    if (w) PHIP(h, hipMemcpyAsync(d_w, w, N * 10 * B, hipMemcpyHostToDevice, h->stream));
+    plant_io io{};
+    io.x0 = d_st;  io.x0_s = 10;
+    io.ctrl = d_ct;  io.ctrl_s = 4;  io.ctrl_v = 2;  io.ctrl_w = 1;
+    io.par = d_par;  io.par_s = FPAR;
+    io.w = d_w;  io.w_s = 10;
+    io.out = d_out;
+    hipLaunchKernelGGL(k_plan_propagate, dim3(lane_blocks(2 * n)), dim3(64 * PW), 0, h->stream, (const int*)nullptr, n,
+                       io);
+    PHIP(h, hipGetLastError());
+    PHIP(h, hipMemcpyAsync(out, d_out, N * 10 * B, hipMemcpyDeviceToHost, h->stream));
+    PHIP(h, hipStreamSynchronize(h->stream));
+    return 0;
+  };
+  const int rc = run();
+  if (rc) (void)hipStreamSynchronize(h->stream);
+  void* dev[] = {d_st, d_ct, d_par, d_w, d_out};
+  for (void* q : dev)
+    if (q) (void)hipFree(q);
+  return rc;
+}
+
+int32_t piadmm_obca_feedback_plan(piadmm_obca_t h, int32_t mode, const double* par, int32_t rows, const double* tape,
+                                  int32_t cap) {
+  using namespace obca_plan;
+  piadmm_obca_plan_s* p = nullptr;
+  if (int rc = open_plan(h, &p, "obca_feedback_plan")) return rc;
+  if (mode != 0 && mode != 1) return pfail(h, PIADMM_E_ARG, "obca_feedback_plan: mode 0 (detach) or 1 (attach)");
+  const int n = p->n;
+  const size_t N = (size_t)n;
+  double nominal[FPAR];
+  feedback_row_nominal(nominal);
+  if (mode == 1) {
+    if (par) {
+      if (rows != 1 && rows != n)
+        return pfail(h, PIADMM_E_ARG, "obca_feedback_plan: rows must be 1 or n (" + std::to_string(n) + ")");
+      for (int k = 0; k < rows; ++k)
+        if (const char* why = feedback_row_check(par + (size_t)k * FPAR))
+          return pfail(h, PIADMM_E_ARG, "obca_feedback_plan: row " + std::to_string(k) + ": " + why);
+    } else {
+      par = nominal;
+      rows = 1;
+    }
+    if (tape) {
+      if (cap < 0 || cap > (1 << 20)) return pfail(h, PIADMM_E_ARG, "obca_feedback_plan: 0 <= cap <= 2^20");
+      const int64_t bad = first_not_finite(tape, N * (size_t)cap * 10);
+      if (bad >= 0)
+        return pfail(h, PIADMM_E_ARG, "obca_feedback_plan: the tape of scenario " +
+                     std::to_string(bad / ((int64_t)cap * 10)) + " is not finite (step " +
+                     std::to_string(bad / 10 % cap) + ")");
+    }
+    if (p->ck.on)
+      return pfail(h, PIADMM_E_STATE, "obca_feedback_plan: a clock is attached (obca_clock_plan: the tape has no per-scenario clocks)");
+  }
+  if (p->i_iter != 0) return pfail(h, PIADMM_E_STATE, "obca_feedback_plan: only at a step boundary (an MPC step is open)");
+  PHIP(h, hipSetDevice(h->device));
+  PHIP(h, hipStreamSynchronize(h->stream));
+  if (mode == 0) {
+    feedback_free(p);
+    return 0;
+  }
+  // the new attachment is complete before it replaces the earlier one
+  piadmm_obca_plan_s::feedback_s nf;
+  const size_t T = N * (size_t)cap * 10;
+  hipError_t e = hipMalloc(&nf.par, (size_t)rows * FPAR * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc(&nf.next, N * 10 * sizeof(double));
+  if (e == hipSuccess) e = hipMemset(nf.next, 0, N * 10 * sizeof(double));
+  if (e == hipSuccess) e = hipMemcpy(nf.par, par, (size_t)rows * FPAR * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess && tape) {
+    // a tape without rows still counts as one: every shift is then refused
+    e = hipMalloc(&nf.tape, std::max(T, (size_t)1) * sizeof(double));
+    if (e == hipSuccess && T) e = hipMemcpy(nf.tape, tape, T * sizeof(double), hipMemcpyHostToDevice);
+  }
+  if (e != hipSuccess) {
+    feedback_free_buffers(nf);
+    return pfail(h, PIADMM_E_HIP, std::string("obca_feedback_plan: ") + hipGetErrorString(e));
+  }
+  feedback_free(p);
+  p->fb = nf;
+  p->fb.rows = rows;
+  p->fb.stride = rows > 1 ? FPAR : 0;
+  p->fb.cap = tape ? cap : 0;
+  p->fb.steps = 0;
+  p->fb.on = true;
+  return 0;
+}
+
+int32_t piadmm_obca_feedback_measure(piadmm_obca_t h, int32_t m, const int32_t* slots, const double* states) {
+  using namespace obca_plan;
+  piadmm_obca_plan_s* p = nullptr;
+  if (int rc = open_plan(h, &p, "obca_feedback_measure")) return rc;
+  const int n = p->n;
+  if (m < 1 || m > n) return pfail(h, PIADMM_E_ARG, "obca_feedback_measure: 1 <= m <= n_scenarios");
+  if (!slots || !states) return pfail(h, PIADMM_E_ARG, "obca_feedback_measure: null argument");
+  for (int k = 0; k < m; ++k)
+    if (slots[k] < 0 || slots[k] >= n || (k > 0 && slots[k] <= slots[k - 1]))
+      return pfail(h, PIADMM_E_ARG, "obca_feedback_measure: slots[" + std::to_string(k) +
+                   "] must be a scenario below n, the slots ascending and distinct");
+  const int64_t bad = first_not_finite(states, (size_t)m * 10);
+  if (bad >= 0)
+    return pfail(h, PIADMM_E_ARG, "obca_feedback_measure: state pair " + std::to_string(bad / 10) + " is not finite");
+  if (p->i_iter != 0) return pfail(h, PIADMM_E_STATE, "obca_feedback_measure: only at a step boundary (an MPC step is open)");
+  if (p->tr.on)
+    return pfail(h, PIADMM_E_STATE, "obca_feedback_measure: a trace is attached (its last row was computed from the state being replaced)");
+  PHIP(h, hipSetDevice(h->device));
+  // the states, then the slot numbers, through the staging buffer; one scatter launch
+  const size_t body = (size_t)m * 10 * sizeof(double);
+  if (int rc = stage_ensure(h, p, body, m)) return rc;
+  int* d_list = reinterpret_cast<int*>(p->stg.buf + body);
+  PHIP(h, hipMemcpyAsync(p->stg.buf, states, body, hipMemcpyHostToDevice, h->stream));
+  PHIP(h, hipMemcpyAsync(d_list, slots, (size_t)m * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(k_plan_set_init, dim3(lane_blocks(2 * m)), dim3(64 * PW), 0, h->stream, (const int*)d_list, m,
+                     reinterpret_cast<const double*>(p->stg.buf), p->bar, p->barp);
+  PHIP(h, hipGetLastError());
+  PHIP(h, hipStreamSynchronize(h->stream));
   return 0;
 }
 

@@ -133,12 +133,17 @@ SYMBOLS = [
     ("piadmm_obca_tenant_export_bytes", c_i32, [_H, c_i32, _P(ctypes.c_int64)]),
     ("piadmm_obca_tenant_export", c_i32, [_H, c_i32, _ip, ctypes.c_void_p, ctypes.c_int64]),
     ("piadmm_obca_tenant_import", c_i32, [_H, c_i32, _ip, ctypes.c_void_p, ctypes.c_int64]),
+    ("piadmm_obca_propagate", c_i32, [_H, c_i32, _dp, _dp, _dp, _dp, _dp]),
+    ("piadmm_obca_feedback_plan", c_i32, [_H, c_i32, _dp, c_i32, _dp, c_i32]),
+    ("piadmm_obca_feedback_measure", c_i32, [_H, c_i32, _ip, _dp]),
 ]
 
 # PIADMM_OBCA_FLEET_PAR: doubles per parameter row of piadmm_obca_fleet_begin
 FLEET_PAR = 16
 # PIADMM_OBCA_DUAL_PAR: doubles per gains row of piadmm_obca_dual_plan
 DUAL_PAR = 8
+# PIADMM_OBCA_FEEDBACK_PAR: doubles per plant row of piadmm_obca_feedback_plan / piadmm_obca_propagate
+FEEDBACK_PAR = 16
 
 # error codes of include/piadmm.h the OBCA bindings name
 E_ARG, E_HIP, E_STATE, E_NODEV = -1, -2, -3, -4

@@ -518,6 +518,107 @@ def clock_rows(n, clock, t_step, n_ref):
     return rows
 
 
+# a plant row of the closed-loop feedback (piadmm_obca_feedback_plan / piadmm_obca_propagate,
+# include/piadmm.h): these 8 doubles per vehicle, vehicle 0 first
+FEEDBACK_ROW = ("method", "n_sub", "lr", "lf", "gain_a", "gain_w", "a_max", "w_max")
+FEEDBACK_PAR = 16                     # doubles per row (PIADMM_OBCA_FEEDBACK_PAR)
+FEEDBACK_N_SUB_MAX = 64
+MAX_STEER = 0.6                       # max_front_wheel_angle (veh_config.py)
+# the nominal plant: the NLP's own transition st + dt f(st, con) (optimizer.py:92-96)
+_FEEDBACK_DEFAULT = dict(method=0, n_sub=1, lr=1.0, lf=1.5, gain_a=1.0, gain_w=1.0, a_max=5.0, w_max=20.0)
+
+
+def feedback_row(**kw):
+    """One plant row (FEEDBACK_PAR doubles) from FEEDBACK_ROW names, each one value for both vehicles
+    or a pair (vehicle 0, vehicle 1); absent: the nominal plant (Euler, n_sub 1, lr 1.0, lf 1.5,
+    gains 1, a_max 5, w_max 20)."""
+    assert set(kw) <= set(FEEDBACK_ROW), set(kw) - set(FEEDBACK_ROW)
+    row = np.zeros((2, len(FEEDBACK_ROW)))
+    for j, k in enumerate(FEEDBACK_ROW):
+        row[:, j] = np.broadcast_to(np.asarray(kw.get(k, _FEEDBACK_DEFAULT[k]), np.float64), (2,))
+    return row.reshape(FEEDBACK_PAR)
+
+
+def feedback_row_check(row):
+    """None when the plant row is good, else what is wrong with it: the library's check."""
+    row = np.asarray(row, np.float64).reshape(2, len(FEEDBACK_ROW))
+    if not np.isfinite(row).all():
+        return "every entry finite"
+    for method, n_sub, lr, lf, _, _, a_max, w_max in row:
+        if method not in (0.0, 1.0):
+            return "method 0 (Euler) or 1 (RK4)"
+        if not (1.0 <= n_sub <= FEEDBACK_N_SUB_MAX and n_sub == math.floor(n_sub)):
+            return "1 <= n_sub <= 64, an integer"
+        if not (lr > 0.0 and lf > 0.0):
+            return "lr, lf > 0"
+        if not (a_max > 0.0 and w_max > 0.0):
+            return "a_max, w_max > 0"
+    return None
+
+
+def _plant_rhs(x, a_eff, w_eff, lr, lf):
+    """The reference's right-hand side (optimizer.py:75-77) of the states x (..., 5)."""
+    beta = np.arctan(lr * np.tan(x[..., 4]) / (lr + lf))
+    ph = x[..., 3] + beta
+    v = x[..., 2]
+    return np.stack((v * np.cos(ph), v * np.sin(ph), a_eff, v / lr * np.sin(beta), w_eff), axis=-1)
+
+
+def propagate(states, ctrl, par, w=None):
+    """One plant step of length DT per vehicle, host restatement of k_plan_propagate
+    (csrc/piadmm_obca_plan.hip) with the same statements in the same order: states n x 2 x 5
+    (x, y, v, theta, delta), ctrl n x 2 x 2 the held (a, omega), par one plant row for all or n rows
+    (`feedback_row`), w n x 2 x 5 the disturbance or None.  n_sub substeps of DT / n_sub of
+        beta = atan(lr tan(delta) / (lr + lf))
+        rhs = (v cos(theta + beta), v sin(theta + beta), a_eff, v / lr sin(beta), w_eff)
+    with a_eff = clip(gain_a a, +-a_max), w_eff = clip(gain_w omega, +-w_max): explicit Euler
+    (method 0) or classical RK4 (method 1), delta clipped to +-MAX_STEER after every substep, w added
+    after the last.  The nominal row with w = None is st + DT f(st, con)."""
+    x = np.array(states, np.float64)
+    n = x.shape[0] if x.ndim == 3 else 0
+    ctrl = np.asarray(ctrl, np.float64)
+    assert x.shape == (n, 2, NX) and ctrl.shape == (n, 2, NU), (x.shape, ctrl.shape)
+    P = np.broadcast_to(np.asarray(par, np.float64).reshape(-1, 2, len(FEEDBACK_ROW)), (n, 2, len(FEEDBACK_ROW)))
+    for k in range(n):
+        why = feedback_row_check(P[k])
+        if why is not None:
+            raise ValueError(f"obca.propagate: row {k}: {why}")
+    rk4, n_sub, lr, lf = P[..., 0] != 0.0, P[..., 1].astype(np.int64), P[..., 2], P[..., 3]
+    a_eff = np.minimum(P[..., 6], np.maximum(P[..., 4] * ctrl[..., 0], -P[..., 6]))
+    w_eff = np.minimum(P[..., 7], np.maximum(P[..., 5] * ctrl[..., 1], -P[..., 7]))
+    hs = (DT / n_sub.astype(np.float64))[..., None]
+    for sub in range(int(n_sub.max()) if n else 0):
+        k1 = _plant_rhs(x, a_eff, w_eff, lr, lf)
+        nxt = x + hs * k1
+        if rk4.any():
+            k2 = _plant_rhs(x + (0.5 * hs) * k1, a_eff, w_eff, lr, lf)
+            k3 = _plant_rhs(x + (0.5 * hs) * k2, a_eff, w_eff, lr, lf)
+            k4 = _plant_rhs(x + hs * k3, a_eff, w_eff, lr, lf)
+            acc = k1 + 2.0 * k2 + 2.0 * k3 + k4
+            nxt = np.where(rk4[..., None], x + (hs / 6.0) * acc, nxt)
+        nxt[..., 4] = np.minimum(MAX_STEER, np.maximum(nxt[..., 4], -MAX_STEER))
+        x = np.where((sub < n_sub)[..., None], nxt, x)
+    if w is not None:
+        w = np.asarray(w, np.float64)
+        assert w.shape == x.shape, (w.shape, x.shape)
+        x = x + w
+    return x
+
+
+def feedback_args(n, feedback):
+    """(par, tape) of a planner's feedback argument dict(par=, tape=): par one plant row or n rows
+    (None: the nominal row), as rows x FEEDBACK_PAR; tape n x cap x 2 x 5 or None."""
+    assert set(feedback) <= {"par", "tape"}, set(feedback)
+    par, tape = feedback.get("par"), feedback.get("tape")
+    par = feedback_row() if par is None else par
+    par = np.ascontiguousarray(np.asarray(par, np.float64).reshape(-1, FEEDBACK_PAR))
+    assert par.shape[0] in (1, n), par.shape
+    if tape is not None:
+        tape = np.ascontiguousarray(tape, np.float64)
+        assert tape.ndim == 4 and tape.shape[0] == n and tape.shape[2:] == (2, NX), tape.shape
+    return par, tape
+
+
 def check_converge(bar, thres, min_dis):
     """`check_converge` (optimizer.py:225-235): the coupled constraints at the exchanged
     halfspaces and lamb_ij."""
@@ -733,6 +834,26 @@ class OBCABatch:
         assert 0 <= count[0] <= n and not lst[count[0]:].any()
         return out, win, lst[:count[0]].copy()
 
+    def propagate(self, states, ctrl, par, w=None) -> np.ndarray:
+        """One launch of k_plan_propagate on the call's own buffers (piadmm_obca_propagate): the
+        states n x 2 x 5 the vehicles reach from `states` under the held controls ctrl (n x 2 x 2:
+        a, omega), the plant rows par (one for all, or n) and the disturbance w (n x 2 x 5 or None),
+        as `propagate` states it."""
+        from . import _lib
+        states = np.ascontiguousarray(states, np.float64)
+        n = states.shape[0] if states.ndim == 3 else 0
+        ctrl = np.ascontiguousarray(ctrl, np.float64)
+        assert states.shape == (n, 2, NX) and ctrl.shape == (n, 2, NU), (states.shape, ctrl.shape)
+        par = np.ascontiguousarray(np.broadcast_to(np.asarray(par, np.float64).reshape(-1, FEEDBACK_PAR),
+                                                   (n, FEEDBACK_PAR)))
+        if w is not None:
+            w = np.ascontiguousarray(w, np.float64)
+            assert w.shape == states.shape, w.shape
+        out = np.zeros((n, 2, NX))
+        self._check(self._lib.piadmm_obca_propagate(self._h, n, _lib.dptr(states), _lib.dptr(ctrl), _lib.dptr(par),
+                                                    _lib.dptr(w), _lib.dptr(out)))
+        return out
+
     def time_edge(self, recs: np.ndarray, repeats: int) -> float:
         """ms per edge launch over `repeats` launches of `recs` (HIP events)."""
         from . import _lib
@@ -855,12 +976,19 @@ class OBCAPlanner:
     clock: None keeps the one step of all scenarios; n x 2 rows (c0, len), or True for everyone at
     t_step0 over the whole reference, gives every scenario its own step (`clock`, n x 3: c, len,
     alive, ticked by `clock_tick`): it is seeded at c0, reads its reference at c, and once
-    c + 8 > len it is retired -- skipped by every later step, its state frozen, its stop iterate 0."""
+    c + 8 > len it is retired -- skipped by every later step, its state frozen, its stop iterate 0.
+
+    feedback: None closes a step with init_state = X[1]; dict(par=, tape=) closes it through the
+    plant instead (`propagate`): init_state = propagate(the closing step's init_state, the first
+    control of the stopping local solution, par, tape[s][k]) with k the steps since the attachment.
+    par: one plant row or n (`feedback_row`; None: the nominal plant), tape: n x cap x 2 x 5
+    disturbance rows or None.  `measure` overwrites init_state with states measured outside.
+    OBCADevicePlanner takes the same argument.  Not together with clock."""
 
     def __init__(self, batch, n_scenarios, prob=1, t_step0=0, rho=1.0, min_dis=0.1, max_admm_iter=50,
                  primal_thres=0.01, dual_thres=0.01, round_decimals=4, start=1, update_lamb_ij=0, max_iter=60,
                  conv_thres=0.1, on_stage=None, max_x=150.0, max_y=20.0, r=1e4, q=1e5, x_bound=1000.0,
-                 mu_max=100000.0, g_max=1000.0, ref_traj=None, specs=None, dual=None, clock=None):
+                 mu_max=100000.0, g_max=1000.0, ref_traj=None, specs=None, dual=None, clock=None, feedback=None):
         self.batch = batch
         self.n = int(n_scenarios)
         self.prob = [int(prob)] * self.n if np.isscalar(prob) else [int(p) for p in prob]
@@ -897,8 +1025,33 @@ class OBCAPlanner:
         if dual is not None:
             self.dual_S = [b["lamb_bar"].copy() for b in self.bar_prev]
             self.dual_D = [np.zeros((2, NT, 9)) for _ in range(self.n)]
+        self.feedback = None
+        if feedback is not None:
+            self.set_feedback(**feedback)
         self.record = OBCARunRecord()
         self.record.state_record.append(np.stack(self.init_state))
+
+    def set_feedback(self, par=None, tape=None):
+        """Attach the plant (see the class): from the next step on a step closes through `propagate`."""
+        assert self.clock is None, "feedback and clock do not go together"
+        self.feedback = feedback_args(self.n, dict(par=par, tape=tape))
+        self._feedback_steps = 0
+
+    def clear_feedback(self):
+        self.feedback = None
+
+    def feedback_steps(self):
+        """The steps closed since the attachment."""
+        assert self.feedback is not None, "no feedback attached"
+        return self._feedback_steps
+
+    def measure(self, slots, states):
+        """init_state of the scenarios `slots` = the measured `states` (m x 2 x 5); nothing else changes."""
+        states = np.asarray(states, np.float64)
+        assert states.shape == (len(slots), 2, NX) and np.isfinite(states).all(), states.shape
+        self.init_state = list(self.init_state)
+        for k, s in enumerate(slots):
+            self.init_state[int(s)] = states[k].copy()
 
     @staticmethod
     def _copy(bar):
@@ -907,6 +1060,8 @@ class OBCAPlanner:
     def step(self):
         """One MPC step of every scenario."""
         n = self.n
+        if self.feedback is not None and self.feedback[1] is not None:
+            assert self._feedback_steps < self.feedback[1].shape[1], "disturbance tape exhausted"
         if self.clock is None:
             assert self.t_step + N_HORZ <= self.n_ref, "reference exhausted"
             ran = list(range(n))
@@ -918,8 +1073,10 @@ class OBCAPlanner:
             t_of = [int(c) for c in self.clock[:, 0]]
         bar = [self._copy(b) for b in self.bar_prev]
         bar_prev = [self._copy(b) for b in self.bar_prev]
+        x0_step = [np.array(x, np.float64) for x in self.init_state]
         ctrl_prev = [np.zeros((2, NT * NU)) for _ in range(n)]
         X = [None] * n
+        U0 = [None] * n
         iters = np.zeros(n, int)
         shift_in = [None] * n
         active = list(ran)
@@ -940,6 +1097,7 @@ class OBCAPlanner:
                     for k in range(len(active))]
             for k, s in enumerate(active):
                 X[s] = [res.X[2 * k].copy(), res.X[2 * k + 1].copy()]
+                U0[s] = np.stack([res.U[2 * k + v][0] for v in (0, 1)])
             # ---- information exchange ----
             before = [bar[s] for s in active]
             for k, s in enumerate(active):
@@ -1011,6 +1169,14 @@ class OBCAPlanner:
                 self.dual_S[s], self.dual_D[s] = shift_dual(self.dual_S[s], self.dual_D[s])
             self.init_state[s] = np.stack([X[s][0][1], X[s][1][1]])
             self.lamb_last[s] = bar[s]["lamb_bar"]
+        if self.feedback is not None:
+            # the vehicle instead of the prediction: from the closing step's init_state under the
+            # stopping solution's first control (every scenario ran: no clock with feedback)
+            par, tape = self.feedback
+            nxt = propagate(np.stack(x0_step), np.stack(U0), par,
+                            None if tape is None else tape[:, self._feedback_steps])
+            self.init_state = [nxt[s] for s in range(n)]
+            self._feedback_steps += 1
         self.on_stage("shift", dict(bar_prev=shift_in, X=X, iters=iters.copy()), dict(bar_next=self.bar_prev, init_state=self.init_state))
         self.record.state_record.append(np.stack(self.init_state))
         self.record.iter_num_record.append(iters)
@@ -1045,7 +1211,8 @@ PLAN_GET = {"STATE": (0, np.float64), "STATE_PREV": (1, np.float64), "CTRL": (2,
             "DUAL_S": (23, np.float64), "DUAL_D": (24, np.float64), "DUAL_PAR": (25, np.float64),
             "WORK": (26, np.int32), "CLOCK": (27, np.int32), "WINDOW": (28, np.float64),
             "PRIMAL_THRES": (29, np.float64), "DUAL_THRES": (30, np.float64), "PROB": (31, np.int32),
-            "DUAL_S_PREV": (32, np.float64), "DUAL_D_PREV": (33, np.float64)}
+            "DUAL_S_PREV": (32, np.float64), "DUAL_D_PREV": (33, np.float64),
+            "FEEDBACK_PAR": (34, np.float64), "FEEDBACK_STEPS": (35, np.int32)}
 
 
 # piadmm_obca_trace_get items: name -> (code, dtype); piadmm_obca_trace_begin's flag
@@ -1272,13 +1439,22 @@ class OBCADevicePlanner:
     Running tenants move as records (piadmm_obca_tenant_export / _import): `export_tenants` of any
     plan, `import_tenants` into a clocked fleet plan, `compact()` for a new planner with the alive
     tenants only, `save` / `load` for a checkpoint of the whole plan; a moved tenant continues bit
-    for bit."""
+    for bit.
+
+    With feedback=dict(par=, tape=) a step closes through a plant instead of with init_state = X[1]
+    (piadmm_obca_feedback_plan, `propagate`): par one plant row or n (`feedback_row`; None: the
+    nominal plant), tape n x cap x 2 x 5 disturbance rows or None.  `set_feedback` / `clear_feedback`
+    attach and detach it at a step boundary, `feedback_steps()` counts the steps closed since,
+    `measure(slots, states)` writes states measured outside over init_state
+    (piadmm_obca_feedback_measure; any plan, no trace).  `run_traced` works with it unchanged: the
+    trace's states and clearances are those of the states the vehicles reached.  Not together with
+    clock or the tenant calls."""
 
     def __init__(self, batch, n_scenarios, prob=1, t_step0=0, rho=1.0, min_dis=0.1, max_admm_iter=50,
                  primal_thres=0.01, dual_thres=0.01, round_decimals=4, start=1, update_lamb_ij=0, max_iter=60,
                  conv_thres=0.1, on_stage=None, max_x=150.0, max_y=20.0, r=1e4, q=1e5, x_bound=1000.0,
                  mu_max=100000.0, g_max=1000.0, ref_traj=None, state=None, specs=None, dual=None, order=False,
-                 work_init=None, clock=None):
+                 work_init=None, clock=None, feedback=None):
         from . import _lib
         self.batch = batch
         self._lib = batch._lib
@@ -1342,6 +1518,7 @@ class OBCADevicePlanner:
                                                           _lib.dptr(self.primal_thres), _lib.dptr(self.dual_thres),
                                                           _lib.dptr(ref), _lib.dptr(self.par), _lib.dptr(state)))
         self.dual_par = None
+        self._feedback = None
         if dual is not None:
             self.set_dual(**dual)
         self.order = False
@@ -1352,8 +1529,44 @@ class OBCADevicePlanner:
         self._clock = None
         if clock is not None:
             self.set_clock(None if clock is True else rows)
+        if feedback is not None:
+            self.set_feedback(**feedback)
         self.record = OBCARunRecord()
         self.record.state_record.append(np.stack(self.init_state))
+
+    def set_feedback(self, par=None, tape=None):
+        """Attach the plant (piadmm_obca_feedback_plan; a step boundary only, no clock): par one plant
+        row or n rows (None: the nominal plant), tape n x cap x 2 x 5 disturbance rows or None.  A
+        second call replaces the first and starts its tape again."""
+        from . import _lib
+        rows, tape = feedback_args(self.n, dict(par=par, tape=tape))
+        self._check(self._lib.piadmm_obca_feedback_plan(self.batch._h, 1, None if par is None else _lib.dptr(rows),
+                                                        rows.shape[0], _lib.dptr(tape),
+                                                        0 if tape is None else tape.shape[1]))
+        self._feedback = (rows, tape)
+
+    def clear_feedback(self):
+        """Detach the plant (a step boundary only): a step closes with init_state = X[1] again."""
+        self._check(self._lib.piadmm_obca_feedback_plan(self.batch._h, 0, None, 0, None, 0))
+        self._feedback = None
+
+    def feedback_steps(self):
+        """The steps closed since the attachment (PLAN_GET FEEDBACK_STEPS)."""
+        return int(self.get("FEEDBACK_STEPS")[0])
+
+    def measure(self, slots, states):
+        """init_state of both state copies of the scenarios `slots` (ascending, distinct) = the
+        measured `states` (m x 2 x 5), one scatter launch (piadmm_obca_feedback_measure; a step
+        boundary, no trace); nothing else changes."""
+        from . import _lib
+        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        states = np.ascontiguousarray(states, np.float64)
+        assert states.shape == (len(slots), 2, NX), states.shape
+        self._check(self._lib.piadmm_obca_feedback_measure(self.batch._h, len(slots), _lib.iptr(slots),
+                                                           _lib.dptr(states)))
+        self.init_state = list(self.init_state)
+        for k, s in enumerate(slots):
+            self.init_state[int(s)] = states[k].copy()
 
     def set_clock(self, clock_init=None):
         """Attach the per-scenario clocks (piadmm_obca_clock_plan; a step boundary only): clock_init
@@ -1640,7 +1853,9 @@ class OBCADevicePlanner:
                  "PAR": (rows, FLEET_PAR), "DUAL_S": (n, 2, NT, 9), "DUAL_D": (n, 2, NT, 9),
                  "DUAL_PAR": (1 if self.dual_par is None else len(self.dual_par), DUAL_PAR), "WORK": (n, 2),
                  "CLOCK": (n, 3), "WINDOW": (n, 2, N_HORZ, NX), "PRIMAL_THRES": (n,), "DUAL_THRES": (n,),
-                 "PROB": (n,), "DUAL_S_PREV": (n, 2, NT, 9), "DUAL_D_PREV": (n, 2, NT, 9)}[what]
+                 "PROB": (n,), "DUAL_S_PREV": (n, 2, NT, 9), "DUAL_D_PREV": (n, 2, NT, 9),
+                 "FEEDBACK_PAR": (1 if self._feedback is None else len(self._feedback[0]), FEEDBACK_PAR),
+                 "FEEDBACK_STEPS": (1,)}[what]
         out = np.zeros(shape, dt)
         self._check(self._lib.piadmm_obca_plan_get(self.batch._h, code, out.ctypes.data, out.nbytes))
         return out
@@ -1666,11 +1881,12 @@ class OBCADevicePlanner:
             self._lib.piadmm_obca_plan_end(self.batch._h)
 
     def _close_step(self, iters, status):
-        if self._clock is None:
+        if self._clock is None and self._feedback is None:
             X = self.get("X")
             self.init_state = [X[s, :, 1].copy() for s in range(self.n)]
         else:
-            # a retired scenario's init_state is frozen, an admitted one's X is zero until it runs
+            # a retired scenario's init_state is frozen, an admitted one's X is zero until it runs;
+            # with feedback init_state is the state the vehicle reached, not X[1]
             st = self.get("STATE")
             self.init_state = [unpack_state(st[s])[1] for s in range(self.n)]
         self.record.state_record.append(np.stack(self.init_state))

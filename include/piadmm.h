@@ -799,6 +799,81 @@ int32_t piadmm_obca_tenant_export(piadmm_obca_t h, int32_t m, const int32_t* slo
 int32_t piadmm_obca_tenant_import(piadmm_obca_t h, int32_t m, const int32_t* slots /* m */, const void* blob,
                                 int64_t bytes);
 
+/* ---- closed-loop feedback for an open plan: plant, disturbance, measurement -------------------
+ * piadmm_obca_plan_shift closes an MPC step with init_state = X[1]: the next step starts from the
+ * planner's own Euler prediction (decentralized_overtaking_ADMM.py:99).  The calls below put a
+ * vehicle between two steps instead: a plant model that need not be the NLP's, an additive
+ * disturbance, or a state measured outside.  Opt-in: without the attachment the plan issues exactly
+ * the launches it issued before.
+ *
+ * The plant step.  State (x, y, v, theta, delta), held control (a, omega), one step of length
+ * DT = 0.1 of the reference's right-hand side (decentralized/optimizer.py:75-77)
+ *   beta = atan(lr tan(delta) / (lr + lf))
+ *   rhs  = (v cos(theta + beta), v sin(theta + beta), a_eff, v / lr sin(beta), w_eff)
+ * with a_eff = clip(gain_a a, +-a_max) and w_eff = clip(gain_w omega, +-w_max), in n_sub substeps of
+ * DT / n_sub, explicit Euler (method 0) or classical RK4 (method 1); after every substep delta is
+ * clipped to +-0.6 (max_front_wheel_angle), after the last one the disturbance row is added:
+ * x_next = F(x0, u) + w.  A parameter row is PIADMM_OBCA_FEEDBACK_PAR = 16 doubles, 8 per vehicle,
+ * vehicle 0 first, the integers stored as doubles:
+ *   method (0 / 1), n_sub (1..64), lr, lf (> 0), gain_a, gain_w (finite), a_max, w_max (> 0)
+ * The nominal row (Euler, 1, 1.0, 1.5, 1, 1, 5, 20) with w = 0 is the NLP's own transition
+ * st + dt f(st, con) (optimizer.py:92-96).  piadmm.obca.propagate is the same statement in NumPy.
+ *
+ * piadmm_obca_propagate runs k_plan_propagate (one lane per vehicle) alone on the call's own device
+ * buffers; the handle's buffers and an open plan stay as they are.  Before any device call:
+ * 1 <= n <= 2^20, non-null pointers (w may be NULL: no disturbance), every input finite, every row
+ * valid -- a bad row is PIADMM_E_ARG with "obca_propagate: row k: ...".
+ *
+ * piadmm_obca_feedback_plan, mode 1, attaches the plant to the open plan: par holds `rows` = 1 (every
+ * scenario) or n parameter rows, NULL is the nominal row; tape holds `cap` disturbance rows per
+ * scenario (n x cap x 2 x 5, 0 <= cap <= 2^20), NULL is no disturbance.  A second call replaces the
+ * first; mode 0 detaches.  Rows and tape (every value finite) are checked on the host before any
+ * device call: PIADMM_E_ARG, a bad row with "obca_feedback_plan: row k: ...".  Then, PIADMM_E_STATE:
+ * only at a step boundary (no iterate of the open step has run), and not while a clock is attached.
+ * A refused call leaves the plan and an earlier attachment as they were.
+ *
+ * While attached, piadmm_obca_plan_shift (called directly, by piadmm_obca_plan_step or by
+ * piadmm_obca_trace_run) computes for every scenario
+ *   next = propagate(x0, u0, par[s], tape[s][k])
+ * with x0 the closing step's init_state bit for bit (not X[0], which equals it only to the solver's
+ * tolerance), u0 = (U[0, 0], U[0, 1]) of the local solution whose X[1] the shift would take (the
+ * CTRL item holds it) and k the steps consumed since the attachment; then it runs the unchanged
+ * shift and writes `next` over init_state of STATE and STATE_PREV.  Everything else the shift
+ * produces -- the shifted duals and halfspaces, LAMBDA, CTRL_PREV = 0, the order's list, the dual
+ * law's integrators -- is unchanged bit for bit.  It runs before the trace's row is appended: the
+ * row's STATES and clearances are those of the state the vehicle reached.  With a tape, at k >= cap
+ * the shift, piadmm_obca_plan_step and piadmm_obca_trace_run (whose n_steps must fit what is left)
+ * return PIADMM_E_STATE ("disturbance tape exhausted") before any launch and the plan stays as it
+ * was, as "trace full" does.  piadmm_obca_plan_get gains
+ *   FEEDBACK_PAR        rows x PIADMM_OBCA_FEEDBACK_PAR fp64   the rows as attached (1 nominal row for NULL)
+ *   FEEDBACK_STEPS      1 int32                                the steps consumed since the attachment
+ * (PIADMM_E_STATE without the attachment).  piadmm_obca_plan_end, a new piadmm_obca_plan_begin /
+ * _fleet_begin and any upload that ends the plan free the attachment.
+ *
+ * piadmm_obca_feedback_measure writes m measured states over init_state of both state copies of the
+ * scenarios `slots` (ascending, distinct, below n) of any open plan, attached or not, in one scatter
+ * launch; nothing else changes.  PIADMM_E_ARG before any device call for bad slots or a state that is
+ * not finite; PIADMM_E_STATE while an MPC step is open, and while a trace is attached (its last row
+ * and running minima were computed from the state being replaced).
+ *
+ * Out of scope, PIADMM_E_STATE before any device call: piadmm_obca_feedback_plan(mode 1) while a
+ * clock is attached, piadmm_obca_clock_plan(mode 1) while feedback is attached, and
+ * piadmm_obca_tenant_export / _import while feedback is attached (the tenant record's layout is
+ * fixed and has no room for the tape). */
+#define PIADMM_OBCA_FEEDBACK_PAR 16
+#define PIADMM_OBCA_PLAN_GET_FEEDBACK_PAR 34
+#define PIADMM_OBCA_PLAN_GET_FEEDBACK_STEPS 35
+int32_t piadmm_obca_propagate(piadmm_obca_t h, int32_t n, const double* states /* n x 2 x 5 */,
+                              const double* ctrl /* n x 2 x 2: a, omega */,
+                              const double* par /* n x PIADMM_OBCA_FEEDBACK_PAR */,
+                              const double* w /* n x 2 x 5 or NULL */, double* out /* n x 2 x 5 */);
+int32_t piadmm_obca_feedback_plan(piadmm_obca_t h, int32_t mode,
+                                  const double* par /* rows x PIADMM_OBCA_FEEDBACK_PAR, may be NULL */,
+                                  int32_t rows /* 1 or n */, const double* tape /* n x cap x 2 x 5, may be NULL */,
+                                  int32_t cap);
+int32_t piadmm_obca_feedback_measure(piadmm_obca_t h, int32_t m, const int32_t* slots /* m, ascending */,
+                                     const double* states /* m x 2 x 5 */);
+
 #ifdef __cplusplus
 }
 #endif

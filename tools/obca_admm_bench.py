@@ -75,6 +75,21 @@
                    own spread.  No ratio is fixed in advance.  Written under the key "migrate" of the
                    same JSON, the other keys kept.
 
+  --feedback       instead of the above, in one process at --scenarios scenarios of
+                   obca.overtaking_fleet(--scenarios, seed=0) over --steps MPC steps from step 8 through
+                   run_traced, the repeats of legs (a) and (b) alternating after a warm-up step of each
+                   on its own plan, best of --repeats: (a) the plain fleet (the yardstick: the launches
+                   of a plan that never heard of feedback), (b) the same fleet with the nominal plant and
+                   a zero tape (piadmm_obca_feedback_plan: two more launches per MPC step, 2 x
+                   --scenarios lanes of work next to the batched SQP launches).  (b)/(a) is reported
+                   next to the max/min spread of (a)'s own repeats; no ratio is fixed in advance.  (c)
+                   one run_traced each with prob = 0 and with prob = 1 for every scenario under the same
+                   Gaussian tape (seed 0) on x and y, sigma = VAR_DELAY * the vehicle's reference speed
+                   (the position scale of the delay statistics the tightening is built from): per
+                   setting the share of scenarios whose smallest plain clearance over the run fell
+                   below their min_dis.  Findings, not criteria.  Written under the key "feedback" of
+                   the same JSON, the other keys kept.
+
 There is no CPU baseline on an equal footing (the C++ port of the local solver has no edge step);
 the edge launch is reported next to the local launch so the reader sees its share of an iterate.
 Writes one JSON (default profiles/obca_admm_bench.json) and prints it.
@@ -518,8 +533,80 @@ def migrate_main(a):
     print(json.dumps(dict(migrate=res)))
 
 
+def feedback_main(a):
+    """--feedback: (a) the plain fleet, (b) the same fleet with the nominal plant and a zero tape, the
+    repeats alternating; (c) the fleet under one Gaussian tape with prob = 0 and with prob = 1."""
+    b = obca.OBCABatch(0)
+    n, K = a.scenarios, a.steps
+    specs, par = obca.overtaking_fleet(n, seed=0)
+    kw = dict(prob=[k % 2 for k in range(n)], t_step0=8, max_admm_iter=a.iterates - 1, specs=specs, **par)
+    zero = dict(par=None, tape=np.zeros((n, K, 2, obca.NX)))
+    legs_fb = dict(a_fleet=None, b_fleet_nominal_plant_zero_tape=zero)
+    states, ms, traces = {}, {k: [] for k in legs_fb}, {}
+    for name, fb in legs_fb.items():
+        warm = obca.OBCADevicePlanner(b, n, feedback=fb, **kw)
+        states[name] = warm.get("STATE")              # the seeded state, so the later plans skip the host seeding
+        warm.step()
+        warm.close()
+    for _ in range(a.repeats):
+        for name, fb in legs_fb.items():
+            dp = obca.OBCADevicePlanner(b, n, feedback=fb, state=states[name], **kw)
+            t0 = time.perf_counter()
+            traces[name] = dp.run_traced(K, keep_lambda=False)
+            ms[name].append((time.perf_counter() - t0) * 1e3)
+            dp.close()
+    legs = {}
+    for name in legs_fb:
+        tr = traces[name]
+        n_it, best = int(tr.iters.max(axis=1).sum()), min(ms[name])
+        legs[name] = dict(steps_run=int(tr.iters.shape[0]), admm_iterates=n_it, step_ms=best / max(tr.iters.shape[0], 1),
+                          iterate_ms=best / max(n_it, 1), total_ms_runs=ms[name], spread_max_over_min=max(ms[name]) / best,
+                          stop_iterate_histogram=np.bincount(tr.iters.ravel()).tolist())
+    ratio = min(ms["b_fleet_nominal_plant_zero_tape"]) / min(ms["a_fleet"])
+    # the nominal plant with a zero tape closes a step at st + DT f(st, u0): the NLP's own constraint, met to
+    # the solver's tolerance only, so the two records agree to that tolerance and not bit for bit
+    dev = float(np.abs(traces["a_fleet"].states - traces["b_fleet_nominal_plant_zero_tape"].states).max())
+    # (c) the disturbed fleet, with and without the delay tightening
+    v_ref = np.array([[sp.v0, sp.v1] for sp in specs])
+    tape = np.zeros((n, K, 2, obca.NX))
+    tape[..., :2] = np.random.default_rng(0).standard_normal((n, K, 2, 2)) * (obca.VAR_DELAY * v_ref)[:, None, :, None]
+    min_dis = np.broadcast_to(np.asarray(par.get("min_dis", 0.1), np.float64), (n,))
+    disturbed = {}
+    for prob in (0, 1):
+        dp = obca.OBCADevicePlanner(b, n, feedback=dict(par=None, tape=tape), **dict(kw, prob=[prob] * n))
+        tr = dp.run_traced(K, keep_lambda=False)
+        dp.close()
+        below = tr.min_clearance < min_dis
+        disturbed[f"prob_{prob}"] = dict(
+            share_below_min_dis=float(below.mean()), scenarios_below_min_dis=int(below.sum()),
+            share_touching=float((tr.min_clearance == 0.0).mean()), min_clearance_smallest=float(tr.min_clearance.min()),
+            min_clearance_median=float(np.median(tr.min_clearance)),
+            min_clearance_tight_median=float(np.median(tr.min_clearance_tight)),
+            stop_iterate_histogram=np.bincount(tr.iters.ravel()).tolist(),
+            local_status_mask_or=int(np.bitwise_or.reduce(tr.status_mask[:, :, 0].ravel())),
+            edge_status_mask_or=int(np.bitwise_or.reduce(tr.status_mask[:, :, 1].ravel())))
+    res = dict(scenarios=n, steps=K, repeats=a.repeats, max_admm_iter=a.iterates - 1, legs=legs,
+               nominal_plant_over_plain=ratio, plain_spread_max_over_min=legs["a_fleet"]["spread_max_over_min"],
+               ratio_exceeds_plain_spread=bool(ratio > legs["a_fleet"]["spread_max_over_min"]),
+               nominal_plant_max_state_deviation=dev,
+               disturbed=dict(tape="Gaussian on x, y: sigma = VAR_DELAY * reference speed, seed 0",
+                              sigma_m=dict(min=float((obca.VAR_DELAY * v_ref).min()), max=float((obca.VAR_DELAY * v_ref).max())),
+                              **disturbed))
+    b.close()
+    out = {}
+    if os.path.exists(a.out):
+        with open(a.out) as f:
+            out = json.load(f)
+    out["feedback"] = res
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+    print(json.dumps(dict(feedback=res)))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--feedback", action="store_true")
     ap.add_argument("--migrate", action="store_true")
     ap.add_argument("--clock", action="store_true")
     ap.add_argument("--order", action="store_true")
@@ -533,6 +620,8 @@ def main():
     ap.add_argument("--iterates", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "obca_admm_bench.json"))
     a = ap.parse_args()
+    if a.feedback:
+        return feedback_main(a)
     if a.migrate:
         return migrate_main(a)
     if a.clock:
