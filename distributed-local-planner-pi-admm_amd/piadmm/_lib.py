@@ -38,6 +38,15 @@ class PiadmmConfigC(ctypes.Structure):
     ]
 
 
+class ObcaStatsC(ctypes.Structure):
+    """Byte-for-byte mirror of ``piadmm_obca_stats_t`` (``piadmm_obca_stats_size``)."""
+    _fields_ = [
+        ("nonfinite", ctypes.c_int64 * 2), ("iter_sum", ctypes.c_int64), ("flagged", ctypes.c_int64),
+        ("fleet_min", c_dbl * 2), ("fleet_arg", c_i32 * 2), ("iter_max", c_i32), ("mask_or", c_i32 * 2),
+        ("reserved", c_i32),
+    ]
+
+
 class ObcaPlanCfgC(ctypes.Structure):
     """Byte-for-byte mirror of ``piadmm_obca_plan_cfg_t`` (``piadmm_obca_plan_cfg_size``)."""
     _fields_ = [
@@ -136,6 +145,12 @@ SYMBOLS = [
     ("piadmm_obca_propagate", c_i32, [_H, c_i32, _dp, _dp, _dp, _dp, _dp]),
     ("piadmm_obca_feedback_plan", c_i32, [_H, c_i32, _dp, c_i32, _dp, c_i32]),
     ("piadmm_obca_feedback_measure", c_i32, [_H, c_i32, _ip, _dp]),
+    ("piadmm_obca_stats_size", c_i32, []),
+    ("piadmm_obca_fleet_stats", c_i32, [_H, c_i32, c_i32, _dp, _dp, _ip, _ip, _dp, c_i32, c_i32, _P(ObcaStatsC),
+                                        _P(ctypes.c_int64), _dp, _ip, _ip, _ip]),
+    ("piadmm_obca_stats_trace", c_i32, [_H, _dp, c_i32, c_i32, _P(ObcaStatsC), _P(ctypes.c_int64), _dp, _ip, _ip, _ip]),
+    ("piadmm_obca_gather_trace_bytes", c_i32, [_H, c_i32, _P(ctypes.c_int64)]),
+    ("piadmm_obca_gather_trace", c_i32, [_H, c_i32, _ip, ctypes.c_void_p, ctypes.c_int64]),
 ]
 
 # PIADMM_OBCA_FLEET_PAR: doubles per parameter row of piadmm_obca_fleet_begin
@@ -144,6 +159,10 @@ FLEET_PAR = 16
 DUAL_PAR = 8
 # PIADMM_OBCA_FEEDBACK_PAR: doubles per plant row of piadmm_obca_feedback_plan / piadmm_obca_propagate
 FEEDBACK_PAR = 16
+
+# PIADMM_OBCA_STATS_EDGES / _WORST: the most edges and the most worst scenarios of the statistics calls
+STATS_EDGES = 64
+STATS_WORST = 64
 
 # error codes of include/piadmm.h the OBCA bindings name
 E_ARG, E_HIP, E_STATE, E_NODEV = -1, -2, -3, -4
@@ -180,6 +199,8 @@ def load(path: str | None = None):
         f.argtypes = args
     if lib.piadmm_config_size() != ctypes.sizeof(PiadmmConfigC):
         raise PiadmmError("piadmm_config_t layout mismatch between header and binding")
+    if lib.piadmm_obca_stats_size() != ctypes.sizeof(ObcaStatsC):
+        raise PiadmmError("piadmm_obca_stats_t layout mismatch between header and binding")
     if path is None:
         _lib = lib
     return lib

@@ -874,6 +874,96 @@ int32_t piadmm_obca_feedback_plan(piadmm_obca_t h, int32_t mode,
 int32_t piadmm_obca_feedback_measure(piadmm_obca_t h, int32_t m, const int32_t* slots /* m, ascending */,
                                      const double* states /* m x 2 x 5 */);
 
+/* ---- fleet risk statistics and the worst-case gather of a run record ---------------------------
+ * A Monte-Carlo study over a traced fleet asks how many runs came closer than d, at which step the
+ * fleet is most at risk, and which runs were the worst.  piadmm_obca_trace_get can only copy the
+ * whole record, O(R n) bytes; the calls below reduce it on the device and bring back the counts, the
+ * minima and the record of a chosen few scenarios, O(R B + R m) bytes.
+ *
+ * The ordering key.  Values are ordered by (value ascending, then scenario ascending); a value that
+ * is not finite (NaN, +inf, -inf) orders after every finite one, again by scenario: a strict total
+ * order, as the one of piadmm_obca_order.  Equal values are compared with ==, so -0.0 ties with 0.0.
+ *
+ * With ascending edges e_0 < ... < e_(B-1), R recorded steps and n scenarios, over a summary (n x 4:
+ * min plain clearance, its row, min tightened clearance, sum of the stop iterates -- the SUMMARY item),
+ * the clearances ((R + 1) x n x 2), the stop iterates (R x n) and the status masks (R x n x 2):
+ *   piadmm_obca_stats_t  nonfinite[k]   the scenarios whose minimum k (0 plain, 1 tightened) is not finite
+ *                        iter_sum       the sum of the summary's iterate sums, each converted to an integer
+ *                        flagged        the scenarios whose OR over the rows, of either mask, has a bit other
+ *                                       than 1 << PIADMM_OBCA_CONVERGED
+ *                        fleet_min[k], fleet_arg[k]   the first finite minimum k under the key and its
+ *                                       scenario; +inf and -1 when none is finite
+ *                        iter_max       the largest stop iterate (0 for R = 0)
+ *                        mask_or[j]     the OR of the local (0) / the edge (1) mask over rows and scenarios
+ *   hist       2 x (B + 1) int64        of the plain / the tightened minima: bin 0 counts x < e_0, bin b
+ *                                       e_(b-1) <= x < e_b, bin B x >= e_(B-1); a minimum that is not finite
+ *                                       is in no bin
+ *   row_min    (R + 1) x 2 fp64         per row the first finite clearance under the key ...
+ *   row_arg    (R + 1) x 2 int32        ... and its scenario; +inf and -1 when the row has none
+ *   row_below  (R + 1) x 2 x B int32    the scenarios of the row with a finite clearance < e_b (cumulative in b)
+ *   worst      K int32                  the K scenarios that come first under the key on the plain minimum,
+ *                                       in that order (the ones that are not finite last)
+ * Every result is an integer count, a minimum of doubles or a comparison: exact, a function of the
+ * inputs alone, the same on every run.  k_stats_fleet, k_stats_rows and k_stats_worst reduce 128
+ * scenarios per workgroup with wave reductions and LDS partials and write one partial record each; a
+ * second, small launch (several for `worst` on a large fleet) reduces the records.  No atomic decides
+ * a value or a position and no kernel waits for another workgroup.  piadmm.obca.fleet_stats_host is
+ * the same statement in NumPy.
+ *
+ * piadmm_obca_fleet_stats runs the reductions on the caller's arrays, on the call's own device
+ * buffers: the handle's buffers and an open plan stay as they are.  rows_R may be 0; iters and mask
+ * may then be NULL.  piadmm_obca_stats_trace runs them on the attached trace in place (R = the steps
+ * recorded, PIADMM_OBCA_TRACE_GET_ROWS): nothing but the results is copied, the plan and the trace
+ * are not changed, and it works with a dual law, an order, a clock or feedback attached.  Under a
+ * clock a retired scenario's rows hold its frozen values and are counted as they stand.
+ * Before any device call, PIADMM_E_ARG: non-null pointers, 1 <= n <= 2^20, 0 <= rows_R <= 2^20,
+ * 1 <= B <= PIADMM_OBCA_STATS_EDGES, every edge finite and above the one before it ("obca_fleet_stats:
+ * edge k: ..."), 1 <= K <= min(PIADMM_OBCA_STATS_WORST, n) and, for piadmm_obca_fleet_stats, every
+ * iterate sum of the summary an integer in [0, 2^40] ("obca_fleet_stats: row k: ...").
+ * piadmm_obca_stats_trace without an open plan or an attached trace is PIADMM_E_STATE.  A refused
+ * call writes nothing.
+ *
+ * piadmm_obca_gather_trace copies every row of the m scenarios `slots` (distinct, below n, any order)
+ * out of the attached trace: the slot numbers go to the device, one launch of k_trace_gather (one wave
+ * per row and column) fills a staging buffer there and one copy brings it to the host.  Column k is
+ * scenario slots[k]; every value is an exact copy.  The blob, offsets in bytes with R = the steps
+ * recorded and P = R m:
+ *   0                       STATES       (R + 1) x m x 2 x 5 fp64
+ *   80 (R + 1) m            CLEARANCE    (R + 1) x m x 2 fp64
+ *   96 (R + 1) m            PRIMAL       R x m fp64
+ *   96 (R + 1) m + 8 P      DUAL         R x m fp64
+ *   96 (R + 1) m + 16 P     SUMMARY      m x 4 fp64
+ *   I = 96 (R + 1) m + 16 P + 32 m       ITERS        R x m int32
+ *   I + 4 P                 STATUS_MASK  R x m x 2 int32
+ *   L = I + 12 P + (4 if P is odd)       LAMBDA       R x m x 2 x 7 x 9 fp64, only with PIADMM_OBCA_TRACE_LAMBDA
+ * The blob is L bytes without the flag and L + 1008 P with it; piadmm_obca_gather_trace_bytes returns
+ * that number, and `bytes` must equal it.  piadmm.obca.trace_gather_unpack is the same statement in
+ * NumPy.  PIADMM_E_ARG before any device call: 1 <= m <= n, non-null pointers, the slots, `bytes`;
+ * PIADMM_E_STATE without an open plan or an attached trace.  Neither the plan nor the trace changes. */
+#define PIADMM_OBCA_STATS_EDGES 64
+#define PIADMM_OBCA_STATS_WORST 64
+typedef struct {
+  int64_t nonfinite[2];
+  int64_t iter_sum, flagged;
+  double fleet_min[2];
+  int32_t fleet_arg[2];
+  int32_t iter_max;
+  int32_t mask_or[2];
+  int32_t reserved;
+} piadmm_obca_stats_t;
+int32_t piadmm_obca_stats_size(void);
+int32_t piadmm_obca_fleet_stats(piadmm_obca_t h, int32_t rows_R, int32_t n, const double* clear /* (R + 1) x n x 2 */,
+                                const double* summary /* n x 4 */, const int32_t* iters /* R x n */,
+                                const int32_t* mask /* R x n x 2 */, const double* edges /* B */, int32_t B, int32_t K,
+                                piadmm_obca_stats_t* stats, int64_t* hist /* 2 x (B + 1) */,
+                                double* row_min /* (R + 1) x 2 */, int32_t* row_arg /* (R + 1) x 2 */,
+                                int32_t* row_below /* (R + 1) x 2 x B */, int32_t* worst /* K */);
+int32_t piadmm_obca_stats_trace(piadmm_obca_t h, const double* edges /* B */, int32_t B, int32_t K,
+                                piadmm_obca_stats_t* stats, int64_t* hist, double* row_min, int32_t* row_arg,
+                                int32_t* row_below, int32_t* worst);
+int32_t piadmm_obca_gather_trace_bytes(piadmm_obca_t h, int32_t m, int64_t* bytes);
+int32_t piadmm_obca_gather_trace(piadmm_obca_t h, int32_t m, const int32_t* slots /* m */, void* blob, int64_t bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -90,6 +90,17 @@
                    below their min_dis.  Findings, not criteria.  Written under the key "feedback" of
                    the same JSON, the other keys kept.
 
+  --stats          instead of the above, in one process: a traced run of --steps MPC steps from step 8 of
+                   --scenarios scenarios of obca.overtaking_fleet(--scenarios, seed=0) under a Gaussian
+                   disturbance tape (as --feedback's (c)), LAMBDA kept; then on that one trace, the
+                   repeats alternating, best of --repeats: (a) trace_get of every item followed by
+                   obca.fleet_stats_host (the yardstick: what a study had to do before), (b)
+                   trace_stats + trace_gather of the 16 worst (piadmm_obca_stats_trace /
+                   piadmm_obca_gather_trace: the reductions and the gather on the device).  Both
+                   times, the bytes each leg brought to the host (exact, from the layouts) and whether
+                   the two legs agree bit for bit.  No ratio is fixed in advance.  Written under the
+                   key "stats" of the same JSON, the other keys kept.
+
 There is no CPU baseline on an equal footing (the C++ port of the local solver has no edge step);
 the edge launch is reported next to the local launch so the reader sees its share of an iterate.
 Writes one JSON (default profiles/obca_admm_bench.json) and prints it.
@@ -604,8 +615,68 @@ def feedback_main(a):
     print(json.dumps(dict(feedback=res)))
 
 
+def stats_main(a):
+    """--stats: on one traced, disturbed fleet run, (a) trace_get of everything + fleet_stats_host against
+    (b) trace_stats + trace_gather of the 16 worst."""
+    b = obca.OBCABatch(0)
+    n, K, worst, B = a.scenarios, a.steps, min(16, a.scenarios), 32
+    specs, par = obca.overtaking_fleet(n, seed=0)
+    v_ref = np.array([[sp.v0, sp.v1] for sp in specs])
+    tape = np.zeros((n, K, 2, obca.NX))
+    tape[..., :2] = np.random.default_rng(0).standard_normal((n, K, 2, 2)) * (obca.VAR_DELAY * v_ref)[:, None, :, None]
+    dp = obca.OBCADevicePlanner(b, n, feedback=dict(par=None, tape=tape), prob=[k % 2 for k in range(n)], t_step0=8,
+                                max_admm_iter=a.iterates - 1, specs=specs, **par)
+    dp.trace_begin(K, keep_lambda=True)
+    R = dp.trace_run(K)
+    names = ("STATES", "CLEARANCE", "ITERS", "STATUS_MASK", "PRIMAL", "DUAL", "LAMBDA", "SUMMARY")
+    edges = np.linspace(0.0, 8.0, B)
+
+    def leg_host():
+        items = {k: dp.trace_get(k) for k in names}
+        st = obca.fleet_stats_host(items["CLEARANCE"], items["SUMMARY"], items["ITERS"], items["STATUS_MASK"], edges, worst)
+        w = st.worst
+        return st, {k: (v[w] if k == "SUMMARY" else v[:, w]) for k, v in items.items()}, sum(v.nbytes for v in items.values())
+
+    def leg_device():
+        st = dp.trace_stats(edges, worst=worst)
+        rec = dp.trace_gather(st.worst)
+        # piadmm_obca_stats_t, hist, row_min, row_arg, row_below, worst; then the gathered record
+        back = 72 + 2 * (B + 1) * 8 + (R + 1) * 2 * (8 + 4 + 4 * B) + 4 * worst
+        return st, rec, back + obca.trace_gather_layout(R, worst, True)[1]
+    leg_host(), leg_device()                              # warm-up
+    ms, out = dict(a=[], b=[]), {}
+    for _ in range(a.repeats):
+        for key, leg in (("a", leg_host), ("b", leg_device)):
+            t0 = time.perf_counter()
+            out[key] = leg()
+            ms[key].append((time.perf_counter() - t0) * 1e3)
+    (sa, ra, bytes_a), (sb, rb, bytes_b) = out["a"], out["b"]
+    same = all(np.array_equal(np.asarray(getattr(sa, f)), np.asarray(getattr(sb, f)), equal_nan=True)
+               for f in ("hist", "nonfinite", "fleet_min", "fleet_arg", "iter_sum", "iter_max", "mask_or", "flagged",
+                         "row_min", "row_arg", "row_below", "worst"))
+    same = same and all(ra[k].tobytes() == rb[k].tobytes() for k in names)
+    dp.close()
+    b.close()
+    res = dict(scenarios=n, steps=R, repeats=a.repeats, max_admm_iter=a.iterates - 1, edges=B, worst=worst,
+               a_trace_get_all_then_host=dict(ms=min(ms["a"]), ms_runs=ms["a"], bytes_to_host=int(bytes_a)),
+               b_trace_stats_then_gather=dict(ms=min(ms["b"]), ms_runs=ms["b"], bytes_to_host=int(bytes_b)),
+               b_over_a_ms=min(ms["b"]) / min(ms["a"]), a_over_b_bytes=bytes_a / bytes_b, legs_equal=bool(same),
+               scenarios_below_first_edges=[int(v) for v in sb.hist[0][:4]], worst_scenarios=[int(v) for v in sb.worst],
+               worst_min_clearance=float(ra["SUMMARY"][0, 0]), flagged=int(sb.flagged), iter_sum=int(sb.iter_sum))
+    out_json = {}
+    if os.path.exists(a.out):
+        with open(a.out) as f:
+            out_json = json.load(f)
+    out_json["stats"] = res
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out_json, f, indent=1)
+    print(json.dumps(dict(stats=res)))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--stats", action="store_true")
     ap.add_argument("--feedback", action="store_true")
     ap.add_argument("--migrate", action="store_true")
     ap.add_argument("--clock", action="store_true")
@@ -620,6 +691,8 @@ def main():
     ap.add_argument("--iterates", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "obca_admm_bench.json"))
     a = ap.parse_args()
+    if a.stats:
+        return stats_main(a)
     if a.feedback:
         return feedback_main(a)
     if a.migrate:
