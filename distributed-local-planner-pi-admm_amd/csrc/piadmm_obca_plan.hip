@@ -28,6 +28,9 @@
 // before k_plan_shift (the plant step from the closing step's init_state and first control) and
 // k_plan_set_init after it (the state the vehicle reached over init_state of both copies); without
 // it neither is launched.  These two run one lane per vehicle, not one wave per item.
+// With the noise attached on top (piadmm_obca_noise_plan) k_plan_noise runs in front of
+// k_plan_propagate and writes the step's disturbance rows, which that kernel reads in the tape's
+// place; without it k_plan_noise is not launched.  One lane per vehicle as well.
 // The statistics of a run record (piadmm_obca_fleet_stats / _stats_trace: k_stats_fleet, k_stats_rows,
 // k_stats_worst and their merges) and k_trace_gather are launched by those calls alone and write
 // nothing of the plan or the trace.
@@ -981,6 +984,126 @@ __global__ void __launch_bounds__(64 * PW) k_plan_set_init(const int* __restrict
 }
 
 // ---------------------------------------------------------------------------------------------
+// Device-side disturbance noise (piadmm_obca_noise_plan / piadmm_obca_noise_tape): the disturbance
+// row of stream t at step k as a pure function of (seed, t, k).  Opt-in: without the attachment
+// piadmm_obca_plan_shift does not launch k_plan_noise.
+// ---------------------------------------------------------------------------------------------
+// a noise row (include/piadmm.h): sigma[2][5], bias[2][5], trunc, one reserved zero
+constexpr int ZPAR = PIADMM_OBCA_NOISE_PAR;
+constexpr int Z_SIGMA = 0, Z_BIAS = 10, Z_TRUNC = 20, Z_RESERVED = 21;
+static_assert(Z_RESERVED + 1 == ZPAR, "noise row layout");
+
+// Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11):
+// c the counter's four words, replaced by the result; (k0, k1) the key.  Ten rounds of two
+// 32 x 32 -> 64 products (the high halves by __umulhi), the key bumped between rounds.  All 32-bit.
+__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
+  constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t hi0 = __umulhi(M0, c[0]), lo0 = M0 * c[0];
+    const uint32_t hi1 = __umulhi(M1, c[2]), lo1 = M1 * c[2];
+    c[0] = hi1 ^ c[1] ^ k0;
+    c[1] = lo1;
+    c[2] = hi0 ^ c[3] ^ k1;
+    c[3] = lo0;
+    k0 += W0;
+    k1 += W1;
+  }
+}
+
+// The five disturbances of vehicle v of stream t at step k under the row's sigma S, bias B and
+// trunc: three Philox calls at counter (k, 4 v + j, t low, t high), each giving two uniforms in
+// (0, 1) on 52 bits and by Box-Muller two normals; the sixth normal is discarded.  raw (12 words,
+// or nullptr) receives the calls' words.  piadmm.obca.noise_tape is the same statements on the
+// host; products and sums are kept apart (no contraction), so sigma = 0 gives the bias bit for bit.
+// The body of k_plan_noise for the in-plan step and for the stand-alone tape: the same bits.
+__device__ __forceinline__ void noise_draw(uint32_t seed_lo, uint32_t seed_hi, uint32_t t_lo, uint32_t t_hi,
+                                           uint32_t k, int v, const double S[5], const double B[5], double trunc,
+                                           double w[5], uint32_t* raw) {
+#pragma clang fp contract(off)
+  double z[6];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    uint32_t c[4] = {k, (uint32_t)(4 * v + j), t_lo, t_hi};
+    philox4x32_10(c, seed_lo, seed_hi);
+    if (raw) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) raw[4 * j + q] = c[q];
+    }
+    const unsigned long long a = ((unsigned long long)c[0] << 32) | c[1];
+    const unsigned long long b = ((unsigned long long)c[2] << 32) | c[3];
+    const double u1 = ((double)(a >> 12) + 0.5) * 0x1p-52;
+    const double u2 = ((double)(b >> 12) + 0.5) * 0x1p-52;
+    const double rad = sqrt(-2.0 * log(u1));
+    const double ang = 6.283185307179586 * u2;
+    z[2 * j] = rad * cos(ang);
+    z[2 * j + 1] = rad * sin(ang);
+  }
+#pragma unroll
+  for (int i = 0; i < 5; ++i) {
+    double zi = z[i];
+    if (trunc != 0.0) zi = fmin(trunc, fmax(zi, -trunc));
+    w[i] = B[i] + S[i] * zi;
+  }
+}
+
+// where the arrays of one k_plan_noise launch sit, indexed by scenario: par the noise rows (par_s =
+// 0: one shared row), streams the stream ids (nullptr: the scenario's number), tape the rows added
+// in front (nullptr: none), out the result, raw the Philox words (nullptr: not kept); the strides
+// in elements per scenario, and per step index (blockIdx.y) 10 doubles of tape and out and 24 words
+// of raw; k = the step index of blockIdx.y = 0
+struct noise_io {
+  const double *par, *tape;
+  const long long* streams;
+  double* out;
+  uint32_t* raw;
+  long long tape_s, out_s, raw_s;
+  uint32_t seed_lo, seed_hi, k;
+  int par_s;
+};
+
+// One lane per vehicle: lane g of a grid row = vehicle g & 1 of entry g >> 1 of `list` (nullptr: of
+// scenario g >> 1), 2 m lanes; grid row y is step index k + y (the in-plan step launches one row).
+// No LDS, no atomics, nothing shared between lanes: the counter is the lane's own, the arithmetic
+// 32-bit integer and fp64 in registers.  The lane's 11 parameters are 8-byte loads from the row;
+// its five results 8-byte stores, neighbouring lanes to neighbouring rows as in k_plan_propagate.
+// With a tape the written value is tape + w, the tape term first.
+__global__ void __launch_bounds__(64 * PW) k_plan_noise(const int* __restrict__ list, int m, noise_io io) {
+  const int g = blockIdx.x * (64 * PW) + threadIdx.x;
+  if (g >= 2 * m) return;
+  const int v = g & 1;
+  const size_t s = (size_t)(list ? list[g >> 1] : (g >> 1));
+  const size_t y = blockIdx.y;
+  const double* P = io.par + s * io.par_s;
+  double S[5], B[5];
+#pragma unroll
+  for (int i = 0; i < 5; ++i) {
+    S[i] = P[Z_SIGMA + v * 5 + i];
+    B[i] = P[Z_BIAS + v * 5 + i];
+  }
+  const unsigned long long t = io.streams ? (unsigned long long)io.streams[s] : (unsigned long long)s;
+  uint32_t words[12];
+  double w[5];
+  noise_draw(io.seed_lo, io.seed_hi, (uint32_t)t, (uint32_t)(t >> 32), io.k + (uint32_t)y, v, S, B, P[Z_TRUNC], w,
+             io.raw ? words : nullptr);
+  double* o = io.out + s * io.out_s + y * 10 + v * 5;
+  if (io.tape) {
+#pragma clang fp contract(off)
+    const double* tr = io.tape + s * io.tape_s + y * 10 + v * 5;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) o[i] = tr[i] + w[i];
+  } else {
+#pragma unroll
+    for (int i = 0; i < 5; ++i) o[i] = w[i];
+  }
+  if (io.raw) {
+    uint32_t* r = io.raw + s * io.raw_s + y * 24 + v * 12;
+#pragma unroll
+    for (int q = 0; q < 12; ++q) r[q] = words[q];
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Fleet risk statistics and the worst-case gather of a run record (piadmm_obca_fleet_stats,
 // piadmm_obca_stats_trace, piadmm_obca_gather_trace).  Every result is an integer count, a minimum
 // of doubles or a comparison, so it is exact and does not depend on the order it is taken in: a
@@ -1458,6 +1581,17 @@ struct piadmm_obca_plan_s {
     int rows = 0, stride = 0, cap = 0, steps = 0;
     double *par = nullptr, *tape = nullptr, *next = nullptr;
   } fb;
+  // the device-side noise on top of the feedback (piadmm_obca_noise_plan): rows = 1 with stride 0 or n
+  // noise rows; streams = the stream id of every scenario; wbuf = the disturbance rows of the step
+  // that closes, n x 10, which k_plan_noise writes and k_plan_propagate reads; the step index of a
+  // shift is k0 + fb.steps
+  struct noise_s {
+    bool on = false;
+    int rows = 0, stride = 0, k0 = 0;
+    uint64_t seed = 0;
+    double *par = nullptr, *wbuf = nullptr;
+    long long* streams = nullptr;
+  } nz;
   // the staging buffer of piadmm_obca_tenant_export / _import: the records, then the slot list; grown on demand
   struct stage_s {
     char* buf = nullptr;
@@ -1515,7 +1649,18 @@ void feedback_free_buffers(piadmm_obca_plan_s::feedback_s& f) {
   f = piadmm_obca_plan_s::feedback_s();
 }
 
-void feedback_free(piadmm_obca_plan_s* p) { feedback_free_buffers(p->fb); }
+void noise_free_buffers(piadmm_obca_plan_s::noise_s& z) {
+  void* d[] = {z.par, z.wbuf, z.streams};
+  for (void* q : d)
+    if (q) (void)hipFree(q);
+  z = piadmm_obca_plan_s::noise_s();
+}
+
+// the noise counts its steps by the feedback's: it goes whenever the feedback goes or is replaced
+void feedback_free(piadmm_obca_plan_s* p) {
+  feedback_free_buffers(p->fb);
+  noise_free_buffers(p->nz);
+}
 
 void stage_free(piadmm_obca_plan_s* p) {
   if (p->stg.buf) (void)hipFree(p->stg.buf);
@@ -1655,6 +1800,10 @@ int lane_blocks(int lanes) { return (lanes + 64 * PW - 1) / (64 * PW); }
 // true when the attached feedback has a tape and the next `steps` shifts do not fit what is left of it
 bool feedback_exhausted(const piadmm_obca_plan_s* p, int64_t steps) {
   return p->fb.on && p->fb.tape && (int64_t)p->fb.steps + steps > p->fb.cap;
+}
+// true when the attached noise would pass step index 2^31 - 1 within the next `steps` shifts
+bool noise_exhausted(const piadmm_obca_plan_s* p, int64_t steps) {
+  return p->nz.on && (int64_t)p->nz.k0 + p->fb.steps + steps > ((int64_t)1 << 31);
 }
 }  // namespace
 
@@ -1962,6 +2111,7 @@ int32_t piadmm_obca_plan_shift(piadmm_obca_t h) {
   if (p->i_iter == 0) return pfail(h, PIADMM_E_STATE, "obca_plan_shift: no iterate ran in this step");
   if (p->tr.on && p->tr.rows >= p->tr.cap) return pfail(h, PIADMM_E_STATE, "obca_plan_shift: trace full");
   if (feedback_exhausted(p, 1)) return pfail(h, PIADMM_E_STATE, "obca_plan_shift: disturbance tape exhausted");
+  if (noise_exhausted(p, 1)) return pfail(h, PIADMM_E_STATE, "obca_plan_shift: noise step index exhausted");
   PHIP(h, hipSetDevice(h->device));
   if (p->ck.on) return clock_shift(h, p);
   if (p->fb.on) {
@@ -1973,6 +2123,20 @@ int32_t piadmm_obca_plan_shift(piadmm_obca_t h) {
     io.par = p->fb.par;  io.par_s = p->fb.stride;
     io.w = p->fb.tape ? p->fb.tape + (size_t)p->fb.steps * 10 : nullptr;  io.w_s = (long long)p->fb.cap * 10;
     io.out = p->fb.next;
+    if (p->nz.on) {
+      // the step's disturbance rows first (the tape's row added in front), then read in the tape's place
+      noise_io zo{};
+      zo.par = p->nz.par;  zo.par_s = p->nz.stride;
+      zo.streams = p->nz.streams;
+      zo.tape = io.w;  zo.tape_s = io.w_s;
+      zo.out = p->nz.wbuf;  zo.out_s = 10;
+      zo.seed_lo = (uint32_t)p->nz.seed;  zo.seed_hi = (uint32_t)(p->nz.seed >> 32);
+      zo.k = (uint32_t)p->nz.k0 + (uint32_t)p->fb.steps;
+      hipLaunchKernelGGL(k_plan_noise, dim3(lane_blocks(2 * p->n)), dim3(64 * PW), 0, h->stream, (const int*)nullptr,
+                         p->n, zo);
+      PHIP(h, hipGetLastError());
+      io.w = p->nz.wbuf;  io.w_s = 10;
+    }
     hipLaunchKernelGGL(k_plan_propagate, dim3(lane_blocks(2 * p->n)), dim3(64 * PW), 0, h->stream, (const int*)nullptr,
                        p->n, io);
     PHIP(h, hipGetLastError());
@@ -2018,6 +2182,7 @@ int32_t piadmm_obca_plan_step(piadmm_obca_t h, int32_t* iters_out) {
   if (!p->ck.on && p->t_step + 8 > p->cfg.n_ref) return pfail(h, PIADMM_E_STATE, "obca_plan_step: reference exhausted");
   if (p->tr.on && p->tr.rows >= p->tr.cap) return pfail(h, PIADMM_E_STATE, "obca_plan_step: trace full");
   if (feedback_exhausted(p, 1)) return pfail(h, PIADMM_E_STATE, "obca_plan_step: disturbance tape exhausted");
+  if (noise_exhausted(p, 1)) return pfail(h, PIADMM_E_STATE, "obca_plan_step: noise step index exhausted");
   // i_iter > max_admm_iter stops a scenario: at most the largest max_admm_iter + 1 iterates in a step
   while (p->n_act > 0 && p->i_iter <= p->max_iter_all) {
     if (int rc = piadmm_obca_plan_iterate(h, nullptr)) return rc;
@@ -2089,6 +2254,14 @@ int32_t piadmm_obca_plan_get(piadmm_obca_t h, int32_t what, void* out, int64_t b
       if (what == PIADMM_OBCA_PLAN_GET_FEEDBACK_PAR) { src = p->fb.par; want = (int64_t)p->fb.rows * FPAR * D; }
       else want = I;
       break;
+    case PIADMM_OBCA_NOISE_GET_PAR:
+    case PIADMM_OBCA_NOISE_GET_STREAMS:
+    case PIADMM_OBCA_NOISE_GET_SEED:
+      if (!p->nz.on) return pfail(h, PIADMM_E_STATE, "obca_plan_get: no noise attached (obca_noise_plan)");
+      if (what == PIADMM_OBCA_NOISE_GET_PAR) { src = p->nz.par; want = (int64_t)p->nz.rows * ZPAR * D; }
+      else if (what == PIADMM_OBCA_NOISE_GET_STREAMS) { src = p->nz.streams; want = n * (int64_t)sizeof(int64_t); }
+      else want = 2 * (int64_t)sizeof(uint64_t);
+      break;
     case PIADMM_OBCA_PLAN_GET_T_STEP: want = I; break;
     case PIADMM_OBCA_PLAN_GET_COUNTS: want = 3 * I; break;
     default: return pfail(h, PIADMM_E_ARG, "obca_plan_get: unknown item " + std::to_string(what));
@@ -2100,6 +2273,11 @@ int32_t piadmm_obca_plan_get(piadmm_obca_t h, int32_t what, void* out, int64_t b
   if (!out) return pfail(h, PIADMM_E_ARG, "obca_plan_get: out");
   if (what == PIADMM_OBCA_PLAN_GET_T_STEP) { *static_cast<int32_t*>(out) = p->t_step; return 0; }
   if (what == PIADMM_OBCA_PLAN_GET_FEEDBACK_STEPS) { *static_cast<int32_t*>(out) = p->fb.steps; return 0; }
+  if (what == PIADMM_OBCA_NOISE_GET_SEED) {
+    static_cast<uint64_t*>(out)[0] = p->nz.seed;
+    static_cast<uint64_t*>(out)[1] = (uint64_t)p->nz.k0;
+    return 0;
+  }
   if (what == PIADMM_OBCA_PLAN_GET_COUNTS) { for (int i = 0; i < 3; ++i) static_cast<int32_t*>(out)[i] = counts[i]; return 0; }
   PHIP(h, hipSetDevice(h->device));
   PHIP(h, hipMemcpyAsync(out, src, (size_t)want, hipMemcpyDeviceToHost, h->stream));
@@ -2623,6 +2801,8 @@ int32_t piadmm_obca_trace_run(piadmm_obca_t h, int32_t n_steps, int32_t* steps_d
   if (feedback_exhausted(p, n_steps))
     return pfail(h, PIADMM_E_STATE, "obca_trace_run: disturbance tape exhausted before " + std::to_string(n_steps) +
                  " steps (" + std::to_string(p->fb.steps) + " of " + std::to_string(p->fb.cap) + " rows used)");
+  if (noise_exhausted(p, n_steps))
+    return pfail(h, PIADMM_E_STATE, "obca_trace_run: noise step index exhausted before " + std::to_string(n_steps) + " steps");
   if (p->ck.on) {
     // the steps the longest-lived scenario has left
     int left = 0;
@@ -3045,6 +3225,145 @@ int32_t piadmm_obca_feedback_measure(piadmm_obca_t h, int32_t m, const int32_t* 
                      reinterpret_cast<const double*>(p->stg.buf), p->bar, p->barp);
   PHIP(h, hipGetLastError());
   PHIP(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// Device-side disturbance noise (include/piadmm.h)
+// ---------------------------------------------------------------------------------------------
+namespace {
+// One noise row: nullptr when it is good, else what is wrong with it.
+const char* noise_row_check(const double* row) {
+  using namespace obca_plan;
+  for (int i = 0; i < ZPAR; ++i)
+    if (!std::isfinite(row[i])) return "every entry finite";
+  for (int i = 0; i < 10; ++i)
+    if (!(row[Z_SIGMA + i] >= 0.0)) return "sigma >= 0";
+  if (!(row[Z_TRUNC] >= 0.0)) return "trunc 0 (none) or > 0";
+  if (row[Z_RESERVED] != 0.0) return "the reserved entry must be 0";
+  return nullptr;
+}
+
+// rows, streams and k0 of both noise calls, on the host
+int noise_args_check(piadmm_obca_t h, int n, const double* par, int rows, const int64_t* streams, int32_t k0,
+                     int64_t steps, const std::string& who) {
+  if (!par) return pfail(h, PIADMM_E_ARG, who + ": null argument");
+  if (rows != 1 && rows != n) return pfail(h, PIADMM_E_ARG, who + ": rows must be 1 or n (" + std::to_string(n) + ")");
+  for (int k = 0; k < rows; ++k)
+    if (const char* why = noise_row_check(par + (size_t)k * obca_plan::ZPAR))
+      return pfail(h, PIADMM_E_ARG, who + ": row " + std::to_string(k) + ": " + why);
+  if (streams)
+    for (int k = 0; k < n; ++k)
+      if (streams[k] < 0) return pfail(h, PIADMM_E_ARG, who + ": streams[" + std::to_string(k) + "] must be >= 0");
+  if (k0 < 0 || (int64_t)k0 + steps > ((int64_t)1 << 31))
+    return pfail(h, PIADMM_E_ARG, who + ": k0 >= 0 and every step index below 2^31");
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int32_t piadmm_obca_noise_tape(piadmm_obca_t h, int32_t n, int32_t cap, const double* par, int32_t rows,
+                               const int64_t* streams, uint64_t seed, int32_t k0, double* tape_out, uint32_t* raw_out) {
+  using namespace obca_plan;
+  if (!h) return PIADMM_E_ARG;
+  if (n < 1 || n > (1 << 20)) return pfail(h, PIADMM_E_ARG, "obca_noise_tape: 1 <= n <= 2^20");
+  if (cap < 0 || cap > (1 << 20)) return pfail(h, PIADMM_E_ARG, "obca_noise_tape: 0 <= cap <= 2^20");
+  const size_t N = (size_t)n, C = (size_t)cap, B = sizeof(double);
+  if (N * C * 10 * B >= ((size_t)1 << 31))
+    return pfail(h, PIADMM_E_ARG, "obca_noise_tape: n x cap x 80 bytes must stay below 2 GiB");
+  if (int rc = noise_args_check(h, n, par, rows, streams, k0, cap, "obca_noise_tape")) return rc;
+  if (cap == 0) return 0;
+  if (!tape_out) return pfail(h, PIADMM_E_ARG, "obca_noise_tape: null argument");
+  PHIP(h, hipSetDevice(h->device));
+  // the call's own buffers: neither the handle's local and edge buffers nor an open plan is touched
+  double *d_par = nullptr, *d_out = nullptr;
+  long long* d_str = nullptr;
+  uint32_t* d_raw = nullptr;
+  auto run = [&]() -> int {
+    if (int rc = dalloc(h, &d_par, (size_t)rows * ZPAR, false)) return rc;
+    if (int rc = dalloc(h, &d_out, N * C * 10, false)) return rc;
+    if (streams)
+      if (int rc = dalloc(h, &d_str, N, false)) return rc;
+    if (raw_out)
+      if (int rc = dalloc(h, &d_raw, N * C * 24, false)) return rc;
+    PHIP(h, hipMemcpyAsync(d_par, par, (size_t)rows * ZPAR * B, hipMemcpyHostToDevice, h->stream));
+    if (streams) PHIP(h, hipMemcpyAsync(d_str, streams, N * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    noise_io zo{};
+    zo.par = d_par;  zo.par_s = rows > 1 ? ZPAR : 0;
+    zo.streams = d_str;
+    zo.out_s = (long long)C * 10;  zo.raw_s = (long long)C * 24;
+    zo.seed_lo = (uint32_t)seed;  zo.seed_hi = (uint32_t)(seed >> 32);
+    // one grid row per step index, at most 32768 rows a launch
+    for (int at = 0; at < cap; at += 32768) {
+      const int ny = std::min(cap - at, 32768);
+      zo.out = d_out + (size_t)at * 10;
+      zo.raw = d_raw ? d_raw + (size_t)at * 24 : nullptr;
+      zo.k = (uint32_t)k0 + (uint32_t)at;
+      hipLaunchKernelGGL(k_plan_noise, dim3(lane_blocks(2 * n), ny), dim3(64 * PW), 0, h->stream, (const int*)nullptr,
+                         n, zo);
+      PHIP(h, hipGetLastError());
+    }
+    PHIP(h, hipMemcpyAsync(tape_out, d_out, N * C * 10 * B, hipMemcpyDeviceToHost, h->stream));
+    if (raw_out)
+      PHIP(h, hipMemcpyAsync(raw_out, d_raw, N * C * 24 * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    PHIP(h, hipStreamSynchronize(h->stream));
+    return 0;
+  };
+  const int rc = run();
+  if (rc) (void)hipStreamSynchronize(h->stream);
+  void* dev[] = {d_par, d_out, d_str, d_raw};
+  for (void* q : dev)
+    if (q) (void)hipFree(q);
+  return rc;
+}
+
+int32_t piadmm_obca_noise_plan(piadmm_obca_t h, int32_t mode, const double* par, int32_t rows, const int64_t* streams,
+                               uint64_t seed, int32_t k0) {
+  using namespace obca_plan;
+  piadmm_obca_plan_s* p = nullptr;
+  if (int rc = open_plan(h, &p, "obca_noise_plan")) return rc;
+  if (mode != 0 && mode != 1) return pfail(h, PIADMM_E_ARG, "obca_noise_plan: mode 0 (detach) or 1 (attach)");
+  const int n = p->n;
+  const size_t N = (size_t)n;
+  if (mode == 1)
+    if (int rc = noise_args_check(h, n, par, rows, streams, k0, 0, "obca_noise_plan")) return rc;
+  if (mode == 1 && !p->fb.on)
+    return pfail(h, PIADMM_E_STATE, "obca_noise_plan: no feedback attached (obca_feedback_plan: the noise enters through the plant step)");
+  if (p->i_iter != 0) return pfail(h, PIADMM_E_STATE, "obca_noise_plan: only at a step boundary (an MPC step is open)");
+  PHIP(h, hipSetDevice(h->device));
+  PHIP(h, hipStreamSynchronize(h->stream));
+  if (mode == 0) {
+    noise_free_buffers(p->nz);
+    return 0;
+  }
+  // the new attachment is complete before it replaces the earlier one
+  piadmm_obca_plan_s::noise_s nz;
+  std::vector<long long> ident;
+  if (!streams) {
+    ident.resize(N);
+    for (size_t k = 0; k < N; ++k) ident[k] = (long long)k;
+  }
+  const void* src = streams ? static_cast<const void*>(streams) : static_cast<const void*>(ident.data());
+  hipError_t e = hipMalloc(&nz.par, (size_t)rows * ZPAR * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc(&nz.wbuf, N * 10 * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc(&nz.streams, N * sizeof(long long));
+  if (e == hipSuccess) e = hipMemset(nz.wbuf, 0, N * 10 * sizeof(double));
+  if (e == hipSuccess) e = hipMemcpy(nz.par, par, (size_t)rows * ZPAR * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(nz.streams, src, N * sizeof(long long), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    noise_free_buffers(nz);
+    return pfail(h, PIADMM_E_HIP, std::string("obca_noise_plan: ") + hipGetErrorString(e));
+  }
+  noise_free_buffers(p->nz);
+  p->nz = nz;
+  p->nz.rows = rows;
+  p->nz.stride = rows > 1 ? ZPAR : 0;
+  p->nz.seed = seed;
+  p->nz.k0 = k0;
+  p->nz.on = true;
   return 0;
 }
 

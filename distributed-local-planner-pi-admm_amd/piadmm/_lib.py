@@ -151,6 +151,9 @@ SYMBOLS = [
     ("piadmm_obca_stats_trace", c_i32, [_H, _dp, c_i32, c_i32, _P(ObcaStatsC), _P(ctypes.c_int64), _dp, _ip, _ip, _ip]),
     ("piadmm_obca_gather_trace_bytes", c_i32, [_H, c_i32, _P(ctypes.c_int64)]),
     ("piadmm_obca_gather_trace", c_i32, [_H, c_i32, _ip, ctypes.c_void_p, ctypes.c_int64]),
+    ("piadmm_obca_noise_tape", c_i32, [_H, c_i32, c_i32, _dp, c_i32, _P(ctypes.c_int64), ctypes.c_uint64, c_i32, _dp,
+                                       _P(ctypes.c_uint32)]),
+    ("piadmm_obca_noise_plan", c_i32, [_H, c_i32, _dp, c_i32, _P(ctypes.c_int64), ctypes.c_uint64, c_i32]),
 ]
 
 # PIADMM_OBCA_FLEET_PAR: doubles per parameter row of piadmm_obca_fleet_begin
@@ -159,6 +162,8 @@ FLEET_PAR = 16
 DUAL_PAR = 8
 # PIADMM_OBCA_FEEDBACK_PAR: doubles per plant row of piadmm_obca_feedback_plan / piadmm_obca_propagate
 FEEDBACK_PAR = 16
+# PIADMM_OBCA_NOISE_PAR: doubles per noise row of piadmm_obca_noise_plan / piadmm_obca_noise_tape
+NOISE_PAR = 22
 
 # PIADMM_OBCA_STATS_EDGES / _WORST: the most edges and the most worst scenarios of the statistics calls
 STATS_EDGES = 64

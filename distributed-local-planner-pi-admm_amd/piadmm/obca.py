@@ -619,6 +619,135 @@ def feedback_args(n, feedback):
     return par, tape
 
 
+# the device-side disturbance noise (piadmm_obca_noise_plan / piadmm_obca_noise_tape,
+# include/piadmm.h): a noise row is sigma[2][5], bias[2][5], trunc and one reserved zero
+NOISE_PAR = 22                        # doubles per row (PIADMM_OBCA_NOISE_PAR)
+NOISE_K_MAX = 1 << 31                 # step indices stay below it
+# the noise items of piadmm_obca_plan_get: name -> (code, dtype) (PIADMM_OBCA_NOISE_GET_*)
+NOISE_GET = {"NOISE_PAR": (36, np.float64), "NOISE_STREAMS": (37, np.int64), "NOISE_SEED": (38, np.uint64)}
+_PHILOX_M = (np.uint64(0xD2511F53), np.uint64(0xCD9E8D57))
+_PHILOX_W = (np.uint64(0x9E3779B9), np.uint64(0xBB67AE85))
+_U32 = np.uint64(0xFFFFFFFF)
+
+
+def philox4x32(counter, key):
+    """Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC'11), vectorised over leading axes: counter
+    (..., 4) and key (..., 2) 32-bit words (broadcast against each other), the result (..., 4)
+    uint32.  Ten rounds; a round takes the 64-bit products of the multipliers 0xD2511F53 with c0 and
+    0xCD9E8D57 with c2 to (hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0), the key bumped by 0x9E3779B9 and
+    0xBB67AE85 between rounds.  k_plan_noise runs the same statements in 32-bit registers."""
+    c = np.asarray(counter).astype(np.uint64) & _U32
+    k = np.asarray(key).astype(np.uint64) & _U32
+    assert c.shape[-1] == 4 and k.shape[-1] == 2, (c.shape, k.shape)
+    lead = np.broadcast_shapes(c.shape[:-1], k.shape[:-1])
+    c0, c1, c2, c3 = (np.broadcast_to(c[..., i], lead) for i in range(4))
+    k0, k1 = (np.broadcast_to(k[..., i], lead) for i in range(2))
+    for _ in range(10):
+        p0, p1 = _PHILOX_M[0] * c0, _PHILOX_M[1] * c2
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & _U32, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & _U32
+        k0, k1 = (k0 + _PHILOX_W[0]) & _U32, (k1 + _PHILOX_W[1]) & _U32
+    return np.stack((c0, c1, c2, c3), axis=-1).astype(np.uint32)
+
+
+def noise_raw(seed, streams, k):
+    """The generator's words of the streams `streams` (m int64, >= 0) at step index k: m x 2 x 3 x 4
+    uint32, the call j of vehicle v at counter (k, 4 v + j, t & 0xffffffff, t >> 32) under the key
+    (seed & 0xffffffff, seed >> 32)."""
+    t = np.asarray(streams, np.int64).reshape(-1)
+    seed, k = int(seed), int(k)
+    assert (t >= 0).all() and 0 <= seed < 1 << 64 and 0 <= k < NOISE_K_MAX, (seed, k)
+    t = t.astype(np.uint64)
+    counter = np.zeros((len(t), 2, 3, 4), np.uint64)
+    counter[..., 0] = k
+    counter[..., 1] = (4 * np.arange(2)[:, None] + np.arange(3)[None, :])[None]
+    counter[..., 2] = (t & _U32)[:, None, None]
+    counter[..., 3] = (t >> np.uint64(32))[:, None, None]
+    return philox4x32(counter, np.array([seed & 0xFFFFFFFF, seed >> 32], np.uint64))
+
+
+def noise_uniform(seed, streams, k):
+    """The uniforms of `noise_raw`: m x 2 x 3 x 2 fp64, (u1, u2) of every call,
+    u = (((hi << 32 | lo) >> 12) + 0.5) 2^-52 -- 52 bits and the half, exact in fp64 and strictly
+    inside (0, 1)."""
+    r = noise_raw(seed, streams, k).astype(np.uint64)
+    a = (r[..., 0::2] << np.uint64(32) | r[..., 1::2]) >> np.uint64(12)
+    return (a.astype(np.float64) + 0.5) * 2.0 ** -52
+
+
+def noise_normal(seed, streams, k):
+    """The standard normals of the streams at step index k: m x 2 x 5, by Box-Muller from
+    `noise_uniform` -- rad = sqrt(-2 log(u1)), z[2 j] = rad cos(2 pi u2), z[2 j + 1] = rad sin(2 pi u2)
+    -- for (x, y, v, theta, delta) of each vehicle; the sixth is discarded."""
+    u = noise_uniform(seed, streams, k)
+    rad = np.sqrt(-2.0 * np.log(u[..., 0]))
+    ang = (2.0 * np.pi) * u[..., 1]
+    z = np.stack((rad * np.cos(ang), rad * np.sin(ang)), axis=-1)
+    return z.reshape(z.shape[0], 2, 6)[..., :NX]
+
+
+def noise_row(sigma=0.0, bias=0.0, trunc=0.0):
+    """One noise row (NOISE_PAR doubles): sigma and bias each one value, five (x, y, v, theta, delta;
+    both vehicles) or 2 x 5; trunc 0 for none, else z is clipped to +-trunc before it is scaled."""
+    row = np.zeros(NOISE_PAR)
+    row[0:10] = np.broadcast_to(np.asarray(sigma, np.float64), (2, NX)).reshape(10)
+    row[10:20] = np.broadcast_to(np.asarray(bias, np.float64), (2, NX)).reshape(10)
+    row[20] = float(trunc)
+    return row
+
+
+def noise_row_check(row):
+    """None when the noise row is good, else what is wrong with it: the library's check."""
+    row = np.asarray(row, np.float64).reshape(NOISE_PAR)
+    if not np.isfinite(row).all():
+        return "every entry finite"
+    if not (row[0:10] >= 0.0).all():
+        return "sigma >= 0"
+    if not row[20] >= 0.0:
+        return "trunc 0 (none) or > 0"
+    if row[21] != 0.0:
+        return "the reserved entry must be 0"
+    return None
+
+
+def noise_args(n, par=None, streams=None, seed=0, k0=0):
+    """(par, streams, seed, k0) of a noise argument: par one noise row or n rows (None: the zero
+    row), as rows x NOISE_PAR; streams n int64 (None: 0 .. n-1); checked as the library checks."""
+    par = noise_row() if par is None else par
+    par = np.ascontiguousarray(np.asarray(par, np.float64).reshape(-1, NOISE_PAR))
+    if par.shape[0] not in (1, n):
+        raise ValueError(f"obca.noise: rows must be 1 or n ({n})")
+    for k, row in enumerate(par):
+        why = noise_row_check(row)
+        if why is not None:
+            raise ValueError(f"obca.noise: row {k}: {why}")
+    streams = np.arange(n, dtype=np.int64) if streams is None else np.ascontiguousarray(streams, np.int64).reshape(-1)
+    if streams.shape != (n,) or (streams < 0).any():
+        raise ValueError(f"obca.noise: streams must be {n} ids >= 0")
+    seed, k0 = int(seed), int(k0)
+    if not (0 <= seed < 1 << 64 and 0 <= k0 < NOISE_K_MAX):
+        raise ValueError("obca.noise: seed a uint64 and 0 <= k0 < 2^31")
+    return par, streams, seed, k0
+
+
+def noise_tape(n, cap, par, streams=None, seed=0, k0=0):
+    """The disturbance rows k_plan_noise draws, host restatement with the same statements in the
+    same order: n x cap x 2 x 5, row [s][i] = bias + sigma * clip(z, +-trunc) with z the normals of
+    stream streams[s] (None: s) at step index k0 + i (`noise_normal`) under par (one noise row or
+    n).  A pure function of (seed, stream, step index): any row can be drawn alone."""
+    n, cap = int(n), int(cap)
+    par, streams, seed, k0 = noise_args(n, par, streams, seed, k0)
+    if k0 + cap > NOISE_K_MAX:
+        raise ValueError("obca.noise_tape: every step index below 2^31")
+    P = np.broadcast_to(par, (n, NOISE_PAR))
+    sigma, bias, trunc = P[:, 0:10].reshape(n, 2, NX), P[:, 10:20].reshape(n, 2, NX), P[:, 20][:, None, None]
+    out = np.zeros((n, cap, 2, NX))
+    for i in range(cap):
+        z = noise_normal(seed, streams, k0 + i)
+        z = np.where(trunc != 0.0, np.minimum(trunc, np.maximum(z, -trunc)), z)
+        out[:, i] = bias + sigma * z
+    return out
+
+
 def check_converge(bar, thres, min_dis):
     """`check_converge` (optimizer.py:225-235): the coupled constraints at the exchanged
     halfspaces and lamb_ij."""
@@ -854,6 +983,27 @@ class OBCABatch:
                                                     _lib.dptr(w), _lib.dptr(out)))
         return out
 
+    def noise_tape(self, n, cap, par, streams=None, seed=0, k0=0, raw=False):
+        """k_plan_noise on the call's own buffers (piadmm_obca_noise_tape): the disturbance rows
+        n x cap x 2 x 5 of the streams `streams` (None: 0 .. n-1) at step indices k0 .. k0 + cap - 1
+        under the noise rows par (one for all, or n), as `noise_tape` states them; with raw=True
+        also the generator's words, n x cap x 2 x 3 x 4 uint32 (`noise_raw`).  The library checks
+        the arguments."""
+        from . import _lib
+        n, cap = int(n), int(cap)
+        par = np.ascontiguousarray(np.asarray(par, np.float64).reshape(-1, NOISE_PAR))
+        if streams is not None:
+            streams = np.ascontiguousarray(streams, np.int64).reshape(-1)
+            assert streams.shape == (n,), streams.shape
+        tape = np.zeros((max(n, 0), max(cap, 0), 2, NX))
+        words = np.zeros((max(n, 0), max(cap, 0), 2, 3, 4), np.uint32) if raw else None
+        self._check(self._lib.piadmm_obca_noise_tape(
+            self._h, n, cap, _lib.dptr(par), par.shape[0],
+            None if streams is None else streams.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+            ctypes.c_uint64(int(seed)), int(k0), _lib.dptr(tape),
+            None if words is None else words.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))))
+        return (tape, words) if raw else tape
+
     def fleet_stats(self, clear, summary, iters=None, mask=None, edges=(0.0,), worst=1) -> "OBCAFleetStats":
         """The fleet statistics of the caller's arrays (piadmm_obca_fleet_stats: k_stats_fleet,
         k_stats_rows and k_stats_worst on the call's own buffers), as `fleet_stats_host` states them:
@@ -1003,12 +1153,20 @@ class OBCAPlanner:
     control of the stopping local solution, par, tape[s][k]) with k the steps since the attachment.
     par: one plant row or n (`feedback_row`; None: the nominal plant), tape: n x cap x 2 x 5
     disturbance rows or None.  `measure` overwrites init_state with states measured outside.
-    OBCADevicePlanner takes the same argument.  Not together with clock."""
+    OBCADevicePlanner takes the same argument.  Not together with clock.
+
+    noise: None, or dict(par=, streams=, seed=, k0=) on top of feedback: the disturbance of scenario
+    s at the step k since the feedback's attachment is tape[s][k] (if any) plus the row
+    `noise_tape` draws for stream streams[s] at step index k0 + k -- a pure function of (seed,
+    stream, step index), so no tape is kept.  `set_noise` / `clear_noise` attach and detach it; a
+    new `set_feedback` and `clear_feedback` drop it.  OBCADevicePlanner takes the same argument and
+    draws the same disturbances (k_plan_noise)."""
 
     def __init__(self, batch, n_scenarios, prob=1, t_step0=0, rho=1.0, min_dis=0.1, max_admm_iter=50,
                  primal_thres=0.01, dual_thres=0.01, round_decimals=4, start=1, update_lamb_ij=0, max_iter=60,
                  conv_thres=0.1, on_stage=None, max_x=150.0, max_y=20.0, r=1e4, q=1e5, x_bound=1000.0,
-                 mu_max=100000.0, g_max=1000.0, ref_traj=None, specs=None, dual=None, clock=None, feedback=None):
+                 mu_max=100000.0, g_max=1000.0, ref_traj=None, specs=None, dual=None, clock=None, feedback=None,
+                 noise=None):
         self.batch = batch
         self.n = int(n_scenarios)
         self.prob = [int(prob)] * self.n if np.isscalar(prob) else [int(p) for p in prob]
@@ -1046,19 +1204,40 @@ class OBCAPlanner:
             self.dual_S = [b["lamb_bar"].copy() for b in self.bar_prev]
             self.dual_D = [np.zeros((2, NT, 9)) for _ in range(self.n)]
         self.feedback = None
+        self.noise = None
         if feedback is not None:
             self.set_feedback(**feedback)
+        if noise is not None:
+            self.set_noise(**noise)
         self.record = OBCARunRecord()
         self.record.state_record.append(np.stack(self.init_state))
 
     def set_feedback(self, par=None, tape=None):
-        """Attach the plant (see the class): from the next step on a step closes through `propagate`."""
+        """Attach the plant (see the class): from the next step on a step closes through `propagate`.
+        The step count starts again, so an attached noise is dropped."""
         assert self.clock is None, "feedback and clock do not go together"
         self.feedback = feedback_args(self.n, dict(par=par, tape=tape))
         self._feedback_steps = 0
+        self.noise = None
 
     def clear_feedback(self):
         self.feedback = None
+        self.noise = None
+
+    def set_noise(self, par=None, streams=None, seed=0, k0=0):
+        """Attach the noise (see the class; feedback must be attached, as piadmm_obca_noise_plan
+        refuses without it)."""
+        from . import _lib
+        noise = noise_args(self.n, par, streams, seed, k0)
+        if self.feedback is None:
+            err = _lib.PiadmmError("obca_noise_plan: no feedback attached (obca_feedback_plan: the noise enters "
+                                   "through the plant step)")
+            err.code = _lib.E_STATE
+            raise err
+        self.noise = noise
+
+    def clear_noise(self):
+        self.noise = None
 
     def feedback_steps(self):
         """The steps closed since the attachment."""
@@ -1193,8 +1372,13 @@ class OBCAPlanner:
             # the vehicle instead of the prediction: from the closing step's init_state under the
             # stopping solution's first control (every scenario ran: no clock with feedback)
             par, tape = self.feedback
-            nxt = propagate(np.stack(x0_step), np.stack(U0), par,
-                            None if tape is None else tape[:, self._feedback_steps])
+            w = None if tape is None else tape[:, self._feedback_steps]
+            if self.noise is not None:
+                # the step's row of every stream, the tape's row in front
+                zpar, streams, seed, k0 = self.noise
+                wn = noise_tape(n, 1, zpar, streams, seed, k0 + self._feedback_steps)[:, 0]
+                w = wn if w is None else w + wn
+            nxt = propagate(np.stack(x0_step), np.stack(U0), par, w)
             self.init_state = [nxt[s] for s in range(n)]
             self._feedback_steps += 1
         self.on_stage("shift", dict(bar_prev=shift_in, X=X, iters=iters.copy()), dict(bar_next=self.bar_prev, init_state=self.init_state))
@@ -1665,13 +1849,20 @@ class OBCADevicePlanner:
     `measure(slots, states)` writes states measured outside over init_state
     (piadmm_obca_feedback_measure; any plan, no trace).  `run_traced` works with it unchanged: the
     trace's states and clearances are those of the states the vehicles reached.  Not together with
-    clock or the tenant calls."""
+    clock or the tenant calls.
+
+    With noise=dict(par=, streams=, seed=, k0=) on top of feedback the disturbance is drawn on the
+    device (piadmm_obca_noise_plan, k_plan_noise; `noise_tape` is the statement): scenario s at the
+    step k since the feedback's attachment gets the row of stream streams[s] (None: s) at step index
+    k0 + k, added behind the tape's row if there is a tape.  `set_noise` / `clear_noise` attach and
+    detach it; `set_feedback` and `clear_feedback` drop it.  A scenario is re-run alone from (seed,
+    its stream id, k0): a plan of the worst few with streams = their ids draws what they drew."""
 
     def __init__(self, batch, n_scenarios, prob=1, t_step0=0, rho=1.0, min_dis=0.1, max_admm_iter=50,
                  primal_thres=0.01, dual_thres=0.01, round_decimals=4, start=1, update_lamb_ij=0, max_iter=60,
                  conv_thres=0.1, on_stage=None, max_x=150.0, max_y=20.0, r=1e4, q=1e5, x_bound=1000.0,
                  mu_max=100000.0, g_max=1000.0, ref_traj=None, state=None, specs=None, dual=None, order=False,
-                 work_init=None, clock=None, feedback=None):
+                 work_init=None, clock=None, feedback=None, noise=None):
         from . import _lib
         self.batch = batch
         self._lib = batch._lib
@@ -1736,6 +1927,7 @@ class OBCADevicePlanner:
                                                           _lib.dptr(ref), _lib.dptr(self.par), _lib.dptr(state)))
         self.dual_par = None
         self._feedback = None
+        self._noise = None
         if dual is not None:
             self.set_dual(**dual)
         self.order = False
@@ -1748,24 +1940,50 @@ class OBCADevicePlanner:
             self.set_clock(None if clock is True else rows)
         if feedback is not None:
             self.set_feedback(**feedback)
+        if noise is not None:
+            self.set_noise(**noise)
         self.record = OBCARunRecord()
         self.record.state_record.append(np.stack(self.init_state))
 
     def set_feedback(self, par=None, tape=None):
         """Attach the plant (piadmm_obca_feedback_plan; a step boundary only, no clock): par one plant
         row or n rows (None: the nominal plant), tape n x cap x 2 x 5 disturbance rows or None.  A
-        second call replaces the first and starts its tape again."""
+        second call replaces the first and starts its tape again; an attached noise is dropped."""
         from . import _lib
         rows, tape = feedback_args(self.n, dict(par=par, tape=tape))
         self._check(self._lib.piadmm_obca_feedback_plan(self.batch._h, 1, None if par is None else _lib.dptr(rows),
                                                         rows.shape[0], _lib.dptr(tape),
                                                         0 if tape is None else tape.shape[1]))
         self._feedback = (rows, tape)
+        self._noise = None
 
     def clear_feedback(self):
-        """Detach the plant (a step boundary only): a step closes with init_state = X[1] again."""
+        """Detach the plant (a step boundary only): a step closes with init_state = X[1] again.  An
+        attached noise goes with it."""
         self._check(self._lib.piadmm_obca_feedback_plan(self.batch._h, 0, None, 0, None, 0))
         self._feedback = None
+        self._noise = None
+
+    def set_noise(self, par=None, streams=None, seed=0, k0=0):
+        """Attach the device-side noise (piadmm_obca_noise_plan; a step boundary only, feedback
+        attached): par one noise row or n rows (`noise_row`; None: the zero row), streams n stream ids
+        (None: 0 .. n-1), seed a uint64, k0 the step index of the feedback's step 0.  A second call
+        replaces the first.  The library checks the arguments."""
+        from . import _lib
+        rows = np.ascontiguousarray(np.asarray(noise_row() if par is None else par, np.float64).reshape(-1, NOISE_PAR))
+        if streams is not None:
+            streams = np.ascontiguousarray(streams, np.int64).reshape(-1)
+            assert streams.shape == (self.n,), streams.shape
+        self._check(self._lib.piadmm_obca_noise_plan(
+            self.batch._h, 1, _lib.dptr(rows), rows.shape[0],
+            None if streams is None else streams.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+            ctypes.c_uint64(int(seed)), int(k0)))
+        self._noise = (rows, streams, int(seed), int(k0))
+
+    def clear_noise(self):
+        """Detach the noise (a step boundary only): the tape alone, or nothing, disturbs the plant."""
+        self._check(self._lib.piadmm_obca_noise_plan(self.batch._h, 0, None, 0, None, 0, 0))
+        self._noise = None
 
     def feedback_steps(self):
         """The steps closed since the attachment (PLAN_GET FEEDBACK_STEPS)."""
@@ -2057,7 +2275,15 @@ class OBCADevicePlanner:
         return int(c[0]), int(c[1]), int(c[2])
 
     def get(self, what):
-        """One item of the resident plan (include/piadmm.h, piadmm_obca_plan_get), shaped."""
+        """One item of the resident plan (include/piadmm.h, piadmm_obca_plan_get), shaped: a name of
+        PLAN_GET or of NOISE_GET."""
+        if what in NOISE_GET:
+            code, dt = NOISE_GET[what]
+            shape = {"NOISE_PAR": (1 if self._noise is None else len(self._noise[0]), NOISE_PAR),
+                     "NOISE_STREAMS": (self.n,), "NOISE_SEED": (2,)}[what]
+            out = np.zeros(shape, dt)
+            self._check(self._lib.piadmm_obca_plan_get(self.batch._h, code, out.ctypes.data, out.nbytes))
+            return out
         code, dt = PLAN_GET[what]
         n, m = self.n, (self.counts()[0] if what != "COUNTS" else 0)
         rows = n if self.fleet else 1

@@ -874,6 +874,72 @@ int32_t piadmm_obca_feedback_plan(piadmm_obca_t h, int32_t mode,
 int32_t piadmm_obca_feedback_measure(piadmm_obca_t h, int32_t m, const int32_t* slots /* m, ascending */,
                                      const double* states /* m x 2 x 5 */);
 
+/* ---- device-side disturbance noise for the closed-loop plan -------------------------------------
+ * The tape of piadmm_obca_feedback_plan is the caller's: n x cap x 80 bytes generated, checked and
+ * uploaded, and a scenario's disturbance is a function of nothing the library knows.  The calls below
+ * draw it on the device from a counter-based generator: the disturbance row of a scenario at a step
+ * is a pure function of (seed, stream id, step index), the same in NumPy (piadmm.obca.noise_tape)
+ * and on the device, so a scenario can be re-run alone -- in another plan, handle or process -- from
+ * three integers.  Opt-in: without the attachment the plan issues exactly the launches it issued
+ * before.
+ *
+ * The statement.  Philox4x32-10 (Salmon, Moraes, Dror, Shaw, "Parallel random numbers: as easy as
+ * 1, 2, 3", SC'11): multipliers 0xD2511F53 and 0xCD9E8D57, key increments 0x9E3779B9 and 0xBB67AE85,
+ * ten rounds.  For vehicle v (0 / 1) of stream t (int64, 0 <= t < 2^63), step index k
+ * (0 <= k < 2^31) and call j (0, 1, 2):
+ *   counter = (k, 4 v + j, t & 0xffffffff, t >> 32),  key = (seed & 0xffffffff, seed >> 32)
+ *   (r0, r1, r2, r3) = philox4x32_10(counter, key)
+ *   u1 = (((r0 << 32 | r1) >> 12) + 0.5) 2^-52,  u2 = (((r2 << 32 | r3) >> 12) + 0.5) 2^-52    in (0, 1), exact
+ *   rad = sqrt(-2 log(u1)),  z[2 j] = rad cos(2 pi u2),  z[2 j + 1] = rad sin(2 pi u2)
+ * z[0 .. 4] are the vehicle's normals for (x, y, v, theta, delta), z[5] is discarded.  A noise row is
+ * PIADMM_OBCA_NOISE_PAR = 22 doubles:
+ *   sigma[2][5] (finite, >= 0), bias[2][5] (finite), trunc (0: none, else > 0: z is clipped to
+ *   +-trunc before it is scaled), one reserved zero
+ * and the disturbance is w[v][i] = bias[v][i] + sigma[v][i] z[i], product and sum kept apart (no
+ * contraction): sigma = 0 gives the bias bit for bit.  The integer part is exact everywhere; log, sqrt,
+ * cos and sin are the device's, so a device row equals the NumPy one to a few ulp, not bit for bit,
+ * and two device rows of the same (seed, t, k) are equal bit for bit.
+ *
+ * piadmm_obca_noise_tape runs k_plan_noise (one lane per vehicle, one grid row per step index) alone
+ * on the call's own device buffers; the handle's buffers and an open plan stay as they are.  It
+ * fills tape_out[s][i] (n x cap x 2 x 5) with the row of stream streams[s] (NULL: s) at step index
+ * k0 + i under par (`rows` = 1 row for every scenario, or n), and raw_out (n x cap x 2 x 3 x 4, may
+ * be NULL) with the generator's words.  Before any device call, PIADMM_E_ARG: 1 <= n <= 2^20,
+ * 0 <= cap <= 2^20, n x cap x 80 bytes below 2 GiB, rows 1 or n, every row valid ("obca_noise_tape:
+ * row k: ..."), streams >= 0, k0 >= 0 and k0 + cap <= 2^31.
+ *
+ * piadmm_obca_noise_plan, mode 1, attaches the generator to an open plan that has feedback attached:
+ * from then on piadmm_obca_plan_shift launches k_plan_noise in front of the unchanged
+ * k_plan_propagate, which reads the step's rows in the tape's place:
+ *   next = propagate(x0, u0, par[s], tape[s][k] + noise(seed, streams[s], k0 + k))
+ * with k the feedback's FEEDBACK_STEPS; the tape term comes first and is absent without a tape.  One
+ * more launch per MPC step and nothing else.  A second call replaces the first; mode 0 detaches (the
+ * other arguments are then ignored).  The same host checks as above (PIADMM_E_ARG, "obca_noise_plan:
+ * row k: ..."), then PIADMM_E_STATE: no open plan, no feedback attached, an MPC step open.  A refused
+ * call leaves the plan and an earlier noise attachment as they were.  The noise counts its steps by
+ * the feedback's: piadmm_obca_feedback_plan mode 0 detaches the noise too, and so does mode 1 (a new
+ * feedback attachment restarts FEEDBACK_STEPS) -- attach the noise again after it.  Without a tape
+ * nothing is ever "exhausted" (only the step index: k0 + k stays below 2^31, else PIADMM_E_STATE
+ * "noise step index exhausted"); with a tape its cap applies unchanged.
+ * piadmm_obca_plan_get gains the items
+ *   PIADMM_OBCA_NOISE_GET_PAR       rows x PIADMM_OBCA_NOISE_PAR fp64   the rows as attached
+ *   PIADMM_OBCA_NOISE_GET_STREAMS   n int64                             the stream ids (0 .. n-1 for NULL)
+ *   PIADMM_OBCA_NOISE_GET_SEED      2 uint64                            seed, k0
+ * (PIADMM_E_STATE without the attachment).  Out of scope: noise with a clock or the tenant calls
+ * (feedback refuses both), noise in piadmm_obca_feedback_measure, time-correlated noise. */
+#define PIADMM_OBCA_NOISE_PAR 22
+#define PIADMM_OBCA_NOISE_GET_PAR 36
+#define PIADMM_OBCA_NOISE_GET_STREAMS 37
+#define PIADMM_OBCA_NOISE_GET_SEED 38
+int32_t piadmm_obca_noise_tape(piadmm_obca_t h, int32_t n, int32_t cap,
+                               const double* par /* rows x PIADMM_OBCA_NOISE_PAR */, int32_t rows /* 1 or n */,
+                               const int64_t* streams /* n, may be NULL: 0 .. n-1 */, uint64_t seed, int32_t k0,
+                               double* tape_out /* n x cap x 2 x 5 */,
+                               uint32_t* raw_out /* n x cap x 2 x 3 x 4, may be NULL */);
+int32_t piadmm_obca_noise_plan(piadmm_obca_t h, int32_t mode, const double* par /* rows x PIADMM_OBCA_NOISE_PAR */,
+                               int32_t rows /* 1 or n */, const int64_t* streams /* n, may be NULL: 0 .. n-1 */,
+                               uint64_t seed, int32_t k0);
+
 /* ---- fleet risk statistics and the worst-case gather of a run record ---------------------------
  * A Monte-Carlo study over a traced fleet asks how many runs came closer than d, at which step the
  * fleet is most at risk, and which runs were the worst.  piadmm_obca_trace_get can only copy the

@@ -101,6 +101,24 @@
                    the two legs agree bit for bit.  No ratio is fixed in advance.  Written under the
                    key "stats" of the same JSON, the other keys kept.
 
+  --noise          instead of the above, in one process at --scenarios scenarios of
+                   obca.overtaking_fleet(--scenarios, seed=0) over --steps MPC steps from step 8 through
+                   run_traced, the repeats of the legs alternating after a warm-up step of each on its
+                   own plan, best of --repeats.  Setup, timed around the Python calls: (a) a tape from
+                   numpy.random.default_rng(0).normal (generation, then piadmm_obca_feedback_plan's
+                   finiteness check and upload of --scenarios x --steps x 80 bytes), (b)
+                   piadmm_obca_noise_plan (one noise row, the stream ids, seed and k0).  The --steps
+                   steps of both are timed too, but (a) and (b) draw different numbers and so run
+                   different solves: no per-step claim is made from them.  The per-step cost of the one
+                   extra launch is measured where the solves are the same: (p) the nominal plant under
+                   a zero tape (--feedback's leg (b): the launches of the parent commit) against (z)
+                   the same with a noise row of sigma = bias = 0 attached; (z)/(p) is reported next to
+                   the max/min spread of (p)'s own repeats.  Stand-alone: piadmm_obca_noise_tape at
+                   n = 65536, cap = 42 against the NumPy statement obca.noise_tape and against
+                   rng.normal of the same shape, with the largest deviation from the statement.  No
+                   ratio is fixed in advance.  Written under the key "noise" of the same JSON, the
+                   other keys kept.
+
 There is no CPU baseline on an equal footing (the C++ port of the local solver has no edge step);
 the edge launch is reported next to the local launch so the reader sees its share of an iterate.
 Writes one JSON (default profiles/obca_admm_bench.json) and prints it.
@@ -674,8 +692,110 @@ def stats_main(a):
     print(json.dumps(dict(stats=res)))
 
 
+def noise_main(a):
+    """--noise: setup and steps of (a) a NumPy tape through feedback_plan and (b) noise_plan; the extra
+    launch alone, (p) zero tape against (z) zero tape + zero noise; the stand-alone tape call."""
+    b = obca.OBCABatch(0)
+    n, K = a.scenarios, a.steps
+    specs, par = obca.overtaking_fleet(n, seed=0)
+    kw = dict(prob=[k % 2 for k in range(n)], t_step0=8, max_admm_iter=a.iterates - 1, specs=specs, **par)
+    sigma = (0.05, 0.05, 0.02, 0.002, 0.001)
+    row = obca.noise_row(sigma=sigma)
+    zero_tape = np.zeros((n, K, 2, obca.NX))
+
+    def attach_a(dp):
+        t0 = time.perf_counter()
+        tape = np.random.default_rng(0).normal(0.0, sigma, (n, K, 2, obca.NX))
+        t1 = time.perf_counter()
+        dp.set_feedback(tape=tape)
+        return dict(generate_ms=(t1 - t0) * 1e3, attach_ms=(time.perf_counter() - t1) * 1e3)
+
+    def attach_b(dp):
+        dp.set_feedback()
+        t0 = time.perf_counter()
+        dp.set_noise(par=row, seed=0)
+        return dict(generate_ms=0.0, attach_ms=(time.perf_counter() - t0) * 1e3)
+
+    def attach_p(dp):
+        dp.set_feedback(tape=zero_tape)
+        return {}
+
+    def attach_z(dp):
+        dp.set_feedback(tape=zero_tape)
+        dp.set_noise(par=obca.noise_row(), seed=0)
+        return {}
+    legs_at = dict(a_numpy_tape=attach_a, b_noise_plan=attach_b, p_zero_tape=attach_p, z_zero_tape_zero_noise=attach_z)
+    warm = obca.OBCADevicePlanner(b, n, **kw)
+    state = warm.get("STATE")                          # the seeded state, so the later plans skip the host seeding
+    for at in legs_at.values():
+        at(warm)
+        warm.step()
+    warm.close()
+    ms, setup, traces = {k: [] for k in legs_at}, {k: [] for k in legs_at}, {}
+    for _ in range(a.repeats):
+        for name, at in legs_at.items():
+            dp = obca.OBCADevicePlanner(b, n, state=state, **kw)
+            setup[name].append(at(dp))
+            t0 = time.perf_counter()
+            traces[name] = dp.run_traced(K, keep_lambda=False)
+            ms[name].append((time.perf_counter() - t0) * 1e3)
+            dp.close()
+    legs = {}
+    for name in legs_at:
+        tr = traces[name]
+        n_it, best = int(tr.iters.max(axis=1).sum()), min(ms[name])
+        legs[name] = dict(steps_run=int(tr.iters.shape[0]), admm_iterates=n_it, step_ms=best / max(tr.iters.shape[0], 1),
+                          total_ms_runs=ms[name], spread_max_over_min=max(ms[name]) / best,
+                          stop_iterate_histogram=np.bincount(tr.iters.ravel()).tolist())
+        if setup[name][0]:
+            legs[name].update(generate_ms=min(s["generate_ms"] for s in setup[name]),
+                              attach_ms=min(s["attach_ms"] for s in setup[name]),
+                              attach_ms_runs=[s["attach_ms"] for s in setup[name]])
+    legs["a_numpy_tape"]["bytes_uploaded"] = int(n * K * 2 * obca.NX * 8)
+    legs["b_noise_plan"]["bytes_uploaded"] = int(obca.NOISE_PAR * 8 + n * 8)
+    ratio = min(ms["z_zero_tape_zero_noise"]) / min(ms["p_zero_tape"])
+    same = bool(np.array_equal(traces["p_zero_tape"].states, traces["z_zero_tape_zero_noise"].states)
+                and np.array_equal(traces["p_zero_tape"].iters, traces["z_zero_tape_zero_noise"].iters))
+    # the stand-alone tape at the size of a whole study
+    n_big, cap = 65536, 42
+    unit = obca.noise_row(sigma=1.0)
+    b.noise_tape(1024, 2, unit)                         # warm-up
+    alone = dict(device=[], numpy_statement=[], rng_normal=[])
+    for _ in range(3):
+        t0 = time.perf_counter()
+        dev = b.noise_tape(n_big, cap, unit, seed=0)
+        alone["device"].append((time.perf_counter() - t0) * 1e3)
+        t0 = time.perf_counter()
+        np.random.default_rng(0).normal(0.0, 1.0, (n_big, cap, 2, obca.NX))
+        alone["rng_normal"].append((time.perf_counter() - t0) * 1e3)
+    t0 = time.perf_counter()
+    host = obca.noise_tape(n_big, cap, unit, seed=0)
+    alone["numpy_statement"].append((time.perf_counter() - t0) * 1e3)
+    res = dict(scenarios=n, steps=K, repeats=a.repeats, max_admm_iter=a.iterates - 1, sigma=list(sigma), legs=legs,
+               zero_noise_over_zero_tape=ratio, zero_tape_spread_max_over_min=legs["p_zero_tape"]["spread_max_over_min"],
+               ratio_exceeds_zero_tape_spread=bool(ratio > legs["p_zero_tape"]["spread_max_over_min"]),
+               zero_noise_run_equals_zero_tape_run=same,
+               extra_launch_ms_per_step=(min(ms["z_zero_tape_zero_noise"]) - min(ms["p_zero_tape"])) / K,
+               stand_alone=dict(n=n_big, cap=cap, bytes=int(dev.nbytes), device_ms=min(alone["device"]),
+                                device_ms_runs=alone["device"], numpy_statement_ms=alone["numpy_statement"][0],
+                                rng_normal_ms=min(alone["rng_normal"]), rng_normal_ms_runs=alone["rng_normal"],
+                                max_abs_deviation_from_statement=float(np.abs(dev - host).max()),
+                                max_abs_z=float(np.abs(host).max()), mean=float(dev.mean()), variance=float(dev.var())))
+    b.close()
+    out = {}
+    if os.path.exists(a.out):
+        with open(a.out) as f:
+            out = json.load(f)
+    out["noise"] = res
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+    print(json.dumps(dict(noise=res)))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--noise", action="store_true")
     ap.add_argument("--stats", action="store_true")
     ap.add_argument("--feedback", action="store_true")
     ap.add_argument("--migrate", action="store_true")
@@ -691,6 +811,8 @@ def main():
     ap.add_argument("--iterates", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "obca_admm_bench.json"))
     a = ap.parse_args()
+    if a.noise:
+        return noise_main(a)
     if a.stats:
         return stats_main(a)
     if a.feedback:
