@@ -1,6 +1,6 @@
 // piadmm_obca_handle.h -- the piadmm_obca_t handle, shared by the local batch
 // (csrc/piadmm_obca.hip), the edge step (csrc/piadmm_obca_edge.hip) and the device-resident
-// consensus loop (csrc/piadmm_obca_plan.hip).
+// consensus loop (csrc/piadmm_obca_plan.hip and the csrc/piadmm_obca_plan_*.hip units of its attachments).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -10,7 +10,7 @@
 
 #include "piadmm.h"
 
-struct piadmm_obca_plan_s;      // csrc/piadmm_obca_plan.hip
+struct piadmm_obca_plan_s;      // csrc/piadmm_obca_plan.h
 
 struct piadmm_obca_s {
   int device = 0;

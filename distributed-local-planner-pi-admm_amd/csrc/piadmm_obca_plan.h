@@ -1,0 +1,396 @@
+// piadmm_obca_plan.h -- what the units of the device-resident OBCA-ADMM consensus loop share
+// (internal, not installed): the layouts, the kernel-argument structs, the owners of device memory,
+// the plan and the small host helpers.  csrc/piadmm_obca_plan.hip holds the iterate and the shift and
+// describes the launch sequence; csrc/piadmm_obca_plan_{attach,trace,tenant,feedback}.hip hold the
+// attachments.  Every kernel is defined in one unit; there is no relocatable device code, a unit
+// launches another unit's kernel through the declaration here.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <numeric>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "pd_common.h"
+#include "piadmm.h"
+#include "piadmm_obca_handle.h"
+
+namespace obca_plan {
+
+constexpr int NT = 7;
+constexpr int PW = 4;                          // waves per workgroup
+constexpr int STATE = PIADMM_OBCA_PLAN_STATE;
+constexpr int REC = PIADMM_OBCA_REC, OUT = PIADMM_OBCA_OUT;
+constexpr int EREC = PIADMM_OBCA_EDGE_REC, EOUT = PIADMM_OBCA_EDGE_OUT;
+// the state's fields (include/piadmm.h)
+constexpr int S_ZB = 0, S_A = 126, S_B = 238, S_LB = 294, S_LIJ = 420, S_LX = 476, S_INIT = 546;
+static_assert(S_INIT + 10 == STATE, "state layout");
+// local record / output (csrc/piadmm_obca.hip), edge record / output (csrc/piadmm_obca_edge.hip)
+constexpr int R_INIT = 0, R_REF = 5, R_AO = 45, R_BO = 101, R_LIJ = 129, R_LB = 157, R_ZB = 220, R_PAR = 283;
+constexpr int O_X = 0, O_U = 40, O_LAM = 54;
+constexpr int E_LX = 0, E_LIJ = 70, E_LB = 126, E_PAR = 252;
+constexpr int EO_ZB = 126, EO_LBN = 252, EO_DRES = 532;
+constexpr int NCTRL = 28, NX = 80;
+
+constexpr double LENGTH = 3.5, WIDTH = 2.0;
+constexpr double AVG_DELAY = 0.05, VAR_DELAY = 0.025;
+
+// a parameter row (include/piadmm.h): the integers are stored as doubles, as the records do
+constexpr int TAB = PIADMM_OBCA_FLEET_PAR;
+constexpr int T_RHO = 0, T_MIN_DIS = 1, T_CONV = 2, T_MAX_X = 3, T_MAX_Y = 4, T_R = 5, T_Q = 6, T_XB = 7,
+              T_MU = 8, T_G = 9, T_ADMM = 10, T_SQP = 11, T_ROUND = 12, T_START = 13;
+static_assert(T_START < TAB, "row layout");
+
+constexpr int CT = 256;              // the one workgroup of k_plan_compact
+// a gains row of the dual law (include/piadmm.h)
+constexpr int DPAR = PIADMM_OBCA_DUAL_PAR;
+constexpr int G_KP = 0, G_KI = 1, G_SAT = 2, G_DGAIN = 3, G_WINDUP = 4;
+static_assert(G_WINDUP < DPAR, "gains row layout");
+constexpr int TSUM = 4;     // summary per scenario: min plain clearance, its row, min tightened clearance, sum of iterates
+constexpr int WIN = 2 * 8 * 5;       // a window: ref_s[v][c .. c + 7], the 80 doubles k_plan_pack_local reads
+// a plant row (include/piadmm.h): 8 doubles per vehicle, vehicle 0 first
+constexpr int FPAR = PIADMM_OBCA_FEEDBACK_PAR, FV = FPAR / 2;
+constexpr int F_METHOD = 0, F_NSUB = 1, F_LR = 2, F_LF = 3, F_GA = 4, F_GW = 5, F_AMAX = 6, F_WMAX = 7;
+constexpr int F_NSUB_MAX = 64;
+constexpr double PLANT_DT = 0.1, MAX_STEER = 0.6;
+static_assert(F_WMAX + 1 == FV && FV % 2 == 0, "plant row layout");
+// a noise row (include/piadmm.h): sigma[2][5], bias[2][5], trunc, one reserved zero
+constexpr int ZPAR = PIADMM_OBCA_NOISE_PAR;
+constexpr int Z_SIGMA = 0, Z_BIAS = 10, Z_TRUNC = 20, Z_RESERVED = 21;
+static_assert(Z_RESERVED + 1 == ZPAR, "noise row layout");
+
+// dst[0 .. len) = src[0 .. len) by the 64 lanes of a wave in strided passes: 16 bytes a lane where
+// both ends sit on a 16-byte boundary and len is even, 8 bytes a lane otherwise.  The pointers are
+// wave-uniform, so the choice is.
+__device__ __forceinline__ void copy_seg(double* dst, const double* src, int len, int lane) {
+  const bool wide = ((((uintptr_t)dst) | ((uintptr_t)src)) & 15u) == 0 && (len & 1) == 0;
+  if (wide) {
+    double2* d2 = reinterpret_cast<double2*>(dst);
+    const double2* s2 = reinterpret_cast<const double2*>(src);
+    for (int i = lane; i < len / 2; i += 64) d2[i] = s2[i];
+  } else {
+    for (int i = lane; i < len; i += 64) dst[i] = src[i];
+  }
+}
+
+// where the arrays of one k_plan_propagate launch sit, all indexed by scenario: the strides in
+// doubles per scenario; the vehicle's state row at + v * 5, its controls a and omega at
+// ctrl + v * ctrl_v and + ctrl_w behind it, its plant row at + v * 8 (par_s = 0: one shared row),
+// its disturbance row at + v * 5 (w = nullptr: none), its result at out + s * 10 + v * 5
+struct plant_io {
+  const double *x0, *ctrl, *par, *w;
+  double* out;
+  long long x0_s, w_s;
+  int ctrl_s, ctrl_v, ctrl_w, par_s;
+};
+
+// where the arrays of one k_plan_noise launch sit, indexed by scenario: par the noise rows (par_s =
+// 0: one shared row), streams the stream ids (nullptr: the scenario's number), tape the rows added
+// in front (nullptr: none), out the result, raw the Philox words (nullptr: not kept); the strides
+// in elements per scenario, and per step index (blockIdx.y) 10 doubles of tape and out and 24 words
+// of raw; k = the step index of blockIdx.y = 0
+struct noise_io {
+  const double *par, *tape;
+  const long long* streams;
+  double* out;
+  uint32_t* raw;
+  long long tape_s, out_s, raw_s;
+  uint32_t seed_lo, seed_hi, k;
+  int par_s;
+};
+
+// The kernels launched from a unit other than their own (the comments are at the definitions).
+// csrc/piadmm_obca_plan.hip
+__global__ void __launch_bounds__(CT) k_plan_compact(const int* __restrict__ active, const int* __restrict__ keep,
+                                                     int n_act, int* __restrict__ next, int* __restrict__ count);
+__global__ void __launch_bounds__(64) k_plan_shift_list(const int* __restrict__ list, int m,
+                                                        double* __restrict__ bar, double* __restrict__ barp,
+                                                        const double* __restrict__ X, double* __restrict__ lamb,
+                                                        double* __restrict__ ctrlp);
+// csrc/piadmm_obca_plan_attach.hip
+__global__ void __launch_bounds__(64 * PW) k_plan_dual_pi(const int* __restrict__ active, int n_act,
+                                                          const double* __restrict__ erecs,
+                                                          double* __restrict__ eout, const int* __restrict__ eist,
+                                                          const double* __restrict__ gains, int g_stride,
+                                                          double* __restrict__ S, double* __restrict__ D,
+                                                          double* __restrict__ Sp, double* __restrict__ Dp);
+__global__ void __launch_bounds__(64) k_plan_dual_shift(int n, double* __restrict__ S, double* __restrict__ D,
+                                                        double* __restrict__ Sp, double* __restrict__ Dp);
+__global__ void __launch_bounds__(64 * PW) k_plan_work(const int* __restrict__ active, int n_act,
+                                                       const int* __restrict__ list, const int* __restrict__ eist,
+                                                       int* __restrict__ work);
+__global__ void __launch_bounds__(64 * PW) k_plan_order(const int* __restrict__ list_in,
+                                                        const int* __restrict__ count, int m,
+                                                        const int* __restrict__ work, int* __restrict__ list_out);
+// csrc/piadmm_obca_plan_feedback.hip
+__global__ void __launch_bounds__(64 * PW) k_plan_propagate(const int* __restrict__ list, int m, plant_io io);
+__global__ void __launch_bounds__(64 * PW) k_plan_set_init(const int* __restrict__ list, int m,
+                                                           const double* __restrict__ states,
+                                                           double* __restrict__ bar, double* __restrict__ barp);
+__global__ void __launch_bounds__(64 * PW) k_plan_noise(const int* __restrict__ list, int m, noise_io io);
+
+// ---------------------------------------------------------------------------------------------
+// The host side
+// ---------------------------------------------------------------------------------------------
+inline int pfail(piadmm_obca_t h, int code, const std::string& msg) {
+  if (h) h->err = msg;
+  return code;
+}
+#define PHIP(h, call)                                                                  \
+  do {                                                                                 \
+    hipError_t _e = (call);                                                            \
+    if (_e != hipSuccess) return pfail(h, PIADMM_E_HIP, std::string(#call ": ") + hipGetErrorString(_e)); \
+  } while (0)
+
+// The zero fill is done when this returns: hipMemset of device memory does not wait, and the handle's
+// stream does not wait for the null stream, so the fill could otherwise land after a kernel's writes.
+template <typename T>
+int dalloc(piadmm_obca_t h, T** p, size_t count, bool zero) {
+  PHIP(h, hipMalloc(p, count * sizeof(T)));
+  if (zero) PHIP(h, hipMemset(*p, 0, count * sizeof(T)));
+  if (zero) PHIP(h, hipStreamSynchronize(nullptr));
+  return 0;
+}
+
+// The owner of one hipMalloc'ed array (Pinned: of one hipHostMalloc'ed): move-only, freed when it
+// goes.  It converts to the pointer, so a launch or a copy names it as it would the raw pointer.
+// Whoever lets one go while the stream may still use it synchronises the stream first.
+template <typename T, bool Pinned = false>
+class dev_buf {
+ public:
+  dev_buf() = default;
+  dev_buf(dev_buf&& o) noexcept : p_(std::exchange(o.p_, nullptr)) {}
+  dev_buf& operator=(dev_buf&& o) noexcept {
+    if (this != &o) {
+      release();
+      p_ = std::exchange(o.p_, nullptr);
+    }
+    return *this;
+  }
+  ~dev_buf() { release(); }
+  // the project's error code, h->err set; the array is owned even when the memset fails
+  int alloc(piadmm_obca_t h, size_t count, bool zero) {
+    release();
+    if constexpr (Pinned) {
+      PHIP(h, hipHostMalloc(reinterpret_cast<void**>(&p_), count * sizeof(T)));
+      return 0;
+    } else {
+      return dalloc(h, &p_, count, zero);
+    }
+  }
+  // the bare allocation, for a caller that words the failure itself
+  hipError_t make(size_t count) {
+    release();
+    return hipMalloc(&p_, count * sizeof(T));
+  }
+  T* get() const { return p_; }
+  operator T*() const { return p_; }
+
+ private:
+  void release() {
+    if (p_) (void)(Pinned ? hipHostFree(p_) : hipFree(p_));
+    p_ = nullptr;
+  }
+  T* p_ = nullptr;
+};
+
+// The device arrays of one stand-alone call, on the stack: neither the handle's local and edge
+// buffers nor an open plan is touched.  After a failed take every later one hands out nullptr and
+// rc keeps the first failure, so a call takes all its arrays and asks once.  When the call leaves,
+// on whichever path, the stream is synchronised and then the arrays are freed.
+class scratch {
+ public:
+  explicit scratch(piadmm_obca_t h) : h_(h) {}
+  scratch(const scratch&) = delete;
+  scratch& operator=(const scratch&) = delete;
+  ~scratch() {
+    (void)hipStreamSynchronize(h_->stream);
+    for (void* q : held_) (void)hipFree(q);
+  }
+  template <typename T>
+  T* take(size_t count, bool zero) {
+    T* p = nullptr;
+    if (rc) return nullptr;
+    rc = dalloc(h_, &p, count, zero);
+    if (p) held_.push_back(p);
+    return p;
+  }
+  int rc = 0;
+
+ private:
+  piadmm_obca_t h_;
+  std::vector<void*> held_;
+};
+
+}  // namespace obca_plan
+
+// The plan.  Every array is owned: detaching a feature is assigning a fresh one of its struct
+// (p->tr = {}), and an attach builds its struct in a local and moves it in once it is complete, so
+// a failure on the way releases the local and leaves the attached one as it was.
+struct piadmm_obca_plan_s {
+  template <typename T>
+  using dbuf = obca_plan::dev_buf<T>;
+  piadmm_obca_plan_cfg_t cfg{};
+  bool open = false;
+  int n = 0, t_step = 0, i_iter = 0, n_act = 0, n_last = 0, cur = 0;
+  // the parameter rows and the references: rows = 1 with stride 0 (piadmm_obca_plan_begin) or
+  // rows = n (piadmm_obca_fleet_begin); max_iter_all = the largest max_admm_iter of the rows
+  int tab_rows = 0, ref_rows = 0, tab_stride = 0, ref_stride = 0, max_iter_all = 0;
+  double sigd = 0.0;
+  dbuf<double> bar, barp, ctrl, ctrlp, X, primal, dual, pth, dth, ref, lamb, tab;
+  dbuf<int> iters, stop, conv, prob, act[2], keep, count, mask;
+  obca_plan::dev_buf<int, true> h_count;        // pinned: the 4 bytes read back per iterate
+  // the run record (piadmm_obca_trace_begin): rows = MPC steps recorded, row-major over steps.
+  // states / clear hold cap + 1 rows (row 0: where the trace was attached), the rest cap.
+  struct trace_s {
+    bool on = false;
+    int cap = 0, rows = 0, flags = 0;
+    dbuf<double> states, clear, primal, dual, lamb, summary;
+    dbuf<int> iters, mask;
+  } tr;
+  // the PI anti-windup dual law (piadmm_obca_dual_plan): rows = 1 with stride 0 or n gains rows;
+  // the integrator S, D and the previous iterate's copy of each, n x 126
+  struct dual_s {
+    bool on = false;
+    int rows = 0, stride = 0;
+    dbuf<double> par, S, D, Sp, Dp;
+  } du;
+  // the longest-first order (piadmm_obca_order_plan): work = (Q, I) per scenario, n x 2; tmp = the
+  // unsorted list k_plan_compact / k_plan_shift write and k_plan_order reads, n ints
+  struct order_s {
+    bool on = false;
+    dbuf<int> work, tmp;
+  } ord;
+  // the per-scenario clocks (piadmm_obca_clock_plan): clk = (c, len, alive) per scenario, n x 3, and
+  // `host` its mirror; win = the reference windows, n x 80; flag[cur] = the alive flags (the next
+  // tick's `ran`), flag[1 - cur] the ones the next tick writes; list = the n_list scenarios alive
+  // when the open step opened, ascending (the active lists are overwritten as the step iterates);
+  // ident = 0 .. n - 1, the list k_plan_compact filters by the flags
+  struct clock_s {
+    bool on = false;
+    int cur = 0, n_list = 0;
+    dbuf<int> clk, flag[2], list, ident;
+    dbuf<double> win;
+    std::vector<int> host;
+  } ck;
+  std::vector<int> admm_rows;    // max_admm_iter of every parameter row (max_iter_all is their maximum)
+  // the closed-loop feedback (piadmm_obca_feedback_plan): rows = 1 with stride 0 or n plant rows; tape
+  // = cap disturbance rows per scenario (nullptr: none), n x cap x 10; steps = the shifts since the
+  // attachment (the tape row the next shift adds); next = the states the plant reached, n x 10
+  struct feedback_s {
+    bool on = false;
+    int rows = 0, stride = 0, cap = 0, steps = 0;
+    dbuf<double> par, tape, next;
+  } fb;
+  // the device-side noise on top of the feedback (piadmm_obca_noise_plan): rows = 1 with stride 0 or n
+  // noise rows; streams = the stream id of every scenario; wbuf = the disturbance rows of the step
+  // that closes, n x 10, which k_plan_noise writes and k_plan_propagate reads; the step index of a
+  // shift is k0 + fb.steps
+  struct noise_s {
+    bool on = false;
+    int rows = 0, stride = 0, k0 = 0;
+    uint64_t seed = 0;
+    dbuf<double> par, wbuf;
+    dbuf<long long> streams;
+  } nz;
+  // the staging buffer of piadmm_obca_tenant_export / _import: the records, then the slot list; grown on demand
+  struct stage_s {
+    dbuf<char> buf;
+    size_t cap = 0;
+  } stg;
+};
+
+namespace obca_plan {
+
+inline int open_plan(piadmm_obca_t h, piadmm_obca_plan_s** out, const char* who) {
+  if (!h) return PIADMM_E_ARG;
+  if (!h->plan || !h->plan->open) return pfail(h, PIADMM_E_STATE, std::string(who) + ": no open plan (obca_plan_begin)");
+  *out = h->plan;
+  return 0;
+}
+inline int open_trace(piadmm_obca_t h, piadmm_obca_plan_s** out, const char* who) {
+  if (int rc = open_plan(h, out, who)) return rc;
+  if (!(*out)->tr.on) return pfail(h, PIADMM_E_STATE, std::string(who) + ": no trace attached (obca_trace_begin)");
+  return 0;
+}
+
+inline std::vector<int> identity_list(size_t n) {      // 0 .. n - 1
+  std::vector<int> v(n);
+  std::iota(v.begin(), v.end(), 0);
+  return v;
+}
+inline int blocks_for(int waves) { return (waves + PW - 1) / PW; }
+// workgroups of 64 * PW lanes for a kernel that runs one lane per item
+inline int lane_blocks(int lanes) { return (lanes + 64 * PW - 1) / (64 * PW); }
+// true when the attached feedback has a tape and the next `steps` shifts do not fit what is left of it
+inline bool feedback_exhausted(const piadmm_obca_plan_s* p, int64_t steps) {
+  return p->fb.on && p->fb.tape && (int64_t)p->fb.steps + steps > p->fb.cap;
+}
+// true when the attached noise would pass step index 2^31 - 1 within the next `steps` shifts
+inline bool noise_exhausted(const piadmm_obca_plan_s* p, int64_t steps) {
+  return p->nz.on && (int64_t)p->nz.k0 + p->fb.steps + steps > ((int64_t)1 << 31);
+}
+
+// The checks more than one call makes, each worded once; `who` is the call's name.
+// list[0 .. m) (`item`: what the call names it) holds distinct scenarios below n
+inline int slots_check(piadmm_obca_t h, const std::string& who, const char* item, const int32_t* list, int m, int n) {
+  std::vector<char> seen((size_t)n, 0);
+  for (int k = 0; k < m; ++k) {
+    if (list[k] < 0 || list[k] >= n || seen[(size_t)list[k]])
+      return pfail(h, PIADMM_E_ARG, who + ": " + item + "[" + std::to_string(k) + "] must be a scenario below n, listed once");
+    seen[(size_t)list[k]] = 1;
+  }
+  return 0;
+}
+// m, the pointers and the slots of an export, an import or a gather
+inline int tenant_slots_check(piadmm_obca_t h, const piadmm_obca_plan_s* p, int m, const int32_t* slots,
+                              const void* blob, const std::string& who) {
+  if (m < 1 || m > p->n) return pfail(h, PIADMM_E_ARG, who + ": 1 <= m <= n_scenarios");
+  if (!slots || !blob) return pfail(h, PIADMM_E_ARG, who + ": null argument (slots, blob)");
+  return slots_check(h, who, "slots", slots, m, p->n);
+}
+inline int prob_check(piadmm_obca_t h, const std::string& who, const int32_t* prob, int k) {
+  if (prob[k] != 0 && prob[k] != 1) return pfail(h, PIADMM_E_ARG, who + ": prob[" + std::to_string(k) + "] must be 0 or 1");
+  return 0;
+}
+inline int rows_check(piadmm_obca_t h, const std::string& who, int rows, int n) {
+  if (rows != 1 && rows != n) return pfail(h, PIADMM_E_ARG, who + ": rows must be 1 or n (" + std::to_string(n) + ")");
+  return 0;
+}
+// The tail of a _get call: item `what` is `want` bytes at src, on the host (`host`) or on the device.
+inline int get_finish(piadmm_obca_t h, const std::string& who, int what, const void* src, bool host, int64_t want,
+                      void* out, int64_t bytes) {
+  if (bytes != want)
+    return pfail(h, PIADMM_E_ARG, who + ": item " + std::to_string(what) + " is " + std::to_string(want) +
+                 " bytes, not " + std::to_string(bytes));
+  if (want == 0) return 0;
+  if (!out) return pfail(h, PIADMM_E_ARG, who + ": out");
+  if (host) {
+    std::memcpy(out, src, (size_t)want);
+    return 0;
+  }
+  PHIP(h, hipSetDevice(h->device));
+  PHIP(h, hipMemcpyAsync(out, src, (size_t)want, hipMemcpyDeviceToHost, h->stream));
+  PHIP(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// csrc/piadmm_obca_plan.hip
+const char* row_check(const double* row);
+int stage_ensure(piadmm_obca_t h, piadmm_obca_plan_s* p, size_t bytes, int m);
+// csrc/piadmm_obca_plan_attach.hip
+const char* dual_row_check(const double* row);
+int clock_lists(piadmm_obca_t h, piadmm_obca_plan_s* p, const int* ran, int dst, int n_alive);
+int clock_shift(piadmm_obca_t h, piadmm_obca_plan_s* p);
+int clock_relist(piadmm_obca_t h, piadmm_obca_plan_s* p);
+// csrc/piadmm_obca_plan_trace.hip
+int trace_append(piadmm_obca_t h, piadmm_obca_plan_s* p, int row);
+
+}  // namespace obca_plan

@@ -1,0 +1,512 @@
+// piadmm_obca_plan_feedback.hip -- the closed loop of the device-resident OBCA-ADMM plan: the plant
+// step, the measurement and the device-side noise (gfx950).  csrc/piadmm_obca_plan.hip describes the
+// launch sequence; of it:
+// With the feedback attached (piadmm_obca_feedback_plan) piadmm_obca_plan_shift runs k_plan_propagate
+// before k_plan_shift (the plant step from the closing step's init_state and first control) and
+// k_plan_set_init after it (the state the vehicle reached over init_state of both copies); without
+// it neither is launched.  These two run one lane per vehicle, not one wave per item.
+// With the noise attached on top (piadmm_obca_noise_plan) k_plan_noise runs in front of
+// k_plan_propagate and writes the step's disturbance rows, which that kernel reads in the tape's
+// place; without it k_plan_noise is not launched.  One lane per vehicle as well.
+
+#include "piadmm_obca_plan.h"
+
+namespace obca_plan {
+
+// ---------------------------------------------------------------------------------------------
+// Closed-loop feedback (piadmm_obca_feedback_plan / _measure, piadmm_obca_propagate): the plant step
+// between two MPC steps and the scatter of states over init_state.  Opt-in: without the attachment
+// neither kernel is launched by piadmm_obca_plan_shift.
+// ---------------------------------------------------------------------------------------------
+
+// One plant step of one vehicle, all in registers: x (5) <- F(x, (a, om)) under the vehicle's row P
+// (8), without the disturbance.  n_sub substeps of DT / n_sub; a substep is 1 stage (Euler) or 4
+// (classical RK4) of the one right-hand side below, the stage loop kept rolled so that the libm
+// calls are inlined once; then delta is clipped.  n_sub is clamped to its range, so the loop is
+// bounded whatever the row holds.  piadmm.obca.propagate is the same statements on the host;
+// products and sums are kept apart (no contraction).  The body of both entry points of
+// k_plan_propagate: the stand-alone call and the in-plan step give the same bits.
+__device__ __forceinline__ void plant_step(double x[5], double a, double om, const double P[FV]) {
+#pragma clang fp contract(off)
+  const double lr = P[F_LR], lf = P[F_LF];
+  const double a_eff = fmin(P[F_AMAX], fmax(P[F_GA] * a, -P[F_AMAX]));
+  const double w_eff = fmin(P[F_WMAX], fmax(P[F_GW] * om, -P[F_WMAX]));
+  const int n_sub = min(max((int)P[F_NSUB], 1), F_NSUB_MAX);
+  const int n_stage = P[F_METHOD] != 0.0 ? 4 : 1;
+  const double hs = PLANT_DT / (double)n_sub;
+  const double scale = n_stage == 4 ? hs / 6.0 : hs;
+#pragma unroll 1
+  for (int sub = 0; sub < n_sub; ++sub) {
+    double xs[5], acc[5];
+#pragma unroll
+    for (int i = 0; i < 5; ++i) { xs[i] = x[i]; acc[i] = 0.0; }
+#pragma unroll 1
+    for (int st = 0; st < n_stage; ++st) {
+      const double beta = atan(lr * tan(xs[4]) / (lr + lf));
+      const double ph = xs[3] + beta;
+      const double f[5] = {xs[2] * cos(ph), xs[2] * sin(ph), a_eff, xs[2] / lr * sin(beta), w_eff};
+      const double wgt = (st == 1 || st == 2) ? 2.0 : 1.0;
+      const double c = st < 2 ? 0.5 * hs : hs;          // the next stage's point: x + c f
+#pragma unroll
+      for (int i = 0; i < 5; ++i) {
+        acc[i] = st == 0 ? f[i] : acc[i] + wgt * f[i];
+        xs[i] = x[i] + c * f[i];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 5; ++i) x[i] = x[i] + scale * acc[i];
+    x[4] = fmin(MAX_STEER, fmax(x[4], -MAX_STEER));
+  }
+}
+
+
+// One lane per vehicle: lane g of the grid = vehicle g & 1 of entry g >> 1 of `list` (nullptr: of
+// scenario g >> 1), 2 m lanes.  No LDS; the state, the stage point and the RK4 sum stay in
+// registers over the runtime substep loop.  The plant row is 64 bytes on a 64-byte boundary (the
+// base comes from hipMalloc): four 16-byte loads.  The 5-wide rows (state, disturbance, result) are
+// 40 bytes, only 8-byte aligned for the odd vehicle and inside the plan's state: five 8-byte
+// accesses each; neighbouring lanes hold neighbouring rows, so a wave's accesses fall into the
+// same few cache lines.
+__global__ void __launch_bounds__(64 * PW) k_plan_propagate(const int* __restrict__ list, int m, plant_io io) {
+  const int g = blockIdx.x * (64 * PW) + threadIdx.x;
+  if (g >= 2 * m) return;
+  const int v = g & 1;
+  const size_t s = (size_t)(list ? list[g >> 1] : (g >> 1));
+  const double2* P2 = reinterpret_cast<const double2*>(io.par + s * io.par_s + v * FV);
+  double P[FV];
+#pragma unroll
+  for (int i = 0; i < FV / 2; ++i) {
+    const double2 q = P2[i];
+    P[2 * i] = q.x;
+    P[2 * i + 1] = q.y;
+  }
+  const double* xin = io.x0 + s * io.x0_s + v * 5;
+  const double* cu = io.ctrl + s * io.ctrl_s + v * io.ctrl_v;
+  double x[5];
+#pragma unroll
+  for (int i = 0; i < 5; ++i) x[i] = xin[i];
+  plant_step(x, cu[0], cu[io.ctrl_w], P);
+  double* o = io.out + s * 10 + v * 5;
+  if (io.w) {
+#pragma clang fp contract(off)
+    const double* wr = io.w + s * io.w_s + v * 5;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) o[i] = x[i] + wr[i];
+  } else {
+#pragma unroll
+    for (int i = 0; i < 5; ++i) o[i] = x[i];
+  }
+}
+
+// One lane per vehicle, 2 m lanes: init_state of both state copies of scenario list[k] (nullptr: of
+// scenario k) = states[k] (m x 2 x 5).  Pure copies; nothing else of the state is written.
+__global__ void __launch_bounds__(64 * PW) k_plan_set_init(const int* __restrict__ list, int m,
+                                                           const double* __restrict__ states,
+                                                           double* __restrict__ bar, double* __restrict__ barp) {
+  const int g = blockIdx.x * (64 * PW) + threadIdx.x;
+  if (g >= 2 * m) return;
+  const int k = g >> 1, v = g & 1;
+  const size_t s = (size_t)(list ? list[k] : k);
+  const double* src = states + (size_t)k * 10 + v * 5;
+  const size_t at = s * STATE + S_INIT + v * 5;
+#pragma unroll
+  for (int i = 0; i < 5; ++i) {
+    const double val = src[i];
+    bar[at + i] = val;
+    barp[at + i] = val;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Device-side disturbance noise (piadmm_obca_noise_plan / piadmm_obca_noise_tape): the disturbance
+// row of stream t at step k as a pure function of (seed, t, k).  Opt-in: without the attachment
+// piadmm_obca_plan_shift does not launch k_plan_noise.
+// ---------------------------------------------------------------------------------------------
+
+// Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11):
+// c the counter's four words, replaced by the result; (k0, k1) the key.  Ten rounds of two
+// 32 x 32 -> 64 products (the high halves by __umulhi), the key bumped between rounds.  All 32-bit.
+__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
+  constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t hi0 = __umulhi(M0, c[0]), lo0 = M0 * c[0];
+    const uint32_t hi1 = __umulhi(M1, c[2]), lo1 = M1 * c[2];
+    c[0] = hi1 ^ c[1] ^ k0;
+    c[1] = lo1;
+    c[2] = hi0 ^ c[3] ^ k1;
+    c[3] = lo0;
+    k0 += W0;
+    k1 += W1;
+  }
+}
+
+// The five disturbances of vehicle v of stream t at step k under the row's sigma S, bias B and
+// trunc: three Philox calls at counter (k, 4 v + j, t low, t high), each giving two uniforms in
+// (0, 1) on 52 bits and by Box-Muller two normals; the sixth normal is discarded.  raw (12 words,
+// or nullptr) receives the calls' words.  piadmm.obca.noise_tape is the same statements on the
+// host; products and sums are kept apart (no contraction), so sigma = 0 gives the bias bit for bit.
+// The body of k_plan_noise for the in-plan step and for the stand-alone tape: the same bits.
+__device__ __forceinline__ void noise_draw(uint32_t seed_lo, uint32_t seed_hi, uint32_t t_lo, uint32_t t_hi,
+                                           uint32_t k, int v, const double S[5], const double B[5], double trunc,
+                                           double w[5], uint32_t* raw) {
+#pragma clang fp contract(off)
+  double z[6];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    uint32_t c[4] = {k, (uint32_t)(4 * v + j), t_lo, t_hi};
+    philox4x32_10(c, seed_lo, seed_hi);
+    if (raw) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) raw[4 * j + q] = c[q];
+    }
+    const unsigned long long a = ((unsigned long long)c[0] << 32) | c[1];
+    const unsigned long long b = ((unsigned long long)c[2] << 32) | c[3];
+    const double u1 = ((double)(a >> 12) + 0.5) * 0x1p-52;
+    const double u2 = ((double)(b >> 12) + 0.5) * 0x1p-52;
+    const double rad = sqrt(-2.0 * log(u1));
+    const double ang = 6.283185307179586 * u2;
+    z[2 * j] = rad * cos(ang);
+    z[2 * j + 1] = rad * sin(ang);
+  }
+#pragma unroll
+  for (int i = 0; i < 5; ++i) {
+    double zi = z[i];
+    if (trunc != 0.0) zi = fmin(trunc, fmax(zi, -trunc));
+    w[i] = B[i] + S[i] * zi;
+  }
+}
+
+
+// One lane per vehicle: lane g of a grid row = vehicle g & 1 of entry g >> 1 of `list` (nullptr: of
+// scenario g >> 1), 2 m lanes; grid row y is step index k + y (the in-plan step launches one row).
+// No LDS, no atomics, nothing shared between lanes: the counter is the lane's own, the arithmetic
+// 32-bit integer and fp64 in registers.  The lane's 11 parameters are 8-byte loads from the row;
+// its five results 8-byte stores, neighbouring lanes to neighbouring rows as in k_plan_propagate.
+// With a tape the written value is tape + w, the tape term first.
+__global__ void __launch_bounds__(64 * PW) k_plan_noise(const int* __restrict__ list, int m, noise_io io) {
+  const int g = blockIdx.x * (64 * PW) + threadIdx.x;
+  if (g >= 2 * m) return;
+  const int v = g & 1;
+  const size_t s = (size_t)(list ? list[g >> 1] : (g >> 1));
+  const size_t y = blockIdx.y;
+  const double* P = io.par + s * io.par_s;
+  double S[5], B[5];
+#pragma unroll
+  for (int i = 0; i < 5; ++i) {
+    S[i] = P[Z_SIGMA + v * 5 + i];
+    B[i] = P[Z_BIAS + v * 5 + i];
+  }
+  const unsigned long long t = io.streams ? (unsigned long long)io.streams[s] : (unsigned long long)s;
+  uint32_t words[12];
+  double w[5];
+  noise_draw(io.seed_lo, io.seed_hi, (uint32_t)t, (uint32_t)(t >> 32), io.k + (uint32_t)y, v, S, B, P[Z_TRUNC], w,
+             io.raw ? words : nullptr);
+  double* o = io.out + s * io.out_s + y * 10 + v * 5;
+  if (io.tape) {
+#pragma clang fp contract(off)
+    const double* tr = io.tape + s * io.tape_s + y * 10 + v * 5;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) o[i] = tr[i] + w[i];
+  } else {
+#pragma unroll
+    for (int i = 0; i < 5; ++i) o[i] = w[i];
+  }
+  if (io.raw) {
+    uint32_t* r = io.raw + s * io.raw_s + y * 24 + v * 12;
+#pragma unroll
+    for (int q = 0; q < 12; ++q) r[q] = words[q];
+  }
+}
+
+}  // namespace obca_plan
+
+using namespace obca_plan;
+
+namespace {
+// One plant row of the feedback (both vehicles): nullptr when it is good, else what is wrong with it.
+const char* feedback_row_check(const double* row) {
+  for (int i = 0; i < FPAR; ++i)
+    if (!std::isfinite(row[i])) return "every entry finite";
+  for (int v = 0; v < 2; ++v) {
+    const double* P = row + v * FV;
+    if (P[F_METHOD] != 0.0 && P[F_METHOD] != 1.0) return "method 0 (Euler) or 1 (RK4)";
+    if (!(P[F_NSUB] >= 1.0 && P[F_NSUB] <= (double)F_NSUB_MAX && P[F_NSUB] == std::floor(P[F_NSUB])))
+      return "1 <= n_sub <= 64, an integer";
+    if (!(P[F_LR] > 0.0) || !(P[F_LF] > 0.0)) return "lr, lf > 0";
+    if (!(P[F_AMAX] > 0.0) || !(P[F_WMAX] > 0.0)) return "a_max, w_max > 0";
+  }
+  return nullptr;
+}
+
+// the nominal plant: the NLP's own transition
+void feedback_row_nominal(double* row) {
+  for (int v = 0; v < 2; ++v) {
+    double* P = row + v * FV;
+    P[F_METHOD] = 0.0;  P[F_NSUB] = 1.0;  P[F_LR] = 1.0;  P[F_LF] = 1.5;
+    P[F_GA] = 1.0;  P[F_GW] = 1.0;  P[F_AMAX] = 5.0;  P[F_WMAX] = 20.0;
+  }
+}
+
+// the first entry of a[0 .. count) that is not finite, or -1
+int64_t first_not_finite(const double* a, size_t count) {
+  for (size_t i = 0; i < count; ++i)
+    if (!std::isfinite(a[i])) return (int64_t)i;
+  return -1;
+}
+}  // namespace
+
+extern "C" {
+
+int32_t piadmm_obca_propagate(piadmm_obca_t h, int32_t n, const double* states, const double* ctrl, const double* par,
+                              const double* w, double* out) {
+  if (!h) return PIADMM_E_ARG;
+  if (n < 1 || n > (1 << 20)) return pfail(h, PIADMM_E_ARG, "obca_propagate: 1 <= n <= 2^20");
+  if (!states || !ctrl || !par || !out) return pfail(h, PIADMM_E_ARG, "obca_propagate: null argument");
+  const size_t N = (size_t)n;
+  int64_t bad = -1;
+  if ((bad = first_not_finite(states, N * 10)) >= 0)
+    return pfail(h, PIADMM_E_ARG, "obca_propagate: state pair " + std::to_string(bad / 10) + " is not finite");
+  if ((bad = first_not_finite(ctrl, N * 4)) >= 0)
+    return pfail(h, PIADMM_E_ARG, "obca_propagate: ctrl of scenario " + std::to_string(bad / 4) + " is not finite");
+  if (w && (bad = first_not_finite(w, N * 10)) >= 0)
+    return pfail(h, PIADMM_E_ARG, "obca_propagate: w of scenario " + std::to_string(bad / 10) + " is not finite");
+  for (int k = 0; k < n; ++k)
+    if (const char* why = feedback_row_check(par + (size_t)k * FPAR))
+      return pfail(h, PIADMM_E_ARG, "obca_propagate: row " + std::to_string(k) + ": " + why);
+  PHIP(h, hipSetDevice(h->device));
+  const size_t B = sizeof(double);
+  scratch a(h);
+  double *d_st = a.take<double>(N * 10, false), *d_ct = a.take<double>(N * 4, false),
+         *d_par = a.take<double>(N * FPAR, false), *d_w = w ? a.take<double>(N * 10, false) : nullptr,
+         *d_out = a.take<double>(N * 10, true);
+  if (a.rc) return a.rc;
+  PHIP(h, hipMemcpyAsync(d_st, states, N * 10 * B, hipMemcpyHostToDevice, h->stream));
+  PHIP(h, hipMemcpyAsync(d_ct, ctrl, N * 4 * B, hipMemcpyHostToDevice, h->stream));
+  PHIP(h, hipMemcpyAsync(d_par, par, N * FPAR * B, hipMemcpyHostToDevice, h->stream));
+  if (w) PHIP(h, hipMemcpyAsync(d_w, w, N * 10 * B, hipMemcpyHostToDevice, h->stream));
+  plant_io io{};
+  io.x0 = d_st;  io.x0_s = 10;
+  io.ctrl = d_ct;  io.ctrl_s = 4;  io.ctrl_v = 2;  io.ctrl_w = 1;
+  io.par = d_par;  io.par_s = FPAR;
+  io.w = d_w;  io.w_s = 10;
+  io.out = d_out;
+  hipLaunchKernelGGL(k_plan_propagate, dim3(lane_blocks(2 * n)), dim3(64 * PW), 0, h->stream, (const int*)nullptr, n,
+                     io);
+  PHIP(h, hipGetLastError());
+  PHIP(h, hipMemcpyAsync(out, d_out, N * 10 * B, hipMemcpyDeviceToHost, h->stream));
+  PHIP(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int32_t piadmm_obca_feedback_plan(piadmm_obca_t h, int32_t mode, const double* par, int32_t rows, const double* tape,
+                                  int32_t cap) {
+  piadmm_obca_plan_s* p = nullptr;
+  if (int rc = open_plan(h, &p, "obca_feedback_plan")) return rc;
+  if (mode != 0 && mode != 1) return pfail(h, PIADMM_E_ARG, "obca_feedback_plan: mode 0 (detach) or 1 (attach)");
+  const int n = p->n;
+  const size_t N = (size_t)n;
+  double nominal[FPAR];
+  feedback_row_nominal(nominal);
+  if (mode == 1) {
+    if (par) {
+      if (int rc = rows_check(h, "obca_feedback_plan", rows, n)) return rc;
+      for (int k = 0; k < rows; ++k)
+        if (const char* why = feedback_row_check(par + (size_t)k * FPAR))
+          return pfail(h, PIADMM_E_ARG, "obca_feedback_plan: row " + std::to_string(k) + ": " + why);
+    } else {
+      par = nominal;
+      rows = 1;
+    }
+    if (tape) {
+      if (cap < 0 || cap > (1 << 20)) return pfail(h, PIADMM_E_ARG, "obca_feedback_plan: 0 <= cap <= 2^20");
+      const int64_t bad = first_not_finite(tape, N * (size_t)cap * 10);
+      if (bad >= 0)
+        return pfail(h, PIADMM_E_ARG, "obca_feedback_plan: the tape of scenario " +
+                     std::to_string(bad / ((int64_t)cap * 10)) + " is not finite (step " +
+                     std::to_string(bad / 10 % cap) + ")");
+    }
+    if (p->ck.on)
+      return pfail(h, PIADMM_E_STATE, "obca_feedback_plan: a clock is attached (obca_clock_plan: the tape has no per-scenario clocks)");
+  }
+  if (p->i_iter != 0) return pfail(h, PIADMM_E_STATE, "obca_feedback_plan: only at a step boundary (an MPC step is open)");
+  PHIP(h, hipSetDevice(h->device));
+  PHIP(h, hipStreamSynchronize(h->stream));
+  if (mode == 0) {
+    p->fb = {};
+    p->nz = {};    // the noise counts its steps by the feedback's: it goes whenever the feedback goes or is replaced
+    return 0;
+  }
+  // the new attachment is complete before it replaces the earlier one
+  piadmm_obca_plan_s::feedback_s nf;
+  const size_t T = N * (size_t)cap * 10;
+  hipError_t e = nf.par.make((size_t)rows * FPAR);
+  if (e == hipSuccess) e = nf.next.make(N * 10);
+  if (e == hipSuccess) e = hipMemset(nf.next, 0, N * 10 * sizeof(double));
+  if (e == hipSuccess) e = hipMemcpy(nf.par, par, (size_t)rows * FPAR * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess && tape) {
+    // a tape without rows still counts as one: every shift is then refused
+    e = nf.tape.make(std::max(T, (size_t)1));
+    if (e == hipSuccess && T) e = hipMemcpy(nf.tape, tape, T * sizeof(double), hipMemcpyHostToDevice);
+  }
+  if (e != hipSuccess) return pfail(h, PIADMM_E_HIP, std::string("obca_feedback_plan: ") + hipGetErrorString(e));
+  p->fb = std::move(nf);
+  p->nz = {};      // as above
+  p->fb.rows = rows;
+  p->fb.stride = rows > 1 ? FPAR : 0;
+  p->fb.cap = tape ? cap : 0;
+  p->fb.steps = 0;
+  p->fb.on = true;
+  return 0;
+}
+
+int32_t piadmm_obca_feedback_measure(piadmm_obca_t h, int32_t m, const int32_t* slots, const double* states) {
+  piadmm_obca_plan_s* p = nullptr;
+  if (int rc = open_plan(h, &p, "obca_feedback_measure")) return rc;
+  const int n = p->n;
+  if (m < 1 || m > n) return pfail(h, PIADMM_E_ARG, "obca_feedback_measure: 1 <= m <= n_scenarios");
+  if (!slots || !states) return pfail(h, PIADMM_E_ARG, "obca_feedback_measure: null argument");
+  for (int k = 0; k < m; ++k)
+    if (slots[k] < 0 || slots[k] >= n || (k > 0 && slots[k] <= slots[k - 1]))
+      return pfail(h, PIADMM_E_ARG, "obca_feedback_measure: slots[" + std::to_string(k) +
+                   "] must be a scenario below n, the slots ascending and distinct");
+  const int64_t bad = first_not_finite(states, (size_t)m * 10);
+  if (bad >= 0)
+    return pfail(h, PIADMM_E_ARG, "obca_feedback_measure: state pair " + std::to_string(bad / 10) + " is not finite");
+  if (p->i_iter != 0) return pfail(h, PIADMM_E_STATE, "obca_feedback_measure: only at a step boundary (an MPC step is open)");
+  if (p->tr.on)
+    return pfail(h, PIADMM_E_STATE, "obca_feedback_measure: a trace is attached (its last row was computed from the state being replaced)");
+  PHIP(h, hipSetDevice(h->device));
+  // the states, then the slot numbers, through the staging buffer; one scatter launch
+  const size_t body = (size_t)m * 10 * sizeof(double);
+  if (int rc = stage_ensure(h, p, body, m)) return rc;
+  int* d_list = reinterpret_cast<int*>(p->stg.buf + body);
+  PHIP(h, hipMemcpyAsync(p->stg.buf, states, body, hipMemcpyHostToDevice, h->stream));
+  PHIP(h, hipMemcpyAsync(d_list, slots, (size_t)m * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(k_plan_set_init, dim3(lane_blocks(2 * m)), dim3(64 * PW), 0, h->stream, (const int*)d_list, m,
+                     reinterpret_cast<const double*>(p->stg.buf.get()), p->bar, p->barp);
+  PHIP(h, hipGetLastError());
+  PHIP(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// Device-side disturbance noise (include/piadmm.h)
+// ---------------------------------------------------------------------------------------------
+namespace {
+// One noise row: nullptr when it is good, else what is wrong with it.
+const char* noise_row_check(const double* row) {
+  for (int i = 0; i < ZPAR; ++i)
+    if (!std::isfinite(row[i])) return "every entry finite";
+  for (int i = 0; i < 10; ++i)
+    if (!(row[Z_SIGMA + i] >= 0.0)) return "sigma >= 0";
+  if (!(row[Z_TRUNC] >= 0.0)) return "trunc 0 (none) or > 0";
+  if (row[Z_RESERVED] != 0.0) return "the reserved entry must be 0";
+  return nullptr;
+}
+
+// rows, streams and k0 of both noise calls, on the host
+int noise_args_check(piadmm_obca_t h, int n, const double* par, int rows, const int64_t* streams, int32_t k0,
+                     int64_t steps, const std::string& who) {
+  if (!par) return pfail(h, PIADMM_E_ARG, who + ": null argument");
+  if (int rc = rows_check(h, who, rows, n)) return rc;
+  for (int k = 0; k < rows; ++k)
+    if (const char* why = noise_row_check(par + (size_t)k * obca_plan::ZPAR))
+      return pfail(h, PIADMM_E_ARG, who + ": row " + std::to_string(k) + ": " + why);
+  if (streams)
+    for (int k = 0; k < n; ++k)
+      if (streams[k] < 0) return pfail(h, PIADMM_E_ARG, who + ": streams[" + std::to_string(k) + "] must be >= 0");
+  if (k0 < 0 || (int64_t)k0 + steps > ((int64_t)1 << 31))
+    return pfail(h, PIADMM_E_ARG, who + ": k0 >= 0 and every step index below 2^31");
+  return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int32_t piadmm_obca_noise_tape(piadmm_obca_t h, int32_t n, int32_t cap, const double* par, int32_t rows,
+                               const int64_t* streams, uint64_t seed, int32_t k0, double* tape_out, uint32_t* raw_out) {
+  if (!h) return PIADMM_E_ARG;
+  if (n < 1 || n > (1 << 20)) return pfail(h, PIADMM_E_ARG, "obca_noise_tape: 1 <= n <= 2^20");
+  if (cap < 0 || cap > (1 << 20)) return pfail(h, PIADMM_E_ARG, "obca_noise_tape: 0 <= cap <= 2^20");
+  const size_t N = (size_t)n, C = (size_t)cap, B = sizeof(double);
+  if (N * C * 10 * B >= ((size_t)1 << 31))
+    return pfail(h, PIADMM_E_ARG, "obca_noise_tape: n x cap x 80 bytes must stay below 2 GiB");
+  if (int rc = noise_args_check(h, n, par, rows, streams, k0, cap, "obca_noise_tape")) return rc;
+  if (cap == 0) return 0;
+  if (!tape_out) return pfail(h, PIADMM_E_ARG, "obca_noise_tape: null argument");
+  PHIP(h, hipSetDevice(h->device));
+  scratch a(h);
+  double *d_par = a.take<double>((size_t)rows * ZPAR, false), *d_out = a.take<double>(N * C * 10, false);
+  long long* d_str = streams ? a.take<long long>(N, false) : nullptr;
+  uint32_t* d_raw = raw_out ? a.take<uint32_t>(N * C * 24, false) : nullptr;
+  if (a.rc) return a.rc;
+  PHIP(h, hipMemcpyAsync(d_par, par, (size_t)rows * ZPAR * B, hipMemcpyHostToDevice, h->stream));
+  if (streams) PHIP(h, hipMemcpyAsync(d_str, streams, N * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+  noise_io zo{};
+  zo.par = d_par;  zo.par_s = rows > 1 ? ZPAR : 0;
+  zo.streams = d_str;
+  zo.out_s = (long long)C * 10;  zo.raw_s = (long long)C * 24;
+  zo.seed_lo = (uint32_t)seed;  zo.seed_hi = (uint32_t)(seed >> 32);
+  // one grid row per step index, at most 32768 rows a launch
+  for (int at = 0; at < cap; at += 32768) {
+    const int ny = std::min(cap - at, 32768);
+    zo.out = d_out + (size_t)at * 10;
+    zo.raw = d_raw ? d_raw + (size_t)at * 24 : nullptr;
+    zo.k = (uint32_t)k0 + (uint32_t)at;
+    hipLaunchKernelGGL(k_plan_noise, dim3(lane_blocks(2 * n), ny), dim3(64 * PW), 0, h->stream, (const int*)nullptr,
+                       n, zo);
+    PHIP(h, hipGetLastError());
+  }
+  PHIP(h, hipMemcpyAsync(tape_out, d_out, N * C * 10 * B, hipMemcpyDeviceToHost, h->stream));
+  if (raw_out)
+    PHIP(h, hipMemcpyAsync(raw_out, d_raw, N * C * 24 * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+  PHIP(h, hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int32_t piadmm_obca_noise_plan(piadmm_obca_t h, int32_t mode, const double* par, int32_t rows, const int64_t* streams,
+                               uint64_t seed, int32_t k0) {
+  piadmm_obca_plan_s* p = nullptr;
+  if (int rc = open_plan(h, &p, "obca_noise_plan")) return rc;
+  if (mode != 0 && mode != 1) return pfail(h, PIADMM_E_ARG, "obca_noise_plan: mode 0 (detach) or 1 (attach)");
+  const int n = p->n;
+  const size_t N = (size_t)n;
+  if (mode == 1)
+    if (int rc = noise_args_check(h, n, par, rows, streams, k0, 0, "obca_noise_plan")) return rc;
+  if (mode == 1 && !p->fb.on)
+    return pfail(h, PIADMM_E_STATE, "obca_noise_plan: no feedback attached (obca_feedback_plan: the noise enters through the plant step)");
+  if (p->i_iter != 0) return pfail(h, PIADMM_E_STATE, "obca_noise_plan: only at a step boundary (an MPC step is open)");
+  PHIP(h, hipSetDevice(h->device));
+  PHIP(h, hipStreamSynchronize(h->stream));
+  if (mode == 0) {
+    p->nz = {};
+    return 0;
+  }
+  // the new attachment is complete before it replaces the earlier one
+  piadmm_obca_plan_s::noise_s nz;
+  std::vector<long long> ident;
+  if (!streams) {
+    ident.resize(N);
+    for (size_t k = 0; k < N; ++k) ident[k] = (long long)k;
+  }
+  const void* src = streams ? static_cast<const void*>(streams) : static_cast<const void*>(ident.data());
+  hipError_t e = nz.par.make((size_t)rows * ZPAR);
+  if (e == hipSuccess) e = nz.wbuf.make(N * 10);
+  if (e == hipSuccess) e = nz.streams.make(N);
+  if (e == hipSuccess) e = hipMemset(nz.wbuf, 0, N * 10 * sizeof(double));
+  if (e == hipSuccess) e = hipMemcpy(nz.par, par, (size_t)rows * ZPAR * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(nz.streams, src, N * sizeof(long long), hipMemcpyHostToDevice);
+  if (e != hipSuccess) return pfail(h, PIADMM_E_HIP, std::string("obca_noise_plan: ") + hipGetErrorString(e));
+  p->nz = std::move(nz);
+  p->nz.rows = rows;
+  p->nz.stride = rows > 1 ? ZPAR : 0;
+  p->nz.seed = seed;
+  p->nz.k0 = k0;
+  p->nz.on = true;
+  return 0;
+}
+
+}  // extern "C"

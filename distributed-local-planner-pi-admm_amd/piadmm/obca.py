@@ -146,7 +146,7 @@ def box_clearance(box0, box1):
 def clearance(state_pair, prob):
     """(plain, tight): the minimum distance between the two vehicles' rectangles at the state pair
     (2 x 5), and between their delay-tightened boxes (prob = 0: the plain value twice).  Host
-    restatement of k_plan_clearance (csrc/piadmm_obca_plan.hip)."""
+    restatement of k_plan_clearance (csrc/piadmm_obca_plan_trace.hip)."""
     sp = np.asarray(state_pair, np.float64).reshape(2, NX)
     plain = box_clearance(vehicle_box(sp[0]), vehicle_box(sp[1]))[0]
     tight = box_clearance(vehicle_box(sp[0], prob, True), vehicle_box(sp[1], prob, True))[0]
@@ -419,7 +419,7 @@ def dual_rows(n, dual):
 
 def lambda_update_pi(bar, S, D, gains, wrote):
     """The PI anti-windup dual law on the consensus error, host restatement of k_plan_dual_pi
-    (csrc/piadmm_obca_plan.hip) with the same statements in the same order: for every entry of a
+    (csrc/piadmm_obca_plan_attach.hip) with the same statements in the same order: for every entry of a
     slot t with wrote[t]
         e = w - Z_bar;  S' = S + kI e + d_gain D;  raw = S' + kP e;
         lam' = windup ? min(sat, max(raw, -sat)) : raw;  D' = windup ? lam' - raw : 0
@@ -461,7 +461,7 @@ ORDER_CLAMP = (1 << 21) - 1
 
 
 def plan_order(lst, work):
-    """The order k_plan_order (csrc/piadmm_obca_plan.hip) puts a list of scenarios in: by
+    """The order k_plan_order (csrc/piadmm_obca_plan_attach.hip) puts a list of scenarios in: by
     work[s] = (Q, I), Q descending, then I descending, then scenario ascending, Q and I clamped to
     [0, ORDER_CLAMP].  A function of the set in `lst` and of `work` (n x 2) alone."""
     lst = np.asarray(lst, np.int64).reshape(-1)
@@ -482,7 +482,7 @@ def plan_work(local_ist, edge_ist):
 
 
 def clock_tick(clock, ran):
-    """The tick of k_plan_clock (csrc/piadmm_obca_plan.hip) on the record clock[s] = (c, len, alive),
+    """The tick of k_plan_clock (csrc/piadmm_obca_plan_attach.hip) on the record clock[s] = (c, len, alive),
     n x 3: c += 1 for the scenarios flagged in `ran` (n, 0 / 1: the ones the step ran), then
     alive = (c + 8 <= len).  Returns the new record (int32); the argument stays."""
     out = np.array(clock, np.int32).reshape(-1, 3)
@@ -566,7 +566,7 @@ def _plant_rhs(x, a_eff, w_eff, lr, lf):
 
 def propagate(states, ctrl, par, w=None):
     """One plant step of length DT per vehicle, host restatement of k_plan_propagate
-    (csrc/piadmm_obca_plan.hip) with the same statements in the same order: states n x 2 x 5
+    (csrc/piadmm_obca_plan_feedback.hip) with the same statements in the same order: states n x 2 x 5
     (x, y, v, theta, delta), ctrl n x 2 x 2 the held (a, omega), par one plant row for all or n rows
     (`feedback_row`), w n x 2 x 5 the disturbance or None.  n_sub substeps of DT / n_sub of
         beta = atan(lr tan(delta) / (lr + lf))

@@ -9,7 +9,7 @@ import numpy as np
 
 from piadmm import obca
 
-ST = 128                                # scenarios per workgroup of the statistics kernels (csrc/piadmm_obca_plan.hip)
+ST = 128                                # scenarios per workgroup of the statistics kernels (csrc/piadmm_obca_plan_trace.hip)
 # one lane, a wave boundary on either side, more than one workgroup of partials, an odd tail
 SIZES = (1, 2, 63, 64, 65, 130, 1000)
 ROWS = (0, 1, 3)

@@ -1,4 +1,4 @@
-"""k_plan_clearance (csrc/piadmm_obca_plan.hip) behind piadmm_obca_clearance against its host
+"""k_plan_clearance (csrc/piadmm_obca_plan_trace.hip) behind piadmm_obca_clearance against its host
 restatement piadmm.obca.clearance, on the crafted geometry and the 70 seeded random pairs of
 tests/_obca_clearance_cases.py, at n = 1 (a lone wave), 5 (a partial second workgroup) and 70.
 

@@ -1,5 +1,5 @@
 """The per-scenario clocks of the device-resident OBCA-ADMM plan (k_plan_clock and the list-taking
-shifts in csrc/piadmm_obca_plan.hip behind piadmm_obca_clock_plan / _clock_admit / _clock_tick;
+shifts in csrc/piadmm_obca_plan_attach.hip behind piadmm_obca_clock_plan / _clock_admit / _clock_tick;
 OBCADevicePlanner(clock=...), set_clock, clear_clock, clock, admit; OBCABatch.clock_tick).
 
 Bars.  Everything the clock adds is integers or copies, and a scenario's answers do not depend on

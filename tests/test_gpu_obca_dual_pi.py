@@ -1,5 +1,5 @@
 """The PI anti-windup dual law of the device-resident OBCA-ADMM plan (k_plan_dual_pi and
-k_plan_dual_shift in csrc/piadmm_obca_plan.hip behind piadmm_obca_dual_plan / piadmm_obca_dual_pi;
+k_plan_dual_shift in csrc/piadmm_obca_plan_attach.hip behind piadmm_obca_dual_plan / piadmm_obca_dual_pi;
 OBCADevicePlanner(dual=...) / set_dual / clear_dual, OBCABatch.dual_pi), against the host
 restatement piadmm.obca.lambda_update_pi / shift_dual.
 

@@ -1,5 +1,5 @@
 """Closed-loop feedback of the device-resident OBCA-ADMM plan (k_plan_propagate and k_plan_set_init
-in csrc/piadmm_obca_plan.hip behind piadmm_obca_propagate / piadmm_obca_feedback_plan /
+in csrc/piadmm_obca_plan_feedback.hip behind piadmm_obca_propagate / piadmm_obca_feedback_plan /
 piadmm_obca_feedback_measure; OBCABatch.propagate, OBCADevicePlanner(feedback=...), set_feedback,
 clear_feedback, measure, feedback_steps; OBCAPlanner(feedback=...)).
 

@@ -1,5 +1,5 @@
 """Device-side disturbance noise of the closed-loop OBCA plan (k_plan_noise in
-csrc/piadmm_obca_plan.hip behind piadmm_obca_noise_tape / piadmm_obca_noise_plan; OBCABatch.noise_tape,
+csrc/piadmm_obca_plan_feedback.hip behind piadmm_obca_noise_tape / piadmm_obca_noise_plan; OBCABatch.noise_tape,
 OBCADevicePlanner(noise=...), set_noise, clear_noise, the NOISE_ items of `get`).
 
 Bars.  The generator's words are compared with obca.philox4x32 exactly.  The normals are compared

@@ -1,5 +1,5 @@
 """The longest-first scenario order of the device-resident OBCA-ADMM plan (k_plan_work and
-k_plan_order in csrc/piadmm_obca_plan.hip behind piadmm_obca_order_plan / piadmm_obca_order;
+k_plan_order in csrc/piadmm_obca_plan_attach.hip behind piadmm_obca_order_plan / piadmm_obca_order;
 OBCADevicePlanner(order=True, work_init=...), OBCABatch.order), against the host statements
 piadmm.obca.plan_order / plan_work.
 

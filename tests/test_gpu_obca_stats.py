@@ -1,5 +1,5 @@
 """Fleet risk statistics and the worst-case gather of the device-resident OBCA plan (k_stats_fleet,
-k_stats_rows, k_stats_worst and k_trace_gather in csrc/piadmm_obca_plan.hip behind
+k_stats_rows, k_stats_worst and k_trace_gather in csrc/piadmm_obca_plan_trace.hip behind
 piadmm_obca_fleet_stats / piadmm_obca_stats_trace / piadmm_obca_gather_trace; OBCABatch.fleet_stats,
 OBCADevicePlanner.trace_stats, trace_gather, trace_worst).
 

@@ -1,5 +1,5 @@
 """Export and import of running tenants of the device-resident OBCA-ADMM plan (k_plan_export and
-k_plan_import in csrc/piadmm_obca_plan.hip behind piadmm_obca_tenant_export_bytes / _export / _import;
+k_plan_import in csrc/piadmm_obca_plan_tenant.hip behind piadmm_obca_tenant_export_bytes / _export / _import;
 OBCADevicePlanner.export_tenants, import_tenants, from_tenants, compact, save, load).
 
 Bars.  Both kernels are pure copies and a scenario's answers do not depend on its place in a batch

@@ -1,5 +1,5 @@
 """The device-side run record of an open plan (piadmm_obca_trace_*, k_plan_trace and
-k_plan_clearance in csrc/piadmm_obca_plan.hip; OBCADevicePlanner.run_traced).
+k_plan_clearance in csrc/piadmm_obca_plan_trace.hip; OBCADevicePlanner.run_traced).
 
 What the trace copies (states, stop iterates, status masks, residuals, lamb_bar) is compared bit for
 bit with a second handle that runs piadmm_obca_plan_step and downloads after every step: attaching a

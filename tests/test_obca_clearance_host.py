@@ -1,5 +1,5 @@
 """Host side of the clearance record: piadmm.obca.clearance (the host restatement of
-k_plan_clearance, csrc/piadmm_obca_plan.hip) against closed forms and against a brute-force
+k_plan_clearance, csrc/piadmm_obca_plan_trace.hip) against closed forms and against a brute-force
 restatement, the tightened boxes against the offset of util.py:83-99 written out, and the header
 and bindings of piadmm_obca_clearance / piadmm_obca_trace_*.  No kernel runs here."""
 import ctypes
