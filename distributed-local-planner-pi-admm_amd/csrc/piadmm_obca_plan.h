@@ -1,8 +1,8 @@
 // piadmm_obca_plan.h -- what the units of the device-resident OBCA-ADMM consensus loop share
 // (internal, not installed): the layouts, the kernel-argument structs, the owners of device memory,
 // the plan and the small host helpers.  csrc/piadmm_obca_plan.hip holds the iterate and the shift and
-// describes the launch sequence; csrc/piadmm_obca_plan_{attach,trace,tenant,feedback}.hip hold the
-// attachments.  Every kernel is defined in one unit; there is no relocatable device code, a unit
+// describes the launch sequence; csrc/piadmm_obca_plan_{attach,trace,tenant,feedback,delay}.hip hold
+// the attachments.  Every kernel is defined in one unit; there is no relocatable device code, a unit
 // launches another unit's kernel through the declaration here.
 #pragma once
 
@@ -65,6 +65,10 @@ static_assert(F_WMAX + 1 == FV && FV % 2 == 0, "plant row layout");
 constexpr int ZPAR = PIADMM_OBCA_NOISE_PAR;
 constexpr int Z_SIGMA = 0, Z_BIAS = 10, Z_TRUNC = 20, Z_RESERVED = 21;
 static_assert(Z_RESERVED + 1 == ZPAR, "noise row layout");
+// a delay row (include/piadmm.h): avg[2], std[2], tau_max[2], trunc, one reserved zero
+constexpr int YPAR = PIADMM_OBCA_DELAY_PAR;
+constexpr int Y_AVG = 0, Y_STD = 2, Y_TMAX = 4, Y_TRUNC = 6, Y_RESERVED = 7;
+static_assert(Y_RESERVED + 1 == YPAR, "delay row layout");
 
 // dst[0 .. len) = src[0 .. len) by the 64 lanes of a wave in strided passes: 16 bytes a lane where
 // both ends sit on a 16-byte boundary and len is even, 8 bytes a lane otherwise.  The pointers are
@@ -106,6 +110,85 @@ struct noise_io {
   int par_s;
 };
 
+// where the arrays of one k_plan_delay launch sit, indexed by scenario: par the delay rows (par_s =
+// 0: one shared row), streams the stream ids (nullptr: the scenario's number), tape the recorded
+// latencies added in front (nullptr: none), out the latencies, raw the Philox words (nullptr: not
+// kept); the strides in elements per scenario, and per step index (blockIdx.y) 2 doubles of tape and
+// out and 8 words of raw; k = the step index of blockIdx.y = 0
+struct delay_io {
+  const double *par, *tape;
+  const long long* streams;
+  double* out;
+  uint32_t* raw;
+  long long tape_s, out_s, raw_s;
+  uint32_t seed_lo, seed_hi, k;
+  int par_s;
+};
+
+// (A, b) of a vehicle at `st` -- halfspaces (piadmm/obca.py) in the host's order of operations,
+// products and sums kept apart (no contraction) so the two stay within rounding of each other.
+__device__ __forceinline__ void halfspaces(const double* st, int prob, double sigd, double A[4][2], double b[4]) {
+#pragma clang fp contract(off)
+  const double x = st[0], y = st[1], vel = st[2], th = st[3];
+  const double c = cos(th), s = sin(th);
+  double dx = 0.0, dy = 0.0;
+  A[0][0] = c;  A[0][1] = s;
+  A[2][0] = -c; A[2][1] = -s;
+  if (prob) {
+    A[1][0] = -s; A[1][1] = c;
+    A[3][0] = s;  A[3][1] = -c;
+    const double qx = VAR_DELAY * vel * c, qy = VAR_DELAY * vel * s;
+    dx = AVG_DELAY * vel * c + sigd * (qx * qx);
+    dy = AVG_DELAY * vel * s + sigd * (qy * qy);
+  } else {
+    A[1][0] = s;  A[1][1] = -c;
+    A[3][0] = -s; A[3][1] = c;
+  }
+  const double px = x + dx, py = y + dy;
+  const double b0[4] = {LENGTH / 2, WIDTH / 2, LENGTH / 2, WIDTH / 2};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) b[i] = b0[i] + (A[i][0] * px + A[i][1] * py);
+}
+
+// The state a vehicle's message describes when it arrives tau late: x1 = X[t + 1] is what the
+// vehicle plans for the slot, x0 = X[t] where it planned to be one step earlier.  tau == 0 is x1 bit
+// for bit; otherwise x1 + (tau / DT) (x0 - x1), all five entries, the heading linearly.
+// piadmm.obca.stale_states is the same statements on the host; products and sums are kept apart, and
+// every operation is exact IEEE arithmetic, so the two agree bit for bit.  The body of the plan's
+// stale exchange and of the stand-alone k_delay_exchange.
+__device__ __forceinline__ void stale_state(const double* x0, const double* x1, double tau, double st[5]) {
+#pragma clang fp contract(off)
+  if (tau == 0.0) {
+#pragma unroll
+    for (int j = 0; j < 5; ++j) st[j] = x1[j];
+  } else {
+    const double f = tau / PLANT_DT;
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+      const double a = x1[j];
+      st[j] = a + f * (x0[j] - a);
+    }
+  }
+}
+
+// Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11):
+// c the counter's four words, replaced by the result; (k0, k1) the key.  Ten rounds of two
+// 32 x 32 -> 64 products (the high halves by __umulhi), the key bumped between rounds.  All 32-bit.
+__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
+  constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t hi0 = __umulhi(M0, c[0]), lo0 = M0 * c[0];
+    const uint32_t hi1 = __umulhi(M1, c[2]), lo1 = M1 * c[2];
+    c[0] = hi1 ^ c[1] ^ k0;
+    c[1] = lo1;
+    c[2] = hi0 ^ c[3] ^ k1;
+    c[3] = lo0;
+    k0 += W0;
+    k1 += W1;
+  }
+}
+
 // The kernels launched from a unit other than their own (the comments are at the definitions).
 // csrc/piadmm_obca_plan.hip
 __global__ void __launch_bounds__(CT) k_plan_compact(const int* __restrict__ active, const int* __restrict__ keep,
@@ -135,6 +218,8 @@ __global__ void __launch_bounds__(64 * PW) k_plan_set_init(const int* __restrict
                                                            const double* __restrict__ states,
                                                            double* __restrict__ bar, double* __restrict__ barp);
 __global__ void __launch_bounds__(64 * PW) k_plan_noise(const int* __restrict__ list, int m, noise_io io);
+// csrc/piadmm_obca_plan_delay.hip
+__global__ void __launch_bounds__(64 * PW) k_plan_delay(const int* __restrict__ list, int m, delay_io io);
 
 // ---------------------------------------------------------------------------------------------
 // The host side
@@ -300,6 +385,18 @@ struct piadmm_obca_plan_s {
     dbuf<double> par, wbuf;
     dbuf<long long> streams;
   } nz;
+  // the communication delay of the exchange (piadmm_obca_delay_plan): rows = 1 with stride 0 or n
+  // delay rows; streams = the stream id of every scenario; tape = cap recorded latencies per scenario
+  // (nullptr: none), n x cap x 2; steps = the shifts since the attachment; tau = the open step's
+  // latencies, n x 2, which k_plan_delay writes at the attachment and after every shift and
+  // k_plan_exchange_stale reads; the open step's index is k0 + steps
+  struct delay_s {
+    bool on = false;
+    int rows = 0, stride = 0, k0 = 0, cap = 0, steps = 0;
+    uint64_t seed = 0;
+    dbuf<double> par, tape, tau;
+    dbuf<long long> streams;
+  } dl;
   // the staging buffer of piadmm_obca_tenant_export / _import: the records, then the slot list; grown on demand
   struct stage_s {
     dbuf<char> buf;
@@ -336,6 +433,15 @@ inline bool feedback_exhausted(const piadmm_obca_plan_s* p, int64_t steps) {
 // true when the attached noise would pass step index 2^31 - 1 within the next `steps` shifts
 inline bool noise_exhausted(const piadmm_obca_plan_s* p, int64_t steps) {
   return p->nz.on && (int64_t)p->nz.k0 + p->fb.steps + steps > ((int64_t)1 << 31);
+}
+
+// What refuses the next `steps` MPC steps of a plan with the delay attached, or nullptr: step k since
+// the attachment needs its tape row (k < cap with a tape) and a step index k0 + k below 2^31
+inline const char* delay_refusal(const piadmm_obca_plan_s* p, int64_t steps) {
+  if (!p->dl.on) return nullptr;
+  if (p->dl.tape && (int64_t)p->dl.steps + steps > p->dl.cap) return "latency tape exhausted";
+  if ((int64_t)p->dl.k0 + p->dl.steps + steps > ((int64_t)1 << 31)) return "delay step index exhausted";
+  return nullptr;
 }
 
 // The checks more than one call makes, each worded once; `who` is the call's name.
@@ -390,6 +496,8 @@ const char* dual_row_check(const double* row);
 int clock_lists(piadmm_obca_t h, piadmm_obca_plan_s* p, const int* ran, int dst, int n_alive);
 int clock_shift(piadmm_obca_t h, piadmm_obca_plan_s* p);
 int clock_relist(piadmm_obca_t h, piadmm_obca_plan_s* p);
+// csrc/piadmm_obca_plan_delay.hip
+int delay_next(piadmm_obca_t h, piadmm_obca_plan_s* p);
 // csrc/piadmm_obca_plan_trace.hip
 int trace_append(piadmm_obca_t h, piadmm_obca_plan_s* p, int row);
 

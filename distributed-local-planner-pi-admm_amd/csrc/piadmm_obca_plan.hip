@@ -31,6 +31,10 @@
 // With the noise attached on top (piadmm_obca_noise_plan) k_plan_noise runs in front of
 // k_plan_propagate and writes the step's disturbance rows, which that kernel reads in the tape's
 // place; without it k_plan_noise is not launched.  One lane per vehicle as well.
+// With the communication delay attached (piadmm_obca_delay_plan) k_plan_exchange_stale runs in
+// k_plan_exchange's place (what a vehicle sends is computed from its plan interpolated tau back) and
+// piadmm_obca_plan_shift launches k_plan_delay last, one lane per vehicle: the latencies of the step
+// that opens; without it neither is launched.
 // The statistics of a run record (piadmm_obca_fleet_stats / _stats_trace: k_stats_fleet, k_stats_rows,
 // k_stats_worst and their merges) and k_trace_gather are launched by those calls alone and write
 // nothing of the plan or the trace.
@@ -46,7 +50,7 @@
 // min_dis, max_admm_iter) is a uniform load; the record parameters are loaded by the few lanes
 // that store them.
 //
-// The attachments' kernels and calls are in csrc/piadmm_obca_plan_{attach,trace,tenant,feedback}.hip;
+// The attachments' kernels and calls are in csrc/piadmm_obca_plan_{attach,trace,tenant,feedback,delay}.hip;
 // the launches above that are theirs go through the declarations in csrc/piadmm_obca_plan.h.
 
 #include "piadmm_obca_plan.h"
@@ -93,39 +97,20 @@ __global__ void __launch_bounds__(64 * PW) k_plan_pack_local(const int* __restri
   }
 }
 
-// (A, b) of a vehicle at `st` -- halfspaces (piadmm/obca.py) in the host's order of operations,
-// products and sums kept apart (no contraction) so the two stay within rounding of each other.
-__device__ __forceinline__ void halfspaces(const double* st, int prob, double sigd, double A[4][2], double b[4]) {
-#pragma clang fp contract(off)
-  const double x = st[0], y = st[1], vel = st[2], th = st[3];
-  const double c = cos(th), s = sin(th);
-  double dx = 0.0, dy = 0.0;
-  A[0][0] = c;  A[0][1] = s;
-  A[2][0] = -c; A[2][1] = -s;
-  if (prob) {
-    A[1][0] = -s; A[1][1] = c;
-    A[3][0] = s;  A[3][1] = -c;
-    const double qx = VAR_DELAY * vel * c, qy = VAR_DELAY * vel * s;
-    dx = AVG_DELAY * vel * c + sigd * (qx * qx);
-    dy = AVG_DELAY * vel * s + sigd * (qy * qy);
-  } else {
-    A[1][0] = s;  A[1][1] = -c;
-    A[3][0] = -s; A[3][1] = c;
-  }
-  const double px = x + dx, py = y + dy;
-  const double b0[4] = {LENGTH / 2, WIDTH / 2, LENGTH / 2, WIDTH / 2};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) b[i] = b0[i] + (A[i][0] * px + A[i][1] * py);
-}
-
-// One wave per active scenario; lane < 14 owns the (vehicle, slot) item lane = v * 7 + t.
-__global__ void __launch_bounds__(64 * PW) k_plan_exchange(const int* __restrict__ active, int n_act,
-                                                           double* __restrict__ bar, const int* __restrict__ prob,
-                                                           const double* __restrict__ lout,
-                                                           const double* __restrict__ tab, int tab_stride,
-                                                           double sigd, int update_lamb_ij,
-                                                           double* __restrict__ ctrl, double* __restrict__ X,
-                                                           int* __restrict__ conv, double* __restrict__ erecs) {
+// One wave per active scenario; lane < 14 owns the (vehicle, slot) item lane = v * 7 + t.  The body
+// of k_plan_exchange (STALE = false: tau is not read, the statements are the plain exchange's) and of
+// k_plan_exchange_stale (STALE = true: the item's state is stale_state of X[t] and X[t + 1] under the
+// vehicle's latency tau[s][v]; the two latencies are loads at a wave-uniform address, X[t] 40 more
+// bytes per lane next to the ones it reads anyway).
+template <bool STALE>
+__device__ __forceinline__ void plan_exchange(const int* __restrict__ active, int n_act,
+                                              double* __restrict__ bar, const int* __restrict__ prob,
+                                              const double* __restrict__ lout,
+                                              const double* __restrict__ tab, int tab_stride,
+                                              double sigd, int update_lamb_ij,
+                                              double* __restrict__ ctrl, double* __restrict__ X,
+                                              int* __restrict__ conv, double* __restrict__ erecs,
+                                              const double* __restrict__ tau) {
   const int lane = threadIdx.x & 63;
   const int k = blockIdx.x * PW + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (k >= n_act) return;
@@ -141,6 +126,12 @@ __global__ void __launch_bounds__(64 * PW) k_plan_exchange(const int* __restrict
     const int v = lane / NT, t = lane % NT, vt = lane;
     const double* ov = o2 + (size_t)v * OUT;
     const double* st = ov + O_X + (t + 1) * 5;
+    double stale[5];
+    if constexpr (STALE) {
+      const double tau0 = tau[(size_t)2 * s], tau1 = tau[(size_t)2 * s + 1];
+      stale_state(st - 5, st, v ? tau1 : tau0, stale);
+      st = stale;
+    }
     double A[4][2], b[4], l[4];
     halfspaces(st, pr, sigd, A, b);
 #pragma unroll
@@ -178,6 +169,31 @@ __global__ void __launch_bounds__(64 * PW) k_plan_exchange(const int* __restrict
   const bool ok = lane >= NT || (fabs(e0) <= conv_thres && fabs(e1) <= conv_thres && ueq >= min_dis);
   const int all_ok = __all(ok);
   if (lane == 0) conv[s] = all_ok ? 1 : 0;
+}
+
+__global__ void __launch_bounds__(64 * PW) k_plan_exchange(const int* __restrict__ active, int n_act,
+                                                           double* __restrict__ bar, const int* __restrict__ prob,
+                                                           const double* __restrict__ lout,
+                                                           const double* __restrict__ tab, int tab_stride,
+                                                           double sigd, int update_lamb_ij,
+                                                           double* __restrict__ ctrl, double* __restrict__ X,
+                                                           int* __restrict__ conv, double* __restrict__ erecs) {
+  plan_exchange<false>(active, n_act, bar, prob, lout, tab, tab_stride, sigd, update_lamb_ij, ctrl, X, conv, erecs,
+                       nullptr);
+}
+
+// The same exchange with the communication delay attached (piadmm_obca_delay_plan): what the
+// vehicle sends -- local_x, A, b, and with them the edge record and check_converge -- is computed
+// from the stale state; ctrl and X stay the local solution's.  Launched only while attached.
+__global__ void __launch_bounds__(64 * PW) k_plan_exchange_stale(const int* __restrict__ active, int n_act,
+                                                                 double* __restrict__ bar, const int* __restrict__ prob,
+                                                                 const double* __restrict__ lout,
+                                                                 const double* __restrict__ tab, int tab_stride,
+                                                                 double sigd, int update_lamb_ij,
+                                                                 double* __restrict__ ctrl, double* __restrict__ X,
+                                                                 int* __restrict__ conv, double* __restrict__ erecs,
+                                                                 const double* __restrict__ tau) {
+  plan_exchange<true>(active, n_act, bar, prob, lout, tab, tab_stride, sigd, update_lamb_ij, ctrl, X, conv, erecs, tau);
 }
 
 // One wave per active scenario: the edge answer into the state, the residuals and the stop rule.
@@ -455,7 +471,7 @@ int plan_open(piadmm_obca_t h, const piadmm_obca_plan_cfg_t* cfg, const int32_t*
 void piadmm_obca_plan_release(piadmm_obca_t h) {
   piadmm_obca_plan_s* p = h->plan;
   if (!p) return;
-  if (p->tr.on || p->du.on || p->ord.on || p->ck.on || p->fb.on) {
+  if (p->tr.on || p->du.on || p->ord.on || p->ck.on || p->fb.on || p->dl.on) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     p->tr = {};
@@ -464,6 +480,7 @@ void piadmm_obca_plan_release(piadmm_obca_t h) {
     p->ck = {};
     p->fb = {};
     p->nz = {};    // the noise counts its steps by the feedback's: it goes whenever the feedback goes
+    p->dl = {};
   }
   p->open = false;
 }
@@ -520,6 +537,7 @@ int32_t piadmm_obca_plan_iterate(piadmm_obca_t h, int32_t* n_active_after) {
   if (p->ck.on && p->ck.n_list == 0) return pfail(h, PIADMM_E_STATE, "obca_plan_iterate: no scenario alive");
   if (p->n_act <= 0) return pfail(h, PIADMM_E_STATE, "obca_plan_iterate: no active scenario (obca_plan_shift closes the step)");
   if (!p->ck.on && p->t_step + 8 > p->cfg.n_ref) return pfail(h, PIADMM_E_STATE, "obca_plan_iterate: reference exhausted");
+  if (const char* why = delay_refusal(p, 1)) return pfail(h, PIADMM_E_STATE, std::string("obca_plan_iterate: ") + why);
   PHIP(h, hipSetDevice(h->device));
   const int m = p->n_act;
   if (2 * m > h->cap || m > h->e_cap) return pfail(h, PIADMM_E_STATE, "obca_plan_iterate: the handle's buffers shrank");
@@ -544,8 +562,14 @@ int32_t piadmm_obca_plan_iterate(piadmm_obca_t h, int32_t* n_active_after) {
   if (int rc = piadmm_obca_local_launch(h, 2 * m)) return rc;
   // the edge output starts from zeros, as in piadmm_obca_edge_solve
   PHIP(h, hipMemsetAsync(h->e_out, 0, (size_t)m * EOUT * sizeof(double), st));
-  hipLaunchKernelGGL(k_plan_exchange, dim3(blocks_for(m)), dim3(64 * PW), 0, st, act, m, p->bar, p->prob, h->d_out,
-                     p->tab, p->tab_stride, p->sigd, p->cfg.update_lamb_ij, p->ctrl, p->X, p->conv, h->e_rec);
+  if (p->dl.on) {
+    hipLaunchKernelGGL(k_plan_exchange_stale, dim3(blocks_for(m)), dim3(64 * PW), 0, st, act, m, p->bar, p->prob,
+                       h->d_out, p->tab, p->tab_stride, p->sigd, p->cfg.update_lamb_ij, p->ctrl, p->X, p->conv,
+                       h->e_rec, (const double*)p->dl.tau);
+  } else {
+    hipLaunchKernelGGL(k_plan_exchange, dim3(blocks_for(m)), dim3(64 * PW), 0, st, act, m, p->bar, p->prob, h->d_out,
+                       p->tab, p->tab_stride, p->sigd, p->cfg.update_lamb_ij, p->ctrl, p->X, p->conv, h->e_rec);
+  }
   PHIP(h, hipGetLastError());
   if (int rc = piadmm_obca_edge_launch(h, m)) return rc;
   if (p->du.on) {
@@ -586,6 +610,7 @@ int32_t piadmm_obca_plan_iterate(piadmm_obca_t h, int32_t* n_active_after) {
 int32_t piadmm_obca_plan_shift(piadmm_obca_t h) {
   piadmm_obca_plan_s* p = nullptr;
   if (int rc = open_plan(h, &p, "obca_plan_shift")) return rc;
+  if (const char* why = delay_refusal(p, 1)) return pfail(h, PIADMM_E_STATE, std::string("obca_plan_shift: ") + why);
   if (p->n_act > 0) return pfail(h, PIADMM_E_STATE, "obca_plan_shift: scenarios are still active");
   if (p->i_iter == 0) return pfail(h, PIADMM_E_STATE, "obca_plan_shift: no iterate ran in this step");
   if (p->tr.on && p->tr.rows >= p->tr.cap) return pfail(h, PIADMM_E_STATE, "obca_plan_shift: trace full");
@@ -644,9 +669,14 @@ int32_t piadmm_obca_plan_shift(piadmm_obca_t h) {
   if (p->tr.on) {
     if (int rc = trace_append(h, p, p->tr.rows + 1)) return rc;
   }
+  if (p->dl.on) {
+    // the latencies of the step that opens
+    if (int rc = delay_next(h, p)) return rc;
+  }
   PHIP(h, hipStreamSynchronize(h->stream));
   if (p->tr.on) p->tr.rows += 1;
   if (p->fb.on) p->fb.steps += 1;
+  if (p->dl.on) p->dl.steps += 1;
   p->t_step += 1;
   p->i_iter = 0;
   p->n_act = p->n;
@@ -662,6 +692,7 @@ int32_t piadmm_obca_plan_step(piadmm_obca_t h, int32_t* iters_out) {
   if (p->tr.on && p->tr.rows >= p->tr.cap) return pfail(h, PIADMM_E_STATE, "obca_plan_step: trace full");
   if (feedback_exhausted(p, 1)) return pfail(h, PIADMM_E_STATE, "obca_plan_step: disturbance tape exhausted");
   if (noise_exhausted(p, 1)) return pfail(h, PIADMM_E_STATE, "obca_plan_step: noise step index exhausted");
+  if (const char* why = delay_refusal(p, 1)) return pfail(h, PIADMM_E_STATE, std::string("obca_plan_step: ") + why);
   // i_iter > max_admm_iter stops a scenario: at most the largest max_admm_iter + 1 iterates in a step
   while (p->n_act > 0 && p->i_iter <= p->max_iter_all) {
     if (int rc = piadmm_obca_plan_iterate(h, nullptr)) return rc;
@@ -683,6 +714,7 @@ int32_t piadmm_obca_plan_get(piadmm_obca_t h, int32_t what, void* out, int64_t b
   bool host = false;       // the item is a value of the plan's, not a device array
   const int32_t counts[3] = {p->n_last, p->n_act, p->i_iter};
   const uint64_t seed[2] = {p->nz.seed, (uint64_t)p->nz.k0};
+  const uint64_t dseed[3] = {p->dl.seed, (uint64_t)p->dl.k0, (uint64_t)p->dl.steps};
   switch (what) {
     case PIADMM_OBCA_PLAN_GET_STATE: src = p->bar; want = n * STATE * D; break;
     case PIADMM_OBCA_PLAN_GET_STATE_PREV: src = p->barp; want = n * STATE * D; break;
@@ -741,6 +773,16 @@ int32_t piadmm_obca_plan_get(piadmm_obca_t h, int32_t what, void* out, int64_t b
       if (what == PIADMM_OBCA_NOISE_GET_PAR) { src = p->nz.par; want = (int64_t)p->nz.rows * ZPAR * D; }
       else if (what == PIADMM_OBCA_NOISE_GET_STREAMS) { src = p->nz.streams; want = n * (int64_t)sizeof(int64_t); }
       else { src = seed; want = 2 * (int64_t)sizeof(uint64_t); host = true; }
+      break;
+    case PIADMM_OBCA_DELAY_GET_PAR:
+    case PIADMM_OBCA_DELAY_GET_TAU:
+    case PIADMM_OBCA_DELAY_GET_STREAMS:
+    case PIADMM_OBCA_DELAY_GET_SEED:
+      if (!p->dl.on) return pfail(h, PIADMM_E_STATE, "obca_plan_get: no delay attached (obca_delay_plan)");
+      if (what == PIADMM_OBCA_DELAY_GET_PAR) { src = p->dl.par; want = (int64_t)p->dl.rows * YPAR * D; }
+      else if (what == PIADMM_OBCA_DELAY_GET_TAU) { src = p->dl.tau; want = n * 2 * D; }
+      else if (what == PIADMM_OBCA_DELAY_GET_STREAMS) { src = p->dl.streams; want = n * (int64_t)sizeof(int64_t); }
+      else { src = dseed; want = 3 * (int64_t)sizeof(uint64_t); host = true; }
       break;
     case PIADMM_OBCA_PLAN_GET_T_STEP: src = &p->t_step; want = I; host = true; break;
     case PIADMM_OBCA_PLAN_GET_COUNTS: src = counts; want = 3 * I; host = true; break;

@@ -568,6 +568,8 @@ int32_t piadmm_obca_clock_plan(piadmm_obca_t h, int32_t mode, const int32_t* clo
   }
   if (mode == 1 && p->fb.on)
     return pfail(h, PIADMM_E_STATE, "obca_clock_plan: feedback is attached (obca_feedback_plan: the tape has no per-scenario clocks)");
+  if (mode == 1 && p->dl.on)
+    return pfail(h, PIADMM_E_STATE, "obca_clock_plan: the delay is attached (obca_delay_plan: it counts the plan's steps, not per-scenario clocks)");
   if (p->i_iter != 0) return pfail(h, PIADMM_E_STATE, "obca_clock_plan: only at a step boundary (an MPC step is open)");
   if (mode == 0) {
     if (!p->ck.on) return 0;

@@ -123,24 +123,6 @@ __global__ void __launch_bounds__(64 * PW) k_plan_set_init(const int* __restrict
 // piadmm_obca_plan_shift does not launch k_plan_noise.
 // ---------------------------------------------------------------------------------------------
 
-// Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11):
-// c the counter's four words, replaced by the result; (k0, k1) the key.  Ten rounds of two
-// 32 x 32 -> 64 products (the high halves by __umulhi), the key bumped between rounds.  All 32-bit.
-__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
-  constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(M0, c[0]), lo0 = M0 * c[0];
-    const uint32_t hi1 = __umulhi(M1, c[2]), lo1 = M1 * c[2];
-    c[0] = hi1 ^ c[1] ^ k0;
-    c[1] = lo1;
-    c[2] = hi0 ^ c[3] ^ k1;
-    c[3] = lo0;
-    k0 += W0;
-    k1 += W1;
-  }
-}
-
 // The five disturbances of vehicle v of stream t at step k under the row's sigma S, bias B and
 // trunc: three Philox calls at counter (k, 4 v + j, t low, t high), each giving two uniforms in
 // (0, 1) on 52 bits and by Box-Muller two normals; the sixth normal is discarded.  raw (12 words,

@@ -178,6 +178,7 @@ int32_t piadmm_obca_tenant_export(piadmm_obca_t h, int32_t m, const int32_t* slo
     return pfail(h, PIADMM_E_ARG, "obca_tenant_export: the blob is " + std::to_string(PIADMM_OBCA_TENANT_HEADER + body) +
                  " bytes, not " + std::to_string(bytes));
   if (p->fb.on) return pfail(h, PIADMM_E_STATE, "obca_tenant_export: feedback is attached (the tenant record has no room for the tape)");
+  if (p->dl.on) return pfail(h, PIADMM_E_STATE, "obca_tenant_export: the delay is attached (the tenant record has no room for it)");
   if (p->i_iter != 0) return pfail(h, PIADMM_E_STATE, "obca_tenant_export: only at a step boundary (an MPC step is open)");
   PHIP(h, hipSetDevice(h->device));
   if (int rc = stage_ensure(h, p, (size_t)body, m)) return rc;
@@ -251,6 +252,7 @@ int32_t piadmm_obca_tenant_import(piadmm_obca_t h, int32_t m, const int32_t* slo
   }
   // the destination
   if (p->fb.on) return pfail(h, PIADMM_E_STATE, "obca_tenant_import: feedback is attached (the tenant record has no room for the tape)");
+  if (p->dl.on) return pfail(h, PIADMM_E_STATE, "obca_tenant_import: the delay is attached (the tenant record has no room for it)");
   if (!p->ck.on) return pfail(h, PIADMM_E_STATE, "obca_tenant_import: no clock attached (obca_clock_plan)");
   if (p->tr.on) return pfail(h, PIADMM_E_STATE, "obca_tenant_import: a trace is attached (its minima would mix two tenants)");
   if (p->i_iter != 0) return pfail(h, PIADMM_E_STATE, "obca_tenant_import: only at a step boundary (an MPC step is open)");

@@ -154,6 +154,10 @@ SYMBOLS = [
     ("piadmm_obca_noise_tape", c_i32, [_H, c_i32, c_i32, _dp, c_i32, _P(ctypes.c_int64), ctypes.c_uint64, c_i32, _dp,
                                        _P(ctypes.c_uint32)]),
     ("piadmm_obca_noise_plan", c_i32, [_H, c_i32, _dp, c_i32, _P(ctypes.c_int64), ctypes.c_uint64, c_i32]),
+    ("piadmm_obca_delay_tau", c_i32, [_H, c_i32, c_i32, _dp, c_i32, _P(ctypes.c_int64), ctypes.c_uint64, c_i32, _dp, _dp,
+                                      _P(ctypes.c_uint32)]),
+    ("piadmm_obca_delay_exchange", c_i32, [_H, c_i32, _dp, _ip, _dp, _dp, _dp, _dp]),
+    ("piadmm_obca_delay_plan", c_i32, [_H, c_i32, _dp, c_i32, _P(ctypes.c_int64), ctypes.c_uint64, c_i32, _dp, c_i32]),
 ]
 
 # PIADMM_OBCA_FLEET_PAR: doubles per parameter row of piadmm_obca_fleet_begin
@@ -164,6 +168,8 @@ DUAL_PAR = 8
 FEEDBACK_PAR = 16
 # PIADMM_OBCA_NOISE_PAR: doubles per noise row of piadmm_obca_noise_plan / piadmm_obca_noise_tape
 NOISE_PAR = 22
+# PIADMM_OBCA_DELAY_PAR: doubles per delay row of piadmm_obca_delay_plan / piadmm_obca_delay_tau
+DELAY_PAR = 8
 
 # PIADMM_OBCA_STATS_EDGES / _WORST: the most edges and the most worst scenarios of the statistics calls
 STATS_EDGES = 64

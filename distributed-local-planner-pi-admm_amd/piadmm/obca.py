@@ -279,13 +279,31 @@ def iterate_next_state(bar):
     return out
 
 
-def bar_state_update(bar, bar_fullx, prob=1):
+def stale_states(X, tau):
+    """The states a vehicle's message describes when it arrives tau late: X (..., 8, 5) the local
+    solve's states (X[0] is init_state), tau (...) the latency in [0, DT]; (..., 7, 5) with slot t =
+    X[t+1] where tau == 0 (bit for bit) and X[t+1] + (tau / DT) (X[t] - X[t+1]) otherwise, all five
+    entries, theta linearly, no wrap.  The statements of stale_state (csrc/piadmm_obca_plan.h) in
+    the same order; every operation is exact IEEE arithmetic, so the device gives the same bits."""
+    X = np.asarray(X, np.float64)
+    assert X.shape[-2:] == (N_HORZ, NX), X.shape
+    tau = np.broadcast_to(np.asarray(tau, np.float64), X.shape[:-2])[..., None, None]
+    x0, x1 = X[..., :-1, :], X[..., 1:, :]
+    f = tau / DT
+    return np.where(tau == 0.0, x1, x1 + f * (x0 - x1))
+
+
+def bar_state_update(bar, bar_fullx, prob=1, tau=None, fullX=None):
     """`bar_state_update` (optimizer.py:205-222): each vehicle's halfspaces at its new local
-    states (the lamb_ij update stays commented out, as in the reference, :220)."""
+    states (the lamb_ij update stays commented out, as in the reference, :220).  With tau (one
+    latency per vehicle) and fullX (each vehicle's 8 x 5 states, X[0] = init_state) the message is
+    stale: the states are `stale_states(fullX[v], tau[v])` in place of the local ones."""
     out = {k: v.copy() for k, v in bar.items()}
+    assert (tau is None) == (fullX is None), "tau and fullX go together"
+    sent = None if tau is None else [stale_states(fullX[v], tau[v]) for v in range(len(bar_fullx))]
     for t in range(NT):
         for v in range(len(bar_fullx)):
-            st = np.asarray(bar_fullx[v])[t, :5]
+            st = np.asarray(bar_fullx[v])[t, :5] if sent is None else sent[v][t]
             A, b = halfspaces(st, prob)
             out["A"][v, t] = A
             out["b"][v, t] = b
@@ -649,27 +667,30 @@ def philox4x32(counter, key):
     return np.stack((c0, c1, c2, c3), axis=-1).astype(np.uint32)
 
 
-def noise_raw(seed, streams, k):
+def noise_raw(seed, streams, k, calls=(0, 1, 2)):
     """The generator's words of the streams `streams` (m int64, >= 0) at step index k: m x 2 x 3 x 4
     uint32, the call j of vehicle v at counter (k, 4 v + j, t & 0xffffffff, t >> 32) under the key
-    (seed & 0xffffffff, seed >> 32)."""
+    (seed & 0xffffffff, seed >> 32).  calls: the call indices j (each below 4), the third axis; the
+    noise's are 0, 1, 2 and the communication delay's is 3 (`delay_tau`)."""
     t = np.asarray(streams, np.int64).reshape(-1)
     seed, k = int(seed), int(k)
+    calls = np.asarray(calls, np.int64).reshape(-1)
     assert (t >= 0).all() and 0 <= seed < 1 << 64 and 0 <= k < NOISE_K_MAX, (seed, k)
+    assert ((calls >= 0) & (calls < 4)).all(), calls
     t = t.astype(np.uint64)
-    counter = np.zeros((len(t), 2, 3, 4), np.uint64)
+    counter = np.zeros((len(t), 2, len(calls), 4), np.uint64)
     counter[..., 0] = k
-    counter[..., 1] = (4 * np.arange(2)[:, None] + np.arange(3)[None, :])[None]
+    counter[..., 1] = (4 * np.arange(2)[:, None] + calls[None, :])[None]
     counter[..., 2] = (t & _U32)[:, None, None]
     counter[..., 3] = (t >> np.uint64(32))[:, None, None]
     return philox4x32(counter, np.array([seed & 0xFFFFFFFF, seed >> 32], np.uint64))
 
 
-def noise_uniform(seed, streams, k):
+def noise_uniform(seed, streams, k, calls=(0, 1, 2)):
     """The uniforms of `noise_raw`: m x 2 x 3 x 2 fp64, (u1, u2) of every call,
     u = (((hi << 32 | lo) >> 12) + 0.5) 2^-52 -- 52 bits and the half, exact in fp64 and strictly
     inside (0, 1)."""
-    r = noise_raw(seed, streams, k).astype(np.uint64)
+    r = noise_raw(seed, streams, k, calls).astype(np.uint64)
     a = (r[..., 0::2] << np.uint64(32) | r[..., 1::2]) >> np.uint64(12)
     return (a.astype(np.float64) + 0.5) * 2.0 ** -52
 
@@ -745,6 +766,100 @@ def noise_tape(n, cap, par, streams=None, seed=0, k0=0):
         z = noise_normal(seed, streams, k0 + i)
         z = np.where(trunc != 0.0, np.minimum(trunc, np.maximum(z, -trunc)), z)
         out[:, i] = bias + sigma * z
+    return out
+
+
+# the communication delay of the plan's exchange (piadmm_obca_delay_plan / piadmm_obca_delay_tau /
+# piadmm_obca_delay_exchange, include/piadmm.h): a delay row is avg[2], std[2], tau_max[2], trunc and
+# one reserved zero
+DELAY_PAR = 8                         # doubles per row (PIADMM_OBCA_DELAY_PAR)
+DELAY_CALL = 3                        # the Philox call index of the latency: the one the noise leaves free
+# the delay items of piadmm_obca_plan_get: name -> (code, dtype) (PIADMM_OBCA_DELAY_GET_*)
+DELAY_GET = {"DELAY_PAR": (39, np.float64), "DELAY_TAU": (40, np.float64), "DELAY_STREAMS": (41, np.int64),
+             "DELAY_SEED": (42, np.uint64)}
+
+
+def delay_row(avg=0.0, std=0.0, tau_max=DT, trunc=0.0):
+    """One delay row (DELAY_PAR doubles): avg, std and tau_max each one value or one per vehicle;
+    trunc 0 for none, else z is clipped to +-trunc before it is scaled.  The default row draws
+    tau = 0 always: the plain exchange."""
+    row = np.zeros(DELAY_PAR)
+    row[0:2] = np.broadcast_to(np.asarray(avg, np.float64), (2,))
+    row[2:4] = np.broadcast_to(np.asarray(std, np.float64), (2,))
+    row[4:6] = np.broadcast_to(np.asarray(tau_max, np.float64), (2,))
+    row[6] = float(trunc)
+    return row
+
+
+def delay_row_check(row):
+    """None when the delay row is good, else what is wrong with it: the library's check."""
+    row = np.asarray(row, np.float64).reshape(DELAY_PAR)
+    if not np.isfinite(row).all():
+        return "every entry finite"
+    for v in (0, 1):
+        if not row[0 + v] >= 0.0:
+            return "avg >= 0"
+        if not row[2 + v] >= 0.0:
+            return "std >= 0"
+        if not 0.0 <= row[4 + v] <= DT:
+            return "0 <= tau_max <= DT"
+    if not row[6] >= 0.0:
+        return "trunc 0 (none) or > 0"
+    if row[7] != 0.0:
+        return "the reserved entry must be 0"
+    return None
+
+
+def delay_args(n, par=None, streams=None, seed=0, k0=0, tape=None):
+    """(par, streams, seed, k0, tape) of a delay argument: par one delay row or n rows (None: the
+    default row), as rows x DELAY_PAR; streams n int64 (None: 0 .. n-1); tape n x cap x 2 finite
+    recorded latencies or None; checked as the library checks."""
+    par = delay_row() if par is None else par
+    par = np.ascontiguousarray(np.asarray(par, np.float64).reshape(-1, DELAY_PAR))
+    if par.shape[0] not in (1, n):
+        raise ValueError(f"obca.delay: rows must be 1 or n ({n})")
+    for k, row in enumerate(par):
+        why = delay_row_check(row)
+        if why is not None:
+            raise ValueError(f"obca.delay: row {k}: {why}")
+    streams = np.arange(n, dtype=np.int64) if streams is None else np.ascontiguousarray(streams, np.int64).reshape(-1)
+    if streams.shape != (n,) or (streams < 0).any():
+        raise ValueError(f"obca.delay: streams must be {n} ids >= 0")
+    seed, k0 = int(seed), int(k0)
+    if not (0 <= seed < 1 << 64 and 0 <= k0 < NOISE_K_MAX):
+        raise ValueError("obca.delay: seed a uint64 and 0 <= k0 < 2^31")
+    if tape is not None:
+        tape = np.ascontiguousarray(tape, np.float64)
+        if tape.ndim != 3 or tape.shape[0] != n or tape.shape[2] != 2 or not np.isfinite(tape).all():
+            raise ValueError(f"obca.delay: the tape must be {n} x cap x 2 and finite")
+    return par, streams, seed, k0, tape
+
+
+def delay_tau(n, cap, par, streams=None, seed=0, k0=0, tape=None):
+    """The latencies k_plan_delay draws, host restatement with the same statements in the same
+    order: n x cap x 2, entry [s][i][v] = min(tau_max[v], max(0, tape[s][i][v] + (avg[v] + std[v] *
+    clip(z, +-trunc)))) with z = sqrt(-2 log u1) cos(2 pi u2) of the Philox call DELAY_CALL of
+    vehicle v of stream streams[s] (None: s) at step index k0 + i (`noise_uniform`), under par (one
+    delay row or n); tape the recorded latencies (None: 0).  A pure function of (seed, stream, step
+    index); the noise's calls are 0, 1, 2, so the same seed and streams give independent draws."""
+    n, cap = int(n), int(cap)
+    par, streams, seed, k0, tape = delay_args(n, par, streams, seed, k0, tape)
+    if k0 + cap > NOISE_K_MAX:
+        raise ValueError("obca.delay_tau: every step index below 2^31")
+    if tape is not None and tape.shape[1] != cap:
+        raise ValueError(f"obca.delay_tau: the tape must be {n} x {cap} x 2")
+    P = np.broadcast_to(par, (n, DELAY_PAR))
+    avg, std, tau_max, trunc = P[:, 0:2], P[:, 2:4], P[:, 4:6], P[:, 6][:, None]
+    out = np.zeros((n, cap, 2))
+    for i in range(cap):
+        u = noise_uniform(seed, streams, k0 + i, calls=(DELAY_CALL,))[:, :, 0]
+        rad = np.sqrt(-2.0 * np.log(u[..., 0]))
+        ang = (2.0 * np.pi) * u[..., 1]
+        z = rad * np.cos(ang)
+        z = np.where(trunc != 0.0, np.minimum(trunc, np.maximum(z, -trunc)), z)
+        x = (0.0 if tape is None else tape[:, i]) + (avg + std * z)
+        lo = np.where(x > 0.0, x, 0.0)
+        out[:, i] = np.where(lo < tau_max, lo, tau_max)
     return out
 
 
@@ -1004,6 +1119,46 @@ class OBCABatch:
             None if words is None else words.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))))
         return (tape, words) if raw else tape
 
+    def delay_tau(self, n, cap, par, streams=None, seed=0, k0=0, tape=None, raw=False):
+        """k_plan_delay on the call's own buffers (piadmm_obca_delay_tau): the latencies n x cap x 2
+        of the streams `streams` (None: 0 .. n-1) at step indices k0 .. k0 + cap - 1 under the delay
+        rows par (one for all, or n) and the recorded latencies tape (n x cap x 2 or None), as
+        `delay_tau` states them; with raw=True also the call's words, n x cap x 2 x 4 uint32
+        (`noise_raw` with calls=(3,)).  The library checks the arguments."""
+        from . import _lib
+        n, cap = int(n), int(cap)
+        par = np.ascontiguousarray(np.asarray(par, np.float64).reshape(-1, DELAY_PAR))
+        if streams is not None:
+            streams = np.ascontiguousarray(streams, np.int64).reshape(-1)
+            assert streams.shape == (n,), streams.shape
+        if tape is not None:
+            tape = np.ascontiguousarray(tape, np.float64)
+            assert tape.shape == (n, cap, 2), tape.shape
+        tau = np.zeros((max(n, 0), max(cap, 0), 2))
+        words = np.zeros((max(n, 0), max(cap, 0), 2, 4), np.uint32) if raw else None
+        self._check(self._lib.piadmm_obca_delay_tau(
+            self._h, n, cap, _lib.dptr(par), par.shape[0],
+            None if streams is None else streams.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+            ctypes.c_uint64(int(seed)), int(k0), _lib.dptr(tape), _lib.dptr(tau),
+            None if words is None else words.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))))
+        return (tau, words) if raw else tau
+
+    def delay_exchange(self, X, prob, tau):
+        """The stale message alone, one launch of k_delay_exchange on the call's own buffers
+        (piadmm_obca_delay_exchange): X n x 2 x 8 x 5 the local solves' states, prob one value or one
+        per scenario, tau n x 2 latencies in [0, DT].  Returns (local_x n x 2 x 7 x 5, A n x 2 x 7 x
+        4 x 2, b n x 2 x 7 x 4): `stale_states` and `halfspaces` of it."""
+        from . import _lib
+        X = np.ascontiguousarray(X, np.float64)
+        n = X.shape[0] if X.ndim == 4 else 0
+        tau = np.ascontiguousarray(tau, np.float64)
+        assert X.shape == (n, 2, N_HORZ, NX) and tau.shape == (n, 2), (X.shape, tau.shape)
+        prob = np.ascontiguousarray(np.broadcast_to(np.asarray(prob, np.int32), (n,)))
+        lx, A, b = np.zeros((n, 2, NT, NX)), np.zeros((n, 2, NT, 4, 2)), np.zeros((n, 2, NT, 4))
+        self._check(self._lib.piadmm_obca_delay_exchange(self._h, n, _lib.dptr(X), _lib.iptr(prob), _lib.dptr(tau),
+                                                         _lib.dptr(lx), _lib.dptr(A), _lib.dptr(b)))
+        return lx, A, b
+
     def fleet_stats(self, clear, summary, iters=None, mask=None, edges=(0.0,), worst=1) -> "OBCAFleetStats":
         """The fleet statistics of the caller's arrays (piadmm_obca_fleet_stats: k_stats_fleet,
         k_stats_rows and k_stats_worst on the call's own buffers), as `fleet_stats_host` states them:
@@ -1160,13 +1315,21 @@ class OBCAPlanner:
     `noise_tape` draws for stream streams[s] at step index k0 + k -- a pure function of (seed,
     stream, step index), so no tape is kept.  `set_noise` / `clear_noise` attach and detach it; a
     new `set_feedback` and `clear_feedback` drop it.  OBCADevicePlanner takes the same argument and
-    draws the same disturbances (k_plan_noise)."""
+    draws the same disturbances (k_plan_noise).
+
+    delay: None, or dict(par=, streams=, seed=, k0=, tape=): communication delay in the exchange.
+    Vehicle v of scenario s sends, at every iterate of the step k since the attachment, the
+    halfspaces and local_x of `stale_states(X, tau)` in place of its local states, with tau =
+    `delay_tau`'s latency of stream streams[s] at step index k0 + k (tape n x cap x 2: recorded
+    latencies added in front); what it keeps for itself (controls, X, init_state) is unchanged.
+    `set_delay` / `clear_delay` attach and detach it; independent of feedback and noise, not together
+    with clock.  OBCADevicePlanner takes the same argument (piadmm_obca_delay_plan)."""
 
     def __init__(self, batch, n_scenarios, prob=1, t_step0=0, rho=1.0, min_dis=0.1, max_admm_iter=50,
                  primal_thres=0.01, dual_thres=0.01, round_decimals=4, start=1, update_lamb_ij=0, max_iter=60,
                  conv_thres=0.1, on_stage=None, max_x=150.0, max_y=20.0, r=1e4, q=1e5, x_bound=1000.0,
                  mu_max=100000.0, g_max=1000.0, ref_traj=None, specs=None, dual=None, clock=None, feedback=None,
-                 noise=None):
+                 noise=None, delay=None):
         self.batch = batch
         self.n = int(n_scenarios)
         self.prob = [int(prob)] * self.n if np.isscalar(prob) else [int(p) for p in prob]
@@ -1209,8 +1372,36 @@ class OBCAPlanner:
             self.set_feedback(**feedback)
         if noise is not None:
             self.set_noise(**noise)
+        self.delay = None
+        if delay is not None:
+            self.set_delay(**delay)
         self.record = OBCARunRecord()
         self.record.state_record.append(np.stack(self.init_state))
+
+    def set_delay(self, par=None, streams=None, seed=0, k0=0, tape=None):
+        """Attach the communication delay (see the class): from the next step on the exchange is
+        stale.  The step count starts again."""
+        from . import _lib
+        delay = delay_args(self.n, par, streams, seed, k0, tape)
+        if self.clock is not None:
+            err = _lib.PiadmmError("obca_delay_plan: a clock is attached (obca_clock_plan: the delay counts the "
+                                   "plan's steps, not per-scenario clocks)")
+            err.code = _lib.E_STATE
+            raise err
+        self.delay = delay
+        self._delay_steps = 0
+
+    def clear_delay(self):
+        self.delay = None
+
+    def delay_tau(self):
+        """The open step's latencies, n x 2 (the DELAY_TAU item of OBCADevicePlanner.get)."""
+        assert self.delay is not None, "no delay attached"
+        par, streams, seed, k0, tape = self.delay
+        k = self._delay_steps
+        assert tape is None or k < tape.shape[1], "latency tape exhausted"
+        assert k0 + k < NOISE_K_MAX, "delay step index exhausted"
+        return delay_tau(self.n, 1, par, streams, seed, k0 + k, None if tape is None else tape[:, k:k + 1])[:, 0]
 
     def set_feedback(self, par=None, tape=None):
         """Attach the plant (see the class): from the next step on a step closes through `propagate`.
@@ -1270,6 +1461,7 @@ class OBCAPlanner:
             ran = [s for s in range(n) if self.clock[s, 2]]
             assert ran, "no scenario alive"
             t_of = [int(c) for c in self.clock[:, 0]]
+        tau = None if self.delay is None else self.delay_tau()
         bar = [self._copy(b) for b in self.bar_prev]
         bar_prev = [self._copy(b) for b in self.bar_prev]
         x0_step = [np.array(x, np.float64) for x in self.init_state]
@@ -1300,7 +1492,11 @@ class OBCAPlanner:
             # ---- information exchange ----
             before = [bar[s] for s in active]
             for k, s in enumerate(active):
-                bar[s] = bar_state_update(bar[s], fullx[k], prob=self.prob[s])
+                if tau is None:
+                    bar[s] = bar_state_update(bar[s], fullx[k], prob=self.prob[s])
+                else:
+                    bar[s] = bar_state_update(bar[s], fullx[k], prob=self.prob[s], tau=tau[s],
+                                              fullX=[res.X[2 * k + v] for v in (0, 1)])
                 if self.update_lamb_ij:
                     bar[s]["lamb_ij"] = np.stack([fullx[k][v][:, 5:] for v in (0, 1)])
             self.on_stage("exchange", dict(bar=before, fullx=fullx, scenarios=list(active)),
@@ -1381,6 +1577,8 @@ class OBCAPlanner:
             nxt = propagate(np.stack(x0_step), np.stack(U0), par, w)
             self.init_state = [nxt[s] for s in range(n)]
             self._feedback_steps += 1
+        if self.delay is not None:
+            self._delay_steps += 1
         self.on_stage("shift", dict(bar_prev=shift_in, X=X, iters=iters.copy()), dict(bar_next=self.bar_prev, init_state=self.init_state))
         self.record.state_record.append(np.stack(self.init_state))
         self.record.iter_num_record.append(iters)
@@ -1856,13 +2054,19 @@ class OBCADevicePlanner:
     step k since the feedback's attachment gets the row of stream streams[s] (None: s) at step index
     k0 + k, added behind the tape's row if there is a tape.  `set_noise` / `clear_noise` attach and
     detach it; `set_feedback` and `clear_feedback` drop it.  A scenario is re-run alone from (seed,
-    its stream id, k0): a plan of the worst few with streams = their ids draws what they drew."""
+    its stream id, k0): a plan of the worst few with streams = their ids draws what they drew.
+
+    With delay=dict(par=, streams=, seed=, k0=, tape=) the exchange is stale (piadmm_obca_delay_plan,
+    k_plan_delay and k_plan_exchange_stale; `delay_tau` and `stale_states` are the statements): every
+    vehicle sends the halfspaces of its plan interpolated back by its latency of the open step,
+    `get("DELAY_TAU")`.  `set_delay` / `clear_delay` attach and detach it at a step boundary;
+    independent of feedback and noise, not together with clock or the tenant calls."""
 
     def __init__(self, batch, n_scenarios, prob=1, t_step0=0, rho=1.0, min_dis=0.1, max_admm_iter=50,
                  primal_thres=0.01, dual_thres=0.01, round_decimals=4, start=1, update_lamb_ij=0, max_iter=60,
                  conv_thres=0.1, on_stage=None, max_x=150.0, max_y=20.0, r=1e4, q=1e5, x_bound=1000.0,
                  mu_max=100000.0, g_max=1000.0, ref_traj=None, state=None, specs=None, dual=None, order=False,
-                 work_init=None, clock=None, feedback=None, noise=None):
+                 work_init=None, clock=None, feedback=None, noise=None, delay=None):
         from . import _lib
         self.batch = batch
         self._lib = batch._lib
@@ -1928,6 +2132,7 @@ class OBCADevicePlanner:
         self.dual_par = None
         self._feedback = None
         self._noise = None
+        self._delay = None
         if dual is not None:
             self.set_dual(**dual)
         self.order = False
@@ -1942,8 +2147,34 @@ class OBCADevicePlanner:
             self.set_feedback(**feedback)
         if noise is not None:
             self.set_noise(**noise)
+        if delay is not None:
+            self.set_delay(**delay)
         self.record = OBCARunRecord()
         self.record.state_record.append(np.stack(self.init_state))
+
+    def set_delay(self, par=None, streams=None, seed=0, k0=0, tape=None):
+        """Attach the communication delay (piadmm_obca_delay_plan; a step boundary only, no clock):
+        par one delay row or n rows (`delay_row`; None: the default row), streams n stream ids (None:
+        0 .. n-1), seed a uint64, k0 the step index of the open step, tape n x cap x 2 recorded
+        latencies or None.  A second call replaces the first.  The library checks the arguments."""
+        from . import _lib
+        rows = np.ascontiguousarray(np.asarray(delay_row() if par is None else par, np.float64).reshape(-1, DELAY_PAR))
+        if streams is not None:
+            streams = np.ascontiguousarray(streams, np.int64).reshape(-1)
+            assert streams.shape == (self.n,), streams.shape
+        if tape is not None:
+            tape = np.ascontiguousarray(tape, np.float64)
+            assert tape.ndim == 3 and tape.shape[0] == self.n and tape.shape[2] == 2, tape.shape
+        self._check(self._lib.piadmm_obca_delay_plan(
+            self.batch._h, 1, _lib.dptr(rows), rows.shape[0],
+            None if streams is None else streams.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+            ctypes.c_uint64(int(seed)), int(k0), _lib.dptr(tape), 0 if tape is None else tape.shape[1]))
+        self._delay = (rows, streams, int(seed), int(k0), tape)
+
+    def clear_delay(self):
+        """Detach the delay (a step boundary only): the exchange is the plain one again."""
+        self._check(self._lib.piadmm_obca_delay_plan(self.batch._h, 0, None, 0, None, 0, 0, None, 0))
+        self._delay = None
 
     def set_feedback(self, par=None, tape=None):
         """Attach the plant (piadmm_obca_feedback_plan; a step boundary only, no clock): par one plant
@@ -2276,7 +2507,14 @@ class OBCADevicePlanner:
 
     def get(self, what):
         """One item of the resident plan (include/piadmm.h, piadmm_obca_plan_get), shaped: a name of
-        PLAN_GET or of NOISE_GET."""
+        PLAN_GET, of NOISE_GET or of DELAY_GET."""
+        if what in DELAY_GET:
+            code, dt = DELAY_GET[what]
+            shape = {"DELAY_PAR": (1 if self._delay is None else len(self._delay[0]), DELAY_PAR),
+                     "DELAY_TAU": (self.n, 2), "DELAY_STREAMS": (self.n,), "DELAY_SEED": (3,)}[what]
+            out = np.zeros(shape, dt)
+            self._check(self._lib.piadmm_obca_plan_get(self.batch._h, code, out.ctypes.data, out.nbytes))
+            return out
         if what in NOISE_GET:
             code, dt = NOISE_GET[what]
             shape = {"NOISE_PAR": (1 if self._noise is None else len(self._noise[0]), NOISE_PAR),

@@ -940,6 +940,88 @@ int32_t piadmm_obca_noise_plan(piadmm_obca_t h, int32_t mode, const double* par 
                                int32_t rows /* 1 or n */, const int64_t* streams /* n, may be NULL: 0 .. n-1 */,
                                uint64_t seed, int32_t k0);
 
+/* ---- communication delay in the plan's exchange: stale exchanged plans --------------------------
+ * The delay tightening of the halfspaces (prob = 1: the box moved forward by AVG_DELAY v (cos, sin)
+ * plus a variance term) exists to cover communication delay, yet the plan's exchange is never stale:
+ * every vehicle sends the halfspaces of its current local solution.  The calls below attach a
+ * communication-delay model to the exchange of an open plan.  Opt-in: without the attachment the
+ * plan issues exactly the launches it issued before and gives the same bits.
+ *
+ * The latency.  One value per vehicle and MPC step, held over all ADMM iterates of that step.  A
+ * delay row is PIADMM_OBCA_DELAY_PAR = 8 doubles:
+ *   avg[2] (finite, >= 0), std[2] (finite, >= 0), tau_max[2] (0 <= tau_max <= DT = 0.1),
+ *   trunc (0: none, else > 0: z is clipped to +-trunc first), one reserved zero
+ * For vehicle v of stream t (int64, 0 <= t < 2^63) at step index k (0 <= k < 2^31) under `seed`:
+ *   counter = (k, 4 v + 3, t & 0xffffffff, t >> 32),  key = (seed & 0xffffffff, seed >> 32)
+ * -- the call the noise leaves free (its calls are 4 v + 0, 1, 2), so noise and delay under one seed
+ * and the same streams draw independently -- u1, u2 from the four words as the noise forms them,
+ *   z = sqrt(-2 log(u1)) cos(2 pi u2)                      (the second normal is discarded)
+ *   x = tape + (avg[v] + std[v] z)                         tape: the latency tape's entry, or 0
+ *   tau = min(tau_max[v], max(0, x))                       (x > 0 ? x : 0, then < tau_max ? . : tau_max)
+ * products and sums kept apart; std = 0 without a tape gives min(tau_max, avg) bit for bit.  The
+ * words are exact; log, sqrt and cos are the device's, so a device tau equals the NumPy one
+ * (piadmm.obca.delay_tau) to a few ulp and two device values of the same (seed, t, k) bit for bit.
+ *
+ * The stale message.  With the local solve's states X[0 .. 7] (X[0] is init_state), slot t = 0 .. 6:
+ *   st' = X[t+1]                                      if tau == 0  (the plain exchange, bit for bit)
+ *   st' = X[t+1] + (tau / DT) (X[t] - X[t+1])         otherwise: all five entries, theta linearly
+ * and everything the vehicle sends is computed from st' in place of X[t+1]: local_x of the state and
+ * of the edge record, A and b through the unchanged halfspaces, and with them check_converge.  What
+ * the vehicle keeps for itself (CTRL, X, later init_state) is unchanged: the vehicles move truly,
+ * the other vehicle and the coordinator see stale plans, and a trace's clearances stay the truth.
+ *
+ * piadmm_obca_delay_tau runs k_plan_delay (one lane per vehicle, one grid row per step index) alone
+ * on the call's own device buffers: tau_out[s][i][v] (n x cap x 2) is the latency of stream
+ * streams[s] (NULL: s) at step index k0 + i under par (`rows` = 1 or n), tape (n x cap x 2, may be
+ * NULL) added as above, raw_out (n x cap x 2 x 4, may be NULL) the call's words.  Before any device
+ * call, PIADMM_E_ARG: 1 <= n <= 2^20, 0 <= cap <= 2^20, n x cap x 16 bytes below 2 GiB, rows 1 or n,
+ * every row valid ("obca_delay_tau: row k: ..."), streams >= 0, k0 >= 0 and k0 + cap <= 2^31, the
+ * tape finite.
+ *
+ * piadmm_obca_delay_exchange computes the stale message alone from given latencies (tau n x 2, each
+ * in [0, DT]), one wave per scenario, by the device function the plan's kernel runs: lx_out = st',
+ * (A_out, b_out) = halfspaces(st', prob[s]).  PIADMM_E_ARG before any device call: 1 <= n <= 2^20,
+ * non-null pointers, prob 0 or 1, X finite, tau in [0, DT].
+ *
+ * piadmm_obca_delay_plan, mode 1, attaches the model to an open plan: tau of step index k0 is drawn
+ * at once, from then on every iterate launches the stale exchange in the plain one's place, and
+ * piadmm_obca_plan_shift draws the next step's tau after the shift (one launch more per MPC step).
+ * The delay counts its own steps since the attachment; it works with or without feedback and noise.
+ * tape (n x cap x 2, may be NULL; cap is ignored without one) adds recorded latencies: step k since
+ * the attachment reads tape[s][k][v], and once cap steps are closed piadmm_obca_plan_iterate,
+ * _plan_step, _plan_shift and piadmm_obca_trace_run (whose n_steps must fit what is left) return
+ * PIADMM_E_STATE ("latency tape exhausted") before any launch, as "trace full" does; a step index
+ * reaching 2^31 is refused the same way ("delay step index exhausted").  A second call replaces the
+ * first once the new attachment is complete; mode 0 detaches (the other arguments are ignored).  The
+ * host checks above (PIADMM_E_ARG, "obca_delay_plan: row k: ..."), then PIADMM_E_STATE: no open
+ * plan, a clock attached, an MPC step open.  A refused call leaves everything as it was.  While the
+ * delay is attached piadmm_obca_clock_plan (mode 1) and piadmm_obca_tenant_export / _import return
+ * PIADMM_E_STATE (the record has no room for it).  piadmm_obca_plan_get gains the items
+ *   PIADMM_OBCA_DELAY_GET_PAR       rows x PIADMM_OBCA_DELAY_PAR fp64   the rows as attached
+ *   PIADMM_OBCA_DELAY_GET_TAU       n x 2 fp64                          the open step's latencies
+ *   PIADMM_OBCA_DELAY_GET_STREAMS   n int64                             the stream ids (0 .. n-1 for NULL)
+ *   PIADMM_OBCA_DELAY_GET_SEED      3 uint64                            seed, k0, the steps closed since
+ * (PIADMM_E_STATE without the attachment).  Out of scope: a latency per iterate or per direction,
+ * delays beyond one step, staleness of the coordinator's answer, angle wrapping in the interpolation. */
+#define PIADMM_OBCA_DELAY_PAR 8
+#define PIADMM_OBCA_DELAY_GET_PAR 39
+#define PIADMM_OBCA_DELAY_GET_TAU 40
+#define PIADMM_OBCA_DELAY_GET_STREAMS 41
+#define PIADMM_OBCA_DELAY_GET_SEED 42
+int32_t piadmm_obca_delay_tau(piadmm_obca_t h, int32_t n, int32_t cap,
+                              const double* par /* rows x PIADMM_OBCA_DELAY_PAR */, int32_t rows /* 1 or n */,
+                              const int64_t* streams /* n, may be NULL: 0 .. n-1 */, uint64_t seed, int32_t k0,
+                              const double* tape /* n x cap x 2, may be NULL */, double* tau_out /* n x cap x 2 */,
+                              uint32_t* raw_out /* n x cap x 2 x 4, may be NULL */);
+int32_t piadmm_obca_delay_exchange(piadmm_obca_t h, int32_t n, const double* X /* n x 2 x 8 x 5 */,
+                                   const int32_t* prob /* n */, const double* tau /* n x 2 */,
+                                   double* lx_out /* n x 2 x 7 x 5 */, double* A_out /* n x 2 x 7 x 4 x 2 */,
+                                   double* b_out /* n x 2 x 7 x 4 */);
+int32_t piadmm_obca_delay_plan(piadmm_obca_t h, int32_t mode, const double* par /* rows x PIADMM_OBCA_DELAY_PAR */,
+                               int32_t rows /* 1 or n */, const int64_t* streams /* n, may be NULL: 0 .. n-1 */,
+                               uint64_t seed, int32_t k0, const double* tape /* n x cap x 2, may be NULL */,
+                               int32_t cap);
+
 /* ---- fleet risk statistics and the worst-case gather of a run record ---------------------------
  * A Monte-Carlo study over a traced fleet asks how many runs came closer than d, at which step the
  * fleet is most at risk, and which runs were the worst.  piadmm_obca_trace_get can only copy the

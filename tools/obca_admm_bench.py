@@ -119,6 +119,24 @@
                    ratio is fixed in advance.  Written under the key "noise" of the same JSON, the
                    other keys kept.
 
+  --delay          instead of the above, in one process at --scenarios scenarios of
+                   obca.overtaking_fleet(--scenarios, seed=0) over --steps MPC steps from step 8 through
+                   run_traced.  The cost of the path, the repeats of the legs alternating after a
+                   warm-up step of each, best of --repeats: (p) the nominal plant under a zero tape
+                   (--noise's leg (p): the launches of the parent commit) against (d) the same with
+                   the delay attached under a row that draws tau = 0 (k_plan_exchange_stale in
+                   k_plan_exchange's place, one k_plan_delay launch per step); the two are the same
+                   solves, so their records are compared; (d)/(p) is reported next to the max/min
+                   spread of (p)'s own repeats and next to the (p) the key "noise" of the same JSON
+                   holds from before.  The study: the nominal plant, no position noise, every message
+                   tau ~ N(AVG_DELAY, VAR_DELAY) clipped to [0, DT] late, with prob = 0 and with
+                   prob = 1, and the same two runs without the delay: the share of scenarios below
+                   their own min_dis, the share touching, the median smallest plain clearance (the
+                   columns of --feedback's disturbed runs).  One seed: findings.  Stand-alone:
+                   piadmm_obca_delay_tau at n = 65536, cap = 42 once against obca.delay_tau.  No ratio
+                   is fixed in advance.  Written under the key "delay" of the same JSON, the other
+                   keys kept.
+
 There is no CPU baseline on an equal footing (the C++ port of the local solver has no edge step);
 the edge launch is reported next to the local launch so the reader sees its share of an iterate.
 Writes one JSON (default profiles/obca_admm_bench.json) and prints it.
@@ -793,8 +811,110 @@ def noise_main(a):
     print(json.dumps(dict(noise=res)))
 
 
+def delay_main(a):
+    """--delay: (p) zero tape against (d) zero tape + a delay row that draws tau = 0; the fleet under
+    tau ~ N(AVG_DELAY, VAR_DELAY) with prob = 0 and prob = 1 next to the runs without delay; the
+    stand-alone latencies."""
+    b = obca.OBCABatch(0)
+    n, K = a.scenarios, a.steps
+    specs, par = obca.overtaking_fleet(n, seed=0)
+    kw = dict(prob=[k % 2 for k in range(n)], t_step0=8, max_admm_iter=a.iterates - 1, specs=specs, **par)
+    zero_tape = np.zeros((n, K, 2, obca.NX))
+
+    def attach_p(dp):
+        dp.set_feedback(tape=zero_tape)
+
+    def attach_d(dp):
+        dp.set_feedback(tape=zero_tape)
+        dp.set_delay(par=obca.delay_row(), seed=0)
+    legs_at = dict(p_zero_tape=attach_p, d_zero_tape_zero_delay=attach_d)
+    warm = obca.OBCADevicePlanner(b, n, **kw)
+    state = warm.get("STATE")                          # the seeded state, so the later plans skip the host seeding
+    for at in legs_at.values():
+        at(warm)
+        warm.step()
+    warm.close()
+    ms, traces = {k: [] for k in legs_at}, {}
+    for _ in range(a.repeats):
+        for name, at in legs_at.items():
+            dp = obca.OBCADevicePlanner(b, n, state=state, **kw)
+            at(dp)
+            t0 = time.perf_counter()
+            traces[name] = dp.run_traced(K, keep_lambda=False)
+            ms[name].append((time.perf_counter() - t0) * 1e3)
+            dp.close()
+    legs = {}
+    for name in legs_at:
+        tr = traces[name]
+        n_it, best = int(tr.iters.max(axis=1).sum()), min(ms[name])
+        legs[name] = dict(steps_run=int(tr.iters.shape[0]), admm_iterates=n_it, step_ms=best / max(tr.iters.shape[0], 1),
+                          total_ms_runs=ms[name], spread_max_over_min=max(ms[name]) / best,
+                          stop_iterate_histogram=np.bincount(tr.iters.ravel()).tolist())
+    tp, td = traces["p_zero_tape"], traces["d_zero_tape_zero_delay"]
+    same = bool(all(np.array_equal(getattr(tp, f), getattr(td, f))
+                    for f in ("states", "clearance", "iters", "status_mask", "primal", "dual")))
+    ratio = min(ms["d_zero_tape_zero_delay"]) / min(ms["p_zero_tape"])
+    before = None
+    if os.path.exists(a.out):
+        with open(a.out) as f:
+            before = json.load(f).get("noise", {}).get("legs", {}).get("p_zero_tape", {}).get("step_ms")
+    # the study: stale messages, with and without the delay tightening
+    min_dis = np.broadcast_to(np.asarray(par.get("min_dis", 0.1), np.float64), (n,))
+    row = obca.delay_row(avg=obca.AVG_DELAY, std=obca.VAR_DELAY)
+    study = {}
+    for prob in (0, 1):
+        seeded = None                                   # the seeded state of this prob, from the first plan
+        for delayed in (False, True):
+            dp = obca.OBCADevicePlanner(b, n, state=seeded, feedback=dict(par=None),
+                                        delay=dict(par=row, seed=0) if delayed else None, **dict(kw, prob=[prob] * n))
+            seeded = dp.get("STATE")
+            tr = dp.run_traced(K, keep_lambda=False)
+            dp.close()
+            below = tr.min_clearance < min_dis
+            study[f"{'delay' if delayed else 'no_delay'}_prob_{prob}"] = dict(
+                share_below_min_dis=float(below.mean()), scenarios_below_min_dis=int(below.sum()),
+                share_touching=float((tr.min_clearance == 0.0).mean()), min_clearance_smallest=float(tr.min_clearance.min()),
+                min_clearance_median=float(np.median(tr.min_clearance)),
+                min_clearance_tight_median=float(np.median(tr.min_clearance_tight)),
+                stop_iterate_histogram=np.bincount(tr.iters.ravel()).tolist(),
+                local_status_mask_or=int(np.bitwise_or.reduce(tr.status_mask[:, :, 0].ravel())),
+                edge_status_mask_or=int(np.bitwise_or.reduce(tr.status_mask[:, :, 1].ravel())))
+    # the stand-alone latencies at the size of a whole study, once
+    n_big, cap = 65536, 42
+    b.delay_tau(1024, 2, row)                           # warm-up
+    t0 = time.perf_counter()
+    dev = b.delay_tau(n_big, cap, row, seed=0)
+    dev_ms = (time.perf_counter() - t0) * 1e3
+    t0 = time.perf_counter()
+    host = obca.delay_tau(n_big, cap, row, seed=0)
+    host_ms = (time.perf_counter() - t0) * 1e3
+    res = dict(scenarios=n, steps=K, repeats=a.repeats, max_admm_iter=a.iterates - 1, legs=legs,
+               zero_delay_over_zero_tape=ratio, zero_tape_spread_max_over_min=legs["p_zero_tape"]["spread_max_over_min"],
+               ratio_exceeds_zero_tape_spread=bool(ratio > legs["p_zero_tape"]["spread_max_over_min"]),
+               zero_delay_run_equals_zero_tape_run=same,
+               extra_ms_per_step=(min(ms["d_zero_tape_zero_delay"]) - min(ms["p_zero_tape"])) / K,
+               zero_tape_step_ms_under_key_noise_before=before,
+               study=dict(latency="tau ~ N(AVG_DELAY, VAR_DELAY) clipped to [0, DT], one per vehicle and step, seed 0; "
+                                  "nominal plant, no position noise", **study),
+               stand_alone=dict(n=n_big, cap=cap, bytes=int(dev.nbytes), device_ms=dev_ms, numpy_statement_ms=host_ms,
+                                max_abs_deviation_from_statement=float(np.abs(dev - host).max()),
+                                share_at_0=float((dev == 0.0).mean()), share_at_dt=float((dev == obca.DT).mean()),
+                                mean=float(dev.mean())))
+    b.close()
+    out = {}
+    if os.path.exists(a.out):
+        with open(a.out) as f:
+            out = json.load(f)
+    out["delay"] = res
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+    print(json.dumps(dict(delay=res)))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--delay", action="store_true")
     ap.add_argument("--noise", action="store_true")
     ap.add_argument("--stats", action="store_true")
     ap.add_argument("--feedback", action="store_true")
@@ -811,6 +931,8 @@ def main():
     ap.add_argument("--iterates", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "obca_admm_bench.json"))
     a = ap.parse_args()
+    if a.delay:
+        return delay_main(a)
     if a.noise:
         return noise_main(a)
     if a.stats:
