@@ -249,3 +249,17 @@ def iptr(a: np.ndarray | None):
         return None
     assert a.dtype == np.int32 and a.flags.c_contiguous
     return a.ctypes.data_as(_ip)
+
+
+def i64ptr(a: np.ndarray | None):
+    if a is None:
+        return None
+    assert a.dtype == np.int64 and a.flags.c_contiguous
+    return a.ctypes.data_as(_P(ctypes.c_int64))
+
+
+def u32ptr(a: np.ndarray | None):
+    if a is None:
+        return None
+    assert a.dtype == np.uint32 and a.flags.c_contiguous
+    return a.ctypes.data_as(_P(ctypes.c_uint32))

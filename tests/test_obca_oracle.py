@@ -1,5 +1,5 @@
 """The OBCA local subproblem oracle (oracle/obca_oracle.py) and the host-side record/bar_state
-helpers (piadmm/obca.py), on CPU.
+helpers (piadmm/obca/model.py), on CPU.
 
 Pinned by executing the reference (tests/golden/ref_obca.npz, oracle/gen_ref_obca.py):
 VehicleConfig + ref_traj_gen (veh_config.py:7-47), mid_state (optimizer.py:351-373),
