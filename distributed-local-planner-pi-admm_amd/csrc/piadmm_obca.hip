@@ -1188,21 +1188,18 @@ int fail(piadmm_obca_t h, int code, const std::string& msg) {
 
 int ensure(piadmm_obca_t h, int n) {
   if (n <= h->cap) return 0;
-  if (h->d_rec) { (void)hipFree(h->d_rec); (void)hipFree(h->d_out); (void)hipFree(h->d_ist); (void)hipFree(h->d_qg); }
-  if (h->d_stamps) (void)hipFree(h->d_stamps);
-  h->d_rec = nullptr; h->d_out = nullptr; h->d_ist = nullptr; h->d_qg = nullptr; h->d_stamps = nullptr; h->cap = 0;
-#ifdef PIADMM_STAMPS
-  OHIP(h, hipMalloc(&h->d_stamps, (size_t)n * obca::NSTAMP * sizeof(unsigned long long)));
-  OHIP(h, hipMemset(h->d_stamps, 0, (size_t)n * obca::NSTAMP * sizeof(unsigned long long)));
-#endif
-  OHIP(h, hipMalloc(&h->d_rec, (size_t)n * obca::REC * sizeof(double)));
-  OHIP(h, hipMalloc(&h->d_out, (size_t)n * obca::OUT * sizeof(double)));
-  OHIP(h, hipMalloc(&h->d_ist, (size_t)n * 3 * sizeof(int)));
-  OHIP(h, hipMalloc(&h->d_qg, (size_t)n * sizeof(obca::WsG)));
-  if (h->d_order) (void)hipFree(h->d_order);
-  h->d_order = nullptr;
+  h->cap = 0;
   h->cost_n = 0;
-  OHIP(h, hipMalloc(&h->d_order, (size_t)n * sizeof(int)));
+  // the old arrays go before the new ones are allocated (peak memory)
+  h->d_rec = {}; h->d_out = {}; h->d_ist = {}; h->d_qg = {}; h->d_stamps = {}; h->d_order = {};
+  int rc = 0;
+#ifdef PIADMM_STAMPS
+  if ((rc = h->d_stamps.alloc(h, (size_t)n * obca::NSTAMP, true))) return rc;
+#endif
+  if ((rc = h->d_rec.alloc(h, (size_t)n * obca::REC, false)) || (rc = h->d_out.alloc(h, (size_t)n * obca::OUT, false)) ||
+      (rc = h->d_ist.alloc(h, (size_t)n * 3, false)) || (rc = h->d_qg.alloc(h, (size_t)n * sizeof(obca::WsG), false)) ||
+      (rc = h->d_order.alloc(h, (size_t)n, false)))
+    return rc;
   h->cap = n;
   return 0;
 }
@@ -1244,7 +1241,7 @@ int schedule(piadmm_obca_t h) {
 
 int launch(piadmm_obca_t h) {
   hipLaunchKernelGGL(obca::k_obca_sqp, dim3(h->n), dim3(64), 0, h->stream, h->d_rec, h->n, h->d_out, h->d_ist,
-                     h->d_stamps, static_cast<obca::WsG*>(h->d_qg), h->d_order);
+                     h->d_stamps, reinterpret_cast<obca::WsG*>(h->d_qg.get()), h->d_order);
   OHIP(h, hipGetLastError());
   return 0;
 }
@@ -1262,7 +1259,7 @@ int piadmm_obca_local_ensure(piadmm_obca_t h, int n) { return ensure(h, n); }
 int piadmm_obca_local_launch(piadmm_obca_t h, int n) {
   if (n <= 0 || n > h->cap) return fail(h, PIADMM_E_STATE, "obca local launch: n outside the buffers");
   hipLaunchKernelGGL(obca::k_obca_sqp, dim3(n), dim3(64), 0, h->stream, h->d_rec, n, h->d_out, h->d_ist,
-                     h->d_stamps, static_cast<obca::WsG*>(h->d_qg), h->d_order);
+                     h->d_stamps, reinterpret_cast<obca::WsG*>(h->d_qg.get()), h->d_order);
   OHIP(h, hipGetLastError());
   return 0;
 }
@@ -1289,14 +1286,7 @@ int32_t piadmm_obca_destroy(piadmm_obca_t h) {
   if (!h) return 0;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  if (h->d_rec) { (void)hipFree(h->d_rec); (void)hipFree(h->d_out); (void)hipFree(h->d_ist); (void)hipFree(h->d_qg); }
-  if (h->d_stamps) (void)hipFree(h->d_stamps);
-  if (h->d_order) (void)hipFree(h->d_order);
   piadmm_obca_plan_free(h);
-  piadmm_obca_edge_free(h);
-  if (h->e0) (void)hipEventDestroy(h->e0);
-  if (h->e1) (void)hipEventDestroy(h->e1);
-  if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
   return 0;
 }

@@ -671,10 +671,13 @@ int edge_check(piadmm_obca_t h, const double* recs, int n) {
 
 int edge_ensure(piadmm_obca_t h, int n) {
   if (n <= h->e_cap) return 0;
-  piadmm_obca_edge_free(h);
-  EHIP(h, hipMalloc(&h->e_rec, (size_t)n * obca_edge::REC * sizeof(double)));
-  EHIP(h, hipMalloc(&h->e_out, (size_t)n * obca_edge::OUT * sizeof(double)));
-  EHIP(h, hipMalloc(&h->e_ist, (size_t)n * obca_edge::NT * 3 * sizeof(int)));
+  h->e_cap = 0;
+  h->e_rec = {}; h->e_out = {}; h->e_ist = {};      // the old arrays go first (peak memory)
+  int rc = 0;
+  if ((rc = h->e_rec.alloc(h, (size_t)n * obca_edge::REC, false)) ||
+      (rc = h->e_out.alloc(h, (size_t)n * obca_edge::OUT, false)) ||
+      (rc = h->e_ist.alloc(h, (size_t)n * obca_edge::NT * 3, false)))
+    return rc;
   h->e_cap = n;
   return 0;
 }
@@ -706,13 +709,6 @@ int piadmm_obca_edge_ensure(piadmm_obca_t h, int n) { return edge_ensure(h, n); 
 int piadmm_obca_edge_launch(piadmm_obca_t h, int n) {
   if (n <= 0 || n > h->e_cap) return efail(h, PIADMM_E_STATE, "obca edge launch: n outside the buffers");
   return edge_launch(h, n);
-}
-
-void piadmm_obca_edge_free(piadmm_obca_t h) {
-  if (h->e_rec) (void)hipFree(h->e_rec);
-  if (h->e_out) (void)hipFree(h->e_out);
-  if (h->e_ist) (void)hipFree(h->e_ist);
-  h->e_rec = nullptr; h->e_out = nullptr; h->e_ist = nullptr; h->e_cap = 0;
 }
 
 extern "C" {

@@ -8,29 +8,40 @@
 #include <string>
 #include <vector>
 
+#include "pd_owners.h"
 #include "piadmm.h"
 
 struct piadmm_obca_plan_s;      // csrc/piadmm_obca_plan.h
 
+// Every device array is owned by its member; the destructor lets the events and the stream go, so a
+// handle that was only part made is released by `delete` like a whole one (piadmm_obca_create).
 struct piadmm_obca_s {
+  template <typename T>
+  using dbuf = pd_own::dev_buf<T>;
+  piadmm_obca_s() = default;
+  piadmm_obca_s(const piadmm_obca_s&) = delete;
+  piadmm_obca_s& operator=(const piadmm_obca_s&) = delete;
+  ~piadmm_obca_s() {
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
   int device = 0;
   hipStream_t stream = nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  double* d_rec = nullptr;
-  double* d_out = nullptr;
-  int* d_ist = nullptr;
-  void* d_qg = nullptr;         // per-problem linearisation blocks (obca::WsG, HBM)
-  unsigned long long* d_stamps = nullptr;
-  int* d_order = nullptr;       // the launch's problem order (longest first; cap ints)
+  dbuf<double> d_rec, d_out;
+  dbuf<int> d_ist;
+  dbuf<char> d_qg;              // per-problem linearisation blocks (obca::WsG, HBM)
+  dbuf<unsigned long long> d_stamps;
+  dbuf<int> d_order;            // the launch's problem order (longest first; cap ints)
   std::vector<int> order;       // host copy of the order
   std::vector<int> cost;        // the last solve's status / SQP iterations / QP steps per problem
   int cost_n = 0;               // batch size of the last solve (0: none yet)
   int cap = 0, n = 0;
   // the edge step's own buffers (csrc/piadmm_obca_edge.hip): an edge call never touches the
   // resident local batch above or its longest-first history
-  double* e_rec = nullptr;
-  double* e_out = nullptr;
-  int* e_ist = nullptr;
+  dbuf<double> e_rec, e_out;
+  dbuf<int> e_ist;
   int e_cap = 0;
   // the consensus loop (csrc/piadmm_obca_plan.hip).  piadmm_obca_plan_begin takes the local and
   // edge buffers over: plan_taken stays set (piadmm_obca_run / _time / _download: PIADMM_E_STATE)
@@ -39,9 +50,6 @@ struct piadmm_obca_s {
   bool plan_taken = false;
   std::string err;
 };
-
-// frees the edge buffers (piadmm_obca_destroy)
-void piadmm_obca_edge_free(piadmm_obca_t h);
 
 // The plan path's view of the two solves: grow the handle's buffers to n local problems / n pairs,
 // and enqueue one launch over the first n records already in d_rec (problem order d_order[0..n))

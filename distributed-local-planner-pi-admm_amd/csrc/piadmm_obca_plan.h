@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "pd_common.h"
+#include "pd_owners.h"
 #include "piadmm.h"
 #include "piadmm_obca_handle.h"
 
@@ -234,85 +235,10 @@ inline int pfail(piadmm_obca_t h, int code, const std::string& msg) {
     if (_e != hipSuccess) return pfail(h, PIADMM_E_HIP, std::string(#call ": ") + hipGetErrorString(_e)); \
   } while (0)
 
-// The zero fill is done when this returns: hipMemset of device memory does not wait, and the handle's
-// stream does not wait for the null stream, so the fill could otherwise land after a kernel's writes.
-template <typename T>
-int dalloc(piadmm_obca_t h, T** p, size_t count, bool zero) {
-  PHIP(h, hipMalloc(p, count * sizeof(T)));
-  if (zero) PHIP(h, hipMemset(*p, 0, count * sizeof(T)));
-  if (zero) PHIP(h, hipStreamSynchronize(nullptr));
-  return 0;
-}
-
-// The owner of one hipMalloc'ed array (Pinned: of one hipHostMalloc'ed): move-only, freed when it
-// goes.  It converts to the pointer, so a launch or a copy names it as it would the raw pointer.
-// Whoever lets one go while the stream may still use it synchronises the stream first.
-template <typename T, bool Pinned = false>
-class dev_buf {
- public:
-  dev_buf() = default;
-  dev_buf(dev_buf&& o) noexcept : p_(std::exchange(o.p_, nullptr)) {}
-  dev_buf& operator=(dev_buf&& o) noexcept {
-    if (this != &o) {
-      release();
-      p_ = std::exchange(o.p_, nullptr);
-    }
-    return *this;
-  }
-  ~dev_buf() { release(); }
-  // the project's error code, h->err set; the array is owned even when the memset fails
-  int alloc(piadmm_obca_t h, size_t count, bool zero) {
-    release();
-    if constexpr (Pinned) {
-      PHIP(h, hipHostMalloc(reinterpret_cast<void**>(&p_), count * sizeof(T)));
-      return 0;
-    } else {
-      return dalloc(h, &p_, count, zero);
-    }
-  }
-  // the bare allocation, for a caller that words the failure itself
-  hipError_t make(size_t count) {
-    release();
-    return hipMalloc(&p_, count * sizeof(T));
-  }
-  T* get() const { return p_; }
-  operator T*() const { return p_; }
-
- private:
-  void release() {
-    if (p_) (void)(Pinned ? hipHostFree(p_) : hipFree(p_));
-    p_ = nullptr;
-  }
-  T* p_ = nullptr;
-};
-
-// The device arrays of one stand-alone call, on the stack: neither the handle's local and edge
-// buffers nor an open plan is touched.  After a failed take every later one hands out nullptr and
-// rc keeps the first failure, so a call takes all its arrays and asks once.  When the call leaves,
-// on whichever path, the stream is synchronised and then the arrays are freed.
-class scratch {
- public:
-  explicit scratch(piadmm_obca_t h) : h_(h) {}
-  scratch(const scratch&) = delete;
-  scratch& operator=(const scratch&) = delete;
-  ~scratch() {
-    (void)hipStreamSynchronize(h_->stream);
-    for (void* q : held_) (void)hipFree(q);
-  }
-  template <typename T>
-  T* take(size_t count, bool zero) {
-    T* p = nullptr;
-    if (rc) return nullptr;
-    rc = dalloc(h_, &p, count, zero);
-    if (p) held_.push_back(p);
-    return p;
-  }
-  int rc = 0;
-
- private:
-  piadmm_obca_t h_;
-  std::vector<void*> held_;
-};
+// The owners of device memory (pd_owners.h).  scratch: the device arrays of one stand-alone call, on
+// the stack: neither the handle's local and edge buffers nor an open plan is touched.
+using pd_own::dev_buf;
+using scratch = pd_own::arena<piadmm_obca_s>;
 
 }  // namespace obca_plan
 

@@ -304,7 +304,7 @@ def test_repeating_a_step_forgets_the_stored_active_sets(Solver):
     """a pair's stored dual active set (S^-1, Y columns, codes) is valid only for the
     MPC step that built it.  Solving the same t again (piadmm_mpc_step(h, t) twice: the second
     starts from the propagated state, another geometry) must not restore it; the library forgets
-    the stored sets whenever a step does not continue the sequence (piadmm_capi.cpp
+    the stored sets whenever a step does not continue the sequence (piadmm_steps.cpp
     continue_sequence).  The repeat must equal the same step on a fresh handle started from that
     state, with every QP certified."""
     cfg = config.matlab_pi(H=15)
@@ -324,3 +324,39 @@ def test_repeating_a_step_forgets_the_stored_active_sets(Solver):
     close(rep.xt, ref.xt)
     close(rep.u, ref.u)
     assert ca["inexact"] == 0
+
+
+def test_one_handle_through_fused_graph_split_and_back(Solver, monkeypatch):
+    """One handle takes four scenarios in turn through set_candidate_graph -- the pairs (0, 1), (2, 3)
+    (the fused kernel), all six pairs of the four crossing vehicles (the graph kernel), the same
+    under PIADMM_GRAPH_BLOCK=2 (the component split over two workgroups) and the first again -- and
+    runs 2 MPC steps after each.  Whatever a scenario leaves behind in the handle (arrays, host
+    staging, mode flags) must not reach the next: xt, u, hat and lam are bit-equal to a fresh
+    handle given the same scenario."""
+    H = 10
+    cfg = config.matlab_pi(H=H, term_global=1, fixed_iters=1, max_outer=5)
+    base = scenario.crossing(4, H, n_steps=8, seed=1)
+    tiles = np.array([(0, 1), (2, 3)], np.int32)
+    stages = [(tiles, None, 2), (base.edges, None, 1), (base.edges, "2", 2), (tiles, None, 2)]
+    scn0 = scenario.Scenario(spd=base.spd, xt0=base.xt0, ref=base.ref, edges=tiles, n_steps=base.n_steps)
+    with Solver(cfg, scn0) as s:
+        for k, (edges, block, n_comp) in enumerate(stages):
+            if block is None:
+                monkeypatch.delenv("PIADMM_GRAPH_BLOCK", raising=False)
+            else:
+                monkeypatch.setenv("PIADMM_GRAPH_BLOCK", block)
+            if k:
+                s.set_candidate_graph(edges)
+            assert s.C == n_comp, f"stage {k}"
+            fresh_scn = scenario.Scenario(spd=base.spd, xt0=s.xt.copy(), ref=base.ref, edges=edges,
+                                          n_steps=base.n_steps)
+            with Solver(cfg, fresh_scn) as f:
+                assert f.C == n_comp
+                for t in (2 * k, 2 * k + 1):
+                    r, rf = s.mpc_step(t), f.mpc_step(t)
+                    np.testing.assert_array_equal(r.status, 0)
+                    np.testing.assert_array_equal(r.xt, rf.xt, err_msg=f"stage {k} step {t}")
+                    np.testing.assert_array_equal(r.u, rf.u, err_msg=f"stage {k} step {t}")
+                st, stf = s.state(), f.state()
+            np.testing.assert_array_equal(st["hat"], stf["hat"], err_msg=f"stage {k}")
+            np.testing.assert_array_equal(st["lam"], stf["lam"], err_msg=f"stage {k}")
