@@ -32,11 +32,14 @@
 #include <string>
 #include <vector>
 
+#include "pd_obca.h"
 #include "piadmm.h"
+#include "piadmm_obca_handle.h"
 
 namespace obca {
 
-constexpr int NH = 8, NX = 5, NU = 2, NL = 4, NT = 7;
+using namespace pd_obca;     // NT, the constants, the layouts, the reductions, Geo, the QP core
+constexpr int NH = 8, NX = 5, NU = 2, NL = 4;
 constexpr int NUV = NU * NT;          // 14
 constexpr int NZ = NUV + 2 * NT;      // 28
 constexpr int ROWS_T = 21;            // per stage: state lo/hi x5, (5a) lo/hi, norm, Lambda lo/hi x4
@@ -46,10 +49,11 @@ constexpr int MAXACT = NZ;
 constexpr int NZP = NZ + 1;         // padded LDS row stride of the 28 x 28 matrices (odd: no bank conflicts
                                      // when each lane walks its own row)
 
-// VehicleConfig (veh_config.py:7-27), OBCAOptimizer (optimizer.py:10-37)
-constexpr double LENGTH = 3.5, WIDTH = 2.0, LF = 1.5, LR = 1.0;
+// VehicleConfig (veh_config.py:7-27), OBCAOptimizer (optimizer.py:10-37); the body and the delay
+// statistics are in pd_obca.h
+constexpr double LF = 1.5, LR = 1.0;
 constexpr double MAX_STEER = 0.6, MAX_V = 20.0, MAX_ACC = 5.0, MAX_STEER_RATE = 20.0;
-constexpr double DT = 0.1, AVG_DELAY = 0.05, VAR_DELAY = 0.025;
+constexpr double DT = 0.1;
 constexpr double LAM_MAX = 100000.0, GA_MAX = 1000.0;
 constexpr double KB = LR / (LR + LF);
 constexpr double TWO_PI = 6.283185307179586;
@@ -101,27 +105,6 @@ struct WsG {
 
 static_assert(sizeof(Ws) <= 160 * 1024 / 4, "OBCA workspace: four problems per CU");
 
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double wmax(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
-// min value, lowest index on ties (idx < 0 = none)
-__device__ __forceinline__ void wargmin(double& v, int& i) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    double v2 = __shfl_xor(v, o, 64);
-    int i2 = __shfl_xor(i, o, 64);
-    bool take = (i2 >= 0) && (i < 0 || v2 < v || (v2 == v && i2 < i));
-    if (take) { v = v2; i = i2; }
-  }
-}
-
 #define SYNC() __syncthreads()
 
 // diagnostic build (-DPIADMM_STAMPS, libpiadmm_stamps.so): per-problem cycle sums of the SQP phases
@@ -140,42 +123,9 @@ enum { ST_LIN, ST_COND, ST_HESS, ST_ROWS, ST_MOD, ST_GI, ST_REC, ST_LS, ST_INIT,
 #endif
 
 // ---------------------------------------------------------------------------------------------
-// geometry and dynamics (util.py:12-101, optimizer.py:75-100); same closed forms as the oracle
+// the (5a) terms on the geometry of pd_obca.h, and the dynamics (optimizer.py:75-100); same closed
+// forms as the oracle
 // ---------------------------------------------------------------------------------------------
-struct Geo {
-  double e[2], n[2], m[2], mt[2], mL[2][4], mtL[2][4], d[2], dv[2], dvv[2], dt[2], dtt[2], dvt[2], q[2];
-};
-
-__device__ void geo(const double* Xt, const double* Lt, int prob, double sigd, Geo& G) {
-  double v = Xt[2], th = Xt[3];
-  double c = cos(th), s = sin(th);
-  G.e[0] = c; G.e[1] = s; G.n[0] = -s; G.n[1] = c;
-  double sg = prob ? 1.0 : -1.0;
-  double a1 = Lt[0] - Lt[2], a2 = sg * (Lt[1] - Lt[3]);
-  for (int i = 0; i < 2; ++i) {
-    G.m[i] = a1 * G.e[i] + a2 * G.n[i];
-    G.mt[i] = a1 * G.n[i] - a2 * G.e[i];
-    G.mL[i][0] = G.e[i]; G.mL[i][1] = sg * G.n[i]; G.mL[i][2] = -G.e[i]; G.mL[i][3] = -sg * G.n[i];
-    G.mtL[i][0] = G.n[i]; G.mtL[i][1] = -sg * G.e[i]; G.mtL[i][2] = -G.n[i]; G.mtL[i][3] = sg * G.e[i];
-  }
-  if (prob) {
-    double k = sigd * VAR_DELAY * VAR_DELAY, da = AVG_DELAY;
-    G.d[0] = da * v * c + k * v * v * c * c;           G.d[1] = da * v * s + k * v * v * s * s;
-    G.dv[0] = da * c + 2 * k * v * c * c;              G.dv[1] = da * s + 2 * k * v * s * s;
-    G.dvv[0] = 2 * k * c * c;                          G.dvv[1] = 2 * k * s * s;
-    G.dt[0] = -da * v * s - 2 * k * v * v * c * s;     G.dt[1] = da * v * c + 2 * k * v * v * s * c;
-    G.dtt[0] = -da * v * c - 2 * k * v * v * (c * c - s * s);
-    G.dtt[1] = -da * v * s + 2 * k * v * v * (c * c - s * s);
-    G.dvt[0] = -da * s - 4 * k * v * c * s;            G.dvt[1] = da * c + 4 * k * v * s * c;
-  } else {
-    for (int i = 0; i < 2; ++i) G.d[i] = G.dv[i] = G.dvv[i] = G.dt[i] = G.dtt[i] = G.dvt[i] = 0.0;
-  }
-  G.q[0] = Xt[0] + G.d[0];
-  G.q[1] = Xt[1] + G.d[1];
-}
-
-__device__ __forceinline__ double dot2(const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1]; }
-
 // (5a) value and gradient (9); optionally its Hessian (9 x 9, full)
 __device__ double ga_val_grad(const Geo& G, const double* Lt, double ct, double* g) {
   const double B0[4] = {LENGTH / 2, WIDTH / 2, LENGTH / 2, WIDTH / 2};
@@ -283,31 +233,6 @@ __device__ void cost_viol(Ws& S, const double (*X)[NX], const double (*U)[NU], c
   viol = wsum(v);
 }
 
-// ---------------------------------------------------------------------------------------------
-// dense Cholesky (lower, in place) of the leading n x n block of M, lane i owning row i: per
-// column a pivot read, the column scaled by its owners, then each owner updates its own row
-// (the same operation order per entry as the right-looking form); false if a pivot is <= thr^2
-// (thr = 0: not positive).
-__device__ bool chol_n(double (*M)[NZP], int n, double thr) {
-  int lane = threadIdx.x;
-  for (int j = 0; j < n; ++j) {
-    SYNC();
-    double piv = M[j][j];
-    if (!(piv > 0.0)) { SYNC(); return false; }
-    double l = sqrt(piv);
-    if (!(l > thr)) { SYNC(); return false; }
-    double lij = 0.0;
-    if (lane > j && lane < n) { lij = M[lane][j] / l; M[lane][j] = lij; }
-    if (lane == j) M[j][j] = l;
-    SYNC();
-    if (lane > j && lane < n)
-      for (int k = j + 1; k <= lane; ++k) M[lane][k] -= lij * M[k][j];
-  }
-  SYNC();
-  return true;
-}
-__device__ __forceinline__ bool chol(Ws& S) { return chol_n(S.Hm, NZ, 0.0); }
-
 // row c of the constraint matrix (C z >= din) dotted with v (28)
 __device__ double row_dot(const Ws& S, int c, const double* v) {
   if (c >= ROWS_T * NT) {            // control rows: u_j >= lo | -u_j >= -hi (ROWS_T * NT is odd)
@@ -358,134 +283,18 @@ __device__ __forceinline__ double wval(const WsG& Q, int t, int i, int j) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Goldfarb-Idnani on min 1/2 z'Hz + gq'z, C z >= din (no equalities); H = L L' in S.Hm.
-// Returns 0 ok, 2 infeasible, 1 step limit; S.x = solution, S.uin = multipliers (dense).
+// The QP min 1/2 z'Hz + gq'z, C z >= din (no equalities; H = L L' in S.Hm) as pd_obca.h's active-set
+// core sees it: gi_drop, gi_add and the opening and closing of gi_solve are stated there.
 // ---------------------------------------------------------------------------------------------
-// Lane ownership inside the active-set updates: lane i owns row i of J (every Givens rotation of a
-// J column pair is row-local), lane c owns column c of R during a drop's rotations; rotation
-// parameters are uniform (computed by every lane from LDS / a shuffle), so the rotation chains run
-// without barriers.
-__device__ void gi_drop(Ws& S, int k) {
-  int lane = threadIdx.x;
-  SYNC();
-  int q = S.nact;
-  // remove column k of R (row-owned shift)
-  if (lane < NZ) {
-    for (int j = k; j < q - 1; ++j) S.R[lane][j] = S.R[lane][j + 1];
-    S.R[lane][q - 1] = 0.0;
-  }
-  SYNC();
-  for (int j = k; j < q - 1; ++j) {
-    // column j is lane j's: its (R[j][j], R[j+1][j]) after the previous rotations
-    double aj = (lane < NZ) ? S.R[j][lane] : 0.0;
-    double bj = (lane < NZ) ? S.R[j + 1][lane] : 0.0;
-    double a = __shfl(aj, j, 64), b = __shfl(bj, j, 64);
-    double h = hypot(a, b);
-    if (h != 0.0) {
-      double cs = a / h, sn = b / h;
-      if (lane >= j && lane < q - 1) {
-        S.R[j][lane] = cs * aj + sn * bj;
-        S.R[j + 1][lane] = -sn * aj + cs * bj;
-      }
-      if (lane < NZ) {
-        double Jj = S.J[lane][j], Jj1 = S.J[lane][j + 1];
-        S.J[lane][j] = cs * Jj + sn * Jj1;
-        S.J[lane][j + 1] = -sn * Jj + cs * Jj1;
-      }
-    }
-  }
-  SYNC();
-  if (lane == 0) {
-    for (int j = k; j < q - 1; ++j) { S.act[j] = S.act[j + 1]; S.u[j] = S.u[j + 1]; }
-    S.nact = q - 1;
-  }
-  SYNC();
-}
-
-// returns 1 added, 0 infeasible, -1 step limit
-__device__ int gi_add(Ws& S, int p, int& steps) {
-  int lane = threadIdx.x;
-  double up = 0.0;
-  const double bp = S.din[p];
-  SYNC();
-  if (lane < NZ) S.npv[lane] = row_elem(S, p, lane);
-  SYNC();
-  const double npl = (lane < NZ) ? S.npv[lane] : 0.0;
-  while (true) {
-    if (++steps > 500) return -1;
-    const int q = S.nact;
-    // d = J' n_p (lane j)
-    double dj = 0.0;
-    if (lane < NZ)
-      for (int i = 0; i < NZ; ++i) dj += S.J[i][lane] * S.npv[i];
-    if (lane < NZ) S.d[lane] = dj;
-    SYNC();
-    // z = J[:, q:] d[q:] (lane i)
-    double zi = 0.0;
-    if (lane < NZ)
-      for (int j = q; j < NZ; ++j) zi += S.J[lane][j] * S.d[j];
-    // r = R^-1 d[:q]: back substitution on the lanes' registers (lane k ends with r_k)
-    double ddk = (lane < q) ? dj : 0.0, rk = 0.0;
-    for (int j = q - 1; j >= 0; --j) {
-      double rj = __shfl(ddk, j, 64) / S.R[j][j];
-      if (lane == j) rk = rj;
-      if (lane < j) ddk -= S.R[lane][j] * rj;
-    }
-    // partial step t1 over active rows with r_k > 1e-13 max(1, max|r|)
-    const double rmax = fmax(1.0, wmax(lane < q ? fabs(rk) : 0.0));
-    double t1v = INFINITY;
-    int l = -1;
-    if (lane < q && rk > 1e-13 * rmax) { t1v = S.u[lane] / rk; l = lane; }
-    wargmin(t1v, l);
-    const double t1 = (l >= 0) ? t1v : INFINITY;
-    // full step t2
-    const double xl = (lane < NZ) ? S.x[lane] : 0.0;
-    const double zn = wsum(zi * npl);
-    const double dd2 = wsum(dj * dj);
-    const double sx = wsum(npl * xl) - bp;
-    const double t2 = (zn > 1e-12 * dd2) ? -sx / zn : INFINITY;
-    const double t = fmin(t1, t2);
-    if (t == INFINITY) return 0;
-    if (t2 == INFINITY) {
-      if (lane < q) S.u[lane] -= t * rk;
-      up += t;
-      gi_drop(S, l);
-      continue;
-    }
-    if (lane < NZ) S.x[lane] = xl + t * zi;
-    if (lane < q) S.u[lane] -= t * rk;
-    up += t;
-    if (t == t2) {
-      // one Householder reflection of J[:, q:] zeroing d[q+1..] (uniform v, each lane its own row)
-      double alpha = S.d[q];
-      if (q < NZ - 1) {
-        double ss = 0.0;
-        for (int j = q + 1; j < NZ; ++j) ss += S.d[j] * S.d[j];
-        if (ss > 0.0) {
-          const double a0 = S.d[q];
-          const double sig = sqrt(a0 * a0 + ss);
-          alpha = (a0 > 0.0) ? -sig : sig;
-          const double v0 = a0 - alpha;
-          const double beta = 1.0 / (sig * (sig + fabs(a0)));     // 2 / v'v
-          if (lane < NZ) {
-            double sv = S.J[lane][q] * v0;
-            for (int j = q + 1; j < NZ; ++j) sv += S.J[lane][j] * S.d[j];
-            sv *= beta;
-            S.J[lane][q] -= sv * v0;
-            for (int j = q + 1; j < NZ; ++j) S.J[lane][j] -= sv * S.d[j];
-          }
-        }
-      }
-      if (lane < q) S.R[lane][q] = S.d[lane];
-      if (lane == q) S.R[q][q] = alpha;
-      SYNC();
-      if (lane == 0) { S.act[q] = p; S.u[q] = up; S.nact = q + 1; }
-      SYNC();
-      return 1;
-    }
-    gi_drop(S, l);
-  }
-}
+struct QP {
+  using State = Ws;
+  static constexpr int N = NZ, NP = NZP, NEQ = 0, NROW = obca::NROW;
+  static __device__ __forceinline__ int lane() { return threadIdx.x; }
+  static __device__ __forceinline__ void fence() { SYNC(); }
+  static __device__ __forceinline__ double elem(const Ws& S, int p, int k) { return row_elem(S, p, k); }
+  static __device__ __forceinline__ double rhs(const Ws& S, int p) { return S.din[p]; }
+};
+__device__ __forceinline__ bool chol(Ws& S) { return chol_n<QP>(S.Hm, NZ, 0.0); }
 
 // ---------------------------------------------------------------------------------------------
 // warm equality solve (oracle warm_eqp): the previous SQP iteration's active rows W as the QP's
@@ -530,7 +339,7 @@ __device__ bool warm_eqp(Ws& S) {
   }
   SYNC();
   const double dmax = wmax(lane < m ? S.Hm[lane][lane] : 0.0);
-  if (!chol_n(S.Hm, m, 1e-7 * sqrt(dmax))) return false;
+  if (!chol_n<QP>(S.Hm, m, 1e-7 * sqrt(dmax))) return false;
   // lam
   double lam = 0.0;
   if (lane < m) {
@@ -587,57 +396,26 @@ __device__ bool warm_eqp(Ws& S) {
 
 __device__ int gi_solve(Ws& S, int& steps) {
   int lane = threadIdx.x;
-  // J = L^-T: lane j solves L y = e_j, J[:, j]... J = (L^-1)'  =>  J[i][j] = (L^-1)[j][i]
-  if (lane < NZ) {
-    // column j of L^-1 (forward substitution of L y = e_j) is row j of J; each lane owns its row
-    int j = lane;
-    double* y = S.J[j];
-    for (int i = 0; i < NZ; ++i) {
-      if (i < j) { y[i] = 0.0; continue; }
-      double s = (i == j) ? 1.0 : 0.0;
-      for (int k = j; k < i; ++k) s -= S.Hm[i][k] * y[k];
-      y[i] = s / S.Hm[i][i];
-    }
-  }
-  SYNC();
-  // x = -J J' g
-  if (lane < NZ) {
-    double s = 0.0;
-    for (int i = 0; i < NZ; ++i) s += S.J[i][lane] * S.gq[i];
-    S.dd[lane] = s;
-  }
-  SYNC();
+  gi_factor<QP>(S, S.gq);
   if (S.npact > 0 && warm_eqp(S)) {
     steps = 0;
   } else {
-  if (lane < NZ) {
-    double s = 0.0;
-    for (int j = 0; j < NZ; ++j) s += S.J[lane][j] * S.dd[j];
-    S.x[lane] = -s;
-  }
-  for (int e = lane; e < NZ * NZ; e += 64) S.R[e / NZ][e % NZ] = 0.0;
-  if (lane == 0) S.nact = 0;
-  SYNC();
-  while (true) {
-    double best = INFINITY;
-    int bi = -1;
-    for (int c = lane; c < NROW; c += 64) {
-      double s = row_dot(S, c, S.x) - S.din[c];
-      if (bi < 0 || s < best) { best = s; bi = c; }
+    gi_start<QP>(S);
+    while (true) {
+      double best = INFINITY;
+      int bi = -1;
+      for (int c = lane; c < NROW; c += 64) {
+        double s = row_dot(S, c, S.x) - S.din[c];
+        if (bi < 0 || s < best) { best = s; bi = c; }
+      }
+      wargmin(best, bi);
+      if (!(best < -1e-11 * (1.0 + fabs(S.din[bi])))) break;
+      int ok = gi_add<QP>(S, bi, steps);
+      if (ok < 0) return 1;
+      if (ok == 0) return 2;
     }
-    wargmin(best, bi);
-    if (!(best < -1e-11 * (1.0 + fabs(S.din[bi])))) break;
-    int ok = gi_add(S, bi, steps);
-    if (ok < 0) return 1;
-    if (ok == 0) return 2;
   }
-  }
-  SYNC();
-  for (int c = lane; c < NROW; c += 64) S.uin[c] = 0.0;
-  SYNC();
-  if (lane == 0)
-    for (int k = 0; k < S.nact; ++k) S.uin[S.act[k]] = S.u[k];
-  SYNC();
+  gi_multipliers<QP>(S);
   return 0;
 }
 
@@ -654,23 +432,23 @@ __device__ __forceinline__ void sqp_one(Ws& S, int pb, const double* __restrict_
   const double* rec = recs + (size_t)pb * REC;
 
   // ---- load the record, derive w_t = A_o' lamb_ij, c_t = b_o' lamb_ij ----
-  if (lane < NX) S.init[lane] = rec[lane];
-  for (int e = lane; e < NH * NX; e += 64) (&S.ref[0][0])[e] = rec[5 + e];
+  if (lane < NX) S.init[lane] = rec[R_INIT + lane];
+  for (int e = lane; e < NH * NX; e += 64) (&S.ref[0][0])[e] = rec[R_REF + e];
   for (int e = lane; e < NT * 9; e += 64) {
-    (&S.lb[0][0])[e] = rec[157 + e];
-    (&S.zb[0][0])[e] = rec[220 + e];
+    (&S.lb[0][0])[e] = rec[R_LB + e];
+    (&S.zb[0][0])[e] = rec[R_ZB + e];
   }
   if (lane < NT) {
     int t = lane;
-    const double* Ao = rec + 45 + t * 8;
-    const double* bo = rec + 101 + t * 4;
-    const double* lij = rec + 129 + t * 4;
+    const double* Ao = rec + R_AO + t * 8;
+    const double* bo = rec + R_BO + t * 4;
+    const double* lij = rec + R_LIJ + t * 4;
     double w0 = 0.0, w1 = 0.0, cc = 0.0;
     for (int i = 0; i < 4; ++i) { w0 += Ao[i * 2 + 0] * lij[i]; w1 += Ao[i * 2 + 1] * lij[i]; cc += bo[i] * lij[i]; }
     S.w[t][0] = w0; S.w[t][1] = w1; S.c[t] = cc;
   }
   if (lane == 0) {
-    const double* par = rec + 283;
+    const double* par = rec + R_PAR;
     S.rho = par[0]; S.min_dis = par[1]; S.max_x = par[2]; S.max_y = par[3];
     S.rr = par[4]; S.qq = par[5]; S.prob = (int)par[6]; S.max_iter = (int)par[7];
     S.sig_delay = sqrt(0.95 / (1.0 - 0.95));
@@ -1129,16 +907,16 @@ __device__ __forceinline__ void sqp_one(Ws& S, int pb, const double* __restrict_
   cost_viol(S, S.X, S.U, S.L, fc, vc);
   // ---- write out ----
   double* o = out + (size_t)pb * OUT;
-  for (int e = lane; e < NH * NX; e += 64) o[e] = (&S.X[0][0])[e];
-  if (lane < NUV) o[40 + lane] = (&S.U[0][0])[lane];
-  if (lane < NT * NL) o[54 + lane] = (&S.L[0][0])[lane];
-  if (lane < NT) { o[82 + lane] = S.ya[lane]; o[89 + 2 * lane] = S.yb[lane][0]; o[90 + 2 * lane] = S.yb[lane][1]; o[103 + lane] = S.yn[lane]; }
-  for (int e = lane; e < NT * NX; e += 64) { o[110 + e] = (&S.yx[0][0])[e]; o[145 + e] = (&S.pi[0][0])[e]; }
-  if (lane < NUV) o[180 + lane] = S.yu[lane];
-  if (lane < NT * NL) o[194 + lane] = (&S.yl[0][0])[lane];
+  for (int e = lane; e < NH * NX; e += 64) o[O_X + e] = (&S.X[0][0])[e];
+  if (lane < NUV) o[O_U + lane] = (&S.U[0][0])[lane];
+  if (lane < NT * NL) o[O_LAM + lane] = (&S.L[0][0])[lane];
+  if (lane < NT) { o[O_YA + lane] = S.ya[lane]; o[O_YB + 2 * lane] = S.yb[lane][0]; o[O_YB + 2 * lane + 1] = S.yb[lane][1]; o[O_YN + lane] = S.yn[lane]; }
+  for (int e = lane; e < NT * NX; e += 64) { o[O_YX + e] = (&S.yx[0][0])[e]; o[O_PI + e] = (&S.pi[0][0])[e]; }
+  if (lane < NUV) o[O_YU + lane] = S.yu[lane];
+  if (lane < NT * NL) o[O_YL + lane] = (&S.yl[0][0])[lane];
   if (lane == 0) {
-    o[222] = fc;
-    o[223] = 0.0;
+    o[O_COST] = fc;
+    o[O_COST + 1] = 0.0;
     ist[(size_t)pb * 3 + 0] = status;
     ist[(size_t)pb * 3 + 1] = (it < max_iter) ? it + 1 : max_iter;
     ist[(size_t)pb * 3 + 2] = qp_total;
@@ -1173,19 +951,7 @@ __global__ void __launch_bounds__(64) k_obca_sqp(const double* __restrict__ recs
 // ---------------------------------------------------------------------------------------------
 // C-ABI (include/piadmm.h)
 // ---------------------------------------------------------------------------------------------
-#include "piadmm_obca_handle.h"
-
 namespace {
-int fail(piadmm_obca_t h, int code, const std::string& msg) {
-  if (h) h->err = msg;
-  return code;
-}
-#define OHIP(h, call)                                                                 \
-  do {                                                                                \
-    hipError_t _e = (call);                                                           \
-    if (_e != hipSuccess) return fail(h, PIADMM_E_HIP, std::string(#call ": ") + hipGetErrorString(_e)); \
-  } while (0)
-
 int ensure(piadmm_obca_t h, int n) {
   if (n <= h->cap) return 0;
   h->cap = 0;
@@ -1207,7 +973,7 @@ int ensure(piadmm_obca_t h, int n) {
 int check_recs(piadmm_obca_t h, const double* recs, int n) {
   // host-side shape checks before any launch: parameters the kernel's bounds assume
   for (int i = 0; i < n; ++i) {
-    const double* par = recs + (size_t)i * obca::REC + 283;
+    const double* par = recs + (size_t)i * obca::REC + obca::R_PAR;
     if (!(par[0] > 0.0) || !(par[4] > 0.0) || !(par[5] > 0.0) || (par[6] != 0.0 && par[6] != 1.0) ||
         !(par[7] >= 1.0 && par[7] <= 1000.0) || !(par[2] > 0.0) || !(par[3] > 0.0))
       return fail(h, PIADMM_E_ARG, "obca record " + std::to_string(i) + ": bad parameters (rho, r, q > 0; prob 0/1; 1 <= max_iter <= 1000)");
@@ -1226,23 +992,23 @@ int schedule(piadmm_obca_t h) {
   if (h->cost_n == n) {
     // the last solve's work (waits for its launches: the batch is rescheduled between runs)
     h->cost.resize((size_t)3 * n);
-    OHIP(h, hipMemcpyAsync(h->cost.data(), h->d_ist, (size_t)n * 3 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    OHIP(h, hipStreamSynchronize(h->stream));
+    OWN_HIP(h, hipMemcpyAsync(h->cost.data(), h->d_ist, (size_t)n * 3 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    OWN_HIP(h, hipStreamSynchronize(h->stream));
     const int* c = h->cost.data();
     std::stable_sort(h->order.begin(), h->order.end(), [&](int a, int b) {
       if (c[3 * a + 2] != c[3 * b + 2]) return c[3 * a + 2] > c[3 * b + 2];
       return c[3 * a + 1] > c[3 * b + 1];
     });
   }
-  OHIP(h, hipStreamSynchronize(h->stream));    // no earlier launch still reads the order
-  OHIP(h, hipMemcpy(h->d_order, h->order.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+  OWN_HIP(h, hipStreamSynchronize(h->stream));    // no earlier launch still reads the order
+  OWN_HIP(h, hipMemcpy(h->d_order, h->order.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
   return 0;
 }
 
 int launch(piadmm_obca_t h) {
   hipLaunchKernelGGL(obca::k_obca_sqp, dim3(h->n), dim3(64), 0, h->stream, h->d_rec, h->n, h->d_out, h->d_ist,
                      h->d_stamps, reinterpret_cast<obca::WsG*>(h->d_qg.get()), h->d_order);
-  OHIP(h, hipGetLastError());
+  OWN_HIP(h, hipGetLastError());
   return 0;
 }
 
@@ -1260,7 +1026,7 @@ int piadmm_obca_local_launch(piadmm_obca_t h, int n) {
   if (n <= 0 || n > h->cap) return fail(h, PIADMM_E_STATE, "obca local launch: n outside the buffers");
   hipLaunchKernelGGL(obca::k_obca_sqp, dim3(n), dim3(64), 0, h->stream, h->d_rec, n, h->d_out, h->d_ist,
                      h->d_stamps, reinterpret_cast<obca::WsG*>(h->d_qg.get()), h->d_order);
-  OHIP(h, hipGetLastError());
+  OWN_HIP(h, hipGetLastError());
   return 0;
 }
 
@@ -1297,7 +1063,7 @@ int32_t piadmm_obca_upload(piadmm_obca_t h, const double* recs, int32_t n) {
   if (!h) return PIADMM_E_ARG;
   if (!recs || n <= 0) return fail(h, PIADMM_E_ARG, "obca_upload: recs / n");
   if (int rc = check_recs(h, recs, n)) return rc;
-  OHIP(h, hipSetDevice(h->device));
+  OWN_HIP(h, hipSetDevice(h->device));
   // the buffers go back to the resident batch: an open plan ends here
   piadmm_obca_plan_release(h);
   h->plan_taken = false;
@@ -1308,8 +1074,8 @@ int32_t piadmm_obca_upload(piadmm_obca_t h, const double* recs, int32_t n) {
   // size is the same), so the next run goes in index order and records this batch's work
   h->cost_n = 0;
   if (int rc = ensure(h, n)) return rc;
-  OHIP(h, hipMemcpyAsync(h->d_rec, recs, (size_t)n * obca::REC * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  OHIP(h, hipStreamSynchronize(h->stream));
+  OWN_HIP(h, hipMemcpyAsync(h->d_rec, recs, (size_t)n * obca::REC * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  OWN_HIP(h, hipStreamSynchronize(h->stream));
   h->n = n;
   return 0;
 }
@@ -1317,7 +1083,7 @@ int32_t piadmm_obca_upload(piadmm_obca_t h, const double* recs, int32_t n) {
 int32_t piadmm_obca_run(piadmm_obca_t h, int32_t repeats) {
   if (!h) return PIADMM_E_ARG;
   if (h->n <= 0) return fail(h, PIADMM_E_STATE, "obca_run before obca_upload");
-  OHIP(h, hipSetDevice(h->device));
+  OWN_HIP(h, hipSetDevice(h->device));
   if (int rc = schedule(h)) return rc;
   for (int r = 0; r < repeats; ++r)
     if (int rc = launch(h)) return rc;
@@ -1327,15 +1093,15 @@ int32_t piadmm_obca_run(piadmm_obca_t h, int32_t repeats) {
 int32_t piadmm_obca_time(piadmm_obca_t h, int32_t repeats, float* ms) {
   if (!h || !ms || repeats <= 0) return PIADMM_E_ARG;
   if (h->n <= 0) return fail(h, PIADMM_E_STATE, "obca_time before obca_upload");
-  OHIP(h, hipSetDevice(h->device));
+  OWN_HIP(h, hipSetDevice(h->device));
   if (int rc = schedule(h)) return rc;
-  OHIP(h, hipEventRecord(h->e0, h->stream));
+  OWN_HIP(h, hipEventRecord(h->e0, h->stream));
   for (int r = 0; r < repeats; ++r)
     if (int rc = launch(h)) return rc;
-  OHIP(h, hipEventRecord(h->e1, h->stream));
-  OHIP(h, hipEventSynchronize(h->e1));
+  OWN_HIP(h, hipEventRecord(h->e1, h->stream));
+  OWN_HIP(h, hipEventSynchronize(h->e1));
   float t = 0.f;
-  OHIP(h, hipEventElapsedTime(&t, h->e0, h->e1));
+  OWN_HIP(h, hipEventElapsedTime(&t, h->e0, h->e1));
   *ms = t / (float)repeats;
   return record_cost(h);
 }
@@ -1344,10 +1110,10 @@ int32_t piadmm_obca_download(piadmm_obca_t h, double* out, int32_t* status3, int
   if (!h) return PIADMM_E_ARG;
   if (h->plan_taken) return fail(h, PIADMM_E_STATE, "obca_download: a plan took the buffers over (obca_upload first)");
   if (n != h->n || !out || !status3) return fail(h, PIADMM_E_ARG, "obca_download: n must equal the uploaded batch");
-  OHIP(h, hipSetDevice(h->device));
-  OHIP(h, hipMemcpyAsync(out, h->d_out, (size_t)n * obca::OUT * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  OHIP(h, hipMemcpyAsync(status3, h->d_ist, (size_t)n * 3 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  OHIP(h, hipStreamSynchronize(h->stream));
+  OWN_HIP(h, hipSetDevice(h->device));
+  OWN_HIP(h, hipMemcpyAsync(out, h->d_out, (size_t)n * obca::OUT * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(status3, h->d_ist, (size_t)n * 3 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  OWN_HIP(h, hipStreamSynchronize(h->stream));
   return 0;
 }
 
@@ -1355,9 +1121,9 @@ int32_t piadmm_obca_debug_stamps(piadmm_obca_t h, uint64_t* out, int32_t n) {
   if (!h) return PIADMM_E_ARG;
   if (!h->d_stamps) return fail(h, PIADMM_E_STATE, "not a stamps build (make stamps)");
   if (n != h->n * obca::NSTAMP) return fail(h, PIADMM_E_ARG, "obca_debug_stamps: n must be 16 x the batch");
-  OHIP(h, hipSetDevice(h->device));
-  OHIP(h, hipMemcpyAsync(out, h->d_stamps, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
-  OHIP(h, hipStreamSynchronize(h->stream));
+  OWN_HIP(h, hipSetDevice(h->device));
+  OWN_HIP(h, hipMemcpyAsync(out, h->d_stamps, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+  OWN_HIP(h, hipStreamSynchronize(h->stream));
   return 0;
 }
 

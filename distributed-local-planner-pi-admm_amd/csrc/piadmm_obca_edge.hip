@@ -28,20 +28,17 @@
 #include <cstdint>
 #include <string>
 
+#include "pd_obca.h"
 #include "piadmm.h"
 #include "piadmm_obca_handle.h"
 
 namespace obca_edge {
 
-constexpr int NT = 7, NE = 18, NEP = NE + 1, NROW = 2 + 2 * NE, NEQ = 2;
+using namespace pd_obca;     // NT, the constants, the layouts, the reductions, Geo, the QP core
+constexpr int NE = 18, NEP = NE + 1, NROW = 2 + 2 * NE, NEQ = 2;
 constexpr int EW = 4;                          // waves (slot problems) per workgroup
 constexpr int REC = PIADMM_OBCA_EDGE_REC, OUT = PIADMM_OBCA_EDGE_OUT;
-constexpr int O_LX = 0, O_LIJ = 70, O_LB = 126, O_PAR = 252;
-constexpr int OO_Z = 0, OO_ZB = 126, OO_LBN = 252, OO_YEQ = 378, OO_YIN = 392, OO_YBND = 399, OO_COST = 525,
-              OO_DRES = 532;
 
-constexpr double LENGTH = 3.5, WIDTH = 2.0;
-constexpr double AVG_DELAY = 0.05, VAR_DELAY = 0.025;
 constexpr double TOL_STEP = 1e-9, TOL_FEAS = 1e-9, ARMIJO = 1e-4;
 constexpr int MAX_HALVINGS = 30;
 
@@ -59,70 +56,11 @@ struct Es {
   int act[NE + 1], pact[NROW];
   int nact, npact;
 };
-
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double wmax(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
-// min value, lowest index on ties (idx < 0 = none)
-__device__ __forceinline__ void wargmin(double& v, int& i) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    double v2 = __shfl_xor(v, o, 64);
-    int i2 = __shfl_xor(i, o, 64);
-    bool take = (i2 >= 0) && (i < 0 || v2 < v || (v2 == v && i2 < i));
-    if (take) { v = v2; i = i2; }
-  }
-}
+static_assert(EW * sizeof(Es) <= 160 * 1024 / 2, "OBCA edge workspace: two workgroups per CU");
 
 // The wave's own LDS slice is shared among its 64 lanes only: LDS operations of one wave execute
 // in order, so a compiler-level fence is what a write -> read by another lane needs.
 #define WSYNC() do { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); __builtin_amdgcn_wave_barrier(); } while (0)
-
-// ---------------------------------------------------------------------------------------------
-// geometry of one vehicle (util.py:12-101); the closed forms of csrc/piadmm_obca.hip
-// ---------------------------------------------------------------------------------------------
-struct Geo {
-  double m[2], mt[2], mL[2][4], mtL[2][4], d[2], dv[2], dvv[2], dt[2], dtt[2], dvt[2], q[2];
-};
-
-__device__ __forceinline__ void geo(const double* Xt, const double* Lt, int prob, double sigd, Geo& G) {
-  double v = Xt[2], th = Xt[3];
-  double c = cos(th), s = sin(th);
-  double e[2] = {c, s}, n[2] = {-s, c};
-  double sg = prob ? 1.0 : -1.0;
-  double a1 = Lt[0] - Lt[2], a2 = sg * (Lt[1] - Lt[3]);
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    G.m[i] = a1 * e[i] + a2 * n[i];
-    G.mt[i] = a1 * n[i] - a2 * e[i];
-    G.mL[i][0] = e[i]; G.mL[i][1] = sg * n[i]; G.mL[i][2] = -e[i]; G.mL[i][3] = -sg * n[i];
-    G.mtL[i][0] = n[i]; G.mtL[i][1] = -sg * e[i]; G.mtL[i][2] = -n[i]; G.mtL[i][3] = sg * e[i];
-  }
-  if (prob) {
-    double k = sigd * VAR_DELAY * VAR_DELAY, da = AVG_DELAY;
-    G.d[0] = da * v * c + k * v * v * c * c;           G.d[1] = da * v * s + k * v * v * s * s;
-    G.dv[0] = da * c + 2 * k * v * c * c;              G.dv[1] = da * s + 2 * k * v * s * s;
-    G.dvv[0] = 2 * k * c * c;                          G.dvv[1] = 2 * k * s * s;
-    G.dt[0] = -da * v * s - 2 * k * v * v * c * s;     G.dt[1] = da * v * c + 2 * k * v * v * s * c;
-    G.dtt[0] = -da * v * c - 2 * k * v * v * (c * c - s * s);
-    G.dtt[1] = -da * v * s + 2 * k * v * v * (c * c - s * s);
-    G.dvt[0] = -da * s - 4 * k * v * c * s;            G.dvt[1] = da * c + 4 * k * v * s * c;
-  } else {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) G.d[i] = G.dv[i] = G.dvv[i] = G.dt[i] = G.dtt[i] = G.dvt[i] = 0.0;
-  }
-  G.q[0] = Xt[0] + G.d[0];
-  G.q[1] = Xt[1] + G.d[1];
-}
-
-__device__ __forceinline__ double dot2(const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1]; }
 
 // this vehicle's term of g_in: -b(s)' mu
 __device__ __forceinline__ double ga_val(const Geo& G, const double* Lt) {
@@ -151,27 +89,6 @@ __device__ void point_eval(const Es& S, const double* zz, int prob, double sigd,
   cost = wsum(cv);
 }
 
-// ---------------------------------------------------------------------------------------------
-// dense Cholesky (lower, in place) of M, lane i owning row i; false if a pivot is not positive
-// ---------------------------------------------------------------------------------------------
-__device__ bool chol(double (*M)[NEP]) {
-  const int lane = threadIdx.x & 63;
-  for (int j = 0; j < NE; ++j) {
-    WSYNC();
-    double piv = M[j][j];
-    if (!(piv > 0.0)) { WSYNC(); return false; }
-    double l = sqrt(piv);
-    double lij = 0.0;
-    if (lane > j && lane < NE) { lij = M[lane][j] / l; M[lane][j] = lij; }
-    if (lane == j) M[j][j] = l;
-    WSYNC();
-    if (lane > j && lane < NE)
-      for (int k = j + 1; k <= lane; ++k) M[lane][k] -= lij * M[k][j];
-  }
-  WSYNC();
-  return true;
-}
-
 // inequality row c of C d >= din: 0 / 1 the range row (+gin / -gin), then per variable j the
 // lower (2 + 2j: +e_j) and upper (3 + 2j: -e_j) bound
 __device__ __forceinline__ double row_elem(const Es& S, int c, int k) {
@@ -197,165 +114,33 @@ __device__ __forceinline__ double con_rhs(const Es& S, int p) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Goldfarb-Idnani (the active-set code of csrc/piadmm_obca.hip at 18 variables, with equalities)
+// The QP as pd_obca.h's active-set core sees it: gi_drop, gi_add and the opening and closing of
+// gi_solve are stated there; the equalities are seeded here.
 // ---------------------------------------------------------------------------------------------
-__device__ void gi_drop(Es& S, int k) {
-  const int lane = threadIdx.x & 63;
-  WSYNC();
-  const int q = S.nact;
-  if (lane < NE) {
-    for (int j = k; j < q - 1; ++j) S.R[lane][j] = S.R[lane][j + 1];
-    S.R[lane][q - 1] = 0.0;
-  }
-  WSYNC();
-  for (int j = k; j < q - 1; ++j) {
-    double aj = (lane < NE) ? S.R[j][lane] : 0.0;
-    double bj = (lane < NE) ? S.R[j + 1][lane] : 0.0;
-    double a = __shfl(aj, j, 64), b = __shfl(bj, j, 64);
-    double h = hypot(a, b);
-    if (h != 0.0) {
-      double cs = a / h, sn = b / h;
-      if (lane >= j && lane < q - 1) {
-        S.R[j][lane] = cs * aj + sn * bj;
-        S.R[j + 1][lane] = -sn * aj + cs * bj;
-      }
-      if (lane < NE) {
-        double Jj = S.J[lane][j], Jj1 = S.J[lane][j + 1];
-        S.J[lane][j] = cs * Jj + sn * Jj1;
-        S.J[lane][j + 1] = -sn * Jj + cs * Jj1;
-      }
-    }
-    WSYNC();
-  }
-  WSYNC();
-  if (lane == 0) {
-    for (int j = k; j < q - 1; ++j) { S.act[j] = S.act[j + 1]; S.u[j] = S.u[j + 1]; }
-    S.nact = q - 1;
-  }
-  WSYNC();
-}
-
-// returns 1 added, 0 infeasible, -1 step limit
-__device__ int gi_add(Es& S, int p, int& steps) {
-  const int lane = threadIdx.x & 63;
-  double up = 0.0;
-  const double bp = con_rhs(S, p);
-  WSYNC();
-  if (lane < NE) S.npv[lane] = con_elem(S, p, lane);
-  WSYNC();
-  const double npl = (lane < NE) ? S.npv[lane] : 0.0;
-  while (true) {
-    if (++steps > 500) return -1;
-    WSYNC();
-    const int q = S.nact;
-    double dj = 0.0;
-    if (lane < NE)
-      for (int i = 0; i < NE; ++i) dj += S.J[i][lane] * S.npv[i];
-    if (lane < NE) S.d[lane] = dj;
-    WSYNC();
-    double zi = 0.0;
-    if (lane < NE)
-      for (int j = q; j < NE; ++j) zi += S.J[lane][j] * S.d[j];
-    // r = R^-1 d[:q]: back substitution on the lanes' registers (lane k ends with r_k)
-    double ddk = (lane < q) ? dj : 0.0, rk = 0.0;
-    for (int j = q - 1; j >= 0; --j) {
-      double rj = __shfl(ddk, j, 64) / S.R[j][j];
-      if (lane == j) rk = rj;
-      if (lane < j) ddk -= S.R[lane][j] * rj;
-    }
-    // partial step t1 over the active inequalities with r_k > 1e-13 max(1, max|r|)
-    const double rmax = fmax(1.0, wmax(lane < q ? fabs(rk) : 0.0));
-    double t1v = INFINITY;
-    int l = -1;
-    if (lane < q && S.act[lane] >= NEQ && rk > 1e-13 * rmax) { t1v = S.u[lane] / rk; l = lane; }
-    wargmin(t1v, l);
-    const double t1 = (l >= 0) ? t1v : INFINITY;
-    const double xl = (lane < NE) ? S.x[lane] : 0.0;
-    const double zn = wsum(zi * npl);
-    const double dd2 = wsum(dj * dj);
-    const double sx = wsum(npl * xl) - bp;
-    const double t2 = (zn > 1e-12 * dd2) ? -sx / zn : INFINITY;
-    const double t = fmin(t1, t2);
-    if (t == INFINITY) return 0;
-    if (t2 == INFINITY) {
-      if (lane < q) S.u[lane] -= t * rk;
-      up += t;
-      gi_drop(S, l);
-      continue;
-    }
-    if (lane < NE) S.x[lane] = xl + t * zi;
-    if (lane < q) S.u[lane] -= t * rk;
-    up += t;
-    if (t == t2) {
-      // one Householder reflection of J[:, q:] zeroing d[q+1..] (uniform v, each lane its own row)
-      double alpha = S.d[q];
-      if (q < NE - 1) {
-        double ss = 0.0;
-        for (int j = q + 1; j < NE; ++j) ss += S.d[j] * S.d[j];
-        if (ss > 0.0) {
-          const double a0 = S.d[q];
-          const double sig = sqrt(a0 * a0 + ss);
-          alpha = (a0 > 0.0) ? -sig : sig;
-          const double v0 = a0 - alpha;
-          const double beta = 1.0 / (sig * (sig + fabs(a0)));
-          if (lane < NE) {
-            double sv = S.J[lane][q] * v0;
-            for (int j = q + 1; j < NE; ++j) sv += S.J[lane][j] * S.d[j];
-            sv *= beta;
-            S.J[lane][q] -= sv * v0;
-            for (int j = q + 1; j < NE; ++j) S.J[lane][j] -= sv * S.d[j];
-          }
-        }
-      }
-      if (lane < q) S.R[lane][q] = S.d[lane];
-      if (lane == q) S.R[q][q] = alpha;
-      WSYNC();
-      if (lane == 0) { S.act[q] = p; S.u[q] = up; S.nact = q + 1; }
-      WSYNC();
-      return 1;
-    }
-    gi_drop(S, l);
-  }
-}
+struct QP {
+  using State = Es;
+  static constexpr int N = NE, NP = NEP, NEQ = obca_edge::NEQ, NROW = obca_edge::NROW;
+  static __device__ __forceinline__ int lane() { return threadIdx.x & 63; }
+  static __device__ __forceinline__ void fence() { WSYNC(); }
+  static __device__ __forceinline__ double elem(const Es& S, int p, int k) { return con_elem(S, p, k); }
+  static __device__ __forceinline__ double rhs(const Es& S, int p) { return con_rhs(S, p); }
+};
+// false if a pivot is not positive
+__device__ __forceinline__ bool chol(double (*M)[NEP]) { return chol_n<QP>(M, NE, 0.0); }
 
 // min 1/2 d'Hd + gm'd, Jeq d = deq, C d >= din; H = L L' in S.Hm.  0 ok, 2 infeasible, 1 step
 // limit; S.x = solution, S.ueq / S.uin = multipliers.
 __device__ int gi_solve(Es& S, int& steps) {
   const int lane = threadIdx.x & 63;
-  // J = L^-T: row j of J is column j of L^-1 (forward substitution of L y = e_j), lane j its row
-  if (lane < NE) {
-    const int j = lane;
-    double* y = S.J[j];
-    for (int i = 0; i < NE; ++i) {
-      if (i < j) { y[i] = 0.0; continue; }
-      double s = (i == j) ? 1.0 : 0.0;
-      for (int k = j; k < i; ++k) s -= S.Hm[i][k] * y[k];
-      y[i] = s / S.Hm[i][i];
-    }
-  }
-  WSYNC();
-  // x = -J J' g
-  if (lane < NE) {
-    double s = 0.0;
-    for (int i = 0; i < NE; ++i) s += S.J[i][lane] * S.gm[i];
-    S.dd[lane] = s;
-  }
-  WSYNC();
-  if (lane < NE) {
-    double s = 0.0;
-    for (int j = 0; j < NE; ++j) s += S.J[lane][j] * S.dd[j];
-    S.x[lane] = -s;
-  }
-  for (int e = lane; e < NE * NE; e += 64) S.R[e / NE][e % NE] = 0.0;
-  if (lane == 0) S.nact = 0;
-  WSYNC();
+  gi_factor<QP>(S, S.gm);
+  gi_start<QP>(S);
   for (int k = 0; k < NEQ; ++k) {
     double s = 0.0;
     for (int i = 0; i < NE; ++i) s += S.Jeq[k][i] * S.x[i];
     WSYNC();
     if (lane == 0) S.sgn[k] = (s - S.deq[k] > 0.0) ? -1.0 : 1.0;
     WSYNC();
-    int ok = gi_add(S, k, steps);
+    int ok = gi_add<QP>(S, k, steps);
     if (ok < 0) return 1;
     if (ok == 0) return 2;
   }
@@ -368,21 +153,11 @@ __device__ int gi_solve(Es& S, int& steps) {
     }
     wargmin(best, bi);
     if (!(best < -1e-11 * (1.0 + fabs(S.din[bi])))) break;
-    int ok = gi_add(S, NEQ + bi, steps);
+    int ok = gi_add<QP>(S, NEQ + bi, steps);
     if (ok < 0) return 1;
     if (ok == 0) return 2;
   }
-  WSYNC();
-  if (lane < NROW) S.uin[lane] = 0.0;
-  if (lane < NEQ) S.ueq[lane] = 0.0;
-  WSYNC();
-  if (lane == 0)
-    for (int k = 0; k < S.nact; ++k) {
-      const int c = S.act[k];
-      if (c < NEQ) S.ueq[c] = S.u[k] * S.sgn[c];
-      else S.uin[c - NEQ] = S.u[k];
-    }
-  WSYNC();
+  gi_multipliers<QP>(S);
   return 0;
 }
 
@@ -401,17 +176,17 @@ __device__ void edge_one(Es& S, int pair, int t, const double* __restrict__ recs
                          int* __restrict__ ist) {
   const int lane = threadIdx.x & 63;
   const double* rec = recs + (size_t)pair * REC;
-  const double* par = rec + O_PAR;
+  const double* par = rec + E_PAR;
   const double rho = par[0], min_dis = par[1], g_max = par[8];
   const int prob = (int)par[2], max_iter = (int)par[3], rdec = (int)par[4], start = (int)par[5];
   const double x_bound = par[6], mu_max = par[7];
   const double sigd = sqrt(0.95 / (1.0 - 0.95));
   const int veh = (lane < NE && lane >= 9) ? 1 : 0, li = (lane < NE) ? lane - 9 * veh : 0;
   if (lane < NE) {
-    const double wl = (li < 5) ? rec[O_LX + (veh * NT + t) * 5 + li] : rec[O_LIJ + (veh * NT + t) * 4 + (li - 5)];
+    const double wl = (li < 5) ? rec[E_LX + (veh * NT + t) * 5 + li] : rec[E_LIJ + (veh * NT + t) * 4 + (li - 5)];
     const double lo = (li < 5) ? -x_bound : 0.0, hi = (li < 5) ? x_bound : mu_max;
     S.w[lane] = wl;
-    S.lb[lane] = rec[O_LB + (veh * NT + t) * 9 + li];
+    S.lb[lane] = rec[E_LB + (veh * NT + t) * 9 + li];
     S.lo[lane] = lo;
     S.hi[lane] = hi;
     S.z[lane] = start ? fmin(fmax(wl, lo), hi) : 0.0;
@@ -609,21 +384,21 @@ __device__ void edge_one(Es& S, int pair, int t, const double* __restrict__ recs
     const double zf = S.z[lane], zb = around(zf, rdec);
     const double lb = S.lb[lane];
     const double lbn = wrote ? lb + rho * (S.w[lane] - zb) : lb;
-    o[OO_Z + k] = zf;
-    o[OO_ZB + k] = zb;
-    o[OO_LBN + k] = lbn;
-    o[OO_YBND + t * NE + lane] = y_bnd;
+    o[EO_Z + k] = zf;
+    o[EO_ZB + k] = zb;
+    o[EO_LBN + k] = lbn;
+    o[EO_YBND + t * NE + lane] = y_bnd;
     dr = fabs(lbn - lb);
   }
   // the slot's sum |delta lamb_bar| in lane order 0..17 (bit-repeatable: no atomics)
   double dsum = 0.0;
   for (int k = 0; k < NE; ++k) dsum += __shfl(dr, k, 64);
   if (lane == 0) {
-    o[OO_YEQ + 2 * t] = y_eq0;
-    o[OO_YEQ + 2 * t + 1] = y_eq1;
-    o[OO_YIN + t] = y_in;
-    o[OO_COST + t] = cost;
-    o[OO_DRES + t] = dsum;
+    o[EO_YEQ + 2 * t] = y_eq0;
+    o[EO_YEQ + 2 * t + 1] = y_eq1;
+    o[EO_YIN + t] = y_in;
+    o[EO_COST + t] = cost;
+    o[EO_DRES + t] = dsum;
     int* s3 = ist + ((size_t)pair * NT + t) * 3;
     s3[0] = status;
     s3[1] = iters;
@@ -646,25 +421,15 @@ __global__ void __launch_bounds__(64 * EW) k_obca_edge(const double* __restrict_
 // C-ABI (include/piadmm.h)
 // ---------------------------------------------------------------------------------------------
 namespace {
-int efail(piadmm_obca_t h, int code, const std::string& msg) {
-  if (h) h->err = msg;
-  return code;
-}
-#define EHIP(h, call)                                                                  \
-  do {                                                                                 \
-    hipError_t _e = (call);                                                            \
-    if (_e != hipSuccess) return efail(h, PIADMM_E_HIP, std::string(#call ": ") + hipGetErrorString(_e)); \
-  } while (0)
-
 int edge_check(piadmm_obca_t h, const double* recs, int n) {
   for (int i = 0; i < n; ++i) {
-    const double* par = recs + (size_t)i * obca_edge::REC + obca_edge::O_PAR;
+    const double* par = recs + (size_t)i * obca_edge::REC + obca_edge::E_PAR;
     if (!(par[0] > 0.0) || (par[2] != 0.0 && par[2] != 1.0) || !(par[3] >= 1.0 && par[3] <= 1000.0) ||
         (par[5] != 0.0 && par[5] != 1.0) || !(par[4] >= -1.0 && par[4] <= 15.0) || !(par[6] > 0.0) || !(par[7] > 0.0) ||
         !std::isfinite(par[1]) || !std::isfinite(par[8]))
-      return efail(h, PIADMM_E_ARG, "record " + std::to_string(i) + ": bad parameters (rho > 0; prob 0/1; "
-                   "1 <= max_iter <= 1000; start 0/1; -1 <= round_decimals <= 15; x_bound, mu_max > 0; "
-                   "min_dis, g_max finite)");
+      return fail(h, PIADMM_E_ARG, "record " + std::to_string(i) + ": bad parameters (rho > 0; prob 0/1; "
+                  "1 <= max_iter <= 1000; start 0/1; -1 <= round_decimals <= 15; x_bound, mu_max > 0; "
+                  "min_dis, g_max finite)");
   }
   return 0;
 }
@@ -683,13 +448,13 @@ int edge_ensure(piadmm_obca_t h, int n) {
 }
 
 int edge_upload(piadmm_obca_t h, const double* recs, int n) {
-  if (!recs || n <= 0) return efail(h, PIADMM_E_ARG, "obca_edge: recs / n_pairs");
+  if (!recs || n <= 0) return fail(h, PIADMM_E_ARG, "obca_edge: recs / n_pairs");
   if (int rc = edge_check(h, recs, n)) return rc;
-  EHIP(h, hipSetDevice(h->device));
+  OWN_HIP(h, hipSetDevice(h->device));
   piadmm_obca_plan_release(h);       // the edge buffers are overwritten: an open plan ends here
   if (int rc = edge_ensure(h, n)) return rc;
-  EHIP(h, hipMemcpyAsync(h->e_rec, recs, (size_t)n * obca_edge::REC * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  EHIP(h, hipMemsetAsync(h->e_out, 0, (size_t)n * obca_edge::OUT * sizeof(double), h->stream));
+  OWN_HIP(h, hipMemcpyAsync(h->e_rec, recs, (size_t)n * obca_edge::REC * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  OWN_HIP(h, hipMemsetAsync(h->e_out, 0, (size_t)n * obca_edge::OUT * sizeof(double), h->stream));
   return 0;
 }
 
@@ -698,7 +463,7 @@ int edge_launch(piadmm_obca_t h, int n) {
   const int blocks = (n_prob + obca_edge::EW - 1) / obca_edge::EW;
   hipLaunchKernelGGL(obca_edge::k_obca_edge, dim3(blocks), dim3(64 * obca_edge::EW), 0, h->stream, h->e_rec, n_prob,
                      h->e_out, h->e_ist);
-  EHIP(h, hipGetLastError());
+  OWN_HIP(h, hipGetLastError());
   return 0;
 }
 }  // namespace
@@ -707,7 +472,7 @@ int edge_launch(piadmm_obca_t h, int n) {
 int piadmm_obca_edge_ensure(piadmm_obca_t h, int n) { return edge_ensure(h, n); }
 
 int piadmm_obca_edge_launch(piadmm_obca_t h, int n) {
-  if (n <= 0 || n > h->e_cap) return efail(h, PIADMM_E_STATE, "obca edge launch: n outside the buffers");
+  if (n <= 0 || n > h->e_cap) return fail(h, PIADMM_E_STATE, "obca edge launch: n outside the buffers");
   return edge_launch(h, n);
 }
 
@@ -715,26 +480,26 @@ extern "C" {
 
 int32_t piadmm_obca_edge_solve(piadmm_obca_t h, const double* recs, int32_t n_pairs, double* out, int32_t* status3) {
   if (!h) return PIADMM_E_ARG;
-  if (!out || !status3) return efail(h, PIADMM_E_ARG, "obca_edge_solve: out / status3");
+  if (!out || !status3) return fail(h, PIADMM_E_ARG, "obca_edge_solve: out / status3");
   if (int rc = edge_upload(h, recs, n_pairs)) return rc;
   if (int rc = edge_launch(h, n_pairs)) return rc;
-  EHIP(h, hipMemcpyAsync(out, h->e_out, (size_t)n_pairs * obca_edge::OUT * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  EHIP(h, hipMemcpyAsync(status3, h->e_ist, (size_t)n_pairs * obca_edge::NT * 3 * sizeof(int), hipMemcpyDeviceToHost,
+  OWN_HIP(h, hipMemcpyAsync(out, h->e_out, (size_t)n_pairs * obca_edge::OUT * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(status3, h->e_ist, (size_t)n_pairs * obca_edge::NT * 3 * sizeof(int), hipMemcpyDeviceToHost,
                          h->stream));
-  EHIP(h, hipStreamSynchronize(h->stream));
+  OWN_HIP(h, hipStreamSynchronize(h->stream));
   return 0;
 }
 
 int32_t piadmm_obca_edge_time(piadmm_obca_t h, const double* recs, int32_t n_pairs, int32_t repeats, float* ms) {
   if (!h || !ms || repeats <= 0) return PIADMM_E_ARG;
   if (int rc = edge_upload(h, recs, n_pairs)) return rc;
-  EHIP(h, hipEventRecord(h->e0, h->stream));
+  OWN_HIP(h, hipEventRecord(h->e0, h->stream));
   for (int r = 0; r < repeats; ++r)
     if (int rc = edge_launch(h, n_pairs)) return rc;
-  EHIP(h, hipEventRecord(h->e1, h->stream));
-  EHIP(h, hipEventSynchronize(h->e1));
+  OWN_HIP(h, hipEventRecord(h->e1, h->stream));
+  OWN_HIP(h, hipEventSynchronize(h->e1));
   float t = 0.f;
-  EHIP(h, hipEventElapsedTime(&t, h->e0, h->e1));
+  OWN_HIP(h, hipEventElapsedTime(&t, h->e0, h->e1));
   *ms = t / (float)repeats;
   return 0;
 }

@@ -51,6 +51,10 @@ struct piadmm_obca_s {
   std::string err;
 };
 
+// The error path of every OBCA unit: the message into the handle, the code back.  A failed runtime
+// call goes through OWN_HIP (pd_owners.h), which words it "<the call as written>: <HIP's text>".
+inline int fail(piadmm_obca_t h, int code, const std::string& msg) { return pd_own::own_fail(h, code, msg); }
+
 // The plan path's view of the two solves: grow the handle's buffers to n local problems / n pairs,
 // and enqueue one launch over the first n records already in d_rec (problem order d_order[0..n))
 // or e_rec on the handle's stream.  No copy, no synchronisation.

@@ -19,13 +19,14 @@
 #include <vector>
 
 #include "pd_common.h"
+#include "pd_obca.h"
 #include "pd_owners.h"
 #include "piadmm.h"
 #include "piadmm_obca_handle.h"
 
 namespace obca_plan {
 
-constexpr int NT = 7;
+using namespace pd_obca;     // NT, the vehicle constants, the record layouts R_*, O_*, E_*, EO_*
 constexpr int PW = 4;                          // waves per workgroup
 constexpr int STATE = PIADMM_OBCA_PLAN_STATE;
 constexpr int REC = PIADMM_OBCA_REC, OUT = PIADMM_OBCA_OUT;
@@ -33,15 +34,7 @@ constexpr int EREC = PIADMM_OBCA_EDGE_REC, EOUT = PIADMM_OBCA_EDGE_OUT;
 // the state's fields (include/piadmm.h)
 constexpr int S_ZB = 0, S_A = 126, S_B = 238, S_LB = 294, S_LIJ = 420, S_LX = 476, S_INIT = 546;
 static_assert(S_INIT + 10 == STATE, "state layout");
-// local record / output (csrc/piadmm_obca.hip), edge record / output (csrc/piadmm_obca_edge.hip)
-constexpr int R_INIT = 0, R_REF = 5, R_AO = 45, R_BO = 101, R_LIJ = 129, R_LB = 157, R_ZB = 220, R_PAR = 283;
-constexpr int O_X = 0, O_U = 40, O_LAM = 54;
-constexpr int E_LX = 0, E_LIJ = 70, E_LB = 126, E_PAR = 252;
-constexpr int EO_ZB = 126, EO_LBN = 252, EO_DRES = 532;
 constexpr int NCTRL = 28, NX = 80;
-
-constexpr double LENGTH = 3.5, WIDTH = 2.0;
-constexpr double AVG_DELAY = 0.05, VAR_DELAY = 0.025;
 
 // a parameter row (include/piadmm.h): the integers are stored as doubles, as the records do
 constexpr int TAB = PIADMM_OBCA_FLEET_PAR;
@@ -225,16 +218,6 @@ __global__ void __launch_bounds__(64 * PW) k_plan_delay(const int* __restrict__ 
 // ---------------------------------------------------------------------------------------------
 // The host side
 // ---------------------------------------------------------------------------------------------
-inline int pfail(piadmm_obca_t h, int code, const std::string& msg) {
-  if (h) h->err = msg;
-  return code;
-}
-#define PHIP(h, call)                                                                  \
-  do {                                                                                 \
-    hipError_t _e = (call);                                                            \
-    if (_e != hipSuccess) return pfail(h, PIADMM_E_HIP, std::string(#call ": ") + hipGetErrorString(_e)); \
-  } while (0)
-
 // The owners of device memory (pd_owners.h).  scratch: the device arrays of one stand-alone call, on
 // the stack: neither the handle's local and edge buffers nor an open plan is touched.
 using pd_own::dev_buf;
@@ -334,13 +317,13 @@ namespace obca_plan {
 
 inline int open_plan(piadmm_obca_t h, piadmm_obca_plan_s** out, const char* who) {
   if (!h) return PIADMM_E_ARG;
-  if (!h->plan || !h->plan->open) return pfail(h, PIADMM_E_STATE, std::string(who) + ": no open plan (obca_plan_begin)");
+  if (!h->plan || !h->plan->open) return fail(h, PIADMM_E_STATE, std::string(who) + ": no open plan (obca_plan_begin)");
   *out = h->plan;
   return 0;
 }
 inline int open_trace(piadmm_obca_t h, piadmm_obca_plan_s** out, const char* who) {
   if (int rc = open_plan(h, out, who)) return rc;
-  if (!(*out)->tr.on) return pfail(h, PIADMM_E_STATE, std::string(who) + ": no trace attached (obca_trace_begin)");
+  if (!(*out)->tr.on) return fail(h, PIADMM_E_STATE, std::string(who) + ": no trace attached (obca_trace_begin)");
   return 0;
 }
 
@@ -376,7 +359,7 @@ inline int slots_check(piadmm_obca_t h, const std::string& who, const char* item
   std::vector<char> seen((size_t)n, 0);
   for (int k = 0; k < m; ++k) {
     if (list[k] < 0 || list[k] >= n || seen[(size_t)list[k]])
-      return pfail(h, PIADMM_E_ARG, who + ": " + item + "[" + std::to_string(k) + "] must be a scenario below n, listed once");
+      return fail(h, PIADMM_E_ARG, who + ": " + item + "[" + std::to_string(k) + "] must be a scenario below n, listed once");
     seen[(size_t)list[k]] = 1;
   }
   return 0;
@@ -384,33 +367,33 @@ inline int slots_check(piadmm_obca_t h, const std::string& who, const char* item
 // m, the pointers and the slots of an export, an import or a gather
 inline int tenant_slots_check(piadmm_obca_t h, const piadmm_obca_plan_s* p, int m, const int32_t* slots,
                               const void* blob, const std::string& who) {
-  if (m < 1 || m > p->n) return pfail(h, PIADMM_E_ARG, who + ": 1 <= m <= n_scenarios");
-  if (!slots || !blob) return pfail(h, PIADMM_E_ARG, who + ": null argument (slots, blob)");
+  if (m < 1 || m > p->n) return fail(h, PIADMM_E_ARG, who + ": 1 <= m <= n_scenarios");
+  if (!slots || !blob) return fail(h, PIADMM_E_ARG, who + ": null argument (slots, blob)");
   return slots_check(h, who, "slots", slots, m, p->n);
 }
 inline int prob_check(piadmm_obca_t h, const std::string& who, const int32_t* prob, int k) {
-  if (prob[k] != 0 && prob[k] != 1) return pfail(h, PIADMM_E_ARG, who + ": prob[" + std::to_string(k) + "] must be 0 or 1");
+  if (prob[k] != 0 && prob[k] != 1) return fail(h, PIADMM_E_ARG, who + ": prob[" + std::to_string(k) + "] must be 0 or 1");
   return 0;
 }
 inline int rows_check(piadmm_obca_t h, const std::string& who, int rows, int n) {
-  if (rows != 1 && rows != n) return pfail(h, PIADMM_E_ARG, who + ": rows must be 1 or n (" + std::to_string(n) + ")");
+  if (rows != 1 && rows != n) return fail(h, PIADMM_E_ARG, who + ": rows must be 1 or n (" + std::to_string(n) + ")");
   return 0;
 }
 // The tail of a _get call: item `what` is `want` bytes at src, on the host (`host`) or on the device.
 inline int get_finish(piadmm_obca_t h, const std::string& who, int what, const void* src, bool host, int64_t want,
                       void* out, int64_t bytes) {
   if (bytes != want)
-    return pfail(h, PIADMM_E_ARG, who + ": item " + std::to_string(what) + " is " + std::to_string(want) +
-                 " bytes, not " + std::to_string(bytes));
+    return fail(h, PIADMM_E_ARG, who + ": item " + std::to_string(what) + " is " + std::to_string(want) +
+                " bytes, not " + std::to_string(bytes));
   if (want == 0) return 0;
-  if (!out) return pfail(h, PIADMM_E_ARG, who + ": out");
+  if (!out) return fail(h, PIADMM_E_ARG, who + ": out");
   if (host) {
     std::memcpy(out, src, (size_t)want);
     return 0;
   }
-  PHIP(h, hipSetDevice(h->device));
-  PHIP(h, hipMemcpyAsync(out, src, (size_t)want, hipMemcpyDeviceToHost, h->stream));
-  PHIP(h, hipStreamSynchronize(h->stream));
+  OWN_HIP(h, hipSetDevice(h->device));
+  OWN_HIP(h, hipMemcpyAsync(out, src, (size_t)want, hipMemcpyDeviceToHost, h->stream));
+  OWN_HIP(h, hipStreamSynchronize(h->stream));
   return 0;
 }
 

@@ -368,7 +368,7 @@ const char* row_check(const double* row) {
 int stage_ensure(piadmm_obca_t h, piadmm_obca_plan_s* p, size_t bytes, int m) {
   const size_t need = bytes + (size_t)m * sizeof(int);
   if (p->stg.cap >= need) return 0;
-  PHIP(h, hipStreamSynchronize(h->stream));
+  OWN_HIP(h, hipStreamSynchronize(h->stream));
   p->stg = {};
   if (int rc = p->stg.buf.alloc(h, need, false)) return rc;
   p->stg.cap = need;
@@ -389,12 +389,12 @@ void row_of_cfg(const piadmm_obca_plan_cfg_t& c, double* row) {
 
 // what every scenario of a plan shares, and prob
 int shared_check(piadmm_obca_t h, const piadmm_obca_plan_cfg_t& c, const int32_t* prob, const std::string& who) {
-  if (c.update_lamb_ij != 0 && c.update_lamb_ij != 1) return pfail(h, PIADMM_E_ARG, who + ": update_lamb_ij 0 or 1");
-  if (c.n_scenarios < 1) return pfail(h, PIADMM_E_ARG, who + ": n_scenarios >= 1");
-  if (c.n_scenarios > (1 << 20)) return pfail(h, PIADMM_E_ARG, who + ": n_scenarios <= 2^20");
+  if (c.update_lamb_ij != 0 && c.update_lamb_ij != 1) return fail(h, PIADMM_E_ARG, who + ": update_lamb_ij 0 or 1");
+  if (c.n_scenarios < 1) return fail(h, PIADMM_E_ARG, who + ": n_scenarios >= 1");
+  if (c.n_scenarios > (1 << 20)) return fail(h, PIADMM_E_ARG, who + ": n_scenarios <= 2^20");
   if (c.t_step0 < 0 || c.n_ref < 8 || c.t_step0 > c.n_ref - 8)
-    return pfail(h, PIADMM_E_ARG, who + ": t_step0 >= 0 and t_step0 + 8 <= n_ref");
-  if (c.n_ref > (1 << 20)) return pfail(h, PIADMM_E_ARG, who + ": n_ref <= 2^20");
+    return fail(h, PIADMM_E_ARG, who + ": t_step0 >= 0 and t_step0 + 8 <= n_ref");
+  if (c.n_ref > (1 << 20)) return fail(h, PIADMM_E_ARG, who + ": n_ref <= 2^20");
   for (int k = 0; k < c.n_scenarios; ++k)
     if (int rc = prob_check(h, who, prob, k)) return rc;
   return 0;
@@ -407,8 +407,8 @@ int plan_open(piadmm_obca_t h, const piadmm_obca_plan_cfg_t* cfg, const int32_t*
               const double* dual_thres, const double* ref_traj, int ref_rows, const std::vector<double>& tab,
               int tab_rows, const double* state) {
   const int n = cfg->n_scenarios;
-  PHIP(h, hipSetDevice(h->device));
-  PHIP(h, hipStreamSynchronize(h->stream));
+  OWN_HIP(h, hipSetDevice(h->device));
+  OWN_HIP(h, hipStreamSynchronize(h->stream));
   if (!h->plan) h->plan = new piadmm_obca_plan_s();
   piadmm_obca_plan_s* p = h->plan;
   *p = piadmm_obca_plan_s();      // everything an earlier plan owned goes; open == false until the end
@@ -419,7 +419,7 @@ int plan_open(piadmm_obca_t h, const piadmm_obca_plan_cfg_t* cfg, const int32_t*
   if (int rc = piadmm_obca_local_ensure(h, 2 * n)) return rc;
   if (int rc = piadmm_obca_edge_ensure(h, n)) return rc;
   const std::vector<int> ident = identity_list((size_t)2 * n);
-  PHIP(h, hipMemcpy(h->d_order, ident.data(), (size_t)2 * n * sizeof(int), hipMemcpyHostToDevice));
+  OWN_HIP(h, hipMemcpy(h->d_order, ident.data(), (size_t)2 * n * sizeof(int), hipMemcpyHostToDevice));
 
   p->cfg = *cfg;
   p->sigd = std::sqrt(0.95 / (1.0 - 0.95));
@@ -449,14 +449,14 @@ int plan_open(piadmm_obca_t h, const piadmm_obca_plan_cfg_t* cfg, const int32_t*
     *p = piadmm_obca_plan_s();
     return rc;
   }
-  PHIP(h, hipMemcpy(p->bar, state, N * STATE * sizeof(double), hipMemcpyHostToDevice));
-  PHIP(h, hipMemcpy(p->barp, state, N * STATE * sizeof(double), hipMemcpyHostToDevice));
-  PHIP(h, hipMemcpy(p->pth, primal_thres, N * sizeof(double), hipMemcpyHostToDevice));
-  PHIP(h, hipMemcpy(p->dth, dual_thres, N * sizeof(double), hipMemcpyHostToDevice));
-  PHIP(h, hipMemcpy(p->ref, ref_traj, ref_one * ref_rows * sizeof(double), hipMemcpyHostToDevice));
-  PHIP(h, hipMemcpy(p->tab, tab.data(), (size_t)tab_rows * TAB * sizeof(double), hipMemcpyHostToDevice));
-  PHIP(h, hipMemcpy(p->prob, prob, N * sizeof(int), hipMemcpyHostToDevice));
-  PHIP(h, hipMemcpy(p->act[0], ident.data(), N * sizeof(int), hipMemcpyHostToDevice));
+  OWN_HIP(h, hipMemcpy(p->bar, state, N * STATE * sizeof(double), hipMemcpyHostToDevice));
+  OWN_HIP(h, hipMemcpy(p->barp, state, N * STATE * sizeof(double), hipMemcpyHostToDevice));
+  OWN_HIP(h, hipMemcpy(p->pth, primal_thres, N * sizeof(double), hipMemcpyHostToDevice));
+  OWN_HIP(h, hipMemcpy(p->dth, dual_thres, N * sizeof(double), hipMemcpyHostToDevice));
+  OWN_HIP(h, hipMemcpy(p->ref, ref_traj, ref_one * ref_rows * sizeof(double), hipMemcpyHostToDevice));
+  OWN_HIP(h, hipMemcpy(p->tab, tab.data(), (size_t)tab_rows * TAB * sizeof(double), hipMemcpyHostToDevice));
+  OWN_HIP(h, hipMemcpy(p->prob, prob, N * sizeof(int), hipMemcpyHostToDevice));
+  OWN_HIP(h, hipMemcpy(p->act[0], ident.data(), N * sizeof(int), hipMemcpyHostToDevice));
   p->t_step = cfg->t_step0;
   p->i_iter = 0;
   p->n_act = n;
@@ -500,10 +500,10 @@ int32_t piadmm_obca_plan_begin(piadmm_obca_t h, const piadmm_obca_plan_cfg_t* cf
                                const double* state) {
   if (!h) return PIADMM_E_ARG;
   if (!cfg || !prob || !primal_thres || !dual_thres || !ref_traj || !state)
-    return pfail(h, PIADMM_E_ARG, "obca_plan_begin: null argument");
+    return fail(h, PIADMM_E_ARG, "obca_plan_begin: null argument");
   std::vector<double> row(obca_plan::TAB);
   row_of_cfg(*cfg, row.data());
-  if (const char* why = row_check(row.data())) return pfail(h, PIADMM_E_ARG, std::string("obca_plan_begin: ") + why);
+  if (const char* why = row_check(row.data())) return fail(h, PIADMM_E_ARG, std::string("obca_plan_begin: ") + why);
   if (int rc = shared_check(h, *cfg, prob, "obca_plan_begin")) return rc;
   return plan_open(h, cfg, prob, primal_thres, dual_thres, ref_traj, 1, row, 1, state);
 }
@@ -513,7 +513,7 @@ int32_t piadmm_obca_fleet_begin(piadmm_obca_t h, const piadmm_obca_plan_cfg_t* c
                                 const double* par, const double* state) {
   if (!h) return PIADMM_E_ARG;
   if (!cfg || !prob || !primal_thres || !dual_thres || !ref_traj || !state)
-    return pfail(h, PIADMM_E_ARG, "obca_fleet_begin: null argument");
+    return fail(h, PIADMM_E_ARG, "obca_fleet_begin: null argument");
   if (int rc = shared_check(h, *cfg, prob, "obca_fleet_begin")) return rc;
   const int n = cfg->n_scenarios;
   // one row per scenario either way: without a table every row is the configuration's
@@ -526,7 +526,7 @@ int32_t piadmm_obca_fleet_begin(piadmm_obca_t h, const piadmm_obca_plan_cfg_t* c
       row_of_cfg(*cfg, row);
     }
     if (const char* why = row_check(row))
-      return pfail(h, PIADMM_E_ARG, "obca_fleet_begin: row " + std::to_string(k) + ": " + why);
+      return fail(h, PIADMM_E_ARG, "obca_fleet_begin: row " + std::to_string(k) + ": " + why);
   }
   return plan_open(h, cfg, prob, primal_thres, dual_thres, ref_traj, n, tab, n, state);
 }
@@ -534,20 +534,20 @@ int32_t piadmm_obca_fleet_begin(piadmm_obca_t h, const piadmm_obca_plan_cfg_t* c
 int32_t piadmm_obca_plan_iterate(piadmm_obca_t h, int32_t* n_active_after) {
   piadmm_obca_plan_s* p = nullptr;
   if (int rc = open_plan(h, &p, "obca_plan_iterate")) return rc;
-  if (p->ck.on && p->ck.n_list == 0) return pfail(h, PIADMM_E_STATE, "obca_plan_iterate: no scenario alive");
-  if (p->n_act <= 0) return pfail(h, PIADMM_E_STATE, "obca_plan_iterate: no active scenario (obca_plan_shift closes the step)");
-  if (!p->ck.on && p->t_step + 8 > p->cfg.n_ref) return pfail(h, PIADMM_E_STATE, "obca_plan_iterate: reference exhausted");
-  if (const char* why = delay_refusal(p, 1)) return pfail(h, PIADMM_E_STATE, std::string("obca_plan_iterate: ") + why);
-  PHIP(h, hipSetDevice(h->device));
+  if (p->ck.on && p->ck.n_list == 0) return fail(h, PIADMM_E_STATE, "obca_plan_iterate: no scenario alive");
+  if (p->n_act <= 0) return fail(h, PIADMM_E_STATE, "obca_plan_iterate: no active scenario (obca_plan_shift closes the step)");
+  if (!p->ck.on && p->t_step + 8 > p->cfg.n_ref) return fail(h, PIADMM_E_STATE, "obca_plan_iterate: reference exhausted");
+  if (const char* why = delay_refusal(p, 1)) return fail(h, PIADMM_E_STATE, std::string("obca_plan_iterate: ") + why);
+  OWN_HIP(h, hipSetDevice(h->device));
   const int m = p->n_act;
-  if (2 * m > h->cap || m > h->e_cap) return pfail(h, PIADMM_E_STATE, "obca_plan_iterate: the handle's buffers shrank");
+  if (2 * m > h->cap || m > h->e_cap) return fail(h, PIADMM_E_STATE, "obca_plan_iterate: the handle's buffers shrank");
   hipStream_t st = h->stream;
   const int* act = p->act[p->cur];
   int* nxt = p->act[1 - p->cur];
   if (p->i_iter == 0) {
     // a new MPC step: the stop iterates and the status bits are the step's own
-    PHIP(h, hipMemsetAsync(p->iters, 0, (size_t)p->n * sizeof(int), st));
-    PHIP(h, hipMemsetAsync(p->mask, 0, (size_t)2 * p->n * sizeof(int), st));
+    OWN_HIP(h, hipMemsetAsync(p->iters, 0, (size_t)p->n * sizeof(int), st));
+    OWN_HIP(h, hipMemsetAsync(p->mask, 0, (size_t)2 * p->n * sizeof(int), st));
   }
   const int i_iter = p->i_iter + 1;
   if (p->ck.on) {
@@ -558,10 +558,10 @@ int32_t piadmm_obca_plan_iterate(piadmm_obca_t h, int32_t* n_active_after) {
     hipLaunchKernelGGL(k_plan_pack_local, dim3(blocks_for(2 * m)), dim3(64 * PW), 0, st, act, m, p->bar, p->prob, p->ref,
                        p->ref_stride, p->cfg.n_ref, p->t_step, p->tab, p->tab_stride, h->d_rec);
   }
-  PHIP(h, hipGetLastError());
+  OWN_HIP(h, hipGetLastError());
   if (int rc = piadmm_obca_local_launch(h, 2 * m)) return rc;
   // the edge output starts from zeros, as in piadmm_obca_edge_solve
-  PHIP(h, hipMemsetAsync(h->e_out, 0, (size_t)m * EOUT * sizeof(double), st));
+  OWN_HIP(h, hipMemsetAsync(h->e_out, 0, (size_t)m * EOUT * sizeof(double), st));
   if (p->dl.on) {
     hipLaunchKernelGGL(k_plan_exchange_stale, dim3(blocks_for(m)), dim3(64 * PW), 0, st, act, m, p->bar, p->prob,
                        h->d_out, p->tab, p->tab_stride, p->sigd, p->cfg.update_lamb_ij, p->ctrl, p->X, p->conv,
@@ -570,35 +570,35 @@ int32_t piadmm_obca_plan_iterate(piadmm_obca_t h, int32_t* n_active_after) {
     hipLaunchKernelGGL(k_plan_exchange, dim3(blocks_for(m)), dim3(64 * PW), 0, st, act, m, p->bar, p->prob, h->d_out,
                        p->tab, p->tab_stride, p->sigd, p->cfg.update_lamb_ij, p->ctrl, p->X, p->conv, h->e_rec);
   }
-  PHIP(h, hipGetLastError());
+  OWN_HIP(h, hipGetLastError());
   if (int rc = piadmm_obca_edge_launch(h, m)) return rc;
   if (p->du.on) {
     // the law's lamb_bar_new and dres partials replace the fused update's in the edge output
     hipLaunchKernelGGL(k_plan_dual_pi, dim3(blocks_for(m)), dim3(64 * PW), 0, st, act, m, h->e_rec, h->e_out, h->e_ist,
                        p->du.par, p->du.stride, p->du.S, p->du.D, p->du.Sp, p->du.Dp);
-    PHIP(h, hipGetLastError());
+    OWN_HIP(h, hipGetLastError());
   }
   if (p->ord.on) {
     hipLaunchKernelGGL(k_plan_work, dim3(blocks_for(m)), dim3(64 * PW), 0, st, act, m, h->d_ist, h->e_ist, p->ord.work);
-    PHIP(h, hipGetLastError());
+    OWN_HIP(h, hipGetLastError());
   }
   hipLaunchKernelGGL(k_plan_residual, dim3(blocks_for(m)), dim3(64 * PW), 0, st, act, m, i_iter, p->bar, p->barp,
                      p->ctrl, p->ctrlp, h->e_out, h->d_ist, h->e_ist, p->pth, p->dth, p->tab, p->tab_stride, p->primal,
                      p->dual,
                      p->stop, p->iters, p->mask, p->keep);
-  PHIP(h, hipGetLastError());
+  OWN_HIP(h, hipGetLastError());
   // with the order on, the kept entries go to the scratch list and are sorted into the next list
   hipLaunchKernelGGL(k_plan_compact, dim3(1), dim3(CT), 0, st, act, p->keep, m, p->ord.on ? p->ord.tmp : nxt, p->count);
-  PHIP(h, hipGetLastError());
+  OWN_HIP(h, hipGetLastError());
   if (p->ord.on) {
     hipLaunchKernelGGL(k_plan_order, dim3(blocks_for(m)), dim3(64 * PW), 0, st, p->ord.tmp, p->count, m, p->ord.work,
                        nxt);
-    PHIP(h, hipGetLastError());
+    OWN_HIP(h, hipGetLastError());
   }
-  PHIP(h, hipMemcpyAsync(p->h_count, p->count, sizeof(int), hipMemcpyDeviceToHost, st));
-  PHIP(h, hipStreamSynchronize(st));
+  OWN_HIP(h, hipMemcpyAsync(p->h_count, p->count, sizeof(int), hipMemcpyDeviceToHost, st));
+  OWN_HIP(h, hipStreamSynchronize(st));
   const int left = *p->h_count.get();
-  if (left < 0 || left > m) return pfail(h, PIADMM_E_STATE, "obca_plan_iterate: active count out of range");
+  if (left < 0 || left > m) return fail(h, PIADMM_E_STATE, "obca_plan_iterate: active count out of range");
   p->i_iter = i_iter;
   p->n_last = m;
   p->n_act = left;
@@ -610,13 +610,13 @@ int32_t piadmm_obca_plan_iterate(piadmm_obca_t h, int32_t* n_active_after) {
 int32_t piadmm_obca_plan_shift(piadmm_obca_t h) {
   piadmm_obca_plan_s* p = nullptr;
   if (int rc = open_plan(h, &p, "obca_plan_shift")) return rc;
-  if (const char* why = delay_refusal(p, 1)) return pfail(h, PIADMM_E_STATE, std::string("obca_plan_shift: ") + why);
-  if (p->n_act > 0) return pfail(h, PIADMM_E_STATE, "obca_plan_shift: scenarios are still active");
-  if (p->i_iter == 0) return pfail(h, PIADMM_E_STATE, "obca_plan_shift: no iterate ran in this step");
-  if (p->tr.on && p->tr.rows >= p->tr.cap) return pfail(h, PIADMM_E_STATE, "obca_plan_shift: trace full");
-  if (feedback_exhausted(p, 1)) return pfail(h, PIADMM_E_STATE, "obca_plan_shift: disturbance tape exhausted");
-  if (noise_exhausted(p, 1)) return pfail(h, PIADMM_E_STATE, "obca_plan_shift: noise step index exhausted");
-  PHIP(h, hipSetDevice(h->device));
+  if (const char* why = delay_refusal(p, 1)) return fail(h, PIADMM_E_STATE, std::string("obca_plan_shift: ") + why);
+  if (p->n_act > 0) return fail(h, PIADMM_E_STATE, "obca_plan_shift: scenarios are still active");
+  if (p->i_iter == 0) return fail(h, PIADMM_E_STATE, "obca_plan_shift: no iterate ran in this step");
+  if (p->tr.on && p->tr.rows >= p->tr.cap) return fail(h, PIADMM_E_STATE, "obca_plan_shift: trace full");
+  if (feedback_exhausted(p, 1)) return fail(h, PIADMM_E_STATE, "obca_plan_shift: disturbance tape exhausted");
+  if (noise_exhausted(p, 1)) return fail(h, PIADMM_E_STATE, "obca_plan_shift: noise step index exhausted");
+  OWN_HIP(h, hipSetDevice(h->device));
   if (p->ck.on) return clock_shift(h, p);
   if (p->fb.on) {
     // the plant step first: it reads the closing step's init_state and the stopping solution's first
@@ -638,33 +638,33 @@ int32_t piadmm_obca_plan_shift(piadmm_obca_t h) {
       zo.k = (uint32_t)p->nz.k0 + (uint32_t)p->fb.steps;
       hipLaunchKernelGGL(k_plan_noise, dim3(lane_blocks(2 * p->n)), dim3(64 * PW), 0, h->stream, (const int*)nullptr,
                          p->n, zo);
-      PHIP(h, hipGetLastError());
+      OWN_HIP(h, hipGetLastError());
       io.w = p->nz.wbuf;  io.w_s = 10;
     }
     hipLaunchKernelGGL(k_plan_propagate, dim3(lane_blocks(2 * p->n)), dim3(64 * PW), 0, h->stream, (const int*)nullptr,
                        p->n, io);
-    PHIP(h, hipGetLastError());
+    OWN_HIP(h, hipGetLastError());
   }
   // every scenario is active again: the list the next iterate reads is the identity, or with the
   // order on the identity sorted by the work of the step that closes
   hipLaunchKernelGGL(k_plan_shift, dim3(p->n), dim3(64), 0, h->stream, p->n, p->bar, p->barp, p->X, p->lamb, p->ctrlp,
                      p->ord.on ? p->ord.tmp : p->act[p->cur]);
-  PHIP(h, hipGetLastError());
+  OWN_HIP(h, hipGetLastError());
   if (p->ord.on) {
     hipLaunchKernelGGL(k_plan_order, dim3(blocks_for(p->n)), dim3(64 * PW), 0, h->stream, p->ord.tmp,
                        (const int*)nullptr, p->n, p->ord.work, p->act[p->cur]);
-    PHIP(h, hipGetLastError());
+    OWN_HIP(h, hipGetLastError());
   }
   if (p->du.on) {
     hipLaunchKernelGGL(k_plan_dual_shift, dim3(p->n), dim3(64), 0, h->stream, p->n, p->du.S, p->du.D, p->du.Sp,
                        p->du.Dp);
-    PHIP(h, hipGetLastError());
+    OWN_HIP(h, hipGetLastError());
   }
   if (p->fb.on) {
     // the state the vehicle reached over init_state of both copies, before the trace reads it
     hipLaunchKernelGGL(k_plan_set_init, dim3(lane_blocks(2 * p->n)), dim3(64 * PW), 0, h->stream, (const int*)nullptr,
                        p->n, p->fb.next, p->bar, p->barp);
-    PHIP(h, hipGetLastError());
+    OWN_HIP(h, hipGetLastError());
   }
   if (p->tr.on) {
     if (int rc = trace_append(h, p, p->tr.rows + 1)) return rc;
@@ -673,7 +673,7 @@ int32_t piadmm_obca_plan_shift(piadmm_obca_t h) {
     // the latencies of the step that opens
     if (int rc = delay_next(h, p)) return rc;
   }
-  PHIP(h, hipStreamSynchronize(h->stream));
+  OWN_HIP(h, hipStreamSynchronize(h->stream));
   if (p->tr.on) p->tr.rows += 1;
   if (p->fb.on) p->fb.steps += 1;
   if (p->dl.on) p->dl.steps += 1;
@@ -687,20 +687,20 @@ int32_t piadmm_obca_plan_shift(piadmm_obca_t h) {
 int32_t piadmm_obca_plan_step(piadmm_obca_t h, int32_t* iters_out) {
   piadmm_obca_plan_s* p = nullptr;
   if (int rc = open_plan(h, &p, "obca_plan_step")) return rc;
-  if (p->ck.on && p->ck.n_list == 0) return pfail(h, PIADMM_E_STATE, "obca_plan_step: no scenario alive");
-  if (!p->ck.on && p->t_step + 8 > p->cfg.n_ref) return pfail(h, PIADMM_E_STATE, "obca_plan_step: reference exhausted");
-  if (p->tr.on && p->tr.rows >= p->tr.cap) return pfail(h, PIADMM_E_STATE, "obca_plan_step: trace full");
-  if (feedback_exhausted(p, 1)) return pfail(h, PIADMM_E_STATE, "obca_plan_step: disturbance tape exhausted");
-  if (noise_exhausted(p, 1)) return pfail(h, PIADMM_E_STATE, "obca_plan_step: noise step index exhausted");
-  if (const char* why = delay_refusal(p, 1)) return pfail(h, PIADMM_E_STATE, std::string("obca_plan_step: ") + why);
+  if (p->ck.on && p->ck.n_list == 0) return fail(h, PIADMM_E_STATE, "obca_plan_step: no scenario alive");
+  if (!p->ck.on && p->t_step + 8 > p->cfg.n_ref) return fail(h, PIADMM_E_STATE, "obca_plan_step: reference exhausted");
+  if (p->tr.on && p->tr.rows >= p->tr.cap) return fail(h, PIADMM_E_STATE, "obca_plan_step: trace full");
+  if (feedback_exhausted(p, 1)) return fail(h, PIADMM_E_STATE, "obca_plan_step: disturbance tape exhausted");
+  if (noise_exhausted(p, 1)) return fail(h, PIADMM_E_STATE, "obca_plan_step: noise step index exhausted");
+  if (const char* why = delay_refusal(p, 1)) return fail(h, PIADMM_E_STATE, std::string("obca_plan_step: ") + why);
   // i_iter > max_admm_iter stops a scenario: at most the largest max_admm_iter + 1 iterates in a step
   while (p->n_act > 0 && p->i_iter <= p->max_iter_all) {
     if (int rc = piadmm_obca_plan_iterate(h, nullptr)) return rc;
   }
-  if (p->n_act > 0) return pfail(h, PIADMM_E_STATE, "obca_plan_step: scenarios active after max_admm_iter + 1 iterates");
+  if (p->n_act > 0) return fail(h, PIADMM_E_STATE, "obca_plan_step: scenarios active after max_admm_iter + 1 iterates");
   if (iters_out) {
-    PHIP(h, hipMemcpyAsync(iters_out, p->iters, (size_t)p->n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    PHIP(h, hipStreamSynchronize(h->stream));
+    OWN_HIP(h, hipMemcpyAsync(iters_out, p->iters, (size_t)p->n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    OWN_HIP(h, hipStreamSynchronize(h->stream));
   }
   return piadmm_obca_plan_shift(h);
 }
@@ -742,7 +742,7 @@ int32_t piadmm_obca_plan_get(piadmm_obca_t h, int32_t what, void* out, int64_t b
     case PIADMM_OBCA_PLAN_GET_DUAL_PAR:
     case PIADMM_OBCA_PLAN_GET_DUAL_S_PREV:
     case PIADMM_OBCA_PLAN_GET_DUAL_D_PREV:
-      if (!p->du.on) return pfail(h, PIADMM_E_STATE, "obca_plan_get: no dual law attached (obca_dual_plan)");
+      if (!p->du.on) return fail(h, PIADMM_E_STATE, "obca_plan_get: no dual law attached (obca_dual_plan)");
       if (what == PIADMM_OBCA_PLAN_GET_DUAL_PAR) { src = p->du.par; want = (int64_t)p->du.rows * DPAR * D; break; }
       src = what == PIADMM_OBCA_PLAN_GET_DUAL_S ? p->du.S : what == PIADMM_OBCA_PLAN_GET_DUAL_D ? p->du.D
             : what == PIADMM_OBCA_PLAN_GET_DUAL_S_PREV ? p->du.Sp : p->du.Dp;
@@ -752,24 +752,24 @@ int32_t piadmm_obca_plan_get(piadmm_obca_t h, int32_t what, void* out, int64_t b
     case PIADMM_OBCA_PLAN_GET_DUAL_THRES: src = p->dth; want = n * D; break;
     case PIADMM_OBCA_PLAN_GET_PROB: src = p->prob; want = n * I; break;
     case PIADMM_OBCA_PLAN_GET_WORK:
-      if (!p->ord.on) return pfail(h, PIADMM_E_STATE, "obca_plan_get: no order attached (obca_order_plan)");
+      if (!p->ord.on) return fail(h, PIADMM_E_STATE, "obca_plan_get: no order attached (obca_order_plan)");
       src = p->ord.work; want = n * 2 * I; break;
     case PIADMM_OBCA_PLAN_GET_CLOCK:
     case PIADMM_OBCA_PLAN_GET_WINDOW:
-      if (!p->ck.on) return pfail(h, PIADMM_E_STATE, "obca_plan_get: no clock attached (obca_clock_plan)");
+      if (!p->ck.on) return fail(h, PIADMM_E_STATE, "obca_plan_get: no clock attached (obca_clock_plan)");
       if (what == PIADMM_OBCA_PLAN_GET_CLOCK) { src = p->ck.clk; want = n * 3 * I; }
       else { src = p->ck.win; want = n * WIN * D; }
       break;
     case PIADMM_OBCA_PLAN_GET_FEEDBACK_PAR:
     case PIADMM_OBCA_PLAN_GET_FEEDBACK_STEPS:
-      if (!p->fb.on) return pfail(h, PIADMM_E_STATE, "obca_plan_get: no feedback attached (obca_feedback_plan)");
+      if (!p->fb.on) return fail(h, PIADMM_E_STATE, "obca_plan_get: no feedback attached (obca_feedback_plan)");
       if (what == PIADMM_OBCA_PLAN_GET_FEEDBACK_PAR) { src = p->fb.par; want = (int64_t)p->fb.rows * FPAR * D; }
       else { src = &p->fb.steps; want = I; host = true; }
       break;
     case PIADMM_OBCA_NOISE_GET_PAR:
     case PIADMM_OBCA_NOISE_GET_STREAMS:
     case PIADMM_OBCA_NOISE_GET_SEED:
-      if (!p->nz.on) return pfail(h, PIADMM_E_STATE, "obca_plan_get: no noise attached (obca_noise_plan)");
+      if (!p->nz.on) return fail(h, PIADMM_E_STATE, "obca_plan_get: no noise attached (obca_noise_plan)");
       if (what == PIADMM_OBCA_NOISE_GET_PAR) { src = p->nz.par; want = (int64_t)p->nz.rows * ZPAR * D; }
       else if (what == PIADMM_OBCA_NOISE_GET_STREAMS) { src = p->nz.streams; want = n * (int64_t)sizeof(int64_t); }
       else { src = seed; want = 2 * (int64_t)sizeof(uint64_t); host = true; }
@@ -778,7 +778,7 @@ int32_t piadmm_obca_plan_get(piadmm_obca_t h, int32_t what, void* out, int64_t b
     case PIADMM_OBCA_DELAY_GET_TAU:
     case PIADMM_OBCA_DELAY_GET_STREAMS:
     case PIADMM_OBCA_DELAY_GET_SEED:
-      if (!p->dl.on) return pfail(h, PIADMM_E_STATE, "obca_plan_get: no delay attached (obca_delay_plan)");
+      if (!p->dl.on) return fail(h, PIADMM_E_STATE, "obca_plan_get: no delay attached (obca_delay_plan)");
       if (what == PIADMM_OBCA_DELAY_GET_PAR) { src = p->dl.par; want = (int64_t)p->dl.rows * YPAR * D; }
       else if (what == PIADMM_OBCA_DELAY_GET_TAU) { src = p->dl.tau; want = n * 2 * D; }
       else if (what == PIADMM_OBCA_DELAY_GET_STREAMS) { src = p->dl.streams; want = n * (int64_t)sizeof(int64_t); }
@@ -786,7 +786,7 @@ int32_t piadmm_obca_plan_get(piadmm_obca_t h, int32_t what, void* out, int64_t b
       break;
     case PIADMM_OBCA_PLAN_GET_T_STEP: src = &p->t_step; want = I; host = true; break;
     case PIADMM_OBCA_PLAN_GET_COUNTS: src = counts; want = 3 * I; host = true; break;
-    default: return pfail(h, PIADMM_E_ARG, "obca_plan_get: unknown item " + std::to_string(what));
+    default: return fail(h, PIADMM_E_ARG, "obca_plan_get: unknown item " + std::to_string(what));
   }
   return get_finish(h, "obca_plan_get", what, src, host, want, out, bytes);
 }

@@ -282,16 +282,16 @@ int clock_lists(piadmm_obca_t h, piadmm_obca_plan_s* p, const int* ran, int dst,
   auto& c = p->ck;
   hipLaunchKernelGGL(k_plan_clock, dim3(blocks_for(p->n)), dim3(64 * PW), 0, h->stream, p->n, c.clk, ran, p->ref,
                      p->ref_stride, p->cfg.n_ref, c.win, c.flag[dst]);
-  PHIP(h, hipGetLastError());
+  OWN_HIP(h, hipGetLastError());
   hipLaunchKernelGGL(k_plan_compact, dim3(1), dim3(CT), 0, h->stream, c.ident, c.flag[dst], p->n, c.list, p->count);
-  PHIP(h, hipGetLastError());
+  OWN_HIP(h, hipGetLastError());
   if (n_alive <= 0) return 0;
   if (p->ord.on) {
     hipLaunchKernelGGL(k_plan_order, dim3(blocks_for(n_alive)), dim3(64 * PW), 0, h->stream, c.list,
                        (const int*)nullptr, n_alive, p->ord.work, p->act[p->cur]);
-    PHIP(h, hipGetLastError());
+    OWN_HIP(h, hipGetLastError());
   } else {
-    PHIP(h, hipMemcpyAsync(p->act[p->cur], c.list, (size_t)n_alive * sizeof(int), hipMemcpyDeviceToDevice, h->stream));
+    OWN_HIP(h, hipMemcpyAsync(p->act[p->cur], c.list, (size_t)n_alive * sizeof(int), hipMemcpyDeviceToDevice, h->stream));
   }
   return 0;
 }
@@ -307,7 +307,7 @@ int clock_relist(piadmm_obca_t h, piadmm_obca_plan_s* p) {
     (void)hipStreamSynchronize(h->stream);
     return rc;
   }
-  PHIP(h, hipStreamSynchronize(h->stream));
+  OWN_HIP(h, hipStreamSynchronize(h->stream));
   p->ck.n_list = n_alive;
   p->n_act = n_alive;
   return 0;
@@ -320,11 +320,11 @@ int clock_shift(piadmm_obca_t h, piadmm_obca_plan_s* p) {
   const int m = c.n_list;
   hipLaunchKernelGGL(k_plan_shift_list, dim3(m), dim3(64), 0, h->stream, c.list, m, p->bar, p->barp, p->X, p->lamb,
                      p->ctrlp);
-  PHIP(h, hipGetLastError());
+  OWN_HIP(h, hipGetLastError());
   if (p->du.on) {
     hipLaunchKernelGGL(k_plan_dual_shift_list, dim3(m), dim3(64), 0, h->stream, c.list, m, p->du.S, p->du.D, p->du.Sp,
                        p->du.Dp);
-    PHIP(h, hipGetLastError());
+    OWN_HIP(h, hipGetLastError());
   }
   // the mirror: the tick is deterministic, nothing is read back for it
   std::vector<int> next = c.host;
@@ -339,7 +339,7 @@ int clock_shift(piadmm_obca_t h, piadmm_obca_plan_s* p) {
   if (p->tr.on) {
     if (int rc = trace_append(h, p, p->tr.rows + 1)) return rc;
   }
-  PHIP(h, hipStreamSynchronize(h->stream));
+  OWN_HIP(h, hipStreamSynchronize(h->stream));
   c.host.swap(next);
   c.cur = 1 - c.cur;
   c.n_list = n_alive;
@@ -357,7 +357,7 @@ int dual_rows_check(piadmm_obca_t h, const double* gains, int rows, int n, const
   if (int rc = rows_check(h, who, rows, n)) return rc;
   for (int k = 0; k < rows; ++k)
     if (const char* why = dual_row_check(gains + (size_t)k * obca_plan::DPAR))
-      return pfail(h, PIADMM_E_ARG, who + ": row " + std::to_string(k) + ": " + why);
+      return fail(h, PIADMM_E_ARG, who + ": row " + std::to_string(k) + ": " + why);
   return 0;
 }
 
@@ -378,9 +378,9 @@ int32_t piadmm_obca_dual_plan(piadmm_obca_t h, const double* gains, int32_t rows
   const bool detach = !gains || rows == 0;
   if (!detach)
     if (int rc = dual_rows_check(h, gains, rows, p->n, "obca_dual_plan")) return rc;
-  if (p->i_iter != 0) return pfail(h, PIADMM_E_STATE, "obca_dual_plan: only at a step boundary (an MPC step is open)");
-  PHIP(h, hipSetDevice(h->device));
-  PHIP(h, hipStreamSynchronize(h->stream));
+  if (p->i_iter != 0) return fail(h, PIADMM_E_STATE, "obca_dual_plan: only at a step boundary (an MPC step is open)");
+  OWN_HIP(h, hipSetDevice(h->device));
+  OWN_HIP(h, hipStreamSynchronize(h->stream));
   // the earlier law goes before the new one is built, not after it: the plan never holds two
   // integrators (peak device memory), and a failure below leaves the plan without a law
   p->du = {};
@@ -401,7 +401,7 @@ int32_t piadmm_obca_dual_plan(piadmm_obca_t h, const double* gains, int32_t rows
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
   if (e != hipSuccess) {
     (void)hipStreamSynchronize(h->stream);
-    return pfail(h, PIADMM_E_HIP, std::string("obca_dual_plan: ") + hipGetErrorString(e));
+    return fail(h, PIADMM_E_HIP, std::string("obca_dual_plan: ") + hipGetErrorString(e));
   }
   d.rows = rows;
   d.stride = rows > 1 ? DPAR : 0;
@@ -414,9 +414,9 @@ int32_t piadmm_obca_dual_pi(piadmm_obca_t h, int32_t n, const double* w, const d
                             const int32_t* status, const double* gains, int32_t rows, double* S, double* D,
                             double* lamb_out, double* dres_out) {
   if (!h) return PIADMM_E_ARG;
-  if (n < 1 || n > (1 << 20)) return pfail(h, PIADMM_E_ARG, "obca_dual_pi: 1 <= n <= 2^20");
+  if (n < 1 || n > (1 << 20)) return fail(h, PIADMM_E_ARG, "obca_dual_pi: 1 <= n <= 2^20");
   if (!w || !zb || !lamb || !status || !gains || !S || !D || !lamb_out || !dres_out)
-    return pfail(h, PIADMM_E_ARG, "obca_dual_pi: null argument");
+    return fail(h, PIADMM_E_ARG, "obca_dual_pi: null argument");
   if (int rc = dual_rows_check(h, gains, rows, n, "obca_dual_pi")) return rc;
   const size_t N = (size_t)n;
   const double* in[] = {w, zb, lamb, S, D};
@@ -424,8 +424,8 @@ int32_t piadmm_obca_dual_pi(piadmm_obca_t h, int32_t n, const double* w, const d
   for (int a = 0; a < 5; ++a)
     for (size_t i = 0; i < N * 126; ++i)
       if (!std::isfinite(in[a][i]))
-        return pfail(h, PIADMM_E_ARG, std::string("obca_dual_pi: ") + names[a] + " of scenario " +
-                     std::to_string(i / 126) + " is not finite");
+        return fail(h, PIADMM_E_ARG, std::string("obca_dual_pi: ") + names[a] + " of scenario " +
+                    std::to_string(i / 126) + " is not finite");
   // the kernel reads an edge record, an edge output and the slots' statuses: the caller's arrays in
   // those layouts, scenario k of the identity list
   std::vector<double> rec(N * EREC, 0.0), out(N * EOUT, 0.0);
@@ -439,7 +439,7 @@ int32_t piadmm_obca_dual_pi(piadmm_obca_t h, int32_t n, const double* w, const d
     }
     for (int t = 0; t < NT; ++t) ist[(k * NT + t) * 3] = status[k * NT + t];
   }
-  PHIP(h, hipSetDevice(h->device));
+  OWN_HIP(h, hipSetDevice(h->device));
   scratch a(h);
   double *d_rec = a.take<double>(N * EREC, false), *d_out = a.take<double>(N * EOUT, false),
          *d_g = a.take<double>((size_t)rows * DPAR, false), *d_S = a.take<double>(N * 126, false),
@@ -448,20 +448,20 @@ int32_t piadmm_obca_dual_pi(piadmm_obca_t h, int32_t n, const double* w, const d
   int *d_ist = a.take<int>(N * NT * 3, false), *d_act = a.take<int>(N, false);
   if (a.rc) return a.rc;
   const size_t B = sizeof(double);
-  PHIP(h, hipMemcpyAsync(d_rec, rec.data(), N * EREC * B, hipMemcpyHostToDevice, h->stream));
-  PHIP(h, hipMemcpyAsync(d_out, out.data(), N * EOUT * B, hipMemcpyHostToDevice, h->stream));
-  PHIP(h, hipMemcpyAsync(d_g, gains, (size_t)rows * DPAR * B, hipMemcpyHostToDevice, h->stream));
-  PHIP(h, hipMemcpyAsync(d_S, S, N * 126 * B, hipMemcpyHostToDevice, h->stream));
-  PHIP(h, hipMemcpyAsync(d_D, D, N * 126 * B, hipMemcpyHostToDevice, h->stream));
-  PHIP(h, hipMemcpyAsync(d_ist, ist.data(), N * NT * 3 * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  PHIP(h, hipMemcpyAsync(d_act, ident.data(), N * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(d_rec, rec.data(), N * EREC * B, hipMemcpyHostToDevice, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(d_out, out.data(), N * EOUT * B, hipMemcpyHostToDevice, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(d_g, gains, (size_t)rows * DPAR * B, hipMemcpyHostToDevice, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(d_S, S, N * 126 * B, hipMemcpyHostToDevice, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(d_D, D, N * 126 * B, hipMemcpyHostToDevice, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(d_ist, ist.data(), N * NT * 3 * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(d_act, ident.data(), N * sizeof(int), hipMemcpyHostToDevice, h->stream));
   hipLaunchKernelGGL(k_plan_dual_pi, dim3(blocks_for(n)), dim3(64 * PW), 0, h->stream, d_act, n, d_rec, d_out, d_ist,
                      d_g, rows > 1 ? DPAR : 0, d_S, d_D, d_Sp, d_Dp);
-  PHIP(h, hipGetLastError());
-  PHIP(h, hipMemcpyAsync(out.data(), d_out, N * EOUT * B, hipMemcpyDeviceToHost, h->stream));
-  PHIP(h, hipMemcpyAsync(S, d_S, N * 126 * B, hipMemcpyDeviceToHost, h->stream));
-  PHIP(h, hipMemcpyAsync(D, d_D, N * 126 * B, hipMemcpyDeviceToHost, h->stream));
-  PHIP(h, hipStreamSynchronize(h->stream));
+  OWN_HIP(h, hipGetLastError());
+  OWN_HIP(h, hipMemcpyAsync(out.data(), d_out, N * EOUT * B, hipMemcpyDeviceToHost, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(S, d_S, N * 126 * B, hipMemcpyDeviceToHost, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(D, d_D, N * 126 * B, hipMemcpyDeviceToHost, h->stream));
+  OWN_HIP(h, hipStreamSynchronize(h->stream));
   for (size_t k = 0; k < N; ++k) {
     for (int i = 0; i < 126; ++i) lamb_out[k * 126 + i] = out[k * EOUT + EO_LBN + i];
     for (int t = 0; t < NT; ++t) dres_out[k * NT + t] = out[k * EOUT + EO_DRES + t];
@@ -472,18 +472,18 @@ int32_t piadmm_obca_dual_pi(piadmm_obca_t h, int32_t n, const double* w, const d
 int32_t piadmm_obca_order_plan(piadmm_obca_t h, int32_t mode, const int32_t* work_init) {
   piadmm_obca_plan_s* p = nullptr;
   if (int rc = open_plan(h, &p, "obca_order_plan")) return rc;
-  if (mode != 0 && mode != 1) return pfail(h, PIADMM_E_ARG, "obca_order_plan: mode 0 (detach) or 1 (attach)");
+  if (mode != 0 && mode != 1) return fail(h, PIADMM_E_ARG, "obca_order_plan: mode 0 (detach) or 1 (attach)");
   const int n = p->n;
   if (mode == 1) {
-    if (n > ORDER_CLAMP) return pfail(h, PIADMM_E_ARG, "obca_order_plan: n_scenarios < 2^21");
+    if (n > ORDER_CLAMP) return fail(h, PIADMM_E_ARG, "obca_order_plan: n_scenarios < 2^21");
     if (work_init)
       for (int k = 0; k < n; ++k)
         if (work_init[2 * (size_t)k] < 0 || work_init[2 * (size_t)k + 1] < 0)
-          return pfail(h, PIADMM_E_ARG, "obca_order_plan: row " + std::to_string(k) + ": work_init >= 0");
+          return fail(h, PIADMM_E_ARG, "obca_order_plan: row " + std::to_string(k) + ": work_init >= 0");
   }
-  if (p->i_iter != 0) return pfail(h, PIADMM_E_STATE, "obca_order_plan: only at a step boundary (an MPC step is open)");
-  PHIP(h, hipSetDevice(h->device));
-  PHIP(h, hipStreamSynchronize(h->stream));
+  if (p->i_iter != 0) return fail(h, PIADMM_E_STATE, "obca_order_plan: only at a step boundary (an MPC step is open)");
+  OWN_HIP(h, hipSetDevice(h->device));
+  OWN_HIP(h, hipStreamSynchronize(h->stream));
   // at a step boundary every scenario is active: the current list is all n of them
   const size_t N = (size_t)n;
   const std::vector<int> ident = identity_list(N);
@@ -492,9 +492,9 @@ int32_t piadmm_obca_order_plan(piadmm_obca_t h, int32_t mode, const int32_t* wor
   if (mode == 0) {
     if (p->ord.on && p->ck.on) {
       if (m_cur > 0)
-        PHIP(h, hipMemcpy(p->act[p->cur], p->ck.list, (size_t)m_cur * sizeof(int), hipMemcpyDeviceToDevice));
+        OWN_HIP(h, hipMemcpy(p->act[p->cur], p->ck.list, (size_t)m_cur * sizeof(int), hipMemcpyDeviceToDevice));
     } else if (p->ord.on) {
-      PHIP(h, hipMemcpy(p->act[p->cur], ident.data(), N * sizeof(int), hipMemcpyHostToDevice));
+      OWN_HIP(h, hipMemcpy(p->act[p->cur], ident.data(), N * sizeof(int), hipMemcpyHostToDevice));
     }
     p->ord = {};
     return 0;
@@ -516,7 +516,7 @@ int32_t piadmm_obca_order_plan(piadmm_obca_t h, int32_t mode, const int32_t* wor
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
   if (e != hipSuccess) {
     (void)hipStreamSynchronize(h->stream);
-    return pfail(h, PIADMM_E_HIP, std::string("obca_order_plan: ") + hipGetErrorString(e));
+    return fail(h, PIADMM_E_HIP, std::string("obca_order_plan: ") + hipGetErrorString(e));
   }
   no.on = true;
   p->ord = std::move(no);
@@ -526,32 +526,32 @@ int32_t piadmm_obca_order_plan(piadmm_obca_t h, int32_t mode, const int32_t* wor
 int32_t piadmm_obca_order(piadmm_obca_t h, const int32_t* list, int32_t m, const int32_t* work, int32_t n,
                           int32_t* out) {
   if (!h) return PIADMM_E_ARG;
-  if (n < 1 || n > ORDER_CLAMP) return pfail(h, PIADMM_E_ARG, "obca_order: 1 <= n < 2^21");
-  if (m < 1 || m > n) return pfail(h, PIADMM_E_ARG, "obca_order: 1 <= m <= n");
-  if (!list || !work || !out) return pfail(h, PIADMM_E_ARG, "obca_order: null argument");
+  if (n < 1 || n > ORDER_CLAMP) return fail(h, PIADMM_E_ARG, "obca_order: 1 <= n < 2^21");
+  if (m < 1 || m > n) return fail(h, PIADMM_E_ARG, "obca_order: 1 <= m <= n");
+  if (!list || !work || !out) return fail(h, PIADMM_E_ARG, "obca_order: null argument");
   if (int rc = slots_check(h, "obca_order", "list", list, m, n)) return rc;
   for (int k = 0; k < n; ++k)
     if (work[2 * (size_t)k] < 0 || work[2 * (size_t)k + 1] < 0)
-      return pfail(h, PIADMM_E_ARG, "obca_order: row " + std::to_string(k) + ": work >= 0");
-  PHIP(h, hipSetDevice(h->device));
+      return fail(h, PIADMM_E_ARG, "obca_order: row " + std::to_string(k) + ": work >= 0");
+  OWN_HIP(h, hipSetDevice(h->device));
   const size_t M = (size_t)m, N = (size_t)n;
   scratch a(h);
   int *d_in = a.take<int>(M, false), *d_work = a.take<int>(2 * N, false), *d_out = a.take<int>(M, true);
   if (a.rc) return a.rc;
-  PHIP(h, hipMemcpyAsync(d_in, list, M * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  PHIP(h, hipMemcpyAsync(d_work, work, 2 * N * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(d_in, list, M * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(d_work, work, 2 * N * sizeof(int), hipMemcpyHostToDevice, h->stream));
   hipLaunchKernelGGL(k_plan_order, dim3(blocks_for(m)), dim3(64 * PW), 0, h->stream, d_in, (const int*)nullptr, m,
                      d_work, d_out);
-  PHIP(h, hipGetLastError());
-  PHIP(h, hipMemcpyAsync(out, d_out, M * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  PHIP(h, hipStreamSynchronize(h->stream));
+  OWN_HIP(h, hipGetLastError());
+  OWN_HIP(h, hipMemcpyAsync(out, d_out, M * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  OWN_HIP(h, hipStreamSynchronize(h->stream));
   return 0;
 }
 
 int32_t piadmm_obca_clock_plan(piadmm_obca_t h, int32_t mode, const int32_t* clock_init) {
   piadmm_obca_plan_s* p = nullptr;
   if (int rc = open_plan(h, &p, "obca_clock_plan")) return rc;
-  if (mode != 0 && mode != 1) return pfail(h, PIADMM_E_ARG, "obca_clock_plan: mode 0 (detach) or 1 (attach)");
+  if (mode != 0 && mode != 1) return fail(h, PIADMM_E_ARG, "obca_clock_plan: mode 0 (detach) or 1 (attach)");
   const int n = p->n, n_ref = p->cfg.n_ref;
   const size_t N = (size_t)n;
   std::vector<int> rec(3 * N);
@@ -560,33 +560,33 @@ int32_t piadmm_obca_clock_plan(piadmm_obca_t h, int32_t mode, const int32_t* clo
       const int c0 = clock_init ? clock_init[2 * (size_t)k] : p->t_step;
       const int len = clock_init ? clock_init[2 * (size_t)k + 1] : n_ref;
       if (const char* why = clock_row_check(c0, len, n_ref))
-        return pfail(h, PIADMM_E_ARG, "obca_clock_plan: row " + std::to_string(k) + ": " + why);
+        return fail(h, PIADMM_E_ARG, "obca_clock_plan: row " + std::to_string(k) + ": " + why);
       rec[3 * (size_t)k] = c0;
       rec[3 * (size_t)k + 1] = len;
       rec[3 * (size_t)k + 2] = 1;
     }
   }
   if (mode == 1 && p->fb.on)
-    return pfail(h, PIADMM_E_STATE, "obca_clock_plan: feedback is attached (obca_feedback_plan: the tape has no per-scenario clocks)");
+    return fail(h, PIADMM_E_STATE, "obca_clock_plan: feedback is attached (obca_feedback_plan: the tape has no per-scenario clocks)");
   if (mode == 1 && p->dl.on)
-    return pfail(h, PIADMM_E_STATE, "obca_clock_plan: the delay is attached (obca_delay_plan: it counts the plan's steps, not per-scenario clocks)");
-  if (p->i_iter != 0) return pfail(h, PIADMM_E_STATE, "obca_clock_plan: only at a step boundary (an MPC step is open)");
+    return fail(h, PIADMM_E_STATE, "obca_clock_plan: the delay is attached (obca_delay_plan: it counts the plan's steps, not per-scenario clocks)");
+  if (p->i_iter != 0) return fail(h, PIADMM_E_STATE, "obca_clock_plan: only at a step boundary (an MPC step is open)");
   if (mode == 0) {
     if (!p->ck.on) return 0;
     const std::vector<int>& k = p->ck.host;
     for (int s = 0; s < n; ++s)
       if (!k[3 * (size_t)s + 2] || k[3 * (size_t)s] != k[0] || k[3 * (size_t)s + 1] != n_ref)
-        return pfail(h, PIADMM_E_STATE, "obca_clock_plan: detaching needs every scenario alive, on one c and with len = n_ref (scenario " +
-                     std::to_string(s) + ")");
-    PHIP(h, hipSetDevice(h->device));
-    PHIP(h, hipStreamSynchronize(h->stream));
+        return fail(h, PIADMM_E_STATE, "obca_clock_plan: detaching needs every scenario alive, on one c and with len = n_ref (scenario " +
+                    std::to_string(s) + ")");
+    OWN_HIP(h, hipSetDevice(h->device));
+    OWN_HIP(h, hipStreamSynchronize(h->stream));
     // every scenario is alive: the current list already holds all n, in the plan's order
     p->t_step = k[0];
     p->ck = {};
     return 0;
   }
-  PHIP(h, hipSetDevice(h->device));
-  PHIP(h, hipStreamSynchronize(h->stream));
+  OWN_HIP(h, hipSetDevice(h->device));
+  OWN_HIP(h, hipStreamSynchronize(h->stream));
   piadmm_obca_plan_s::clock_s nk;
   const std::vector<int> ident = identity_list(N);
   hipError_t e = nk.clk.make(3 * N);
@@ -602,7 +602,7 @@ int32_t piadmm_obca_clock_plan(piadmm_obca_t h, int32_t mode, const int32_t* clo
   if (e == hipSuccess) e = hipMemset(nk.list, 0, N * sizeof(int));
   if (e == hipSuccess) e = hipMemset(nk.win, 0, N * WIN * sizeof(double));
   if (e == hipSuccess) e = hipStreamSynchronize(nullptr);      // the fills are done before the stream's kernels write (dalloc)
-  if (e != hipSuccess) return pfail(h, PIADMM_E_HIP, std::string("obca_clock_plan: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return fail(h, PIADMM_E_HIP, std::string("obca_clock_plan: ") + hipGetErrorString(e));
   p->ck = std::move(nk);
   p->ck.host = rec;
   p->ck.cur = 0;
@@ -613,7 +613,7 @@ int32_t piadmm_obca_clock_plan(piadmm_obca_t h, int32_t mode, const int32_t* clo
     (void)hipStreamSynchronize(h->stream);
     return rc;
   }
-  PHIP(h, hipStreamSynchronize(h->stream));
+  OWN_HIP(h, hipStreamSynchronize(h->stream));
   p->n_act = n;
   return 0;
 }
@@ -624,58 +624,58 @@ int32_t piadmm_obca_clock_admit(piadmm_obca_t h, int32_t m, const int32_t* slots
   piadmm_obca_plan_s* p = nullptr;
   if (int rc = open_plan(h, &p, "obca_clock_admit")) return rc;
   const int n = p->n, n_ref = p->cfg.n_ref;
-  if (m < 1 || m > n) return pfail(h, PIADMM_E_ARG, "obca_clock_admit: 1 <= m <= n_scenarios");
-  if (!slots || !clock) return pfail(h, PIADMM_E_ARG, "obca_clock_admit: null argument (slots, clock)");
+  if (m < 1 || m > n) return fail(h, PIADMM_E_ARG, "obca_clock_admit: 1 <= m <= n_scenarios");
+  if (!slots || !clock) return fail(h, PIADMM_E_ARG, "obca_clock_admit: null argument (slots, clock)");
   if (int rc = slots_check(h, "obca_clock_admit", "slots", slots, m, n)) return rc;
   for (int k = 0; k < m; ++k) {
     const std::string row = "obca_clock_admit: row " + std::to_string(k) + ": ";
     if (const char* why = clock_row_check(clock[2 * (size_t)k], clock[2 * (size_t)k + 1], n_ref))
-      return pfail(h, PIADMM_E_ARG, row + why);
+      return fail(h, PIADMM_E_ARG, row + why);
     if (par)
-      if (const char* why = row_check(par + (size_t)k * TAB)) return pfail(h, PIADMM_E_ARG, row + why);
-    if (prob && prob[k] != 0 && prob[k] != 1) return pfail(h, PIADMM_E_ARG, row + "prob must be 0 or 1");
+      if (const char* why = row_check(par + (size_t)k * TAB)) return fail(h, PIADMM_E_ARG, row + why);
+    if (prob && prob[k] != 0 && prob[k] != 1) return fail(h, PIADMM_E_ARG, row + "prob must be 0 or 1");
   }
-  if (!p->ck.on) return pfail(h, PIADMM_E_STATE, "obca_clock_admit: no clock attached (obca_clock_plan)");
-  if (p->tr.on) return pfail(h, PIADMM_E_STATE, "obca_clock_admit: a trace is attached (its minima would mix two tenants)");
-  if (p->i_iter != 0) return pfail(h, PIADMM_E_STATE, "obca_clock_admit: only at a step boundary (an MPC step is open)");
-  if (ref && p->ref_rows != n) return pfail(h, PIADMM_E_STATE, "obca_clock_admit: ref needs a plan with a reference per scenario (obca_fleet_begin)");
-  if (par && p->tab_rows != n) return pfail(h, PIADMM_E_STATE, "obca_clock_admit: par needs a plan with a parameter row per scenario (obca_fleet_begin)");
-  PHIP(h, hipSetDevice(h->device));
-  PHIP(h, hipStreamSynchronize(h->stream));
+  if (!p->ck.on) return fail(h, PIADMM_E_STATE, "obca_clock_admit: no clock attached (obca_clock_plan)");
+  if (p->tr.on) return fail(h, PIADMM_E_STATE, "obca_clock_admit: a trace is attached (its minima would mix two tenants)");
+  if (p->i_iter != 0) return fail(h, PIADMM_E_STATE, "obca_clock_admit: only at a step boundary (an MPC step is open)");
+  if (ref && p->ref_rows != n) return fail(h, PIADMM_E_STATE, "obca_clock_admit: ref needs a plan with a reference per scenario (obca_fleet_begin)");
+  if (par && p->tab_rows != n) return fail(h, PIADMM_E_STATE, "obca_clock_admit: par needs a plan with a parameter row per scenario (obca_fleet_begin)");
+  OWN_HIP(h, hipSetDevice(h->device));
+  OWN_HIP(h, hipStreamSynchronize(h->stream));
   const size_t D = sizeof(double), ref_one = (size_t)2 * n_ref * 5;
   for (int k = 0; k < m; ++k) {
     const size_t s = (size_t)slots[k], K = (size_t)k;
     if (state) {
-      PHIP(h, hipMemcpy(p->bar + s * STATE, state + K * STATE, STATE * D, hipMemcpyHostToDevice));
-      PHIP(h, hipMemcpy(p->barp + s * STATE, state + K * STATE, STATE * D, hipMemcpyHostToDevice));
+      OWN_HIP(h, hipMemcpy(p->bar + s * STATE, state + K * STATE, STATE * D, hipMemcpyHostToDevice));
+      OWN_HIP(h, hipMemcpy(p->barp + s * STATE, state + K * STATE, STATE * D, hipMemcpyHostToDevice));
     }
-    if (ref) PHIP(h, hipMemcpy(p->ref + s * ref_one, ref + K * ref_one, ref_one * D, hipMemcpyHostToDevice));
+    if (ref) OWN_HIP(h, hipMemcpy(p->ref + s * ref_one, ref + K * ref_one, ref_one * D, hipMemcpyHostToDevice));
     if (par) {
-      PHIP(h, hipMemcpy(p->tab + s * TAB, par + K * TAB, TAB * D, hipMemcpyHostToDevice));
+      OWN_HIP(h, hipMemcpy(p->tab + s * TAB, par + K * TAB, TAB * D, hipMemcpyHostToDevice));
       p->admm_rows[s] = (int)par[K * TAB + T_ADMM];
     }
-    if (prob) PHIP(h, hipMemcpy(p->prob + s, prob + K, sizeof(int), hipMemcpyHostToDevice));
-    if (primal_thres) PHIP(h, hipMemcpy(p->pth + s, primal_thres + K, D, hipMemcpyHostToDevice));
-    if (dual_thres) PHIP(h, hipMemcpy(p->dth + s, dual_thres + K, D, hipMemcpyHostToDevice));
+    if (prob) OWN_HIP(h, hipMemcpy(p->prob + s, prob + K, sizeof(int), hipMemcpyHostToDevice));
+    if (primal_thres) OWN_HIP(h, hipMemcpy(p->pth + s, primal_thres + K, D, hipMemcpyHostToDevice));
+    if (dual_thres) OWN_HIP(h, hipMemcpy(p->dth + s, dual_thres + K, D, hipMemcpyHostToDevice));
     // the slot starts as a scenario of a fresh plan does
-    PHIP(h, hipMemset(p->ctrl + s * NCTRL, 0, NCTRL * D));
-    PHIP(h, hipMemset(p->ctrlp + s * NCTRL, 0, NCTRL * D));
-    PHIP(h, hipMemset(p->X + s * NX, 0, NX * D));
-    PHIP(h, hipMemset(p->lamb + s * 126, 0, 126 * D));
-    PHIP(h, hipMemset(p->iters + s, 0, sizeof(int)));
-    PHIP(h, hipMemset(p->mask + 2 * s, 0, 2 * sizeof(int)));
+    OWN_HIP(h, hipMemset(p->ctrl + s * NCTRL, 0, NCTRL * D));
+    OWN_HIP(h, hipMemset(p->ctrlp + s * NCTRL, 0, NCTRL * D));
+    OWN_HIP(h, hipMemset(p->X + s * NX, 0, NX * D));
+    OWN_HIP(h, hipMemset(p->lamb + s * 126, 0, 126 * D));
+    OWN_HIP(h, hipMemset(p->iters + s, 0, sizeof(int)));
+    OWN_HIP(h, hipMemset(p->mask + 2 * s, 0, 2 * sizeof(int)));
     if (p->du.on) {
-      PHIP(h, hipMemcpy(p->du.S + s * 126, p->bar + s * STATE + S_LB, 126 * D, hipMemcpyDeviceToDevice));
-      PHIP(h, hipMemcpy(p->du.Sp + s * 126, p->bar + s * STATE + S_LB, 126 * D, hipMemcpyDeviceToDevice));
-      PHIP(h, hipMemset(p->du.D + s * 126, 0, 126 * D));
-      PHIP(h, hipMemset(p->du.Dp + s * 126, 0, 126 * D));
+      OWN_HIP(h, hipMemcpy(p->du.S + s * 126, p->bar + s * STATE + S_LB, 126 * D, hipMemcpyDeviceToDevice));
+      OWN_HIP(h, hipMemcpy(p->du.Sp + s * 126, p->bar + s * STATE + S_LB, 126 * D, hipMemcpyDeviceToDevice));
+      OWN_HIP(h, hipMemset(p->du.D + s * 126, 0, 126 * D));
+      OWN_HIP(h, hipMemset(p->du.Dp + s * 126, 0, 126 * D));
     }
-    if (p->ord.on) PHIP(h, hipMemset(p->ord.work + 2 * s, 0, 2 * sizeof(int)));
+    if (p->ord.on) OWN_HIP(h, hipMemset(p->ord.work + 2 * s, 0, 2 * sizeof(int)));
     int* k3 = p->ck.host.data() + 3 * s;
     k3[0] = clock[2 * K];
     k3[1] = clock[2 * K + 1];
     k3[2] = 1;
-    PHIP(h, hipMemcpy(p->ck.clk + 3 * s, k3, 3 * sizeof(int), hipMemcpyHostToDevice));
+    OWN_HIP(h, hipMemcpy(p->ck.clk + 3 * s, k3, 3 * sizeof(int), hipMemcpyHostToDevice));
   }
   return clock_relist(h, p);
 }
@@ -684,18 +684,18 @@ int32_t piadmm_obca_clock_tick(piadmm_obca_t h, int32_t n, const int32_t* clock_
                                const double* ref, int32_t ref_rows, int32_t n_ref, int32_t* clock_out,
                                double* window_out, int32_t* list_out, int32_t* count_out) {
   if (!h) return PIADMM_E_ARG;
-  if (n < 1 || n > (1 << 20)) return pfail(h, PIADMM_E_ARG, "obca_clock_tick: 1 <= n <= 2^20");
+  if (n < 1 || n > (1 << 20)) return fail(h, PIADMM_E_ARG, "obca_clock_tick: 1 <= n <= 2^20");
   if (!clock_in || !ran || !ref || !clock_out || !window_out || !list_out || !count_out)
-    return pfail(h, PIADMM_E_ARG, "obca_clock_tick: null argument");
-  if (ref_rows != 1 && ref_rows != n) return pfail(h, PIADMM_E_ARG, "obca_clock_tick: ref_rows must be 1 or n");
-  if (n_ref < 8 || n_ref > (1 << 20)) return pfail(h, PIADMM_E_ARG, "obca_clock_tick: 8 <= n_ref <= 2^20");
+    return fail(h, PIADMM_E_ARG, "obca_clock_tick: null argument");
+  if (ref_rows != 1 && ref_rows != n) return fail(h, PIADMM_E_ARG, "obca_clock_tick: ref_rows must be 1 or n");
+  if (n_ref < 8 || n_ref > (1 << 20)) return fail(h, PIADMM_E_ARG, "obca_clock_tick: 8 <= n_ref <= 2^20");
   for (int k = 0; k < n; ++k) {
     const int c = clock_in[3 * (size_t)k], len = clock_in[3 * (size_t)k + 1];
     const char* why = c < 0 || c > (1 << 30) ? "0 <= c <= 2^30" : len < 8 || len > n_ref ? "8 <= len <= n_ref"
                       : ran[k] != 0 && ran[k] != 1 ? "ran 0 or 1" : nullptr;
-    if (why) return pfail(h, PIADMM_E_ARG, "obca_clock_tick: row " + std::to_string(k) + ": " + why);
+    if (why) return fail(h, PIADMM_E_ARG, "obca_clock_tick: row " + std::to_string(k) + ": " + why);
   }
-  PHIP(h, hipSetDevice(h->device));
+  OWN_HIP(h, hipSetDevice(h->device));
   const size_t N = (size_t)n, ref_one = (size_t)2 * n_ref * 5, R = ref_one * (size_t)ref_rows;
   const std::vector<int> ident = identity_list(N);
   scratch a(h);
@@ -703,20 +703,20 @@ int32_t piadmm_obca_clock_tick(piadmm_obca_t h, int32_t n, const int32_t* clock_
       *d_ident = a.take<int>(N, false), *d_list = a.take<int>(N, true), *d_count = a.take<int>(1, true);
   double *d_ref = a.take<double>(R, false), *d_win = a.take<double>(N * WIN, true);
   if (a.rc) return a.rc;
-  PHIP(h, hipMemcpyAsync(d_clk, clock_in, 3 * N * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  PHIP(h, hipMemcpyAsync(d_ran, ran, N * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  PHIP(h, hipMemcpyAsync(d_ident, ident.data(), N * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  PHIP(h, hipMemcpyAsync(d_ref, ref, R * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(d_clk, clock_in, 3 * N * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(d_ran, ran, N * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(d_ident, ident.data(), N * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(d_ref, ref, R * sizeof(double), hipMemcpyHostToDevice, h->stream));
   hipLaunchKernelGGL(k_plan_clock, dim3(blocks_for(n)), dim3(64 * PW), 0, h->stream, n, d_clk, d_ran, d_ref,
                      ref_rows > 1 ? (int)ref_one : 0, n_ref, d_win, d_alive);
-  PHIP(h, hipGetLastError());
+  OWN_HIP(h, hipGetLastError());
   hipLaunchKernelGGL(k_plan_compact, dim3(1), dim3(CT), 0, h->stream, d_ident, d_alive, n, d_list, d_count);
-  PHIP(h, hipGetLastError());
-  PHIP(h, hipMemcpyAsync(clock_out, d_clk, 3 * N * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  PHIP(h, hipMemcpyAsync(window_out, d_win, N * WIN * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  PHIP(h, hipMemcpyAsync(list_out, d_list, N * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  PHIP(h, hipMemcpyAsync(count_out, d_count, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  PHIP(h, hipStreamSynchronize(h->stream));
+  OWN_HIP(h, hipGetLastError());
+  OWN_HIP(h, hipMemcpyAsync(clock_out, d_clk, 3 * N * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(window_out, d_win, N * WIN * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(list_out, d_list, N * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(count_out, d_count, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  OWN_HIP(h, hipStreamSynchronize(h->stream));
   return 0;
 }
 

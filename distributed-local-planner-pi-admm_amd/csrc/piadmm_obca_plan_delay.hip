@@ -113,7 +113,7 @@ int delay_next(piadmm_obca_t h, piadmm_obca_plan_s* p) {
   yo.k = (uint32_t)p->dl.k0 + (uint32_t)next;
   hipLaunchKernelGGL(k_plan_delay, dim3(lane_blocks(2 * p->n)), dim3(64 * PW), 0, h->stream, (const int*)nullptr, p->n,
                      yo);
-  PHIP(h, hipGetLastError());
+  OWN_HIP(h, hipGetLastError());
   return 0;
 }
 
@@ -139,22 +139,22 @@ const char* delay_row_check(const double* row) {
 // rows, streams, k0 and the tape of both delay calls that draw, on the host
 int delay_args_check(piadmm_obca_t h, int n, const double* par, int rows, const int64_t* streams, int32_t k0,
                      int64_t steps, const double* tape, int cap, const std::string& who) {
-  if (!par) return pfail(h, PIADMM_E_ARG, who + ": null argument");
+  if (!par) return fail(h, PIADMM_E_ARG, who + ": null argument");
   if (int rc = rows_check(h, who, rows, n)) return rc;
   for (int k = 0; k < rows; ++k)
     if (const char* why = delay_row_check(par + (size_t)k * YPAR))
-      return pfail(h, PIADMM_E_ARG, who + ": row " + std::to_string(k) + ": " + why);
+      return fail(h, PIADMM_E_ARG, who + ": row " + std::to_string(k) + ": " + why);
   if (streams)
     for (int k = 0; k < n; ++k)
-      if (streams[k] < 0) return pfail(h, PIADMM_E_ARG, who + ": streams[" + std::to_string(k) + "] must be >= 0");
+      if (streams[k] < 0) return fail(h, PIADMM_E_ARG, who + ": streams[" + std::to_string(k) + "] must be >= 0");
   if (k0 < 0 || (int64_t)k0 + steps > ((int64_t)1 << 31))
-    return pfail(h, PIADMM_E_ARG, who + ": k0 >= 0 and every step index below 2^31");
+    return fail(h, PIADMM_E_ARG, who + ": k0 >= 0 and every step index below 2^31");
   if (tape) {
     const size_t T = (size_t)n * (size_t)cap * 2;
     for (size_t i = 0; i < T; ++i)
       if (!std::isfinite(tape[i]))
-        return pfail(h, PIADMM_E_ARG, who + ": the tape of scenario " + std::to_string(i / ((size_t)cap * 2)) +
-                     " is not finite (step " + std::to_string(i / 2 % (size_t)cap) + ")");
+        return fail(h, PIADMM_E_ARG, who + ": the tape of scenario " + std::to_string(i / ((size_t)cap * 2)) +
+                    " is not finite (step " + std::to_string(i / 2 % (size_t)cap) + ")");
   }
   return 0;
 }
@@ -166,24 +166,24 @@ int32_t piadmm_obca_delay_tau(piadmm_obca_t h, int32_t n, int32_t cap, const dou
                               const int64_t* streams, uint64_t seed, int32_t k0, const double* tape, double* tau_out,
                               uint32_t* raw_out) {
   if (!h) return PIADMM_E_ARG;
-  if (n < 1 || n > (1 << 20)) return pfail(h, PIADMM_E_ARG, "obca_delay_tau: 1 <= n <= 2^20");
-  if (cap < 0 || cap > (1 << 20)) return pfail(h, PIADMM_E_ARG, "obca_delay_tau: 0 <= cap <= 2^20");
+  if (n < 1 || n > (1 << 20)) return fail(h, PIADMM_E_ARG, "obca_delay_tau: 1 <= n <= 2^20");
+  if (cap < 0 || cap > (1 << 20)) return fail(h, PIADMM_E_ARG, "obca_delay_tau: 0 <= cap <= 2^20");
   const size_t N = (size_t)n, C = (size_t)cap, B = sizeof(double);
   if (N * C * 2 * B >= ((size_t)1 << 31))
-    return pfail(h, PIADMM_E_ARG, "obca_delay_tau: n x cap x 16 bytes must stay below 2 GiB");
+    return fail(h, PIADMM_E_ARG, "obca_delay_tau: n x cap x 16 bytes must stay below 2 GiB");
   if (int rc = delay_args_check(h, n, par, rows, streams, k0, cap, tape, cap, "obca_delay_tau")) return rc;
   if (cap == 0) return 0;
-  if (!tau_out) return pfail(h, PIADMM_E_ARG, "obca_delay_tau: null argument");
-  PHIP(h, hipSetDevice(h->device));
+  if (!tau_out) return fail(h, PIADMM_E_ARG, "obca_delay_tau: null argument");
+  OWN_HIP(h, hipSetDevice(h->device));
   scratch a(h);
   double *d_par = a.take<double>((size_t)rows * YPAR, false), *d_out = a.take<double>(N * C * 2, false),
          *d_tape = tape ? a.take<double>(N * C * 2, false) : nullptr;
   long long* d_str = streams ? a.take<long long>(N, false) : nullptr;
   uint32_t* d_raw = raw_out ? a.take<uint32_t>(N * C * 8, false) : nullptr;
   if (a.rc) return a.rc;
-  PHIP(h, hipMemcpyAsync(d_par, par, (size_t)rows * YPAR * B, hipMemcpyHostToDevice, h->stream));
-  if (streams) PHIP(h, hipMemcpyAsync(d_str, streams, N * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-  if (tape) PHIP(h, hipMemcpyAsync(d_tape, tape, N * C * 2 * B, hipMemcpyHostToDevice, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(d_par, par, (size_t)rows * YPAR * B, hipMemcpyHostToDevice, h->stream));
+  if (streams) OWN_HIP(h, hipMemcpyAsync(d_str, streams, N * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+  if (tape) OWN_HIP(h, hipMemcpyAsync(d_tape, tape, N * C * 2 * B, hipMemcpyHostToDevice, h->stream));
   delay_io yo{};
   yo.par = d_par;  yo.par_s = rows > 1 ? YPAR : 0;
   yo.streams = d_str;
@@ -198,47 +198,47 @@ int32_t piadmm_obca_delay_tau(piadmm_obca_t h, int32_t n, int32_t cap, const dou
     yo.k = (uint32_t)k0 + (uint32_t)at;
     hipLaunchKernelGGL(k_plan_delay, dim3(lane_blocks(2 * n), ny), dim3(64 * PW), 0, h->stream, (const int*)nullptr, n,
                        yo);
-    PHIP(h, hipGetLastError());
+    OWN_HIP(h, hipGetLastError());
   }
-  PHIP(h, hipMemcpyAsync(tau_out, d_out, N * C * 2 * B, hipMemcpyDeviceToHost, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(tau_out, d_out, N * C * 2 * B, hipMemcpyDeviceToHost, h->stream));
   if (raw_out)
-    PHIP(h, hipMemcpyAsync(raw_out, d_raw, N * C * 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-  PHIP(h, hipStreamSynchronize(h->stream));
+    OWN_HIP(h, hipMemcpyAsync(raw_out, d_raw, N * C * 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+  OWN_HIP(h, hipStreamSynchronize(h->stream));
   return 0;
 }
 
 int32_t piadmm_obca_delay_exchange(piadmm_obca_t h, int32_t n, const double* X, const int32_t* prob, const double* tau,
                                    double* lx_out, double* A_out, double* b_out) {
   if (!h) return PIADMM_E_ARG;
-  if (n < 1 || n > (1 << 20)) return pfail(h, PIADMM_E_ARG, "obca_delay_exchange: 1 <= n <= 2^20");
+  if (n < 1 || n > (1 << 20)) return fail(h, PIADMM_E_ARG, "obca_delay_exchange: 1 <= n <= 2^20");
   if (!X || !prob || !tau || !lx_out || !A_out || !b_out)
-    return pfail(h, PIADMM_E_ARG, "obca_delay_exchange: null argument");
+    return fail(h, PIADMM_E_ARG, "obca_delay_exchange: null argument");
   const size_t N = (size_t)n, B = sizeof(double);
   for (int k = 0; k < n; ++k) {
     if (int rc = prob_check(h, "obca_delay_exchange", prob, k)) return rc;
     for (int i = 0; i < NX; ++i)
       if (!std::isfinite(X[(size_t)k * NX + i]))
-        return pfail(h, PIADMM_E_ARG, "obca_delay_exchange: X of scenario " + std::to_string(k) + " is not finite");
+        return fail(h, PIADMM_E_ARG, "obca_delay_exchange: X of scenario " + std::to_string(k) + " is not finite");
     for (int v = 0; v < 2; ++v)
       if (!(tau[2 * (size_t)k + v] >= 0.0 && tau[2 * (size_t)k + v] <= PLANT_DT))
-        return pfail(h, PIADMM_E_ARG, "obca_delay_exchange: tau of scenario " + std::to_string(k) + " must be in [0, DT]");
+        return fail(h, PIADMM_E_ARG, "obca_delay_exchange: tau of scenario " + std::to_string(k) + " must be in [0, DT]");
   }
-  PHIP(h, hipSetDevice(h->device));
+  OWN_HIP(h, hipSetDevice(h->device));
   scratch a(h);
   double *d_X = a.take<double>(N * NX, false), *d_tau = a.take<double>(N * 2, false),
          *d_lx = a.take<double>(N * 70, true), *d_A = a.take<double>(N * 112, true), *d_b = a.take<double>(N * 56, true);
   int* d_prob = a.take<int>(N, false);
   if (a.rc) return a.rc;
-  PHIP(h, hipMemcpyAsync(d_X, X, N * NX * B, hipMemcpyHostToDevice, h->stream));
-  PHIP(h, hipMemcpyAsync(d_tau, tau, N * 2 * B, hipMemcpyHostToDevice, h->stream));
-  PHIP(h, hipMemcpyAsync(d_prob, prob, N * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(d_X, X, N * NX * B, hipMemcpyHostToDevice, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(d_tau, tau, N * 2 * B, hipMemcpyHostToDevice, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(d_prob, prob, N * sizeof(int), hipMemcpyHostToDevice, h->stream));
   hipLaunchKernelGGL(k_delay_exchange, dim3(blocks_for(n)), dim3(64 * PW), 0, h->stream, n, (const double*)d_X,
                      (const int*)d_prob, (const double*)d_tau, std::sqrt(0.95 / (1.0 - 0.95)), d_lx, d_A, d_b);
-  PHIP(h, hipGetLastError());
-  PHIP(h, hipMemcpyAsync(lx_out, d_lx, N * 70 * B, hipMemcpyDeviceToHost, h->stream));
-  PHIP(h, hipMemcpyAsync(A_out, d_A, N * 112 * B, hipMemcpyDeviceToHost, h->stream));
-  PHIP(h, hipMemcpyAsync(b_out, d_b, N * 56 * B, hipMemcpyDeviceToHost, h->stream));
-  PHIP(h, hipStreamSynchronize(h->stream));
+  OWN_HIP(h, hipGetLastError());
+  OWN_HIP(h, hipMemcpyAsync(lx_out, d_lx, N * 70 * B, hipMemcpyDeviceToHost, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(A_out, d_A, N * 112 * B, hipMemcpyDeviceToHost, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(b_out, d_b, N * 56 * B, hipMemcpyDeviceToHost, h->stream));
+  OWN_HIP(h, hipStreamSynchronize(h->stream));
   return 0;
 }
 
@@ -246,18 +246,18 @@ int32_t piadmm_obca_delay_plan(piadmm_obca_t h, int32_t mode, const double* par,
                                uint64_t seed, int32_t k0, const double* tape, int32_t cap) {
   piadmm_obca_plan_s* p = nullptr;
   if (int rc = open_plan(h, &p, "obca_delay_plan")) return rc;
-  if (mode != 0 && mode != 1) return pfail(h, PIADMM_E_ARG, "obca_delay_plan: mode 0 (detach) or 1 (attach)");
+  if (mode != 0 && mode != 1) return fail(h, PIADMM_E_ARG, "obca_delay_plan: mode 0 (detach) or 1 (attach)");
   const int n = p->n;
   const size_t N = (size_t)n;
   if (mode == 1) {
-    if (tape && (cap < 0 || cap > (1 << 20))) return pfail(h, PIADMM_E_ARG, "obca_delay_plan: 0 <= cap <= 2^20");
+    if (tape && (cap < 0 || cap > (1 << 20))) return fail(h, PIADMM_E_ARG, "obca_delay_plan: 0 <= cap <= 2^20");
     if (int rc = delay_args_check(h, n, par, rows, streams, k0, 0, tape, cap, "obca_delay_plan")) return rc;
     if (p->ck.on)
-      return pfail(h, PIADMM_E_STATE, "obca_delay_plan: a clock is attached (obca_clock_plan: the delay counts the plan's steps, not per-scenario clocks)");
+      return fail(h, PIADMM_E_STATE, "obca_delay_plan: a clock is attached (obca_clock_plan: the delay counts the plan's steps, not per-scenario clocks)");
   }
-  if (p->i_iter != 0) return pfail(h, PIADMM_E_STATE, "obca_delay_plan: only at a step boundary (an MPC step is open)");
-  PHIP(h, hipSetDevice(h->device));
-  PHIP(h, hipStreamSynchronize(h->stream));
+  if (p->i_iter != 0) return fail(h, PIADMM_E_STATE, "obca_delay_plan: only at a step boundary (an MPC step is open)");
+  OWN_HIP(h, hipSetDevice(h->device));
+  OWN_HIP(h, hipStreamSynchronize(h->stream));
   if (mode == 0) {
     p->dl = {};
     return 0;
@@ -298,7 +298,7 @@ int32_t piadmm_obca_delay_plan(piadmm_obca_t h, int32_t mode, const double* par,
   }
   if (e != hipSuccess) {
     (void)hipStreamSynchronize(h->stream);
-    return pfail(h, PIADMM_E_HIP, std::string("obca_delay_plan: ") + hipGetErrorString(e));
+    return fail(h, PIADMM_E_HIP, std::string("obca_delay_plan: ") + hipGetErrorString(e));
   }
   p->dl = std::move(nd);
   p->dl.rows = rows;

@@ -243,30 +243,30 @@ extern "C" {
 int32_t piadmm_obca_propagate(piadmm_obca_t h, int32_t n, const double* states, const double* ctrl, const double* par,
                               const double* w, double* out) {
   if (!h) return PIADMM_E_ARG;
-  if (n < 1 || n > (1 << 20)) return pfail(h, PIADMM_E_ARG, "obca_propagate: 1 <= n <= 2^20");
-  if (!states || !ctrl || !par || !out) return pfail(h, PIADMM_E_ARG, "obca_propagate: null argument");
+  if (n < 1 || n > (1 << 20)) return fail(h, PIADMM_E_ARG, "obca_propagate: 1 <= n <= 2^20");
+  if (!states || !ctrl || !par || !out) return fail(h, PIADMM_E_ARG, "obca_propagate: null argument");
   const size_t N = (size_t)n;
   int64_t bad = -1;
   if ((bad = first_not_finite(states, N * 10)) >= 0)
-    return pfail(h, PIADMM_E_ARG, "obca_propagate: state pair " + std::to_string(bad / 10) + " is not finite");
+    return fail(h, PIADMM_E_ARG, "obca_propagate: state pair " + std::to_string(bad / 10) + " is not finite");
   if ((bad = first_not_finite(ctrl, N * 4)) >= 0)
-    return pfail(h, PIADMM_E_ARG, "obca_propagate: ctrl of scenario " + std::to_string(bad / 4) + " is not finite");
+    return fail(h, PIADMM_E_ARG, "obca_propagate: ctrl of scenario " + std::to_string(bad / 4) + " is not finite");
   if (w && (bad = first_not_finite(w, N * 10)) >= 0)
-    return pfail(h, PIADMM_E_ARG, "obca_propagate: w of scenario " + std::to_string(bad / 10) + " is not finite");
+    return fail(h, PIADMM_E_ARG, "obca_propagate: w of scenario " + std::to_string(bad / 10) + " is not finite");
   for (int k = 0; k < n; ++k)
     if (const char* why = feedback_row_check(par + (size_t)k * FPAR))
-      return pfail(h, PIADMM_E_ARG, "obca_propagate: row " + std::to_string(k) + ": " + why);
-  PHIP(h, hipSetDevice(h->device));
+      return fail(h, PIADMM_E_ARG, "obca_propagate: row " + std::to_string(k) + ": " + why);
+  OWN_HIP(h, hipSetDevice(h->device));
   const size_t B = sizeof(double);
   scratch a(h);
   double *d_st = a.take<double>(N * 10, false), *d_ct = a.take<double>(N * 4, false),
          *d_par = a.take<double>(N * FPAR, false), *d_w = w ? a.take<double>(N * 10, false) : nullptr,
          *d_out = a.take<double>(N * 10, true);
   if (a.rc) return a.rc;
-  PHIP(h, hipMemcpyAsync(d_st, states, N * 10 * B, hipMemcpyHostToDevice, h->stream));
-  PHIP(h, hipMemcpyAsync(d_ct, ctrl, N * 4 * B, hipMemcpyHostToDevice, h->stream));
-  PHIP(h, hipMemcpyAsync(d_par, par, N * FPAR * B, hipMemcpyHostToDevice, h->stream));
-  if (w) PHIP(h, hipMemcpyAsync(d_w, w, N * 10 * B, hipMemcpyHostToDevice, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(d_st, states, N * 10 * B, hipMemcpyHostToDevice, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(d_ct, ctrl, N * 4 * B, hipMemcpyHostToDevice, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(d_par, par, N * FPAR * B, hipMemcpyHostToDevice, h->stream));
+  if (w) OWN_HIP(h, hipMemcpyAsync(d_w, w, N * 10 * B, hipMemcpyHostToDevice, h->stream));
   plant_io io{};
   io.x0 = d_st;  io.x0_s = 10;
   io.ctrl = d_ct;  io.ctrl_s = 4;  io.ctrl_v = 2;  io.ctrl_w = 1;
@@ -275,9 +275,9 @@ int32_t piadmm_obca_propagate(piadmm_obca_t h, int32_t n, const double* states, 
   io.out = d_out;
   hipLaunchKernelGGL(k_plan_propagate, dim3(lane_blocks(2 * n)), dim3(64 * PW), 0, h->stream, (const int*)nullptr, n,
                      io);
-  PHIP(h, hipGetLastError());
-  PHIP(h, hipMemcpyAsync(out, d_out, N * 10 * B, hipMemcpyDeviceToHost, h->stream));
-  PHIP(h, hipStreamSynchronize(h->stream));
+  OWN_HIP(h, hipGetLastError());
+  OWN_HIP(h, hipMemcpyAsync(out, d_out, N * 10 * B, hipMemcpyDeviceToHost, h->stream));
+  OWN_HIP(h, hipStreamSynchronize(h->stream));
   return 0;
 }
 
@@ -285,7 +285,7 @@ int32_t piadmm_obca_feedback_plan(piadmm_obca_t h, int32_t mode, const double* p
                                   int32_t cap) {
   piadmm_obca_plan_s* p = nullptr;
   if (int rc = open_plan(h, &p, "obca_feedback_plan")) return rc;
-  if (mode != 0 && mode != 1) return pfail(h, PIADMM_E_ARG, "obca_feedback_plan: mode 0 (detach) or 1 (attach)");
+  if (mode != 0 && mode != 1) return fail(h, PIADMM_E_ARG, "obca_feedback_plan: mode 0 (detach) or 1 (attach)");
   const int n = p->n;
   const size_t N = (size_t)n;
   double nominal[FPAR];
@@ -295,25 +295,25 @@ int32_t piadmm_obca_feedback_plan(piadmm_obca_t h, int32_t mode, const double* p
       if (int rc = rows_check(h, "obca_feedback_plan", rows, n)) return rc;
       for (int k = 0; k < rows; ++k)
         if (const char* why = feedback_row_check(par + (size_t)k * FPAR))
-          return pfail(h, PIADMM_E_ARG, "obca_feedback_plan: row " + std::to_string(k) + ": " + why);
+          return fail(h, PIADMM_E_ARG, "obca_feedback_plan: row " + std::to_string(k) + ": " + why);
     } else {
       par = nominal;
       rows = 1;
     }
     if (tape) {
-      if (cap < 0 || cap > (1 << 20)) return pfail(h, PIADMM_E_ARG, "obca_feedback_plan: 0 <= cap <= 2^20");
+      if (cap < 0 || cap > (1 << 20)) return fail(h, PIADMM_E_ARG, "obca_feedback_plan: 0 <= cap <= 2^20");
       const int64_t bad = first_not_finite(tape, N * (size_t)cap * 10);
       if (bad >= 0)
-        return pfail(h, PIADMM_E_ARG, "obca_feedback_plan: the tape of scenario " +
-                     std::to_string(bad / ((int64_t)cap * 10)) + " is not finite (step " +
-                     std::to_string(bad / 10 % cap) + ")");
+        return fail(h, PIADMM_E_ARG, "obca_feedback_plan: the tape of scenario " +
+                    std::to_string(bad / ((int64_t)cap * 10)) + " is not finite (step " +
+                    std::to_string(bad / 10 % cap) + ")");
     }
     if (p->ck.on)
-      return pfail(h, PIADMM_E_STATE, "obca_feedback_plan: a clock is attached (obca_clock_plan: the tape has no per-scenario clocks)");
+      return fail(h, PIADMM_E_STATE, "obca_feedback_plan: a clock is attached (obca_clock_plan: the tape has no per-scenario clocks)");
   }
-  if (p->i_iter != 0) return pfail(h, PIADMM_E_STATE, "obca_feedback_plan: only at a step boundary (an MPC step is open)");
-  PHIP(h, hipSetDevice(h->device));
-  PHIP(h, hipStreamSynchronize(h->stream));
+  if (p->i_iter != 0) return fail(h, PIADMM_E_STATE, "obca_feedback_plan: only at a step boundary (an MPC step is open)");
+  OWN_HIP(h, hipSetDevice(h->device));
+  OWN_HIP(h, hipStreamSynchronize(h->stream));
   if (mode == 0) {
     p->fb = {};
     p->nz = {};    // the noise counts its steps by the feedback's: it goes whenever the feedback goes or is replaced
@@ -331,7 +331,7 @@ int32_t piadmm_obca_feedback_plan(piadmm_obca_t h, int32_t mode, const double* p
     e = nf.tape.make(std::max(T, (size_t)1));
     if (e == hipSuccess && T) e = hipMemcpy(nf.tape, tape, T * sizeof(double), hipMemcpyHostToDevice);
   }
-  if (e != hipSuccess) return pfail(h, PIADMM_E_HIP, std::string("obca_feedback_plan: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return fail(h, PIADMM_E_HIP, std::string("obca_feedback_plan: ") + hipGetErrorString(e));
   p->fb = std::move(nf);
   p->nz = {};      // as above
   p->fb.rows = rows;
@@ -346,29 +346,29 @@ int32_t piadmm_obca_feedback_measure(piadmm_obca_t h, int32_t m, const int32_t* 
   piadmm_obca_plan_s* p = nullptr;
   if (int rc = open_plan(h, &p, "obca_feedback_measure")) return rc;
   const int n = p->n;
-  if (m < 1 || m > n) return pfail(h, PIADMM_E_ARG, "obca_feedback_measure: 1 <= m <= n_scenarios");
-  if (!slots || !states) return pfail(h, PIADMM_E_ARG, "obca_feedback_measure: null argument");
+  if (m < 1 || m > n) return fail(h, PIADMM_E_ARG, "obca_feedback_measure: 1 <= m <= n_scenarios");
+  if (!slots || !states) return fail(h, PIADMM_E_ARG, "obca_feedback_measure: null argument");
   for (int k = 0; k < m; ++k)
     if (slots[k] < 0 || slots[k] >= n || (k > 0 && slots[k] <= slots[k - 1]))
-      return pfail(h, PIADMM_E_ARG, "obca_feedback_measure: slots[" + std::to_string(k) +
-                   "] must be a scenario below n, the slots ascending and distinct");
+      return fail(h, PIADMM_E_ARG, "obca_feedback_measure: slots[" + std::to_string(k) +
+                  "] must be a scenario below n, the slots ascending and distinct");
   const int64_t bad = first_not_finite(states, (size_t)m * 10);
   if (bad >= 0)
-    return pfail(h, PIADMM_E_ARG, "obca_feedback_measure: state pair " + std::to_string(bad / 10) + " is not finite");
-  if (p->i_iter != 0) return pfail(h, PIADMM_E_STATE, "obca_feedback_measure: only at a step boundary (an MPC step is open)");
+    return fail(h, PIADMM_E_ARG, "obca_feedback_measure: state pair " + std::to_string(bad / 10) + " is not finite");
+  if (p->i_iter != 0) return fail(h, PIADMM_E_STATE, "obca_feedback_measure: only at a step boundary (an MPC step is open)");
   if (p->tr.on)
-    return pfail(h, PIADMM_E_STATE, "obca_feedback_measure: a trace is attached (its last row was computed from the state being replaced)");
-  PHIP(h, hipSetDevice(h->device));
+    return fail(h, PIADMM_E_STATE, "obca_feedback_measure: a trace is attached (its last row was computed from the state being replaced)");
+  OWN_HIP(h, hipSetDevice(h->device));
   // the states, then the slot numbers, through the staging buffer; one scatter launch
   const size_t body = (size_t)m * 10 * sizeof(double);
   if (int rc = stage_ensure(h, p, body, m)) return rc;
   int* d_list = reinterpret_cast<int*>(p->stg.buf + body);
-  PHIP(h, hipMemcpyAsync(p->stg.buf, states, body, hipMemcpyHostToDevice, h->stream));
-  PHIP(h, hipMemcpyAsync(d_list, slots, (size_t)m * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(p->stg.buf, states, body, hipMemcpyHostToDevice, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(d_list, slots, (size_t)m * sizeof(int), hipMemcpyHostToDevice, h->stream));
   hipLaunchKernelGGL(k_plan_set_init, dim3(lane_blocks(2 * m)), dim3(64 * PW), 0, h->stream, (const int*)d_list, m,
                      reinterpret_cast<const double*>(p->stg.buf.get()), p->bar, p->barp);
-  PHIP(h, hipGetLastError());
-  PHIP(h, hipStreamSynchronize(h->stream));
+  OWN_HIP(h, hipGetLastError());
+  OWN_HIP(h, hipStreamSynchronize(h->stream));
   return 0;
 }
 
@@ -392,16 +392,16 @@ const char* noise_row_check(const double* row) {
 // rows, streams and k0 of both noise calls, on the host
 int noise_args_check(piadmm_obca_t h, int n, const double* par, int rows, const int64_t* streams, int32_t k0,
                      int64_t steps, const std::string& who) {
-  if (!par) return pfail(h, PIADMM_E_ARG, who + ": null argument");
+  if (!par) return fail(h, PIADMM_E_ARG, who + ": null argument");
   if (int rc = rows_check(h, who, rows, n)) return rc;
   for (int k = 0; k < rows; ++k)
     if (const char* why = noise_row_check(par + (size_t)k * obca_plan::ZPAR))
-      return pfail(h, PIADMM_E_ARG, who + ": row " + std::to_string(k) + ": " + why);
+      return fail(h, PIADMM_E_ARG, who + ": row " + std::to_string(k) + ": " + why);
   if (streams)
     for (int k = 0; k < n; ++k)
-      if (streams[k] < 0) return pfail(h, PIADMM_E_ARG, who + ": streams[" + std::to_string(k) + "] must be >= 0");
+      if (streams[k] < 0) return fail(h, PIADMM_E_ARG, who + ": streams[" + std::to_string(k) + "] must be >= 0");
   if (k0 < 0 || (int64_t)k0 + steps > ((int64_t)1 << 31))
-    return pfail(h, PIADMM_E_ARG, who + ": k0 >= 0 and every step index below 2^31");
+    return fail(h, PIADMM_E_ARG, who + ": k0 >= 0 and every step index below 2^31");
   return 0;
 }
 }  // namespace
@@ -411,22 +411,22 @@ extern "C" {
 int32_t piadmm_obca_noise_tape(piadmm_obca_t h, int32_t n, int32_t cap, const double* par, int32_t rows,
                                const int64_t* streams, uint64_t seed, int32_t k0, double* tape_out, uint32_t* raw_out) {
   if (!h) return PIADMM_E_ARG;
-  if (n < 1 || n > (1 << 20)) return pfail(h, PIADMM_E_ARG, "obca_noise_tape: 1 <= n <= 2^20");
-  if (cap < 0 || cap > (1 << 20)) return pfail(h, PIADMM_E_ARG, "obca_noise_tape: 0 <= cap <= 2^20");
+  if (n < 1 || n > (1 << 20)) return fail(h, PIADMM_E_ARG, "obca_noise_tape: 1 <= n <= 2^20");
+  if (cap < 0 || cap > (1 << 20)) return fail(h, PIADMM_E_ARG, "obca_noise_tape: 0 <= cap <= 2^20");
   const size_t N = (size_t)n, C = (size_t)cap, B = sizeof(double);
   if (N * C * 10 * B >= ((size_t)1 << 31))
-    return pfail(h, PIADMM_E_ARG, "obca_noise_tape: n x cap x 80 bytes must stay below 2 GiB");
+    return fail(h, PIADMM_E_ARG, "obca_noise_tape: n x cap x 80 bytes must stay below 2 GiB");
   if (int rc = noise_args_check(h, n, par, rows, streams, k0, cap, "obca_noise_tape")) return rc;
   if (cap == 0) return 0;
-  if (!tape_out) return pfail(h, PIADMM_E_ARG, "obca_noise_tape: null argument");
-  PHIP(h, hipSetDevice(h->device));
+  if (!tape_out) return fail(h, PIADMM_E_ARG, "obca_noise_tape: null argument");
+  OWN_HIP(h, hipSetDevice(h->device));
   scratch a(h);
   double *d_par = a.take<double>((size_t)rows * ZPAR, false), *d_out = a.take<double>(N * C * 10, false);
   long long* d_str = streams ? a.take<long long>(N, false) : nullptr;
   uint32_t* d_raw = raw_out ? a.take<uint32_t>(N * C * 24, false) : nullptr;
   if (a.rc) return a.rc;
-  PHIP(h, hipMemcpyAsync(d_par, par, (size_t)rows * ZPAR * B, hipMemcpyHostToDevice, h->stream));
-  if (streams) PHIP(h, hipMemcpyAsync(d_str, streams, N * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(d_par, par, (size_t)rows * ZPAR * B, hipMemcpyHostToDevice, h->stream));
+  if (streams) OWN_HIP(h, hipMemcpyAsync(d_str, streams, N * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
   noise_io zo{};
   zo.par = d_par;  zo.par_s = rows > 1 ? ZPAR : 0;
   zo.streams = d_str;
@@ -440,12 +440,12 @@ int32_t piadmm_obca_noise_tape(piadmm_obca_t h, int32_t n, int32_t cap, const do
     zo.k = (uint32_t)k0 + (uint32_t)at;
     hipLaunchKernelGGL(k_plan_noise, dim3(lane_blocks(2 * n), ny), dim3(64 * PW), 0, h->stream, (const int*)nullptr,
                        n, zo);
-    PHIP(h, hipGetLastError());
+    OWN_HIP(h, hipGetLastError());
   }
-  PHIP(h, hipMemcpyAsync(tape_out, d_out, N * C * 10 * B, hipMemcpyDeviceToHost, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(tape_out, d_out, N * C * 10 * B, hipMemcpyDeviceToHost, h->stream));
   if (raw_out)
-    PHIP(h, hipMemcpyAsync(raw_out, d_raw, N * C * 24 * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-  PHIP(h, hipStreamSynchronize(h->stream));
+    OWN_HIP(h, hipMemcpyAsync(raw_out, d_raw, N * C * 24 * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+  OWN_HIP(h, hipStreamSynchronize(h->stream));
   return 0;
 }
 
@@ -453,16 +453,16 @@ int32_t piadmm_obca_noise_plan(piadmm_obca_t h, int32_t mode, const double* par,
                                uint64_t seed, int32_t k0) {
   piadmm_obca_plan_s* p = nullptr;
   if (int rc = open_plan(h, &p, "obca_noise_plan")) return rc;
-  if (mode != 0 && mode != 1) return pfail(h, PIADMM_E_ARG, "obca_noise_plan: mode 0 (detach) or 1 (attach)");
+  if (mode != 0 && mode != 1) return fail(h, PIADMM_E_ARG, "obca_noise_plan: mode 0 (detach) or 1 (attach)");
   const int n = p->n;
   const size_t N = (size_t)n;
   if (mode == 1)
     if (int rc = noise_args_check(h, n, par, rows, streams, k0, 0, "obca_noise_plan")) return rc;
   if (mode == 1 && !p->fb.on)
-    return pfail(h, PIADMM_E_STATE, "obca_noise_plan: no feedback attached (obca_feedback_plan: the noise enters through the plant step)");
-  if (p->i_iter != 0) return pfail(h, PIADMM_E_STATE, "obca_noise_plan: only at a step boundary (an MPC step is open)");
-  PHIP(h, hipSetDevice(h->device));
-  PHIP(h, hipStreamSynchronize(h->stream));
+    return fail(h, PIADMM_E_STATE, "obca_noise_plan: no feedback attached (obca_feedback_plan: the noise enters through the plant step)");
+  if (p->i_iter != 0) return fail(h, PIADMM_E_STATE, "obca_noise_plan: only at a step boundary (an MPC step is open)");
+  OWN_HIP(h, hipSetDevice(h->device));
+  OWN_HIP(h, hipStreamSynchronize(h->stream));
   if (mode == 0) {
     p->nz = {};
     return 0;
@@ -481,7 +481,7 @@ int32_t piadmm_obca_noise_plan(piadmm_obca_t h, int32_t mode, const double* par,
   if (e == hipSuccess) e = hipMemset(nz.wbuf, 0, N * 10 * sizeof(double));
   if (e == hipSuccess) e = hipMemcpy(nz.par, par, (size_t)rows * ZPAR * sizeof(double), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(nz.streams, src, N * sizeof(long long), hipMemcpyHostToDevice);
-  if (e != hipSuccess) return pfail(h, PIADMM_E_HIP, std::string("obca_noise_plan: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return fail(h, PIADMM_E_HIP, std::string("obca_noise_plan: ") + hipGetErrorString(e));
   p->nz = std::move(nz);
   p->nz.rows = rows;
   p->nz.stride = rows > 1 ? ZPAR : 0;

@@ -163,8 +163,8 @@ extern "C" {
 int32_t piadmm_obca_tenant_export_bytes(piadmm_obca_t h, int32_t m, int64_t* bytes) {
   piadmm_obca_plan_s* p = nullptr;
   if (int rc = open_plan(h, &p, "obca_tenant_export_bytes")) return rc;
-  if (m < 1 || m > p->n) return pfail(h, PIADMM_E_ARG, "obca_tenant_export_bytes: 1 <= m <= n_scenarios");
-  if (!bytes) return pfail(h, PIADMM_E_ARG, "obca_tenant_export_bytes: null argument");
+  if (m < 1 || m > p->n) return fail(h, PIADMM_E_ARG, "obca_tenant_export_bytes: 1 <= m <= n_scenarios");
+  if (!bytes) return fail(h, PIADMM_E_ARG, "obca_tenant_export_bytes: null argument");
   *bytes = PIADMM_OBCA_TENANT_HEADER + (int64_t)m * tenant_rec_bytes(p->cfg.n_ref, p->du.on);
   return 0;
 }
@@ -175,21 +175,21 @@ int32_t piadmm_obca_tenant_export(piadmm_obca_t h, int32_t m, const int32_t* slo
   if (int rc = tenant_slots_check(h, p, m, slots, blob, "obca_tenant_export")) return rc;
   const int64_t rec_bytes = tenant_rec_bytes(p->cfg.n_ref, p->du.on), body = (int64_t)m * rec_bytes;
   if (bytes != PIADMM_OBCA_TENANT_HEADER + body)
-    return pfail(h, PIADMM_E_ARG, "obca_tenant_export: the blob is " + std::to_string(PIADMM_OBCA_TENANT_HEADER + body) +
-                 " bytes, not " + std::to_string(bytes));
-  if (p->fb.on) return pfail(h, PIADMM_E_STATE, "obca_tenant_export: feedback is attached (the tenant record has no room for the tape)");
-  if (p->dl.on) return pfail(h, PIADMM_E_STATE, "obca_tenant_export: the delay is attached (the tenant record has no room for it)");
-  if (p->i_iter != 0) return pfail(h, PIADMM_E_STATE, "obca_tenant_export: only at a step boundary (an MPC step is open)");
-  PHIP(h, hipSetDevice(h->device));
+    return fail(h, PIADMM_E_ARG, "obca_tenant_export: the blob is " + std::to_string(PIADMM_OBCA_TENANT_HEADER + body) +
+                " bytes, not " + std::to_string(bytes));
+  if (p->fb.on) return fail(h, PIADMM_E_STATE, "obca_tenant_export: feedback is attached (the tenant record has no room for the tape)");
+  if (p->dl.on) return fail(h, PIADMM_E_STATE, "obca_tenant_export: the delay is attached (the tenant record has no room for it)");
+  if (p->i_iter != 0) return fail(h, PIADMM_E_STATE, "obca_tenant_export: only at a step boundary (an MPC step is open)");
+  OWN_HIP(h, hipSetDevice(h->device));
   if (int rc = stage_ensure(h, p, (size_t)body, m)) return rc;
   int* d_list = reinterpret_cast<int*>(p->stg.buf + body);
   char* out = static_cast<char*>(blob);
-  PHIP(h, hipMemcpyAsync(d_list, slots, (size_t)m * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(d_list, slots, (size_t)m * sizeof(int), hipMemcpyHostToDevice, h->stream));
   hipLaunchKernelGGL(k_plan_export, dim3(blocks_for(m)), dim3(64 * PW), 0, h->stream, (const int*)d_list, m,
                      tenant_view(p), reinterpret_cast<double*>(p->stg.buf.get()));
-  PHIP(h, hipGetLastError());
-  PHIP(h, hipMemcpyAsync(out + PIADMM_OBCA_TENANT_HEADER, p->stg.buf, (size_t)body, hipMemcpyDeviceToHost, h->stream));
-  PHIP(h, hipStreamSynchronize(h->stream));
+  OWN_HIP(h, hipGetLastError());
+  OWN_HIP(h, hipMemcpyAsync(out + PIADMM_OBCA_TENANT_HEADER, p->stg.buf, (size_t)body, hipMemcpyDeviceToHost, h->stream));
+  OWN_HIP(h, hipStreamSynchronize(h->stream));
   const int32_t hdr[PIADMM_OBCA_TENANT_HEADER / 4] = {
       PIADMM_OBCA_TENANT_MAGIC, PIADMM_ABI_VERSION, m, p->cfg.n_ref, p->cfg.update_lamb_ij, p->du.on ? 1 : 0,
       p->ord.on ? 1 : 0, (int32_t)tenant_f64(p->cfg.n_ref, p->du.on), PIADMM_OBCA_TENANT_INTS, (int32_t)rec_bytes,
@@ -205,26 +205,26 @@ int32_t piadmm_obca_tenant_import(piadmm_obca_t h, int32_t m, const int32_t* slo
   const int n = p->n, n_ref = p->cfg.n_ref;
   const char* in = static_cast<const char*>(blob);
   // the header against itself, then against the plan
-  if (bytes < PIADMM_OBCA_TENANT_HEADER) return pfail(h, PIADMM_E_ARG, "obca_tenant_import: the blob is shorter than its header");
+  if (bytes < PIADMM_OBCA_TENANT_HEADER) return fail(h, PIADMM_E_ARG, "obca_tenant_import: the blob is shorter than its header");
   int32_t hdr[PIADMM_OBCA_TENANT_HEADER / 4];
   std::memcpy(hdr, in, sizeof(hdr));
-  if (hdr[0] != PIADMM_OBCA_TENANT_MAGIC) return pfail(h, PIADMM_E_ARG, "obca_tenant_import: bad magic (not a tenant blob)");
+  if (hdr[0] != PIADMM_OBCA_TENANT_MAGIC) return fail(h, PIADMM_E_ARG, "obca_tenant_import: bad magic (not a tenant blob)");
   if (hdr[1] != PIADMM_ABI_VERSION)
-    return pfail(h, PIADMM_E_ARG, "obca_tenant_import: the blob is of ABI " + std::to_string(hdr[1]));
-  if (hdr[2] != m) return pfail(h, PIADMM_E_ARG, "obca_tenant_import: the blob holds " + std::to_string(hdr[2]) + " tenants, not m");
+    return fail(h, PIADMM_E_ARG, "obca_tenant_import: the blob is of ABI " + std::to_string(hdr[1]));
+  if (hdr[2] != m) return fail(h, PIADMM_E_ARG, "obca_tenant_import: the blob holds " + std::to_string(hdr[2]) + " tenants, not m");
   const bool law = hdr[5] == 1, order = hdr[6] == 1;
   if (hdr[3] < 8 || hdr[3] > (1 << 20) || (hdr[4] != 0 && hdr[4] != 1) || (hdr[5] != 0 && hdr[5] != 1) ||
       (hdr[6] != 0 && hdr[6] != 1) || hdr[10] != PIADMM_OBCA_TENANT_HEADER || hdr[8] != PIADMM_OBCA_TENANT_INTS ||
       (int64_t)hdr[7] != tenant_f64(hdr[3], law) || (int64_t)hdr[9] != tenant_rec_bytes(hdr[3], law))
-    return pfail(h, PIADMM_E_ARG, "obca_tenant_import: bad header (flags or section sizes)");
+    return fail(h, PIADMM_E_ARG, "obca_tenant_import: bad header (flags or section sizes)");
   const int64_t rec_bytes = hdr[9], body = (int64_t)m * rec_bytes;
   if (bytes != PIADMM_OBCA_TENANT_HEADER + body)
-    return pfail(h, PIADMM_E_ARG, "obca_tenant_import: the blob is " + std::to_string(PIADMM_OBCA_TENANT_HEADER + body) +
-                 " bytes, not " + std::to_string(bytes));
+    return fail(h, PIADMM_E_ARG, "obca_tenant_import: the blob is " + std::to_string(PIADMM_OBCA_TENANT_HEADER + body) +
+                " bytes, not " + std::to_string(bytes));
   if (hdr[3] != n_ref)
-    return pfail(h, PIADMM_E_ARG, "obca_tenant_import: n_ref mismatch (the blob " + std::to_string(hdr[3]) + ", the plan " +
-                 std::to_string(n_ref) + ")");
-  if (hdr[4] != p->cfg.update_lamb_ij) return pfail(h, PIADMM_E_ARG, "obca_tenant_import: update_lamb_ij mismatch");
+    return fail(h, PIADMM_E_ARG, "obca_tenant_import: n_ref mismatch (the blob " + std::to_string(hdr[3]) + ", the plan " +
+                std::to_string(n_ref) + ")");
+  if (hdr[4] != p->cfg.update_lamb_ij) return fail(h, PIADMM_E_ARG, "obca_tenant_import: update_lamb_ij mismatch");
   // the records: what the kernels rely on (the rows, prob, the clocks)
   const size_t F = (size_t)hdr[7];
   const size_t law_at = (size_t)PIADMM_OBCA_TENANT_F64 + 10 * (size_t)n_ref;
@@ -237,56 +237,56 @@ int32_t piadmm_obca_tenant_import(piadmm_obca_t h, int32_t m, const int32_t* slo
     const std::string row = "obca_tenant_import: row " + std::to_string(k) + ": ";
     double par[TAB];
     rec_f64(k, TR_PAR, par, TAB);
-    if (const char* why = row_check(par)) return pfail(h, PIADMM_E_ARG, row + why);
+    if (const char* why = row_check(par)) return fail(h, PIADMM_E_ARG, row + why);
     admm[(size_t)k] = (int)par[T_ADMM];
     int32_t* ri = ints.data() + (size_t)k * TR_INTS;
     std::memcpy(ri, in + PIADMM_OBCA_TENANT_HEADER + (size_t)k * rec_bytes + 8 * F, sizeof(int32_t) * TR_INTS);
-    if (ri[TI_PROB] != 0 && ri[TI_PROB] != 1) return pfail(h, PIADMM_E_ARG, row + "prob must be 0 or 1");
-    if (ri[TI_CLOCK] < 0) return pfail(h, PIADMM_E_ARG, row + "c >= 0");
-    if (ri[TI_CLOCK + 1] < 8 || ri[TI_CLOCK + 1] > n_ref) return pfail(h, PIADMM_E_ARG, row + "8 <= len <= n_ref");
+    if (ri[TI_PROB] != 0 && ri[TI_PROB] != 1) return fail(h, PIADMM_E_ARG, row + "prob must be 0 or 1");
+    if (ri[TI_CLOCK] < 0) return fail(h, PIADMM_E_ARG, row + "c >= 0");
+    if (ri[TI_CLOCK + 1] < 8 || ri[TI_CLOCK + 1] > n_ref) return fail(h, PIADMM_E_ARG, row + "8 <= len <= n_ref");
     if (law) {
       double g[DPAR];
       rec_f64(k, law_at + 504, g, DPAR);
-      if (const char* why = dual_row_check(g)) return pfail(h, PIADMM_E_ARG, row + "gains: " + why);
+      if (const char* why = dual_row_check(g)) return fail(h, PIADMM_E_ARG, row + "gains: " + why);
     }
   }
   // the destination
-  if (p->fb.on) return pfail(h, PIADMM_E_STATE, "obca_tenant_import: feedback is attached (the tenant record has no room for the tape)");
-  if (p->dl.on) return pfail(h, PIADMM_E_STATE, "obca_tenant_import: the delay is attached (the tenant record has no room for it)");
-  if (!p->ck.on) return pfail(h, PIADMM_E_STATE, "obca_tenant_import: no clock attached (obca_clock_plan)");
-  if (p->tr.on) return pfail(h, PIADMM_E_STATE, "obca_tenant_import: a trace is attached (its minima would mix two tenants)");
-  if (p->i_iter != 0) return pfail(h, PIADMM_E_STATE, "obca_tenant_import: only at a step boundary (an MPC step is open)");
+  if (p->fb.on) return fail(h, PIADMM_E_STATE, "obca_tenant_import: feedback is attached (the tenant record has no room for the tape)");
+  if (p->dl.on) return fail(h, PIADMM_E_STATE, "obca_tenant_import: the delay is attached (the tenant record has no room for it)");
+  if (!p->ck.on) return fail(h, PIADMM_E_STATE, "obca_tenant_import: no clock attached (obca_clock_plan)");
+  if (p->tr.on) return fail(h, PIADMM_E_STATE, "obca_tenant_import: a trace is attached (its minima would mix two tenants)");
+  if (p->i_iter != 0) return fail(h, PIADMM_E_STATE, "obca_tenant_import: only at a step boundary (an MPC step is open)");
   if (p->ref_rows != n || p->tab_rows != n)
-    return pfail(h, PIADMM_E_STATE, "obca_tenant_import: needs a plan with a reference and a parameter row per scenario (obca_fleet_begin)");
+    return fail(h, PIADMM_E_STATE, "obca_tenant_import: needs a plan with a reference and a parameter row per scenario (obca_fleet_begin)");
   if (law != p->du.on)
-    return pfail(h, PIADMM_E_STATE, law ? "obca_tenant_import: the blob carries a dual law, the plan has none attached"
+    return fail(h, PIADMM_E_STATE, law ? "obca_tenant_import: the blob carries a dual law, the plan has none attached"
                                         : "obca_tenant_import: the plan has a dual law attached, the blob carries none");
   if (order != p->ord.on)
-    return pfail(h, PIADMM_E_STATE, order ? "obca_tenant_import: the blob carries the order's record, the plan has no order attached"
+    return fail(h, PIADMM_E_STATE, order ? "obca_tenant_import: the blob carries the order's record, the plan has no order attached"
                                           : "obca_tenant_import: the plan has the order attached, the blob carries no record");
-  PHIP(h, hipSetDevice(h->device));
+  OWN_HIP(h, hipSetDevice(h->device));
   const bool gains_travel = law && p->du.rows == n;
   if (law && !gains_travel) {
     // one shared gains row: a read of 8 doubles, nothing is written
     double shared[DPAR], g[DPAR];
-    PHIP(h, hipMemcpyAsync(shared, p->du.par, sizeof(shared), hipMemcpyDeviceToHost, h->stream));
-    PHIP(h, hipStreamSynchronize(h->stream));
+    OWN_HIP(h, hipMemcpyAsync(shared, p->du.par, sizeof(shared), hipMemcpyDeviceToHost, h->stream));
+    OWN_HIP(h, hipStreamSynchronize(h->stream));
     for (int k = 0; k < m; ++k) {
       rec_f64(k, law_at + 504, g, DPAR);
       if (std::memcmp(g, shared, sizeof(g)) != 0)
-        return pfail(h, PIADMM_E_ARG, "obca_tenant_import: row " + std::to_string(k) +
-                     ": the gains row differs from the plan's shared one");
+        return fail(h, PIADMM_E_ARG, "obca_tenant_import: row " + std::to_string(k) +
+                    ": the gains row differs from the plan's shared one");
     }
   }
   if (int rc = stage_ensure(h, p, (size_t)body, m)) return rc;
   int* d_list = reinterpret_cast<int*>(p->stg.buf + body);
-  PHIP(h, hipMemcpyAsync(p->stg.buf, in + PIADMM_OBCA_TENANT_HEADER, (size_t)body, hipMemcpyHostToDevice, h->stream));
-  PHIP(h, hipMemcpyAsync(d_list, slots, (size_t)m * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(p->stg.buf, in + PIADMM_OBCA_TENANT_HEADER, (size_t)body, hipMemcpyHostToDevice, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(d_list, slots, (size_t)m * sizeof(int), hipMemcpyHostToDevice, h->stream));
   tenant_arrays a = tenant_view(p);
   if (!gains_travel) a.gains = nullptr;
   hipLaunchKernelGGL(k_plan_import, dim3(blocks_for(m)), dim3(64 * PW), 0, h->stream, (const int*)d_list, m, a,
                      reinterpret_cast<const double*>(p->stg.buf.get()));
-  PHIP(h, hipGetLastError());
+  OWN_HIP(h, hipGetLastError());
   // what an admission does next: the rows' largest max_admm_iter, the mirror, the windows, flags and list
   for (int k = 0; k < m; ++k) {
     const size_t s = (size_t)slots[k];

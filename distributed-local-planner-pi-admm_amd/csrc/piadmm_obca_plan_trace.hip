@@ -560,11 +560,11 @@ int trace_append(piadmm_obca_t h, piadmm_obca_plan_s* p, int row) {
   hipLaunchKernelGGL(k_plan_trace, dim3(blocks_for(p->n)), dim3(64 * PW), 0, h->stream, p->n, row, p->bar, p->iters,
                      p->mask, p->primal, p->dual, p->lamb, t.states, t.iters, t.mask, t.primal, t.dual, t.lamb,
                      t.summary);
-  PHIP(h, hipGetLastError());
+  OWN_HIP(h, hipGetLastError());
   hipLaunchKernelGGL(k_plan_clearance, dim3(blocks_for(p->n)), dim3(64 * PW), 0, h->stream, p->n,
                      t.states + (size_t)row * N * 10, 10, p->prob, p->sigd, row, t.clear + (size_t)row * N * 2,
                      t.summary);
-  PHIP(h, hipGetLastError());
+  OWN_HIP(h, hipGetLastError());
   return 0;
 }
 }  // namespace obca_plan
@@ -582,14 +582,14 @@ struct stats_out {
 // what both statistics calls check of their arguments, before any device call
 int stats_args_check(piadmm_obca_t h, const std::string& who, int n, const double* edges, int B, int K,
                      const stats_out& o) {
-  if (B < 1 || B > PIADMM_OBCA_STATS_EDGES) return pfail(h, PIADMM_E_ARG, who + ": 1 <= B <= 64");
-  if (K < 1 || K > PIADMM_OBCA_STATS_WORST || K > n) return pfail(h, PIADMM_E_ARG, who + ": 1 <= K <= min(64, n)");
+  if (B < 1 || B > PIADMM_OBCA_STATS_EDGES) return fail(h, PIADMM_E_ARG, who + ": 1 <= B <= 64");
+  if (K < 1 || K > PIADMM_OBCA_STATS_WORST || K > n) return fail(h, PIADMM_E_ARG, who + ": 1 <= K <= min(64, n)");
   if (!edges || !o.stats || !o.hist || !o.row_min || !o.row_arg || !o.row_below || !o.worst)
-    return pfail(h, PIADMM_E_ARG, who + ": null argument");
+    return fail(h, PIADMM_E_ARG, who + ": null argument");
   for (int k = 0; k < B; ++k) {
-    if (!std::isfinite(edges[k])) return pfail(h, PIADMM_E_ARG, who + ": edge " + std::to_string(k) + ": not finite");
+    if (!std::isfinite(edges[k])) return fail(h, PIADMM_E_ARG, who + ": edge " + std::to_string(k) + ": not finite");
     if (k > 0 && !(edges[k] > edges[k - 1]))
-      return pfail(h, PIADMM_E_ARG, who + ": edge " + std::to_string(k) + ": the edges must be strictly ascending");
+      return fail(h, PIADMM_E_ARG, who + ": edge " + std::to_string(k) + ": the edges must be strictly ascending");
   }
   return 0;
 }
@@ -621,38 +621,38 @@ int stats_run(piadmm_obca_t h, int R, int n, const double* d_clear, const double
   if (sc.rc) return sc.rc;
   auto D = [&](size_t off) { return reinterpret_cast<double*>(ws + off); };
   auto I = [&](size_t off) { return reinterpret_cast<int*>(ws + off); };
-  PHIP(h, hipMemcpyAsync(ws + o_edges, edges, Bz * 8, hipMemcpyHostToDevice, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(ws + o_edges, edges, Bz * 8, hipMemcpyHostToDevice, h->stream));
   const stat_parts FP{D(f_min), I(f_arg), I(f_fin), I(f_bel)}, RP{D(r_min), I(r_arg), I(r_fin), I(r_bel)};
   const fleet_parts FF{reinterpret_cast<long long*>(ws + f_sum), I(f_max), I(f_or), I(f_flag)};
   hipLaunchKernelGGL(k_stats_fleet, dim3((unsigned)G), dim3(ST), 0, h->stream, n, R, d_summary, d_iters, d_mask,
                      (const double*)D(o_edges), B, FP, FF);
-  PHIP(h, hipGetLastError());
+  OWN_HIP(h, hipGetLastError());
   hipLaunchKernelGGL(k_stats_fleet_merge, dim3(1), dim3(ST), 0, h->stream, n, R, (int)G, B, FP, FF,
                      reinterpret_cast<piadmm_obca_stats_t*>(ws + o_res), reinterpret_cast<long long*>(ws + o_hist));
-  PHIP(h, hipGetLastError());
+  OWN_HIP(h, hipGetLastError());
   hipLaunchKernelGGL(k_stats_rows, dim3((unsigned)rows, (unsigned)G), dim3(ST), 0, h->stream, n, d_clear,
                      (const double*)D(o_edges), B, RP);
-  PHIP(h, hipGetLastError());
+  OWN_HIP(h, hipGetLastError());
   hipLaunchKernelGGL(k_stats_rows_merge, dim3((unsigned)rows), dim3(ST), 0, h->stream, (int)G, B, RP, D(o_rmin),
                      I(o_rarg), I(o_rbel));
-  PHIP(h, hipGetLastError());
+  OWN_HIP(h, hipGetLastError());
   // the first level reads the summary's plain minima once, ST a workgroup; every further level
   // merges WCAND / K lists a workgroup until one is left
   hipLaunchKernelGGL(k_stats_worst, dim3((unsigned)G), dim3(ST), 0, h->stream, d_summary, (int)TSUM,
                      (const int*)nullptr, n, (int)ST, K, D(w_v[0]), I(w_s[0]));
-  PHIP(h, hipGetLastError());
+  OWN_HIP(h, hipGetLastError());
   int cur = 0;
   const int per_lists = WCAND / K;
   for (size_t lists = G; lists > 1; cur ^= 1) {
     const size_t next = (lists + per_lists - 1) / per_lists;
     hipLaunchKernelGGL(k_stats_worst, dim3((unsigned)next), dim3(ST), 0, h->stream, (const double*)D(w_v[cur]), 1,
                        (const int*)I(w_s[cur]), (int)(lists * Kz), per_lists * K, K, D(w_v[cur ^ 1]), I(w_s[cur ^ 1]));
-    PHIP(h, hipGetLastError());
+    OWN_HIP(h, hipGetLastError());
     lists = next;
   }
-  PHIP(h, hipMemcpyAsync(ws + o_worst, ws + w_s[cur], Kz * 4, hipMemcpyDeviceToDevice, h->stream));
-  PHIP(h, hipMemcpyAsync(back.data(), ws, res_bytes, hipMemcpyDeviceToHost, h->stream));
-  PHIP(h, hipStreamSynchronize(h->stream));
+  OWN_HIP(h, hipMemcpyAsync(ws + o_worst, ws + w_s[cur], Kz * 4, hipMemcpyDeviceToDevice, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(back.data(), ws, res_bytes, hipMemcpyDeviceToHost, h->stream));
+  OWN_HIP(h, hipStreamSynchronize(h->stream));
   std::memcpy(o.stats, back.data() + o_res, sizeof(piadmm_obca_stats_t));
   std::memcpy(o.hist, back.data() + o_hist, 2 * (Bz + 1) * 8);
   std::memcpy(o.row_min, back.data() + o_rmin, rows * 2 * 8);
@@ -686,38 +686,38 @@ extern "C" {
 
 int32_t piadmm_obca_clearance(piadmm_obca_t h, int32_t n, const double* states, const int32_t* prob, double* out) {
   if (!h) return PIADMM_E_ARG;
-  if (n < 1 || n > (1 << 20)) return pfail(h, PIADMM_E_ARG, "obca_clearance: 1 <= n <= 2^20");
-  if (!states || !prob || !out) return pfail(h, PIADMM_E_ARG, "obca_clearance: null argument");
+  if (n < 1 || n > (1 << 20)) return fail(h, PIADMM_E_ARG, "obca_clearance: 1 <= n <= 2^20");
+  if (!states || !prob || !out) return fail(h, PIADMM_E_ARG, "obca_clearance: null argument");
   for (int k = 0; k < n; ++k) {
     if (int rc = prob_check(h, "obca_clearance", prob, k)) return rc;
     for (int i = 0; i < 10; ++i)
       if (!std::isfinite(states[(size_t)k * 10 + i]))
-        return pfail(h, PIADMM_E_ARG, "obca_clearance: state pair " + std::to_string(k) + " is not finite");
+        return fail(h, PIADMM_E_ARG, "obca_clearance: state pair " + std::to_string(k) + " is not finite");
   }
-  PHIP(h, hipSetDevice(h->device));
+  OWN_HIP(h, hipSetDevice(h->device));
   const size_t N = (size_t)n;
   scratch a(h);
   double *d_st = a.take<double>(N * 10, false), *d_out = a.take<double>(N * 2, true);
   int* d_pr = a.take<int>(N, false);
   if (a.rc) return a.rc;
-  PHIP(h, hipMemcpyAsync(d_st, states, N * 10 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  PHIP(h, hipMemcpyAsync(d_pr, prob, N * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(d_st, states, N * 10 * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(d_pr, prob, N * sizeof(int), hipMemcpyHostToDevice, h->stream));
   hipLaunchKernelGGL(k_plan_clearance, dim3(blocks_for(n)), dim3(64 * PW), 0, h->stream, n, d_st, 10, d_pr,
                      std::sqrt(0.95 / (1.0 - 0.95)), 0, d_out, (double*)nullptr);
-  PHIP(h, hipGetLastError());
-  PHIP(h, hipMemcpyAsync(out, d_out, N * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  PHIP(h, hipStreamSynchronize(h->stream));
+  OWN_HIP(h, hipGetLastError());
+  OWN_HIP(h, hipMemcpyAsync(out, d_out, N * 2 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  OWN_HIP(h, hipStreamSynchronize(h->stream));
   return 0;
 }
 
 int32_t piadmm_obca_trace_begin(piadmm_obca_t h, int32_t cap_steps, int32_t flags) {
   piadmm_obca_plan_s* p = nullptr;
   if (int rc = open_plan(h, &p, "obca_trace_begin")) return rc;
-  if (cap_steps < 1 || cap_steps > (1 << 20)) return pfail(h, PIADMM_E_ARG, "obca_trace_begin: 1 <= cap_steps <= 2^20");
-  if (flags & ~PIADMM_OBCA_TRACE_LAMBDA) return pfail(h, PIADMM_E_ARG, "obca_trace_begin: unknown flag bits");
-  if (p->i_iter != 0) return pfail(h, PIADMM_E_STATE, "obca_trace_begin: only at a step boundary (an MPC step is open)");
-  PHIP(h, hipSetDevice(h->device));
-  PHIP(h, hipStreamSynchronize(h->stream));
+  if (cap_steps < 1 || cap_steps > (1 << 20)) return fail(h, PIADMM_E_ARG, "obca_trace_begin: 1 <= cap_steps <= 2^20");
+  if (flags & ~PIADMM_OBCA_TRACE_LAMBDA) return fail(h, PIADMM_E_ARG, "obca_trace_begin: unknown flag bits");
+  if (p->i_iter != 0) return fail(h, PIADMM_E_STATE, "obca_trace_begin: only at a step boundary (an MPC step is open)");
+  OWN_HIP(h, hipSetDevice(h->device));
+  OWN_HIP(h, hipStreamSynchronize(h->stream));
   // the earlier record goes before the new one is built, not after it: the plan never holds two
   // records (peak device memory; a trace can be large), and a failure below leaves none attached
   p->tr = {};
@@ -739,7 +739,7 @@ int32_t piadmm_obca_trace_begin(piadmm_obca_t h, int32_t cap_steps, int32_t flag
     p->tr = {};
     return rc;
   }
-  PHIP(h, hipStreamSynchronize(h->stream));
+  OWN_HIP(h, hipStreamSynchronize(h->stream));
   p->tr.on = true;
   return 0;
 }
@@ -748,29 +748,29 @@ int32_t piadmm_obca_trace_run(piadmm_obca_t h, int32_t n_steps, int32_t* steps_d
   piadmm_obca_plan_s* p = nullptr;
   if (steps_done) *steps_done = 0;
   if (int rc = open_trace(h, &p, "obca_trace_run")) return rc;
-  if (n_steps < 1) return pfail(h, PIADMM_E_ARG, "obca_trace_run: n_steps >= 1");
+  if (n_steps < 1) return fail(h, PIADMM_E_ARG, "obca_trace_run: n_steps >= 1");
   if ((int64_t)p->tr.rows + n_steps > p->tr.cap)
-    return pfail(h, PIADMM_E_STATE, "obca_trace_run: " + std::to_string(n_steps) + " steps do not fit the trace (" +
-                 std::to_string(p->tr.rows) + " of " + std::to_string(p->tr.cap) + " rows used)");
+    return fail(h, PIADMM_E_STATE, "obca_trace_run: " + std::to_string(n_steps) + " steps do not fit the trace (" +
+                std::to_string(p->tr.rows) + " of " + std::to_string(p->tr.cap) + " rows used)");
   if (feedback_exhausted(p, n_steps))
-    return pfail(h, PIADMM_E_STATE, "obca_trace_run: disturbance tape exhausted before " + std::to_string(n_steps) +
-                 " steps (" + std::to_string(p->fb.steps) + " of " + std::to_string(p->fb.cap) + " rows used)");
+    return fail(h, PIADMM_E_STATE, "obca_trace_run: disturbance tape exhausted before " + std::to_string(n_steps) +
+                " steps (" + std::to_string(p->fb.steps) + " of " + std::to_string(p->fb.cap) + " rows used)");
   if (noise_exhausted(p, n_steps))
-    return pfail(h, PIADMM_E_STATE, "obca_trace_run: noise step index exhausted before " + std::to_string(n_steps) + " steps");
+    return fail(h, PIADMM_E_STATE, "obca_trace_run: noise step index exhausted before " + std::to_string(n_steps) + " steps");
   if (const char* why = delay_refusal(p, n_steps))
-    return pfail(h, PIADMM_E_STATE, std::string("obca_trace_run: ") + why + " before " + std::to_string(n_steps) + " steps");
+    return fail(h, PIADMM_E_STATE, std::string("obca_trace_run: ") + why + " before " + std::to_string(n_steps) + " steps");
   if (p->ck.on) {
     // the steps the longest-lived scenario has left
     int left = 0;
     for (int s = 0; s < p->n; ++s)
       if (p->ck.host[3 * (size_t)s + 2])
         left = std::max(left, p->ck.host[3 * (size_t)s + 1] - 8 - p->ck.host[3 * (size_t)s] + 1);
-    if (left == 0) return pfail(h, PIADMM_E_STATE, "obca_trace_run: no scenario alive");
+    if (left == 0) return fail(h, PIADMM_E_STATE, "obca_trace_run: no scenario alive");
     if (n_steps > left)
-      return pfail(h, PIADMM_E_STATE, "obca_trace_run: every reference ends before " + std::to_string(n_steps) +
-                   " steps (" + std::to_string(left) + " left)");
+      return fail(h, PIADMM_E_STATE, "obca_trace_run: every reference ends before " + std::to_string(n_steps) +
+                  " steps (" + std::to_string(left) + " left)");
   } else if ((int64_t)p->t_step + n_steps - 1 + 8 > p->cfg.n_ref)
-    return pfail(h, PIADMM_E_STATE, "obca_trace_run: the reference ends before " + std::to_string(n_steps) + " steps");
+    return fail(h, PIADMM_E_STATE, "obca_trace_run: the reference ends before " + std::to_string(n_steps) + " steps");
   // a host loop of the plan's bounded launches: every step ends in piadmm_obca_plan_shift, which appends its row
   for (int k = 0; k < n_steps; ++k) {
     if (int rc = piadmm_obca_plan_step(h, nullptr)) return rc;
@@ -794,11 +794,11 @@ int32_t piadmm_obca_trace_get(piadmm_obca_t h, int32_t what, void* out, int64_t 
     case PIADMM_OBCA_TRACE_GET_PRIMAL: src = t.primal; want = R * n * D; break;
     case PIADMM_OBCA_TRACE_GET_DUAL: src = t.dual; want = R * n * D; break;
     case PIADMM_OBCA_TRACE_GET_LAMBDA:
-      if (!t.lamb) return pfail(h, PIADMM_E_STATE, "obca_trace_get: the trace keeps no lamb_bar (PIADMM_OBCA_TRACE_LAMBDA)");
+      if (!t.lamb) return fail(h, PIADMM_E_STATE, "obca_trace_get: the trace keeps no lamb_bar (PIADMM_OBCA_TRACE_LAMBDA)");
       src = t.lamb; want = R * n * 126 * D; break;
     case PIADMM_OBCA_TRACE_GET_SUMMARY: src = t.summary; want = n * TSUM * D; break;
     case PIADMM_OBCA_TRACE_GET_ROWS: src = &t.rows; want = I; break;
-    default: return pfail(h, PIADMM_E_ARG, "obca_trace_get: unknown item " + std::to_string(what));
+    default: return fail(h, PIADMM_E_ARG, "obca_trace_get: unknown item " + std::to_string(what));
   }
   return get_finish(h, "obca_trace_get", what, src, what == PIADMM_OBCA_TRACE_GET_ROWS, want, out, bytes);
 }
@@ -820,28 +820,28 @@ int32_t piadmm_obca_fleet_stats(piadmm_obca_t h, int32_t rows_R, int32_t n, cons
                                 int32_t* row_below, int32_t* worst) {
   if (!h) return PIADMM_E_ARG;
   const std::string who = "obca_fleet_stats";
-  if (n < 1 || n > (1 << 20)) return pfail(h, PIADMM_E_ARG, who + ": 1 <= n <= 2^20");
-  if (rows_R < 0 || rows_R > (1 << 20)) return pfail(h, PIADMM_E_ARG, who + ": 0 <= rows_R <= 2^20");
-  if (!clear || !summary || (rows_R > 0 && (!iters || !mask))) return pfail(h, PIADMM_E_ARG, who + ": null argument");
+  if (n < 1 || n > (1 << 20)) return fail(h, PIADMM_E_ARG, who + ": 1 <= n <= 2^20");
+  if (rows_R < 0 || rows_R > (1 << 20)) return fail(h, PIADMM_E_ARG, who + ": 0 <= rows_R <= 2^20");
+  if (!clear || !summary || (rows_R > 0 && (!iters || !mask))) return fail(h, PIADMM_E_ARG, who + ": null argument");
   const stats_out o{stats, hist, row_min, row_arg, row_below, worst};
   if (int rc = stats_args_check(h, who, n, edges, B, K, o)) return rc;
   for (int k = 0; k < n; ++k) {
     const double v = summary[(size_t)k * TSUM + 3];
     if (!(v >= 0.0 && v <= 1099511627776.0 && v == std::floor(v)))
-      return pfail(h, PIADMM_E_ARG, who + ": row " + std::to_string(k) + ": the sum of iterates must be an integer in [0, 2^40]");
+      return fail(h, PIADMM_E_ARG, who + ": row " + std::to_string(k) + ": the sum of iterates must be an integer in [0, 2^40]");
   }
-  PHIP(h, hipSetDevice(h->device));
+  OWN_HIP(h, hipSetDevice(h->device));
   const size_t N = (size_t)n, R = (size_t)rows_R;
   const size_t b_clear = (R + 1) * N * 2 * 8, b_sum = N * TSUM * 8, b_it = R * N * 4, b_mask = R * N * 2 * 4;
   const size_t o_sum = up256(b_clear), o_it = o_sum + up256(b_sum), o_mask = o_it + up256(b_it);
   scratch a(h);
   char* in = a.take<char>(o_mask + up256(b_mask) + 256, false);
   if (a.rc) return a.rc;
-  PHIP(h, hipMemcpyAsync(in, clear, b_clear, hipMemcpyHostToDevice, h->stream));
-  PHIP(h, hipMemcpyAsync(in + o_sum, summary, b_sum, hipMemcpyHostToDevice, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(in, clear, b_clear, hipMemcpyHostToDevice, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(in + o_sum, summary, b_sum, hipMemcpyHostToDevice, h->stream));
   if (R) {
-    PHIP(h, hipMemcpyAsync(in + o_it, iters, b_it, hipMemcpyHostToDevice, h->stream));
-    PHIP(h, hipMemcpyAsync(in + o_mask, mask, b_mask, hipMemcpyHostToDevice, h->stream));
+    OWN_HIP(h, hipMemcpyAsync(in + o_it, iters, b_it, hipMemcpyHostToDevice, h->stream));
+    OWN_HIP(h, hipMemcpyAsync(in + o_mask, mask, b_mask, hipMemcpyHostToDevice, h->stream));
   }
   return stats_run(h, rows_R, n, reinterpret_cast<const double*>(in), reinterpret_cast<const double*>(in + o_sum),
                    reinterpret_cast<const int*>(in + o_it), reinterpret_cast<const int*>(in + o_mask), edges, B, K, o);
@@ -853,7 +853,7 @@ int32_t piadmm_obca_stats_trace(piadmm_obca_t h, const double* edges, int32_t B,
   if (int rc = open_trace(h, &p, "obca_stats_trace")) return rc;
   const stats_out o{stats, hist, row_min, row_arg, row_below, worst};
   if (int rc = stats_args_check(h, "obca_stats_trace", p->n, edges, B, K, o)) return rc;
-  PHIP(h, hipSetDevice(h->device));
+  OWN_HIP(h, hipSetDevice(h->device));
   const auto& t = p->tr;
   return stats_run(h, t.rows, p->n, t.clear, t.summary, t.iters, t.mask, edges, B, K, o);
 }
@@ -861,8 +861,8 @@ int32_t piadmm_obca_stats_trace(piadmm_obca_t h, const double* edges, int32_t B,
 int32_t piadmm_obca_gather_trace_bytes(piadmm_obca_t h, int32_t m, int64_t* bytes) {
   piadmm_obca_plan_s* p = nullptr;
   if (int rc = open_trace(h, &p, "obca_gather_trace_bytes")) return rc;
-  if (m < 1 || m > p->n) return pfail(h, PIADMM_E_ARG, "obca_gather_trace_bytes: 1 <= m <= n_scenarios");
-  if (!bytes) return pfail(h, PIADMM_E_ARG, "obca_gather_trace_bytes: null argument");
+  if (m < 1 || m > p->n) return fail(h, PIADMM_E_ARG, "obca_gather_trace_bytes: 1 <= m <= n_scenarios");
+  if (!bytes) return fail(h, PIADMM_E_ARG, "obca_gather_trace_bytes: null argument");
   *bytes = gather_offsets(p->tr.rows, m, p->tr.lamb != nullptr).bytes;
   return 0;
 }
@@ -874,11 +874,11 @@ int32_t piadmm_obca_gather_trace(piadmm_obca_t h, int32_t m, const int32_t* slot
   const auto& t = p->tr;
   const gather_layout g = gather_offsets(t.rows, m, t.lamb != nullptr);
   if (bytes != g.bytes)
-    return pfail(h, PIADMM_E_ARG, "obca_gather_trace: the blob is " + std::to_string(g.bytes) + " bytes, not " +
-                 std::to_string(bytes));
+    return fail(h, PIADMM_E_ARG, "obca_gather_trace: the blob is " + std::to_string(g.bytes) + " bytes, not " +
+                std::to_string(bytes));
   const int64_t waves = ((int64_t)t.rows + 1) * m, blocks = (waves + PW - 1) / PW;
-  if (blocks > INT_MAX) return pfail(h, PIADMM_E_ARG, "obca_gather_trace: (rows + 1) m must stay below 2^33");
-  PHIP(h, hipSetDevice(h->device));
+  if (blocks > INT_MAX) return fail(h, PIADMM_E_ARG, "obca_gather_trace: (rows + 1) m must stay below 2^33");
+  OWN_HIP(h, hipSetDevice(h->device));
   if (int rc = stage_ensure(h, p, (size_t)g.bytes, m)) return rc;
   char* st = p->stg.buf;
   int* d_list = reinterpret_cast<int*>(st + g.bytes);
@@ -886,14 +886,14 @@ int32_t piadmm_obca_gather_trace(piadmm_obca_t h, int32_t m, const int32_t* slot
   const gather_src a{t.states, t.clear, t.primal, t.dual, t.lamb, t.summary, t.iters, t.mask};
   const gather_dst d{D(g.states), D(g.clear), D(g.primal), D(g.dual), D(g.summary), D(g.lamb),
                      reinterpret_cast<int*>(st + g.iters), reinterpret_cast<int*>(st + g.mask)};
-  PHIP(h, hipMemcpyAsync(d_list, slots, (size_t)m * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  OWN_HIP(h, hipMemcpyAsync(d_list, slots, (size_t)m * sizeof(int), hipMemcpyHostToDevice, h->stream));
   // the pad word between STATUS_MASK and LAMBDA has no writer: it goes out as 0
-  if (g.lamb != g.mask + 8 * (int64_t)t.rows * m) PHIP(h, hipMemsetAsync(st + g.lamb - 4, 0, 4, h->stream));
+  if (g.lamb != g.mask + 8 * (int64_t)t.rows * m) OWN_HIP(h, hipMemsetAsync(st + g.lamb - 4, 0, 4, h->stream));
   hipLaunchKernelGGL(k_trace_gather, dim3((unsigned)blocks), dim3(64 * PW), 0, h->stream, (const int*)d_list, m, p->n,
                      t.rows + 1, a, d);
-  PHIP(h, hipGetLastError());
-  PHIP(h, hipMemcpyAsync(blob, st, (size_t)g.bytes, hipMemcpyDeviceToHost, h->stream));
-  PHIP(h, hipStreamSynchronize(h->stream));
+  OWN_HIP(h, hipGetLastError());
+  OWN_HIP(h, hipMemcpyAsync(blob, st, (size_t)g.bytes, hipMemcpyDeviceToHost, h->stream));
+  OWN_HIP(h, hipStreamSynchronize(h->stream));
   return 0;
 }
 
