@@ -1,7 +1,7 @@
 // piadmm_obca_plan.h -- what the units of the device-resident OBCA-ADMM consensus loop share
 // (internal, not installed): the layouts, the kernel-argument structs, the owners of device memory,
 // the plan and the small host helpers.  csrc/piadmm_obca_plan.hip holds the iterate and the shift and
-// describes the launch sequence; csrc/piadmm_obca_plan_{attach,trace,tenant,feedback,delay}.hip hold
+// describes the launch sequence; csrc/piadmm_obca_plan_{attach,trace,tenant,feedback,delay,loop}.hip hold
 // the attachments.  Every kernel is defined in one unit; there is no relocatable device code, a unit
 // launches another unit's kernel through the declaration here.
 #pragma once
@@ -119,6 +119,20 @@ struct delay_io {
   int par_s;
 };
 
+// where the arrays of the loop's launches sit (piadmm_obca_loop_plan), indexed by scenario: plant,
+// noise and delay the rows (a stride 0: one shared row; noise / delay nullptr: that kind is absent),
+// streams the stream ids (nullptr: the scenario's number), clk the clocks (c, len, alive; the step
+// index of scenario s is k0 + clk[3 s]), x0 and ctrl what k_plan_propagate reads of the plan, next
+// the closing states by list position (m x 10), tau the latencies (n x 2)
+struct loop_io {
+  const double *plant, *noise, *delay, *x0, *ctrl;
+  const long long* streams;
+  const int* clk;
+  double *next, *tau;
+  int plant_s, noise_s, delay_s;
+  uint32_t seed_lo, seed_hi, k0;
+};
+
 // (A, b) of a vehicle at `st` -- halfspaces (piadmm/obca.py) in the host's order of operations,
 // products and sums kept apart (no contraction) so the two stay within rounding of each other.
 __device__ __forceinline__ void halfspaces(const double* st, int prob, double sigd, double A[4][2], double b[4]) {
@@ -183,6 +197,114 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32
   }
 }
 
+// One plant step of one vehicle, all in registers: x (5) <- F(x, (a, om)) under the vehicle's row P
+// (8), without the disturbance.  n_sub substeps of DT / n_sub; a substep is 1 stage (Euler) or 4
+// (classical RK4) of the one right-hand side below, the stage loop kept rolled so that the libm
+// calls are inlined once; then delta is clipped.  n_sub is clamped to its range, so the loop is
+// bounded whatever the row holds.  piadmm.obca.propagate is the same statements on the host;
+// products and sums are kept apart (no contraction).  The body of
+// k_plan_propagate (the stand-alone call and the in-plan step) and of k_loop_close: the same bits.
+__device__ __forceinline__ void plant_step(double x[5], double a, double om, const double P[FV]) {
+#pragma clang fp contract(off)
+  const double lr = P[F_LR], lf = P[F_LF];
+  const double a_eff = fmin(P[F_AMAX], fmax(P[F_GA] * a, -P[F_AMAX]));
+  const double w_eff = fmin(P[F_WMAX], fmax(P[F_GW] * om, -P[F_WMAX]));
+  const int n_sub = min(max((int)P[F_NSUB], 1), F_NSUB_MAX);
+  const int n_stage = P[F_METHOD] != 0.0 ? 4 : 1;
+  const double hs = PLANT_DT / (double)n_sub;
+  const double scale = n_stage == 4 ? hs / 6.0 : hs;
+#pragma unroll 1
+  for (int sub = 0; sub < n_sub; ++sub) {
+    double xs[5], acc[5];
+#pragma unroll
+    for (int i = 0; i < 5; ++i) { xs[i] = x[i]; acc[i] = 0.0; }
+#pragma unroll 1
+    for (int st = 0; st < n_stage; ++st) {
+      const double beta = atan(lr * tan(xs[4]) / (lr + lf));
+      const double ph = xs[3] + beta;
+      const double f[5] = {xs[2] * cos(ph), xs[2] * sin(ph), a_eff, xs[2] / lr * sin(beta), w_eff};
+      const double wgt = (st == 1 || st == 2) ? 2.0 : 1.0;
+      const double c = st < 2 ? 0.5 * hs : hs;          // the next stage's point: x + c f
+#pragma unroll
+      for (int i = 0; i < 5; ++i) {
+        acc[i] = st == 0 ? f[i] : acc[i] + wgt * f[i];
+        xs[i] = x[i] + c * f[i];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 5; ++i) x[i] = x[i] + scale * acc[i];
+    x[4] = fmin(MAX_STEER, fmax(x[4], -MAX_STEER));
+  }
+}
+
+// The five disturbances of vehicle v of stream t at step k under the row's sigma S, bias B and
+// trunc: three Philox calls at counter (k, 4 v + j, t low, t high), each giving two uniforms in
+// (0, 1) on 52 bits and by Box-Muller two normals; the sixth normal is discarded.  raw (12 words,
+// or nullptr) receives the calls' words.  piadmm.obca.noise_tape is the same statements on the
+// host; products and sums are kept apart (no contraction), so sigma = 0 gives the bias bit for bit.
+// The body of k_plan_noise (the in-plan step and the stand-alone tape) and of k_loop_close and
+// k_loop_draw: the same bits.
+__device__ __forceinline__ void noise_draw(uint32_t seed_lo, uint32_t seed_hi, uint32_t t_lo, uint32_t t_hi,
+                                           uint32_t k, int v, const double S[5], const double B[5], double trunc,
+                                           double w[5], uint32_t* raw) {
+#pragma clang fp contract(off)
+  double z[6];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    uint32_t c[4] = {k, (uint32_t)(4 * v + j), t_lo, t_hi};
+    philox4x32_10(c, seed_lo, seed_hi);
+    if (raw) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) raw[4 * j + q] = c[q];
+    }
+    const unsigned long long a = ((unsigned long long)c[0] << 32) | c[1];
+    const unsigned long long b = ((unsigned long long)c[2] << 32) | c[3];
+    const double u1 = ((double)(a >> 12) + 0.5) * 0x1p-52;
+    const double u2 = ((double)(b >> 12) + 0.5) * 0x1p-52;
+    const double rad = sqrt(-2.0 * log(u1));
+    const double ang = 6.283185307179586 * u2;
+    z[2 * j] = rad * cos(ang);
+    z[2 * j + 1] = rad * sin(ang);
+  }
+#pragma unroll
+  for (int i = 0; i < 5; ++i) {
+    double zi = z[i];
+    if (trunc != 0.0) zi = fmin(trunc, fmax(zi, -trunc));
+    w[i] = B[i] + S[i] * zi;
+  }
+}
+
+// The latency of vehicle v of stream t at step k under the row's avg, std, tau_max and trunc: one
+// Philox call at counter (k, 4 v + 3, t low, t high) -- the call index the noise leaves free -- two
+// uniforms in (0, 1) on 52 bits as noise_draw forms them, the first Box-Muller normal; the second is
+// discarded.  tape is the recorded latency added in front (0 without one).  raw (4 words, or
+// nullptr) receives the call's words.  piadmm.obca.delay_tau is the same statements on the host;
+// products and sums are kept apart (no contraction), so std = 0 gives min(tau_max, tape + avg) bit
+// for bit.  The body of k_plan_delay (the in-plan step and the stand-alone call), of k_loop_open and
+// of k_loop_draw: the same bits.
+__device__ __forceinline__ double delay_draw(uint32_t seed_lo, uint32_t seed_hi, uint32_t t_lo, uint32_t t_hi,
+                                             uint32_t k, int v, double avg, double sd, double tau_max, double trunc,
+                                             double tape, uint32_t* raw) {
+#pragma clang fp contract(off)
+  uint32_t c[4] = {k, (uint32_t)(4 * v + 3), t_lo, t_hi};
+  philox4x32_10(c, seed_lo, seed_hi);
+  if (raw) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) raw[q] = c[q];
+  }
+  const unsigned long long a = ((unsigned long long)c[0] << 32) | c[1];
+  const unsigned long long b = ((unsigned long long)c[2] << 32) | c[3];
+  const double u1 = ((double)(a >> 12) + 0.5) * 0x1p-52;
+  const double u2 = ((double)(b >> 12) + 0.5) * 0x1p-52;
+  const double rad = sqrt(-2.0 * log(u1));
+  const double ang = 6.283185307179586 * u2;
+  double z = rad * cos(ang);
+  if (trunc != 0.0) z = fmin(trunc, fmax(z, -trunc));
+  const double x = tape + (avg + sd * z);
+  const double lo = x > 0.0 ? x : 0.0;
+  return lo < tau_max ? lo : tau_max;
+}
+
 // The kernels launched from a unit other than their own (the comments are at the definitions).
 // csrc/piadmm_obca_plan.hip
 __global__ void __launch_bounds__(CT) k_plan_compact(const int* __restrict__ active, const int* __restrict__ keep,
@@ -214,6 +336,9 @@ __global__ void __launch_bounds__(64 * PW) k_plan_set_init(const int* __restrict
 __global__ void __launch_bounds__(64 * PW) k_plan_noise(const int* __restrict__ list, int m, noise_io io);
 // csrc/piadmm_obca_plan_delay.hip
 __global__ void __launch_bounds__(64 * PW) k_plan_delay(const int* __restrict__ list, int m, delay_io io);
+// csrc/piadmm_obca_plan_loop.hip
+__global__ void __launch_bounds__(64 * PW) k_loop_close(const int* __restrict__ list, int m, loop_io io);
+__global__ void __launch_bounds__(64 * PW) k_loop_open(const int* __restrict__ list, int m, loop_io io);
 
 // ---------------------------------------------------------------------------------------------
 // The host side
@@ -306,6 +431,18 @@ struct piadmm_obca_plan_s {
     dbuf<double> par, tape, tau;
     dbuf<long long> streams;
   } dl;
+  // the loop (piadmm_obca_loop_plan): the closed loop of a clocked plan, its step index each tenant's
+  // own clock.  flags = 1 (on) + 2 (noise rows) + 4 (delay rows); of each kind rows = 1 with stride 0
+  // or n; streams = the stream id of every scenario; tau = the open step's latencies, n x 2 (zeros
+  // without delay rows), which k_loop_open writes and k_plan_exchange_stale reads; next = the states
+  // the plant reached, by position in ck.list; the step index of scenario s is k0 + its clock
+  struct loop_s {
+    bool on = false;
+    int flags = 0, k0 = 0, plant_rows = 0, noise_rows = 0, delay_rows = 0;
+    uint64_t seed = 0;
+    dbuf<double> plant, noise, delay, tau, next;
+    dbuf<long long> streams;
+  } lp;
   // the staging buffer of piadmm_obca_tenant_export / _import: the records, then the slot list; grown on demand
   struct stage_s {
     dbuf<char> buf;
@@ -351,6 +488,35 @@ inline const char* delay_refusal(const piadmm_obca_plan_s* p, int64_t steps) {
   if (p->dl.tape && (int64_t)p->dl.steps + steps > p->dl.cap) return "latency tape exhausted";
   if ((int64_t)p->dl.k0 + p->dl.steps + steps > ((int64_t)1 << 31)) return "delay step index exhausted";
   return nullptr;
+}
+
+// the launch arguments of the loop `l` on the plan's own arrays
+inline loop_io loop_view(const piadmm_obca_plan_s* p, const piadmm_obca_plan_s::loop_s& l) {
+  loop_io io{};
+  io.plant = l.plant;  io.plant_s = l.plant_rows > 1 ? FPAR : 0;
+  io.noise = (l.flags & 2) ? l.noise.get() : nullptr;  io.noise_s = l.noise_rows > 1 ? ZPAR : 0;
+  io.delay = (l.flags & 4) ? l.delay.get() : nullptr;  io.delay_s = l.delay_rows > 1 ? YPAR : 0;
+  io.streams = l.streams;
+  io.clk = p->ck.clk;
+  io.x0 = p->bar + S_INIT;
+  io.ctrl = p->ctrl;
+  io.next = l.next;
+  io.tau = l.tau;
+  io.seed_lo = (uint32_t)l.seed;  io.seed_hi = (uint32_t)(l.seed >> 32);
+  io.k0 = (uint32_t)l.k0;
+  return io;
+}
+// true when, with the loop attached, the next `steps` MPC steps would take an alive tenant's step
+// index k0 + c to 2^31 (a tenant ticks at most until it retires)
+inline bool loop_exhausted(const piadmm_obca_plan_s* p, int64_t steps) {
+  if (!p->lp.on || !p->ck.on) return false;
+  for (int s = 0; s < p->n; ++s) {
+    const int* k = p->ck.host.data() + 3 * (size_t)s;
+    if (!k[2]) continue;
+    const int64_t ticks = std::min<int64_t>(steps, (int64_t)k[1] - 8 - k[0] + 1);
+    if ((int64_t)p->lp.k0 + k[0] + ticks >= ((int64_t)1 << 31)) return true;
+  }
+  return false;
 }
 
 // The checks more than one call makes, each worded once; `who` is the call's name.
@@ -405,8 +571,17 @@ const char* dual_row_check(const double* row);
 int clock_lists(piadmm_obca_t h, piadmm_obca_plan_s* p, const int* ran, int dst, int n_alive);
 int clock_shift(piadmm_obca_t h, piadmm_obca_plan_s* p);
 int clock_relist(piadmm_obca_t h, piadmm_obca_plan_s* p);
+// csrc/piadmm_obca_plan_feedback.hip
+const char* feedback_row_check(const double* row);
+void feedback_row_nominal(double* row);
+const char* noise_row_check(const double* row);
 // csrc/piadmm_obca_plan_delay.hip
+const char* delay_row_check(const double* row);
 int delay_next(piadmm_obca_t h, piadmm_obca_plan_s* p);
+// csrc/piadmm_obca_plan_loop.hip
+int loop_close(piadmm_obca_t h, piadmm_obca_plan_s* p);
+int loop_set_init(piadmm_obca_t h, piadmm_obca_plan_s* p);
+int loop_open(piadmm_obca_t h, piadmm_obca_plan_s* p, int m);
 // csrc/piadmm_obca_plan_trace.hip
 int trace_append(piadmm_obca_t h, piadmm_obca_plan_s* p, int row);
 

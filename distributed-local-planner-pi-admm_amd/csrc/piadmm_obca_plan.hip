@@ -35,6 +35,12 @@
 // k_plan_exchange's place (what a vehicle sends is computed from its plan interpolated tau back) and
 // piadmm_obca_plan_shift launches k_plan_delay last, one lane per vehicle: the latencies of the step
 // that opens; without it neither is launched.
+// With the loop attached (piadmm_obca_loop_plan; a clocked plan only) piadmm_obca_plan_shift runs
+// k_loop_close before k_plan_shift_list (noise at k0 + c plus the plant step of the scenarios the
+// step ran) and k_plan_set_init after it (the state each reached over init_state of both copies),
+// and with delay rows k_loop_open after the tick (the latencies of the alive scenarios at their new
+// clocks) and every iterate k_plan_exchange_stale in k_plan_exchange's place; without it none is
+// launched.
 // The statistics of a run record (piadmm_obca_fleet_stats / _stats_trace: k_stats_fleet, k_stats_rows,
 // k_stats_worst and their merges) and k_trace_gather are launched by those calls alone and write
 // nothing of the plan or the trace.
@@ -50,7 +56,7 @@
 // min_dis, max_admm_iter) is a uniform load; the record parameters are loaded by the few lanes
 // that store them.
 //
-// The attachments' kernels and calls are in csrc/piadmm_obca_plan_{attach,trace,tenant,feedback,delay}.hip;
+// The attachments' kernels and calls are in csrc/piadmm_obca_plan_{attach,trace,tenant,feedback,delay,loop}.hip;
 // the launches above that are theirs go through the declarations in csrc/piadmm_obca_plan.h.
 
 #include "piadmm_obca_plan.h"
@@ -471,7 +477,7 @@ int plan_open(piadmm_obca_t h, const piadmm_obca_plan_cfg_t* cfg, const int32_t*
 void piadmm_obca_plan_release(piadmm_obca_t h) {
   piadmm_obca_plan_s* p = h->plan;
   if (!p) return;
-  if (p->tr.on || p->du.on || p->ord.on || p->ck.on || p->fb.on || p->dl.on) {
+  if (p->tr.on || p->du.on || p->ord.on || p->ck.on || p->fb.on || p->dl.on || p->lp.on) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     p->tr = {};
@@ -481,6 +487,7 @@ void piadmm_obca_plan_release(piadmm_obca_t h) {
     p->fb = {};
     p->nz = {};    // the noise counts its steps by the feedback's: it goes whenever the feedback goes
     p->dl = {};
+    p->lp = {};
   }
   p->open = false;
 }
@@ -562,10 +569,11 @@ int32_t piadmm_obca_plan_iterate(piadmm_obca_t h, int32_t* n_active_after) {
   if (int rc = piadmm_obca_local_launch(h, 2 * m)) return rc;
   // the edge output starts from zeros, as in piadmm_obca_edge_solve
   OWN_HIP(h, hipMemsetAsync(h->e_out, 0, (size_t)m * EOUT * sizeof(double), st));
-  if (p->dl.on) {
+  if (p->dl.on || (p->lp.on && (p->lp.flags & 4))) {
+    // the open step's latencies: the delay's, or the loop's (the two never attach together)
     hipLaunchKernelGGL(k_plan_exchange_stale, dim3(blocks_for(m)), dim3(64 * PW), 0, st, act, m, p->bar, p->prob,
                        h->d_out, p->tab, p->tab_stride, p->sigd, p->cfg.update_lamb_ij, p->ctrl, p->X, p->conv,
-                       h->e_rec, (const double*)p->dl.tau);
+                       h->e_rec, p->dl.on ? (const double*)p->dl.tau : (const double*)p->lp.tau);
   } else {
     hipLaunchKernelGGL(k_plan_exchange, dim3(blocks_for(m)), dim3(64 * PW), 0, st, act, m, p->bar, p->prob, h->d_out,
                        p->tab, p->tab_stride, p->sigd, p->cfg.update_lamb_ij, p->ctrl, p->X, p->conv, h->e_rec);
@@ -616,6 +624,7 @@ int32_t piadmm_obca_plan_shift(piadmm_obca_t h) {
   if (p->tr.on && p->tr.rows >= p->tr.cap) return fail(h, PIADMM_E_STATE, "obca_plan_shift: trace full");
   if (feedback_exhausted(p, 1)) return fail(h, PIADMM_E_STATE, "obca_plan_shift: disturbance tape exhausted");
   if (noise_exhausted(p, 1)) return fail(h, PIADMM_E_STATE, "obca_plan_shift: noise step index exhausted");
+  if (loop_exhausted(p, 1)) return fail(h, PIADMM_E_STATE, "obca_plan_shift: loop step index exhausted");
   OWN_HIP(h, hipSetDevice(h->device));
   if (p->ck.on) return clock_shift(h, p);
   if (p->fb.on) {
@@ -692,6 +701,7 @@ int32_t piadmm_obca_plan_step(piadmm_obca_t h, int32_t* iters_out) {
   if (p->tr.on && p->tr.rows >= p->tr.cap) return fail(h, PIADMM_E_STATE, "obca_plan_step: trace full");
   if (feedback_exhausted(p, 1)) return fail(h, PIADMM_E_STATE, "obca_plan_step: disturbance tape exhausted");
   if (noise_exhausted(p, 1)) return fail(h, PIADMM_E_STATE, "obca_plan_step: noise step index exhausted");
+  if (loop_exhausted(p, 1)) return fail(h, PIADMM_E_STATE, "obca_plan_step: loop step index exhausted");
   if (const char* why = delay_refusal(p, 1)) return fail(h, PIADMM_E_STATE, std::string("obca_plan_step: ") + why);
   // i_iter > max_admm_iter stops a scenario: at most the largest max_admm_iter + 1 iterates in a step
   while (p->n_act > 0 && p->i_iter <= p->max_iter_all) {
@@ -715,6 +725,7 @@ int32_t piadmm_obca_plan_get(piadmm_obca_t h, int32_t what, void* out, int64_t b
   const int32_t counts[3] = {p->n_last, p->n_act, p->i_iter};
   const uint64_t seed[2] = {p->nz.seed, (uint64_t)p->nz.k0};
   const uint64_t dseed[3] = {p->dl.seed, (uint64_t)p->dl.k0, (uint64_t)p->dl.steps};
+  const uint64_t lseed[3] = {p->lp.seed, (uint64_t)p->lp.k0, (uint64_t)p->lp.flags};
   switch (what) {
     case PIADMM_OBCA_PLAN_GET_STATE: src = p->bar; want = n * STATE * D; break;
     case PIADMM_OBCA_PLAN_GET_STATE_PREV: src = p->barp; want = n * STATE * D; break;
@@ -783,6 +794,24 @@ int32_t piadmm_obca_plan_get(piadmm_obca_t h, int32_t what, void* out, int64_t b
       else if (what == PIADMM_OBCA_DELAY_GET_TAU) { src = p->dl.tau; want = n * 2 * D; }
       else if (what == PIADMM_OBCA_DELAY_GET_STREAMS) { src = p->dl.streams; want = n * (int64_t)sizeof(int64_t); }
       else { src = dseed; want = 3 * (int64_t)sizeof(uint64_t); host = true; }
+      break;
+    case PIADMM_OBCA_LOOP_GET_PLANT:
+    case PIADMM_OBCA_LOOP_GET_NOISE:
+    case PIADMM_OBCA_LOOP_GET_DELAY:
+    case PIADMM_OBCA_LOOP_GET_TAU:
+    case PIADMM_OBCA_LOOP_GET_STREAMS:
+    case PIADMM_OBCA_LOOP_GET_SEED:
+      if (!p->lp.on) return fail(h, PIADMM_E_STATE, "obca_plan_get: no loop attached (obca_loop_plan)");
+      if (what == PIADMM_OBCA_LOOP_GET_PLANT) { src = p->lp.plant; want = (int64_t)p->lp.plant_rows * FPAR * D; }
+      else if (what == PIADMM_OBCA_LOOP_GET_NOISE) {
+        if (!(p->lp.flags & 2)) return fail(h, PIADMM_E_STATE, "obca_plan_get: the loop has no noise rows");
+        src = p->lp.noise; want = (int64_t)p->lp.noise_rows * ZPAR * D;
+      } else if (what == PIADMM_OBCA_LOOP_GET_DELAY) {
+        if (!(p->lp.flags & 4)) return fail(h, PIADMM_E_STATE, "obca_plan_get: the loop has no delay rows");
+        src = p->lp.delay; want = (int64_t)p->lp.delay_rows * YPAR * D;
+      } else if (what == PIADMM_OBCA_LOOP_GET_TAU) { src = p->lp.tau; want = n * 2 * D; }
+      else if (what == PIADMM_OBCA_LOOP_GET_STREAMS) { src = p->lp.streams; want = n * (int64_t)sizeof(int64_t); }
+      else { src = lseed; want = 3 * (int64_t)sizeof(uint64_t); host = true; }
       break;
     case PIADMM_OBCA_PLAN_GET_T_STEP: src = &p->t_step; want = I; host = true; break;
     case PIADMM_OBCA_PLAN_GET_COUNTS: src = counts; want = 3 * I; host = true; break;

@@ -318,6 +318,11 @@ int clock_relist(piadmm_obca_t h, piadmm_obca_plan_s* p) {
 int clock_shift(piadmm_obca_t h, piadmm_obca_plan_s* p) {
   auto& c = p->ck;
   const int m = c.n_list;
+  if (p->lp.on) {
+    // the plant step first: it reads the closing step's init_state, its first control and the clocks
+    // before the shift and the tick overwrite them
+    if (int rc = loop_close(h, p)) return rc;
+  }
   hipLaunchKernelGGL(k_plan_shift_list, dim3(m), dim3(64), 0, h->stream, c.list, m, p->bar, p->barp, p->X, p->lamb,
                      p->ctrlp);
   OWN_HIP(h, hipGetLastError());
@@ -325,6 +330,10 @@ int clock_shift(piadmm_obca_t h, piadmm_obca_plan_s* p) {
     hipLaunchKernelGGL(k_plan_dual_shift_list, dim3(m), dim3(64), 0, h->stream, c.list, m, p->du.S, p->du.D, p->du.Sp,
                        p->du.Dp);
     OWN_HIP(h, hipGetLastError());
+  }
+  if (p->lp.on) {
+    // the state each scenario reached over init_state of both copies, before the tick rebuilds the list
+    if (int rc = loop_set_init(h, p)) return rc;
   }
   // the mirror: the tick is deterministic, nothing is read back for it
   std::vector<int> next = c.host;
@@ -336,6 +345,10 @@ int clock_shift(piadmm_obca_t h, piadmm_obca_plan_s* p) {
     n_alive += k[2];
   }
   if (int rc = clock_lists(h, p, c.flag[c.cur], 1 - c.cur, n_alive)) return rc;
+  if (p->lp.on) {
+    // the latencies of the step that opens, of the scenarios still alive at their new clocks
+    if (int rc = loop_open(h, p, n_alive)) return rc;
+  }
   if (p->tr.on) {
     if (int rc = trace_append(h, p, p->tr.rows + 1)) return rc;
   }
@@ -570,6 +583,8 @@ int32_t piadmm_obca_clock_plan(piadmm_obca_t h, int32_t mode, const int32_t* clo
     return fail(h, PIADMM_E_STATE, "obca_clock_plan: feedback is attached (obca_feedback_plan: the tape has no per-scenario clocks)");
   if (mode == 1 && p->dl.on)
     return fail(h, PIADMM_E_STATE, "obca_clock_plan: the delay is attached (obca_delay_plan: it counts the plan's steps, not per-scenario clocks)");
+  if (p->lp.on)
+    return fail(h, PIADMM_E_STATE, "obca_clock_plan: the loop is attached (obca_loop_plan: its step index is the tenant's clock; detach it first)");
   if (p->i_iter != 0) return fail(h, PIADMM_E_STATE, "obca_clock_plan: only at a step boundary (an MPC step is open)");
   if (mode == 0) {
     if (!p->ck.on) return 0;
@@ -640,6 +655,10 @@ int32_t piadmm_obca_clock_admit(piadmm_obca_t h, int32_t m, const int32_t* slots
   if (p->i_iter != 0) return fail(h, PIADMM_E_STATE, "obca_clock_admit: only at a step boundary (an MPC step is open)");
   if (ref && p->ref_rows != n) return fail(h, PIADMM_E_STATE, "obca_clock_admit: ref needs a plan with a reference per scenario (obca_fleet_begin)");
   if (par && p->tab_rows != n) return fail(h, PIADMM_E_STATE, "obca_clock_admit: par needs a plan with a parameter row per scenario (obca_fleet_begin)");
+  if (p->lp.on)
+    for (int k = 0; k < m; ++k)
+      if ((int64_t)p->lp.k0 + clock[2 * (size_t)k] >= ((int64_t)1 << 31))
+        return fail(h, PIADMM_E_STATE, "obca_clock_admit: row " + std::to_string(k) + ": loop step index exhausted");
   OWN_HIP(h, hipSetDevice(h->device));
   OWN_HIP(h, hipStreamSynchronize(h->stream));
   const size_t D = sizeof(double), ref_one = (size_t)2 * n_ref * 5;
@@ -677,7 +696,16 @@ int32_t piadmm_obca_clock_admit(piadmm_obca_t h, int32_t m, const int32_t* slots
     k3[2] = 1;
     OWN_HIP(h, hipMemcpy(p->ck.clk + 3 * s, k3, 3 * sizeof(int), hipMemcpyHostToDevice));
   }
-  return clock_relist(h, p);
+  if (int rc = clock_relist(h, p)) return rc;
+  if (p->lp.on) {
+    // the admitted slots keep their loop rows and stream ids; their latencies at the new clocks
+    if (int rc = loop_open(h, p, p->ck.n_list)) {
+      (void)hipStreamSynchronize(h->stream);
+      return rc;
+    }
+    OWN_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  return 0;
 }
 
 int32_t piadmm_obca_clock_tick(piadmm_obca_t h, int32_t n, const int32_t* clock_in, const int32_t* ran,

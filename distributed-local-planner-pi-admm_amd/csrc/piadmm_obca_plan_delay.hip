@@ -13,36 +13,6 @@
 
 namespace obca_plan {
 
-// The latency of vehicle v of stream t at step k under the row's avg, std, tau_max and trunc: one
-// Philox call at counter (k, 4 v + 3, t low, t high) -- the call index the noise leaves free -- two
-// uniforms in (0, 1) on 52 bits as noise_draw forms them, the first Box-Muller normal; the second is
-// discarded.  tape is the recorded latency added in front (0 without one).  raw (4 words, or
-// nullptr) receives the call's words.  piadmm.obca.delay_tau is the same statements on the host;
-// products and sums are kept apart (no contraction), so std = 0 gives min(tau_max, tape + avg) bit
-// for bit.  The body of k_plan_delay for the in-plan step and for the stand-alone call: the same bits.
-__device__ __forceinline__ double delay_draw(uint32_t seed_lo, uint32_t seed_hi, uint32_t t_lo, uint32_t t_hi,
-                                             uint32_t k, int v, double avg, double sd, double tau_max, double trunc,
-                                             double tape, uint32_t* raw) {
-#pragma clang fp contract(off)
-  uint32_t c[4] = {k, (uint32_t)(4 * v + 3), t_lo, t_hi};
-  philox4x32_10(c, seed_lo, seed_hi);
-  if (raw) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) raw[q] = c[q];
-  }
-  const unsigned long long a = ((unsigned long long)c[0] << 32) | c[1];
-  const unsigned long long b = ((unsigned long long)c[2] << 32) | c[3];
-  const double u1 = ((double)(a >> 12) + 0.5) * 0x1p-52;
-  const double u2 = ((double)(b >> 12) + 0.5) * 0x1p-52;
-  const double rad = sqrt(-2.0 * log(u1));
-  const double ang = 6.283185307179586 * u2;
-  double z = rad * cos(ang);
-  if (trunc != 0.0) z = fmin(trunc, fmax(z, -trunc));
-  const double x = tape + (avg + sd * z);
-  const double lo = x > 0.0 ? x : 0.0;
-  return lo < tau_max ? lo : tau_max;
-}
-
 // One lane per vehicle: lane g of a grid row = vehicle g & 1 of entry g >> 1 of `list` (nullptr: of
 // scenario g >> 1), 2 m lanes; grid row y is step index k + y (the in-plan step launches one row).
 // No LDS, no atomics, nothing shared between lanes: the counter is the lane's own, the key words and
@@ -121,7 +91,7 @@ int delay_next(piadmm_obca_t h, piadmm_obca_plan_s* p) {
 
 using namespace obca_plan;
 
-namespace {
+namespace obca_plan {
 // One delay row: nullptr when it is good, else what is wrong with it.
 const char* delay_row_check(const double* row) {
   for (int i = 0; i < YPAR; ++i)
@@ -135,7 +105,9 @@ const char* delay_row_check(const double* row) {
   if (row[Y_RESERVED] != 0.0) return "the reserved entry must be 0";
   return nullptr;
 }
+}  // namespace obca_plan
 
+namespace {
 // rows, streams, k0 and the tape of both delay calls that draw, on the host
 int delay_args_check(piadmm_obca_t h, int n, const double* par, int rows, const int64_t* streams, int32_t k0,
                      int64_t steps, const double* tape, int cap, const std::string& who) {

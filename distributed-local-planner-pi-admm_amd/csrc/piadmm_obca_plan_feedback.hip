@@ -19,47 +19,6 @@ namespace obca_plan {
 // neither kernel is launched by piadmm_obca_plan_shift.
 // ---------------------------------------------------------------------------------------------
 
-// One plant step of one vehicle, all in registers: x (5) <- F(x, (a, om)) under the vehicle's row P
-// (8), without the disturbance.  n_sub substeps of DT / n_sub; a substep is 1 stage (Euler) or 4
-// (classical RK4) of the one right-hand side below, the stage loop kept rolled so that the libm
-// calls are inlined once; then delta is clipped.  n_sub is clamped to its range, so the loop is
-// bounded whatever the row holds.  piadmm.obca.propagate is the same statements on the host;
-// products and sums are kept apart (no contraction).  The body of both entry points of
-// k_plan_propagate: the stand-alone call and the in-plan step give the same bits.
-__device__ __forceinline__ void plant_step(double x[5], double a, double om, const double P[FV]) {
-#pragma clang fp contract(off)
-  const double lr = P[F_LR], lf = P[F_LF];
-  const double a_eff = fmin(P[F_AMAX], fmax(P[F_GA] * a, -P[F_AMAX]));
-  const double w_eff = fmin(P[F_WMAX], fmax(P[F_GW] * om, -P[F_WMAX]));
-  const int n_sub = min(max((int)P[F_NSUB], 1), F_NSUB_MAX);
-  const int n_stage = P[F_METHOD] != 0.0 ? 4 : 1;
-  const double hs = PLANT_DT / (double)n_sub;
-  const double scale = n_stage == 4 ? hs / 6.0 : hs;
-#pragma unroll 1
-  for (int sub = 0; sub < n_sub; ++sub) {
-    double xs[5], acc[5];
-#pragma unroll
-    for (int i = 0; i < 5; ++i) { xs[i] = x[i]; acc[i] = 0.0; }
-#pragma unroll 1
-    for (int st = 0; st < n_stage; ++st) {
-      const double beta = atan(lr * tan(xs[4]) / (lr + lf));
-      const double ph = xs[3] + beta;
-      const double f[5] = {xs[2] * cos(ph), xs[2] * sin(ph), a_eff, xs[2] / lr * sin(beta), w_eff};
-      const double wgt = (st == 1 || st == 2) ? 2.0 : 1.0;
-      const double c = st < 2 ? 0.5 * hs : hs;          // the next stage's point: x + c f
-#pragma unroll
-      for (int i = 0; i < 5; ++i) {
-        acc[i] = st == 0 ? f[i] : acc[i] + wgt * f[i];
-        xs[i] = x[i] + c * f[i];
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < 5; ++i) x[i] = x[i] + scale * acc[i];
-    x[4] = fmin(MAX_STEER, fmax(x[4], -MAX_STEER));
-  }
-}
-
-
 // One lane per vehicle: lane g of the grid = vehicle g & 1 of entry g >> 1 of `list` (nullptr: of
 // scenario g >> 1), 2 m lanes.  No LDS; the state, the stage point and the RK4 sum stay in
 // registers over the runtime substep loop.  The plant row is 64 bytes on a 64-byte boundary (the
@@ -123,43 +82,6 @@ __global__ void __launch_bounds__(64 * PW) k_plan_set_init(const int* __restrict
 // piadmm_obca_plan_shift does not launch k_plan_noise.
 // ---------------------------------------------------------------------------------------------
 
-// The five disturbances of vehicle v of stream t at step k under the row's sigma S, bias B and
-// trunc: three Philox calls at counter (k, 4 v + j, t low, t high), each giving two uniforms in
-// (0, 1) on 52 bits and by Box-Muller two normals; the sixth normal is discarded.  raw (12 words,
-// or nullptr) receives the calls' words.  piadmm.obca.noise_tape is the same statements on the
-// host; products and sums are kept apart (no contraction), so sigma = 0 gives the bias bit for bit.
-// The body of k_plan_noise for the in-plan step and for the stand-alone tape: the same bits.
-__device__ __forceinline__ void noise_draw(uint32_t seed_lo, uint32_t seed_hi, uint32_t t_lo, uint32_t t_hi,
-                                           uint32_t k, int v, const double S[5], const double B[5], double trunc,
-                                           double w[5], uint32_t* raw) {
-#pragma clang fp contract(off)
-  double z[6];
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    uint32_t c[4] = {k, (uint32_t)(4 * v + j), t_lo, t_hi};
-    philox4x32_10(c, seed_lo, seed_hi);
-    if (raw) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) raw[4 * j + q] = c[q];
-    }
-    const unsigned long long a = ((unsigned long long)c[0] << 32) | c[1];
-    const unsigned long long b = ((unsigned long long)c[2] << 32) | c[3];
-    const double u1 = ((double)(a >> 12) + 0.5) * 0x1p-52;
-    const double u2 = ((double)(b >> 12) + 0.5) * 0x1p-52;
-    const double rad = sqrt(-2.0 * log(u1));
-    const double ang = 6.283185307179586 * u2;
-    z[2 * j] = rad * cos(ang);
-    z[2 * j + 1] = rad * sin(ang);
-  }
-#pragma unroll
-  for (int i = 0; i < 5; ++i) {
-    double zi = z[i];
-    if (trunc != 0.0) zi = fmin(trunc, fmax(zi, -trunc));
-    w[i] = B[i] + S[i] * zi;
-  }
-}
-
-
 // One lane per vehicle: lane g of a grid row = vehicle g & 1 of entry g >> 1 of `list` (nullptr: of
 // scenario g >> 1), 2 m lanes; grid row y is step index k + y (the in-plan step launches one row).
 // No LDS, no atomics, nothing shared between lanes: the counter is the lane's own, the arithmetic
@@ -205,7 +127,7 @@ __global__ void __launch_bounds__(64 * PW) k_plan_noise(const int* __restrict__ 
 
 using namespace obca_plan;
 
-namespace {
+namespace obca_plan {
 // One plant row of the feedback (both vehicles): nullptr when it is good, else what is wrong with it.
 const char* feedback_row_check(const double* row) {
   for (int i = 0; i < FPAR; ++i)
@@ -229,7 +151,9 @@ void feedback_row_nominal(double* row) {
     P[F_GA] = 1.0;  P[F_GW] = 1.0;  P[F_AMAX] = 5.0;  P[F_WMAX] = 20.0;
   }
 }
+}  // namespace obca_plan
 
+namespace {
 // the first entry of a[0 .. count) that is not finite, or -1
 int64_t first_not_finite(const double* a, size_t count) {
   for (size_t i = 0; i < count; ++i)
@@ -377,7 +301,7 @@ int32_t piadmm_obca_feedback_measure(piadmm_obca_t h, int32_t m, const int32_t* 
 // ---------------------------------------------------------------------------------------------
 // Device-side disturbance noise (include/piadmm.h)
 // ---------------------------------------------------------------------------------------------
-namespace {
+namespace obca_plan {
 // One noise row: nullptr when it is good, else what is wrong with it.
 const char* noise_row_check(const double* row) {
   for (int i = 0; i < ZPAR; ++i)
@@ -388,7 +312,9 @@ const char* noise_row_check(const double* row) {
   if (row[Z_RESERVED] != 0.0) return "the reserved entry must be 0";
   return nullptr;
 }
+}  // namespace obca_plan
 
+namespace {
 // rows, streams and k0 of both noise calls, on the host
 int noise_args_check(piadmm_obca_t h, int n, const double* par, int rows, const int64_t* streams, int32_t k0,
                      int64_t steps, const std::string& who) {

@@ -21,10 +21,19 @@ static_assert(TR_STATE_PREV == STATE && TR_CTRL == 2 * STATE && TR_X == TR_CTRL 
               TR_PRIMAL == TR_LAMBDA + 126 && TR_PAR == TR_PRIMAL + 4 && TR_REF == TR_PAR + TAB &&
               TR_REF + WIN == PIADMM_OBCA_TENANT_F64 && 4 * 126 + DPAR == PIADMM_OBCA_TENANT_F64_LAW &&
               TI_CLOCK + 3 <= TR_INTS && (TR_INTS * 4) % 16 == 0, "tenant record layout");
+// the loop section (doubles), behind the law's: the three rows, the open step's latencies, the stream id
+constexpr int TL_PLANT = 0, TL_NOISE = 16, TL_DELAY = 38, TL_TAU = 46, TL_STREAM = 48, TL_WORDS = PIADMM_OBCA_TENANT_F64_LOOP;
+static_assert(TL_NOISE == FPAR && TL_DELAY == TL_NOISE + ZPAR && TL_TAU == TL_DELAY + YPAR && TL_STREAM == TL_TAU + 2 &&
+              TL_STREAM + 2 == TL_WORDS && TL_WORDS % 2 == 0, "tenant record layout: the loop section");
 
 // the plan's per-scenario arrays, by value.  S .. gains: only with a law (`law`); win, work, clk:
-// nullptr without the clock / the order.  The strides are 0 where the plan shares one row.
+// nullptr without the clock / the order.  The strides are 0 where the plan shares one row.  l_*: only
+// with the loop (`loop`, its flags); l_noise / l_delay nullptr where the kind is absent (export) or
+// the plan shares one row (import, as l_plant and gains).
 struct tenant_arrays {
+  double *l_plant, *l_noise, *l_delay, *l_tau;
+  long long* l_streams;
+  int l_plant_s, l_noise_s, l_delay_s, loop;
   double *bar, *barp, *ctrl, *ctrlp, *X, *lamb, *primal, *dual, *pth, *dth, *tab, *ref, *win, *S, *D, *Sp, *Dp, *gains;
   int *iters, *stop, *conv, *prob, *mask, *work, *clk;
   int tab_stride, ref_stride, g_stride, n_ref, t_step, law, f64_words;
@@ -68,6 +77,16 @@ __global__ void __launch_bounds__(64 * PW) k_plan_export(const int* __restrict__
     copy_seg(L + 252, a.Sp + s * 126, 126, lane);
     copy_seg(L + 378, a.Dp + s * 126, 126, lane);
     copy_seg(L + 504, a.gains + s * a.g_stride, DPAR, lane);
+  }
+  if (a.loop) {
+    double* Q = W + WIN + (a.law ? PIADMM_OBCA_TENANT_F64_LAW : 0);
+    copy_seg(Q + TL_PLANT, a.l_plant + s * a.l_plant_s, FPAR, lane);
+    if (a.l_noise) copy_seg(Q + TL_NOISE, a.l_noise + s * a.l_noise_s, ZPAR, lane);
+    else if (lane < ZPAR) Q[TL_NOISE + lane] = 0.0;
+    if (a.l_delay) copy_seg(Q + TL_DELAY, a.l_delay + s * a.l_delay_s, YPAR, lane);
+    else if (lane < YPAR) Q[TL_DELAY + lane] = 0.0;
+    copy_seg(Q + TL_TAU, a.l_tau + s * 2, 2, lane);
+    if (lane < 2) Q[TL_STREAM + lane] = lane == 0 ? __longlong_as_double(a.l_streams[s]) : 0.0;
   }
   if (lane < TR_INTS) {
     int v = 0;
@@ -117,6 +136,14 @@ __global__ void __launch_bounds__(64 * PW) k_plan_import(const int* __restrict__
     copy_seg(a.Dp + s * 126, L + 378, 126, lane);
     if (a.gains) copy_seg(a.gains + s * a.g_stride, L + 504, DPAR, lane);
   }
+  if (a.loop) {
+    const double* Q = W + WIN + (a.law ? PIADMM_OBCA_TENANT_F64_LAW : 0);
+    if (a.l_plant) copy_seg(a.l_plant + s * FPAR, Q + TL_PLANT, FPAR, lane);
+    if (a.l_noise) copy_seg(a.l_noise + s * ZPAR, Q + TL_NOISE, ZPAR, lane);
+    if (a.l_delay) copy_seg(a.l_delay + s * YPAR, Q + TL_DELAY, YPAR, lane);
+    copy_seg(a.l_tau + s * 2, Q + TL_TAU, 2, lane);
+    if (lane == 0) a.l_streams[s] = __double_as_longlong(Q[TL_STREAM]);
+  }
   if (lane < TR_INTS) {
     const int* ri = reinterpret_cast<const int*>(rec + a.f64_words);
     const int v = ri[lane];
@@ -136,11 +163,14 @@ __global__ void __launch_bounds__(64 * PW) k_plan_import(const int* __restrict__
 using namespace obca_plan;
 
 namespace {
-// the fp64 words of a record of a plan with references of n_ref rows, with or without a law
-int64_t tenant_f64(int n_ref, bool law) {
-  return (int64_t)PIADMM_OBCA_TENANT_F64 + 10 * (int64_t)n_ref + (law ? PIADMM_OBCA_TENANT_F64_LAW : 0);
+// the fp64 words of a record of a plan with references of n_ref rows, with or without a law and the loop
+int64_t tenant_f64(int n_ref, bool law, bool loop) {
+  return (int64_t)PIADMM_OBCA_TENANT_F64 + 10 * (int64_t)n_ref + (law ? PIADMM_OBCA_TENANT_F64_LAW : 0) +
+         (loop ? PIADMM_OBCA_TENANT_F64_LOOP : 0);
 }
-int64_t tenant_rec_bytes(int n_ref, bool law) { return 8 * tenant_f64(n_ref, law) + 4 * PIADMM_OBCA_TENANT_INTS; }
+int64_t tenant_rec_bytes(int n_ref, bool law, bool loop) {
+  return 8 * tenant_f64(n_ref, law, loop) + 4 * PIADMM_OBCA_TENANT_INTS;
+}
 
 obca_plan::tenant_arrays tenant_view(const piadmm_obca_plan_s* p) {
   obca_plan::tenant_arrays a{};
@@ -153,7 +183,12 @@ obca_plan::tenant_arrays tenant_view(const piadmm_obca_plan_s* p) {
   a.clk = p->ck.on ? p->ck.clk : nullptr;
   a.tab_stride = p->tab_stride;  a.ref_stride = p->ref_stride;  a.g_stride = p->du.stride;
   a.n_ref = p->cfg.n_ref;  a.t_step = p->t_step;  a.law = p->du.on ? 1 : 0;
-  a.f64_words = (int)tenant_f64(p->cfg.n_ref, p->du.on);
+  a.f64_words = (int)tenant_f64(p->cfg.n_ref, p->du.on, p->lp.on);
+  a.loop = p->lp.on ? p->lp.flags : 0;
+  a.l_plant = p->lp.plant;  a.l_plant_s = p->lp.plant_rows > 1 ? FPAR : 0;
+  a.l_noise = p->lp.noise;  a.l_noise_s = p->lp.noise_rows > 1 ? ZPAR : 0;
+  a.l_delay = p->lp.delay;  a.l_delay_s = p->lp.delay_rows > 1 ? YPAR : 0;
+  a.l_tau = p->lp.tau;  a.l_streams = p->lp.streams;
   return a;
 }
 }  // namespace
@@ -165,7 +200,7 @@ int32_t piadmm_obca_tenant_export_bytes(piadmm_obca_t h, int32_t m, int64_t* byt
   if (int rc = open_plan(h, &p, "obca_tenant_export_bytes")) return rc;
   if (m < 1 || m > p->n) return fail(h, PIADMM_E_ARG, "obca_tenant_export_bytes: 1 <= m <= n_scenarios");
   if (!bytes) return fail(h, PIADMM_E_ARG, "obca_tenant_export_bytes: null argument");
-  *bytes = PIADMM_OBCA_TENANT_HEADER + (int64_t)m * tenant_rec_bytes(p->cfg.n_ref, p->du.on);
+  *bytes = PIADMM_OBCA_TENANT_HEADER + (int64_t)m * tenant_rec_bytes(p->cfg.n_ref, p->du.on, p->lp.on);
   return 0;
 }
 
@@ -173,7 +208,7 @@ int32_t piadmm_obca_tenant_export(piadmm_obca_t h, int32_t m, const int32_t* slo
   piadmm_obca_plan_s* p = nullptr;
   if (int rc = open_plan(h, &p, "obca_tenant_export")) return rc;
   if (int rc = tenant_slots_check(h, p, m, slots, blob, "obca_tenant_export")) return rc;
-  const int64_t rec_bytes = tenant_rec_bytes(p->cfg.n_ref, p->du.on), body = (int64_t)m * rec_bytes;
+  const int64_t rec_bytes = tenant_rec_bytes(p->cfg.n_ref, p->du.on, p->lp.on), body = (int64_t)m * rec_bytes;
   if (bytes != PIADMM_OBCA_TENANT_HEADER + body)
     return fail(h, PIADMM_E_ARG, "obca_tenant_export: the blob is " + std::to_string(PIADMM_OBCA_TENANT_HEADER + body) +
                 " bytes, not " + std::to_string(bytes));
@@ -192,8 +227,11 @@ int32_t piadmm_obca_tenant_export(piadmm_obca_t h, int32_t m, const int32_t* slo
   OWN_HIP(h, hipStreamSynchronize(h->stream));
   const int32_t hdr[PIADMM_OBCA_TENANT_HEADER / 4] = {
       PIADMM_OBCA_TENANT_MAGIC, PIADMM_ABI_VERSION, m, p->cfg.n_ref, p->cfg.update_lamb_ij, p->du.on ? 1 : 0,
-      p->ord.on ? 1 : 0, (int32_t)tenant_f64(p->cfg.n_ref, p->du.on), PIADMM_OBCA_TENANT_INTS, (int32_t)rec_bytes,
-      PIADMM_OBCA_TENANT_HEADER, 0, 0, 0, 0, 0};
+      p->ord.on ? 1 : 0, (int32_t)tenant_f64(p->cfg.n_ref, p->du.on, p->lp.on), PIADMM_OBCA_TENANT_INTS,
+      (int32_t)rec_bytes, PIADMM_OBCA_TENANT_HEADER,
+      // the loop: its flags, the seed (low, high) and k0; zeros without it
+      p->lp.on ? p->lp.flags : 0, p->lp.on ? (int32_t)(uint32_t)p->lp.seed : 0,
+      p->lp.on ? (int32_t)(uint32_t)(p->lp.seed >> 32) : 0, p->lp.on ? p->lp.k0 : 0, 0};
   std::memcpy(out, hdr, sizeof(hdr));
   return 0;
 }
@@ -212,10 +250,12 @@ int32_t piadmm_obca_tenant_import(piadmm_obca_t h, int32_t m, const int32_t* slo
   if (hdr[1] != PIADMM_ABI_VERSION)
     return fail(h, PIADMM_E_ARG, "obca_tenant_import: the blob is of ABI " + std::to_string(hdr[1]));
   if (hdr[2] != m) return fail(h, PIADMM_E_ARG, "obca_tenant_import: the blob holds " + std::to_string(hdr[2]) + " tenants, not m");
-  const bool law = hdr[5] == 1, order = hdr[6] == 1;
-  if (hdr[3] < 8 || hdr[3] > (1 << 20) || (hdr[4] != 0 && hdr[4] != 1) || (hdr[5] != 0 && hdr[5] != 1) ||
+  const bool law = hdr[5] == 1, order = hdr[6] == 1, loop = hdr[11] != 0;
+  const bool loop_ok = hdr[15] == 0 && (loop ? (hdr[11] & 1) && !(hdr[11] & ~7) && hdr[14] >= 0
+                                              : hdr[12] == 0 && hdr[13] == 0 && hdr[14] == 0);
+  if (!loop_ok || hdr[3] < 8 || hdr[3] > (1 << 20) || (hdr[4] != 0 && hdr[4] != 1) || (hdr[5] != 0 && hdr[5] != 1) ||
       (hdr[6] != 0 && hdr[6] != 1) || hdr[10] != PIADMM_OBCA_TENANT_HEADER || hdr[8] != PIADMM_OBCA_TENANT_INTS ||
-      (int64_t)hdr[7] != tenant_f64(hdr[3], law) || (int64_t)hdr[9] != tenant_rec_bytes(hdr[3], law))
+      (int64_t)hdr[7] != tenant_f64(hdr[3], law, loop) || (int64_t)hdr[9] != tenant_rec_bytes(hdr[3], law, loop))
     return fail(h, PIADMM_E_ARG, "obca_tenant_import: bad header (flags or section sizes)");
   const int64_t rec_bytes = hdr[9], body = (int64_t)m * rec_bytes;
   if (bytes != PIADMM_OBCA_TENANT_HEADER + body)
@@ -225,9 +265,18 @@ int32_t piadmm_obca_tenant_import(piadmm_obca_t h, int32_t m, const int32_t* slo
     return fail(h, PIADMM_E_ARG, "obca_tenant_import: n_ref mismatch (the blob " + std::to_string(hdr[3]) + ", the plan " +
                 std::to_string(n_ref) + ")");
   if (hdr[4] != p->cfg.update_lamb_ij) return fail(h, PIADMM_E_ARG, "obca_tenant_import: update_lamb_ij mismatch");
+  const uint64_t blob_seed = (uint64_t)(uint32_t)hdr[12] | ((uint64_t)(uint32_t)hdr[13] << 32);
+  if (loop && p->lp.on) {
+    if (hdr[11] != p->lp.flags)
+      return fail(h, PIADMM_E_ARG, "obca_tenant_import: the loop's row kinds differ (the blob " + std::to_string(hdr[11]) +
+                  ", the plan " + std::to_string(p->lp.flags) + ")");
+    if (blob_seed != p->lp.seed || hdr[14] != p->lp.k0)
+      return fail(h, PIADMM_E_ARG, "obca_tenant_import: the loop's seed or k0 differ from the plan's");
+  }
   // the records: what the kernels rely on (the rows, prob, the clocks)
   const size_t F = (size_t)hdr[7];
   const size_t law_at = (size_t)PIADMM_OBCA_TENANT_F64 + 10 * (size_t)n_ref;
+  const size_t loop_at = law_at + (law ? PIADMM_OBCA_TENANT_F64_LAW : 0);
   auto rec_f64 = [&](int k, size_t word, double* dst, int count) {
     std::memcpy(dst, in + PIADMM_OBCA_TENANT_HEADER + (size_t)k * rec_bytes + 8 * word, sizeof(double) * (size_t)count);
   };
@@ -249,6 +298,20 @@ int32_t piadmm_obca_tenant_import(piadmm_obca_t h, int32_t m, const int32_t* slo
       rec_f64(k, law_at + 504, g, DPAR);
       if (const char* why = dual_row_check(g)) return fail(h, PIADMM_E_ARG, row + "gains: " + why);
     }
+    if (loop) {
+      double q[TL_WORDS];
+      rec_f64(k, loop_at, q, TL_WORDS);
+      if (const char* why = feedback_row_check(q + TL_PLANT)) return fail(h, PIADMM_E_ARG, row + "plant: " + why);
+      if (const char* why = noise_row_check(q + TL_NOISE)) return fail(h, PIADMM_E_ARG, row + "noise: " + why);
+      if (const char* why = delay_row_check(q + TL_DELAY)) return fail(h, PIADMM_E_ARG, row + "delay: " + why);
+      for (int v = 0; v < 2; ++v)
+        if (!(q[TL_TAU + v] >= 0.0 && q[TL_TAU + v] <= PLANT_DT)) return fail(h, PIADMM_E_ARG, row + "tau must be in [0, DT]");
+      int64_t stream;
+      std::memcpy(&stream, q + TL_STREAM, sizeof(stream));
+      if (stream < 0) return fail(h, PIADMM_E_ARG, row + "the stream id must be >= 0");
+      if ((int64_t)hdr[14] + ri[TI_CLOCK] >= ((int64_t)1 << 31) && ri[TI_CLOCK] + 8 <= ri[TI_CLOCK + 1])
+        return fail(h, PIADMM_E_ARG, row + "loop step index exhausted");
+    }
   }
   // the destination
   if (p->fb.on) return fail(h, PIADMM_E_STATE, "obca_tenant_import: feedback is attached (the tenant record has no room for the tape)");
@@ -261,6 +324,9 @@ int32_t piadmm_obca_tenant_import(piadmm_obca_t h, int32_t m, const int32_t* slo
   if (law != p->du.on)
     return fail(h, PIADMM_E_STATE, law ? "obca_tenant_import: the blob carries a dual law, the plan has none attached"
                                         : "obca_tenant_import: the plan has a dual law attached, the blob carries none");
+  if (loop != p->lp.on)
+    return fail(h, PIADMM_E_STATE, loop ? "obca_tenant_import: the blob carries the loop, the plan has none attached"
+                                         : "obca_tenant_import: the plan has the loop attached, the blob carries none");
   if (order != p->ord.on)
     return fail(h, PIADMM_E_STATE, order ? "obca_tenant_import: the blob carries the order's record, the plan has no order attached"
                                           : "obca_tenant_import: the plan has the order attached, the blob carries no record");
@@ -278,12 +344,34 @@ int32_t piadmm_obca_tenant_import(piadmm_obca_t h, int32_t m, const int32_t* slo
                     ": the gains row differs from the plan's shared one");
     }
   }
+  if (loop) {
+    // a shared row of a kind: a read of that one row, nothing is written
+    const struct { const double* dev; int rows, at, width; const char* kind; } kinds[3] = {
+        {p->lp.plant, p->lp.plant_rows, TL_PLANT, FPAR, "plant"},
+        {p->lp.noise, (p->lp.flags & 2) ? p->lp.noise_rows : n, TL_NOISE, ZPAR, "noise"},
+        {p->lp.delay, (p->lp.flags & 4) ? p->lp.delay_rows : n, TL_DELAY, YPAR, "delay"}};
+    for (const auto& kd : kinds) {
+      if (kd.rows == n) continue;
+      double shared[ZPAR], g[ZPAR];
+      OWN_HIP(h, hipMemcpyAsync(shared, kd.dev, sizeof(double) * (size_t)kd.width, hipMemcpyDeviceToHost, h->stream));
+      OWN_HIP(h, hipStreamSynchronize(h->stream));
+      for (int k = 0; k < m; ++k) {
+        rec_f64(k, loop_at + (size_t)kd.at, g, kd.width);
+        if (std::memcmp(g, shared, sizeof(double) * (size_t)kd.width) != 0)
+          return fail(h, PIADMM_E_ARG, "obca_tenant_import: row " + std::to_string(k) + ": the " + kd.kind +
+                      " row differs from the plan's shared one");
+      }
+    }
+  }
   if (int rc = stage_ensure(h, p, (size_t)body, m)) return rc;
   int* d_list = reinterpret_cast<int*>(p->stg.buf + body);
   OWN_HIP(h, hipMemcpyAsync(p->stg.buf, in + PIADMM_OBCA_TENANT_HEADER, (size_t)body, hipMemcpyHostToDevice, h->stream));
   OWN_HIP(h, hipMemcpyAsync(d_list, slots, (size_t)m * sizeof(int), hipMemcpyHostToDevice, h->stream));
   tenant_arrays a = tenant_view(p);
   if (!gains_travel) a.gains = nullptr;
+  if (p->lp.plant_rows != n) a.l_plant = nullptr;
+  if (!(p->lp.flags & 2) || p->lp.noise_rows != n) a.l_noise = nullptr;
+  if (!(p->lp.flags & 4) || p->lp.delay_rows != n) a.l_delay = nullptr;
   hipLaunchKernelGGL(k_plan_import, dim3(blocks_for(m)), dim3(64 * PW), 0, h->stream, (const int*)d_list, m, a,
                      reinterpret_cast<const double*>(p->stg.buf.get()));
   OWN_HIP(h, hipGetLastError());
@@ -297,7 +385,17 @@ int32_t piadmm_obca_tenant_import(piadmm_obca_t h, int32_t m, const int32_t* slo
     k3[1] = ri[TI_CLOCK + 1];
     k3[2] = k3[0] <= k3[1] - 8 ? 1 : 0;
   }
-  return clock_relist(h, p);
+  if (int rc = clock_relist(h, p)) return rc;
+  if (p->lp.on) {
+    // as after an admission: an alive tenant's latency is the draw at its clock, whatever the record
+    // held; a retired tenant keeps the record's
+    if (int rc = loop_open(h, p, p->ck.n_list)) {
+      (void)hipStreamSynchronize(h->stream);
+      return rc;
+    }
+    OWN_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  return 0;
 }
 
 }  // extern "C"

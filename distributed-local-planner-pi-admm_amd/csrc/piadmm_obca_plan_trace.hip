@@ -759,6 +759,8 @@ int32_t piadmm_obca_trace_run(piadmm_obca_t h, int32_t n_steps, int32_t* steps_d
     return fail(h, PIADMM_E_STATE, "obca_trace_run: noise step index exhausted before " + std::to_string(n_steps) + " steps");
   if (const char* why = delay_refusal(p, n_steps))
     return fail(h, PIADMM_E_STATE, std::string("obca_trace_run: ") + why + " before " + std::to_string(n_steps) + " steps");
+  if (loop_exhausted(p, n_steps))
+    return fail(h, PIADMM_E_STATE, "obca_trace_run: loop step index exhausted before " + std::to_string(n_steps) + " steps");
   if (p->ck.on) {
     // the steps the longest-lived scenario has left
     int left = 0;

@@ -158,6 +158,11 @@ SYMBOLS = [
                                       _P(ctypes.c_uint32)]),
     ("piadmm_obca_delay_exchange", c_i32, [_H, c_i32, _dp, _ip, _dp, _dp, _dp, _dp]),
     ("piadmm_obca_delay_plan", c_i32, [_H, c_i32, _dp, c_i32, _P(ctypes.c_int64), ctypes.c_uint64, c_i32, _dp, c_i32]),
+    ("piadmm_obca_loop_plan", c_i32, [_H, c_i32, _dp, c_i32, _dp, c_i32, _dp, c_i32, _P(ctypes.c_int64), ctypes.c_uint64,
+                                      c_i32]),
+    ("piadmm_obca_loop_admit", c_i32, [_H, c_i32, _ip, _dp, _dp, _dp, _P(ctypes.c_int64)]),
+    ("piadmm_obca_loop_draw", c_i32, [_H, c_i32, _ip, _dp, c_i32, _dp, c_i32, _P(ctypes.c_int64), ctypes.c_uint64, c_i32,
+                                      _dp, _dp]),
 ]
 
 # PIADMM_OBCA_FLEET_PAR: doubles per parameter row of piadmm_obca_fleet_begin

@@ -227,6 +227,26 @@ class OBCABatch:
             _lib.dptr(tape), _lib.dptr(tau), _lib.u32ptr(words)))
         return (tau, words) if raw else tau
 
+    def loop_draw(self, clock, noise=None, delay=None, streams=None, seed=0, k0=0):
+        """k_loop_draw on the call's own buffers (piadmm_obca_loop_draw): (w n x 2 x 5, tau n x 2), the
+        disturbance row and the latency of stream streams[s] (None: s) at step index k0 + clock[s][0]
+        under the noise / delay rows (one for all, or n; None: zeros), as `loop_draw` states them.
+        clock n x 3 as the CLOCK item.  The library checks the arguments."""
+        clock = np.ascontiguousarray(clock, np.int32)
+        n = clock.shape[0]
+        assert clock.shape == (n, 3), clock.shape
+        noise = None if noise is None else _draw_rows(noise, NOISE_PAR, None, n)[0]
+        delay = None if delay is None else _draw_rows(delay, DELAY_PAR, None, n)[0]
+        if streams is not None:
+            streams = np.ascontiguousarray(streams, np.int64).reshape(-1)
+            assert streams.shape == (n,), streams.shape
+        w, tau = np.zeros((n, 2, NX)), np.zeros((n, 2))
+        self._check(self._lib.piadmm_obca_loop_draw(
+            self._h, n, _lib.iptr(clock), _lib.dptr(noise), 0 if noise is None else noise.shape[0], _lib.dptr(delay),
+            0 if delay is None else delay.shape[0], _lib.i64ptr(streams), ctypes.c_uint64(int(seed)), int(k0),
+            _lib.dptr(w), _lib.dptr(tau)))
+        return w, tau
+
     def delay_exchange(self, X, prob, tau):
         """The stale message alone, one launch of k_delay_exchange on the call's own buffers
         (piadmm_obca_delay_exchange): X n x 2 x 8 x 5 the local solves' states, prob one value or one

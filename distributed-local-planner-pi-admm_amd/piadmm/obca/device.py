@@ -8,6 +8,7 @@ from .._lib import DELAY_PAR, DUAL_PAR, FEEDBACK_PAR, FLEET_PAR, NOISE_PAR
 from .attach import clock_rows, clock_tick, dual_rows
 from .batch import OBCAEdgeResult, OBCAResult
 from .feedback import DELAY_GET, NOISE_GET, _draw_rows, delay_row, feedback_args, noise_row
+from .loop import LOOP_GET
 from .model import (DT, EDGE_OUT, EDGE_REC, FLEET_ROW, N_HORZ, NT, NU, NX, OUT, REC, _spec, executed_path, ref_traj_gen,
                     seeded_bar_state)
 from .planner import _planner_init, _spec_of
@@ -72,13 +73,22 @@ class OBCADevicePlanner:
     k_plan_delay and k_plan_exchange_stale; `delay_tau` and `stale_states` are the statements): every
     vehicle sends the halfspaces of its plan interpolated back by its latency of the open step,
     `get("DELAY_TAU")`.  `set_delay` / `clear_delay` attach and detach it at a step boundary;
-    independent of feedback and noise, not together with clock or the tenant calls."""
+    independent of feedback and noise, not together with clock or the tenant calls.
+
+    With clock= and loop=dict(plant=, noise=, delay=, streams=, seed=, k0=) the closed loop runs under
+    the per-scenario clocks (piadmm_obca_loop_plan; `loop_draw` is the statement of its draws): a
+    step closes through the plant under the noise row of stream streams[s] at step index k0 + c, c the
+    scenario's own clock, and with delay rows the exchange is stale by the latency at k0 + c of the
+    open step, `loop_tau()`.  plant one row or n (None: the nominal plant), noise / delay one row or
+    n (None: that kind is absent).  `set_loop` / `clear_loop` attach and detach it at a step boundary,
+    `admit(..., loop=dict(plant=, noise=, delay=, streams=))` gives an admitted tenant its own rows and
+    stream; the tenant records, `compact`, `save` and `load` carry it."""
 
     def __init__(self, batch, n_scenarios, prob=1, t_step0=0, rho=1.0, min_dis=0.1, max_admm_iter=50,
                  primal_thres=0.01, dual_thres=0.01, round_decimals=4, start=1, update_lamb_ij=0, max_iter=60,
                  conv_thres=0.1, on_stage=None, max_x=150.0, max_y=20.0, r=1e4, q=1e5, x_bound=1000.0,
                  mu_max=100000.0, g_max=1000.0, ref_traj=None, state=None, specs=None, dual=None, order=False,
-                 work_init=None, clock=None, feedback=None, noise=None, delay=None):
+                 work_init=None, clock=None, feedback=None, noise=None, delay=None, loop=None):
         self._lib = batch._lib
         any_seq, (ref, ref_each), rows, t0 = _planner_init(
             self, batch, n_scenarios, prob, t_step0, primal_thres, dual_thres, update_lamb_ij, on_stage, specs,
@@ -124,6 +134,7 @@ class OBCADevicePlanner:
         self._feedback = None
         self._noise = None
         self._delay = None
+        self._loop = None
         if dual is not None:
             self.set_dual(**dual)
         self.order = False
@@ -140,8 +151,39 @@ class OBCADevicePlanner:
             self.set_noise(**noise)
         if delay is not None:
             self.set_delay(**delay)
+        if loop is not None:
+            self.set_loop(**loop)
         self.record = OBCARunRecord()
         self.record.state_record.append(np.stack(self.init_state))
+
+    def set_loop(self, plant=None, noise=None, delay=None, streams=None, seed=0, k0=0):
+        """Attach the loop (piadmm_obca_loop_plan; a step boundary only, a clock attached): plant one
+        plant row or n (None: the nominal plant), noise one noise row or n (None: no noise), delay one
+        delay row or n (None: the plain exchange), streams n stream ids (None: 0 .. n-1), seed a
+        uint64, k0 the step index of clock 0.  A second call replaces the first.  The library checks
+        the arguments."""
+        def rows_of(par, width):
+            return None if par is None else np.ascontiguousarray(np.asarray(par, np.float64).reshape(-1, width))
+        plant, noise, delay = rows_of(plant, FEEDBACK_PAR), rows_of(noise, NOISE_PAR), rows_of(delay, DELAY_PAR)
+        if streams is not None:
+            streams = np.ascontiguousarray(streams, np.int64).reshape(-1)
+            assert streams.shape == (self.n,), streams.shape
+        self._check(self._lib.piadmm_obca_loop_plan(
+            self.batch._h, 1, _lib.dptr(plant), 0 if plant is None else len(plant), _lib.dptr(noise),
+            0 if noise is None else len(noise), _lib.dptr(delay), 0 if delay is None else len(delay),
+            _lib.i64ptr(streams), ctypes.c_uint64(int(seed)), int(k0)))
+        self._loop = dict(plant=1 if plant is None else len(plant), noise=None if noise is None else len(noise),
+                          delay=None if delay is None else len(delay), seed=int(seed), k0=int(k0))
+
+    def clear_loop(self):
+        """Detach the loop (a step boundary only): a step closes with init_state = X[1] and the exchange
+        is the plain one again."""
+        self._check(self._lib.piadmm_obca_loop_plan(self.batch._h, 0, None, 0, None, 0, None, 0, None, 0, 0))
+        self._loop = None
+
+    def loop_tau(self):
+        """The open step's latencies, n x 2 (the LOOP_TAU item; zeros without delay rows)."""
+        return self.get("LOOP_TAU")
 
     def set_delay(self, par=None, streams=None, seed=0, k0=0, tape=None):
         """Attach the communication delay (piadmm_obca_delay_plan; a step boundary only, no clock):
@@ -237,12 +279,15 @@ class OBCADevicePlanner:
         return np.ones(self.n, bool) if self._clock is None else self._clock[:, 2].astype(bool)
 
     def admit(self, slots, clock, state=None, ref=None, par=None, prob=None, primal_thres=None, dual_thres=None,
-              specs=None):
+              specs=None, loop=None):
         """New tenants into `slots` of the clocked plan (piadmm_obca_clock_admit; a step boundary, no
         trace): clock m x 2 rows (c0, len); state m x 556, ref m x 2 x n_ref x 5, par m x FLEET_PAR,
         prob, primal_thres, dual_thres m each -- None keeps what the slot has.  With specs= (one
         OvertakeSpec per tenant) a missing ref is the spec's reference and a missing state the
-        state seeded at the tenant's c0, as the constructor seeds it."""
+        state seeded at the tenant's c0, as the constructor seeds it.  With the loop attached the
+        slot keeps its loop rows and stream id and its latency is drawn at the new c0; loop=dict(plant=,
+        noise=, delay=, streams=) then sets them (piadmm_obca_loop_admit: m rows of a kind, which the
+        loop must hold per scenario; m stream ids; None keeps)."""
         slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
         m = len(slots)
         clock = np.ascontiguousarray(clock, np.int32)
@@ -296,6 +341,28 @@ class OBCADevicePlanner:
                     setattr(self, name + "_s", col)
             if specs is not None and self.specs is not None:
                 self.specs[s] = specs[k]
+        if loop is not None:
+            # last: a refusal here leaves the slots admitted, on their earlier loop rows, and the copies true
+            self.loop_admit(slots, **loop)
+
+    def loop_admit(self, slots, plant=None, noise=None, delay=None, streams=None):
+        """The loop rows and stream ids of `slots` (piadmm_obca_loop_admit; a step boundary, no trace):
+        m rows of a kind the loop holds per scenario, m stream ids; None keeps what the slot has."""
+        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        m = len(slots)
+
+        def rows_of(par, width):
+            if par is None:
+                return None
+            par = np.ascontiguousarray(np.asarray(par, np.float64).reshape(-1, width))
+            assert par.shape == (m, width), par.shape
+            return par
+        if streams is not None:
+            streams = np.ascontiguousarray(streams, np.int64).reshape(-1)
+            assert streams.shape == (m,), streams.shape
+        self._check(self._lib.piadmm_obca_loop_admit(
+            self.batch._h, m, _lib.iptr(slots), _lib.dptr(rows_of(plant, FEEDBACK_PAR)), _lib.dptr(rows_of(noise, NOISE_PAR)),
+            _lib.dptr(rows_of(delay, DELAY_PAR)), _lib.i64ptr(streams)))
 
     # -- running tenants: export, import, compaction, checkpoints (piadmm_obca_tenant_export / _import) --
     TENANT_ITEMS = ("STATE", "STATE_PREV", "CTRL", "CTRL_PREV", "X", "LAMBDA", "PRIMAL", "DUAL", "PRIMAL_THRES",
@@ -310,6 +377,10 @@ class OBCADevicePlanner:
             names += ("WORK",)
         if self._clock is not None:
             names += ("CLOCK", "WINDOW")
+        if self._loop is not None:
+            names += ("LOOP_PLANT", "LOOP_TAU", "LOOP_STREAMS", "LOOP_SEED")
+            names += ("LOOP_NOISE",) if self._loop["noise"] else ()
+            names += ("LOOP_DELAY",) if self._loop["delay"] else ()
         return {k: self.get(k) for k in names}
 
     def export_tenants(self, slots) -> bytes:
@@ -373,6 +444,11 @@ class OBCADevicePlanner:
             pl._set_dual_rows(t["DUAL_PAR"] if dual_par is None else np.asarray(dual_par, np.float64).reshape(1, DUAL_PAR))
         if t["order"]:
             pl.set_order()
+        if t["loop"]:
+            # a row per tenant of every kind the blob carries, the blob's; the seed and k0 of its header
+            pl.set_loop(plant=t["LOOP_PLANT"], noise=t["LOOP_NOISE"] if t["loop"] & 2 else None,
+                        delay=t["LOOP_DELAY"] if t["loop"] & 4 else None, streams=t["LOOP_STREAMS"],
+                        seed=int(t["LOOP_SEED"][0]), k0=int(t["LOOP_SEED"][1]))
         pl.import_tenants(np.arange(m), tenants)
         pl.t_step = int(t_step)
         pl.record.state_record[0] = np.stack(pl.init_state)
@@ -475,7 +551,16 @@ class OBCADevicePlanner:
 
     def get(self, what):
         """One item of the resident plan (include/piadmm.h, piadmm_obca_plan_get), shaped: a name of
-        PLAN_GET, of NOISE_GET or of DELAY_GET."""
+        PLAN_GET, of NOISE_GET, of DELAY_GET or of LOOP_GET."""
+        if what in LOOP_GET:
+            code, dt = LOOP_GET[what]
+            lp = self._loop or dict(plant=1, noise=1, delay=1)
+            shape = {"LOOP_PLANT": (lp["plant"], FEEDBACK_PAR), "LOOP_NOISE": (lp["noise"] or 1, NOISE_PAR),
+                     "LOOP_DELAY": (lp["delay"] or 1, DELAY_PAR), "LOOP_TAU": (self.n, 2), "LOOP_STREAMS": (self.n,),
+                     "LOOP_SEED": (3,)}[what]
+            out = np.zeros(shape, dt)
+            self._check(self._lib.piadmm_obca_plan_get(self.batch._h, code, out.ctypes.data, out.nbytes))
+            return out
         if what in DELAY_GET:
             code, dt = DELAY_GET[what]
             shape = {"DELAY_PAR": (1 if self._delay is None else len(self._delay[0]), DELAY_PAR),
@@ -530,7 +615,7 @@ class OBCADevicePlanner:
             self._lib.piadmm_obca_plan_end(self.batch._h)
 
     def _close_step(self, iters, status):
-        if self._clock is None and self._feedback is None:
+        if self._clock is None and self._feedback is None:      # the loop needs a clock: it reads STATE below
             X = self.get("X")
             self.init_state = [X[s, :, 1].copy() for s in range(self.n)]
         else:

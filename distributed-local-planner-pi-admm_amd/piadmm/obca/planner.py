@@ -4,6 +4,7 @@ import numpy as np
 from .. import _lib
 from .attach import clock_rows, clock_tick, dual_rows, lambda_update_pi, shift_dual
 from .feedback import NOISE_K_MAX, delay_args, delay_tau, feedback_args, noise_args, noise_tape, propagate
+from .loop import loop_args, loop_draw
 from .model import (DT, EDGE_WRITES_ITERATE, N_HORZ, NT, NU, NX, _per_scenario, _spec, bar_state_update, check_converge,
                     edge_record, executed_path, iterate_next_state, local_record, ref_traj_gen, seeded_bar_state)
 from .stats import OBCARunRecord
@@ -111,13 +112,20 @@ class OBCAPlanner:
     `delay_tau`'s latency of stream streams[s] at step index k0 + k (tape n x cap x 2: recorded
     latencies added in front); what it keeps for itself (controls, X, init_state) is unchanged.
     `set_delay` / `clear_delay` attach and detach it; independent of feedback and noise, not together
-    with clock.  OBCADevicePlanner takes the same argument (piadmm_obca_delay_plan)."""
+    with clock.  OBCADevicePlanner takes the same argument (piadmm_obca_delay_plan).
+
+    loop: None, or with clock= dict(plant=, noise=, delay=, streams=, seed=, k0=): the same closed loop
+    under the per-scenario clocks, its step index each scenario's own clock c (`loop_draw`).  A step
+    closes, for the scenarios it ran, with init_state = propagate(the closing step's init_state, the
+    first control, plant[s], the noise row of stream streams[s] at step index k0 + c); with delay rows
+    the open step's latency of an alive scenario is `delay_tau`'s at k0 + c (`loop_tau`), a retired
+    one's stays.  OBCADevicePlanner takes the same argument (piadmm_obca_loop_plan)."""
 
     def __init__(self, batch, n_scenarios, prob=1, t_step0=0, rho=1.0, min_dis=0.1, max_admm_iter=50,
                  primal_thres=0.01, dual_thres=0.01, round_decimals=4, start=1, update_lamb_ij=0, max_iter=60,
                  conv_thres=0.1, on_stage=None, max_x=150.0, max_y=20.0, r=1e4, q=1e5, x_bound=1000.0,
                  mu_max=100000.0, g_max=1000.0, ref_traj=None, specs=None, dual=None, clock=None, feedback=None,
-                 noise=None, delay=None):
+                 noise=None, delay=None, loop=None):
         _, _, rows, t0 = _planner_init(
             self, batch, n_scenarios, prob, t_step0, primal_thres, dual_thres, update_lamb_ij,
             on_stage or (lambda name, inputs, outputs: None), specs, ref_traj, clock, rho=rho, min_dis=min_dis,
@@ -145,8 +153,41 @@ class OBCAPlanner:
         self.delay = None
         if delay is not None:
             self.set_delay(**delay)
+        self.loop = None
+        if loop is not None:
+            self.set_loop(**loop)
         self.record = OBCARunRecord()
         self.record.state_record.append(np.stack(self.init_state))
+
+    def set_loop(self, plant=None, noise=None, delay=None, streams=None, seed=0, k0=0):
+        """Attach the loop (see the class; a clock must be attached and neither feedback nor delay, as
+        piadmm_obca_loop_plan refuses otherwise)."""
+        loop = loop_args(self.n, plant, noise, delay, streams, seed, k0)
+        why = ("feedback is attached" if self.feedback is not None else "the delay is attached" if self.delay is not None
+               else "no clock attached" if self.clock is None else None)
+        if why is not None:
+            err = _lib.PiadmmError(f"obca_loop_plan: {why}")
+            err.code = _lib.E_STATE
+            raise err
+        self.loop = loop
+        self._loop_tau = np.zeros((self.n, 2))
+        self._loop_open()
+
+    def clear_loop(self):
+        self.loop = None
+
+    def _loop_open(self):
+        """The open step's latencies of the alive scenarios at their clocks; a retired one's stay."""
+        if self.loop["delay"] is not None:
+            alive = self.clock[:, 2] != 0
+            tau = loop_draw(self.n, np.where(alive, self.clock[:, 0], 0), None, self.loop["delay"], self.loop["streams"],
+                            self.loop["seed"], self.loop["k0"])[1]
+            self._loop_tau[alive] = tau[alive]
+
+    def loop_tau(self):
+        """The open step's latencies, n x 2 (the LOOP_TAU item of OBCADevicePlanner.get)."""
+        assert self.loop is not None, "no loop attached"
+        return self._loop_tau.copy()
 
     def set_delay(self, par=None, streams=None, seed=0, k0=0, tape=None):
         """Attach the communication delay (see the class): from the next step on the exchange is
@@ -230,6 +271,9 @@ class OBCAPlanner:
             assert ran, "no scenario alive"
             t_of = [int(c) for c in self.clock[:, 0]]
         tau = None if self.delay is None else self.delay_tau()
+        if self.loop is not None:
+            assert (self.loop["k0"] + self.clock[ran, 0] + 1 < NOISE_K_MAX).all(), "loop step index exhausted"
+            tau = self.loop_tau() if self.loop["delay"] is not None else None
         bar = [self._copy(b) for b in self.bar_prev]
         bar_prev = [self._copy(b) for b in self.bar_prev]
         x0_step = [np.array(x, np.float64) for x in self.init_state]
@@ -347,12 +391,21 @@ class OBCAPlanner:
             self._feedback_steps += 1
         if self.delay is not None:
             self._delay_steps += 1
+        if self.loop is not None:
+            # the same, for the scenarios the step ran, each at its own clock (before the tick)
+            lp = self.loop
+            for s in ran:
+                w = None if lp["noise"] is None else loop_draw(1, self.clock[s:s + 1], lp["noise"][s % len(lp["noise"])], None,
+                                                               lp["streams"][s:s + 1], lp["seed"], lp["k0"])[0]
+                self.init_state[s] = propagate(x0_step[s][None], U0[s][None], lp["plant"][s % len(lp["plant"])], w)[0]
         self.on_stage("shift", dict(bar_prev=shift_in, X=X, iters=iters.copy()), dict(bar_next=self.bar_prev, init_state=self.init_state))
         self.record.state_record.append(np.stack(self.init_state))
         self.record.iter_num_record.append(iters)
         self.record.lambda_record.append(np.stack(self.lamb_last))
         if self.clock is not None:
             self.clock = clock_tick(self.clock, self.clock[:, 2])
+        if self.loop is not None:
+            self._loop_open()
         self.t_step += 1
 
     def run(self, n_steps):

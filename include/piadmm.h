@@ -739,7 +739,8 @@ int32_t piadmm_obca_clock_tick(piadmm_obca_t h, int32_t n, const int32_t* clock_
  *   0 magic PIADMM_OBCA_TENANT_MAGIC | 1 PIADMM_ABI_VERSION | 2 m | 3 n_ref | 4 update_lamb_ij |
  *   5 law present (0 / 1) | 6 order present (0 / 1) | 7 F, the fp64 words of a record |
  *   8 PIADMM_OBCA_TENANT_INTS, its int32 words | 9 the bytes of a record, 8 F + 48 |
- *   10 the bytes of the header | 11-15 zero
+ *   10 the bytes of the header | 11 the loop's flags (0 without the loop; piadmm_obca_loop_plan:
+ *   1 present, + 2 noise rows, + 4 delay rows) | 12, 13 its seed (low, high) | 14 its k0 | 15 zero
  * Record k starts at byte 64 + k (8 F + 48).  Its fp64 section, offsets in doubles (R = 10 n_ref):
  *   0 STATE 556 | 556 STATE_PREV 556 | 1112 CTRL 28 | 1140 CTRL_PREV 28 | 1168 X 80 |
  *   1248 LAMBDA 126 | 1374 PRIMAL | 1375 DUAL | 1376 primal_thres | 1377 dual_thres |
@@ -748,7 +749,12 @@ int32_t piadmm_obca_clock_tick(piadmm_obca_t h, int32_t n, const int32_t* clock_
  *   zeros when t_step + 8 > n_ref)
  * and, only with a law, from L = 1474 + R:
  *   L S 126 | L + 126 D 126 | L + 252 S_prev 126 | L + 378 D_prev 126 | L + 504 the gains row 8
- * so F = 1474 + R without a law and 1986 + R with one.  Every segment but the four scalars starts
+ * and, only with the loop, PIADMM_OBCA_TENANT_F64_LOOP = 50 words behind the law's section (or the
+ * window), from Q:
+ *   Q the plant row 16 | Q + 16 the noise row 22 (zeros if absent) | Q + 38 the delay row 8 (zeros if
+ *   absent) | Q + 46 the open step's latencies 2 (zeros without delay rows) | Q + 48 the stream id
+ *   (the int64's bits) | Q + 49 zero
+ * so F = 1474 + R without a law and 1986 + R with one, 50 more with the loop.  Every segment but the four scalars starts
  * on an even word and has an even length, and a record is a multiple of 16 bytes.  Its int32
  * section, at byte 8 F of the record:
  *   0 ITERS | 1 STOP | 2 CONVERGE | 3 prob | 4-5 STATUS_MASK | 6-7 WORK (zeros without the order) |
@@ -789,6 +795,7 @@ int32_t piadmm_obca_clock_tick(piadmm_obca_t h, int32_t n, const int32_t* clock_
 #define PIADMM_OBCA_TENANT_INTS 12
 #define PIADMM_OBCA_TENANT_F64 1474       /* + 10 n_ref, + PIADMM_OBCA_TENANT_F64_LAW with a law */
 #define PIADMM_OBCA_TENANT_F64_LAW 512
+#define PIADMM_OBCA_TENANT_F64_LOOP 50    /* + this with the loop (piadmm_obca_loop_plan) */
 #define PIADMM_OBCA_PLAN_GET_PRIMAL_THRES 29
 #define PIADMM_OBCA_PLAN_GET_DUAL_THRES 30
 #define PIADMM_OBCA_PLAN_GET_PROB 31
@@ -1021,6 +1028,90 @@ int32_t piadmm_obca_delay_plan(piadmm_obca_t h, int32_t mode, const double* par 
                                int32_t rows /* 1 or n */, const int64_t* streams /* n, may be NULL: 0 .. n-1 */,
                                uint64_t seed, int32_t k0, const double* tape /* n x cap x 2, may be NULL */,
                                int32_t cap);
+
+/* ---- the loop: closed loop under per-scenario clocks (plant, noise, delay, tenants) -------------
+ * piadmm_obca_feedback_plan, _noise_plan and _delay_plan count the plan's steps and therefore refuse a
+ * clocked plan, and the tenant calls refuse them.  The loop is the same closed loop for a clocked
+ * plan: its step index is each tenant's own clock.  With c the tenant's clock as
+ * PIADMM_OBCA_PLAN_GET_CLOCK shows it, the disturbance row and the latency of scenario s are the pure
+ * functions of (seed, streams[s], k0 + c) the noise and the delay sections define (one seed, one
+ * stream id and one k0 serve both draws: the noise's counter calls are 4 v + 0, 1, 2, the delay's is
+ * 4 v + 3), so a tenant re-run alone, admitted late, retired, exported or imported computes the same
+ * bits.  Opt-in: without the attachment the plan issues exactly the launches it issued before.
+ *
+ * piadmm_obca_loop_plan, mode 1, attaches it; a second call replaces the first once the new
+ * attachment is complete; mode 0 detaches (the other arguments are ignored).  plant: plant rows
+ * (NULL: the nominal row), noise: noise rows (NULL: no noise), delay: delay rows (NULL: no delay, the
+ * plain exchange runs), each `rows` = 1 (shared) or n and each row checked as its own attachment
+ * checks it (PIADMM_E_ARG, "obca_loop_plan: <kind> row k: ..."); streams >= 0 (NULL: 0 .. n-1),
+ * k0 >= 0.  Then PIADMM_E_STATE: no open plan, feedback or the delay attached, no clock attached, an
+ * MPC step open, a step index k0 + c of an alive tenant at 2^31.  A refused call leaves every
+ * piadmm_obca_plan_get item and an earlier loop as they were.  While attached:
+ *   closing a step   piadmm_obca_plan_shift computes, for exactly the scenarios the step ran and before
+ *                    the shift overwrites what it reads, next = propagate(init_state, u0, plant[s]) +
+ *                    (the noise row at k0 + c, if any) with x0, u0 and the order of operations of
+ *                    piadmm_obca_feedback_plan (k_loop_close); after the unchanged shift next goes
+ *                    over init_state of both state copies (k_plan_set_init), before the tick and
+ *                    before a trace row is appended
+ *   opening a step   with delay rows the open step's latency of an alive tenant is tau(seed,
+ *                    streams[s], k0 + c) at its clock after the tick: drawn at the attachment, after
+ *                    every shift and after every admission or import (k_loop_open over the alive
+ *                    scenarios); every iterate launches k_plan_exchange_stale on them
+ *   retired tenants  frozen as the clock section says; their latency and stream id stay as well
+ *   the limit        a shift, step or piadmm_obca_trace_run that would take an alive tenant's k0 + c to
+ *                    2^31 is PIADMM_E_STATE ("loop step index exhausted") before any launch
+ * piadmm_obca_clock_plan (either mode) returns PIADMM_E_STATE ("obca_clock_plan: the loop is
+ * attached"): detach the loop first.  piadmm_obca_feedback_measure, the trace, the order and the dual
+ * law work as before.  piadmm_obca_clock_admit keeps the slot's loop rows and stream id and redraws
+ * its latency at the new c0.
+ *
+ * piadmm_obca_loop_admit sets the loop rows and stream ids of the m slots (distinct, below n): a
+ * non-NULL row array holds m rows of that kind and needs a loop with n rows of it (PIADMM_E_STATE
+ * otherwise); NULL keeps what the slot has.  Only at a step boundary, without a trace; the latencies
+ * of the alive scenarios are drawn again.
+ *
+ * piadmm_obca_loop_draw runs the per-tenant draw alone on the call's own device buffers (k_loop_draw):
+ * w_out[s] and tau_out[s] are the disturbance row and the latency of stream streams[s] at step index
+ * k0 + clock[s][0] (clock n x 3 as the CLOCK item; only c is read); NULL noise gives zeros in w_out,
+ * NULL delay zeros in tau_out.  PIADMM_E_ARG before any device call: 1 <= n <= 2^20, the rows, the
+ * streams, k0 >= 0, c >= 0 and k0 + c < 2^31.
+ *
+ * The tenant record carries the loop (the layout above): piadmm_obca_tenant_export of a plan with the
+ * loop writes the section, a shared row into every record.  piadmm_obca_tenant_import checks, before
+ * any device call: the header's flags, seed and k0 against the plan's loop (PIADMM_E_ARG; the loop
+ * present in one and absent in the other is PIADMM_E_STATE, as the law), per record ("obca_tenant_import:
+ * row k: ...") the three rows, tau in [0, DT], the stream id >= 0, and a row that differs from the
+ * plan's shared row of its kind.  Rows, tau and stream id travel; an alive tenant's latency is then
+ * drawn again at its clock (the value a consistent record holds), a retired tenant keeps the
+ * record's: the tenant continues bit for bit.
+ *
+ * piadmm_obca_plan_get gains (PIADMM_E_STATE without the loop; NOISE / DELAY also without that kind)
+ *   PIADMM_OBCA_LOOP_GET_PLANT     rows x PIADMM_OBCA_FEEDBACK_PAR fp64
+ *   PIADMM_OBCA_LOOP_GET_NOISE     rows x PIADMM_OBCA_NOISE_PAR fp64
+ *   PIADMM_OBCA_LOOP_GET_DELAY     rows x PIADMM_OBCA_DELAY_PAR fp64
+ *   PIADMM_OBCA_LOOP_GET_TAU       n x 2 fp64    the open step's latencies (zeros without delay rows)
+ *   PIADMM_OBCA_LOOP_GET_STREAMS   n int64
+ *   PIADMM_OBCA_LOOP_GET_SEED      3 uint64      seed, k0, flags
+ * Out of scope: tapes (a tape has no per-tenant clock), AR(1) noise, delays beyond one step, admission
+ * under a trace. */
+#define PIADMM_OBCA_LOOP_GET_PLANT 43
+#define PIADMM_OBCA_LOOP_GET_NOISE 44
+#define PIADMM_OBCA_LOOP_GET_DELAY 45
+#define PIADMM_OBCA_LOOP_GET_TAU 46
+#define PIADMM_OBCA_LOOP_GET_STREAMS 47
+#define PIADMM_OBCA_LOOP_GET_SEED 48
+int32_t piadmm_obca_loop_plan(piadmm_obca_t h, int32_t mode,
+                              const double* plant /* rows x PIADMM_OBCA_FEEDBACK_PAR, may be NULL */, int32_t plant_rows,
+                              const double* noise /* rows x PIADMM_OBCA_NOISE_PAR, may be NULL */, int32_t noise_rows,
+                              const double* delay /* rows x PIADMM_OBCA_DELAY_PAR, may be NULL */, int32_t delay_rows,
+                              const int64_t* streams /* n, may be NULL: 0 .. n-1 */, uint64_t seed, int32_t k0);
+int32_t piadmm_obca_loop_admit(piadmm_obca_t h, int32_t m, const int32_t* slots /* m */,
+                               const double* plant, const double* noise, const double* delay /* m rows each, may be NULL */,
+                               const int64_t* streams /* m, may be NULL */);
+int32_t piadmm_obca_loop_draw(piadmm_obca_t h, int32_t n, const int32_t* clock /* n x 3 */,
+                              const double* noise, int32_t noise_rows, const double* delay, int32_t delay_rows,
+                              const int64_t* streams /* n, may be NULL */, uint64_t seed, int32_t k0,
+                              double* w_out /* n x 2 x 5 */, double* tau_out /* n x 2 */);
 
 /* ---- fleet risk statistics and the worst-case gather of a run record ---------------------------
  * A Monte-Carlo study over a traced fleet asks how many runs came closer than d, at which step the

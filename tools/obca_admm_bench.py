@@ -137,6 +137,25 @@
                    is fixed in advance.  Written under the key "delay" of the same JSON, the other
                    keys kept.
 
+  --loop           instead of the above, in one process at --scenarios scenarios of
+                   obca.overtaking_fleet(--scenarios, seed=0), every clock at step 8 over the whole
+                   reference (clock_init = NULL), over --steps MPC steps through run_traced, the
+                   repeats of the legs alternating after a warm-up step of each, best of
+                   --repeats: (c) the clocked fleet without the loop against (l) the same with the
+                   loop attached under rows that draw zero (the nominal plant, a noise row of sigma =
+                   bias = 0, a delay row of tau_max = 0): k_loop_close, k_plan_set_init and k_loop_open
+                   per shift, k_plan_exchange_stale in k_plan_exchange's place.  ms per MPC step of
+                   both, (l)/(c) next to the max/min spread of (c)'s own repeats, and whether the two
+                   records are equal: reported, not assumed -- (l) closes a step through the plant from
+                   init_state under u0, (c) with X[1] of a solve that max_admm_iter may have cut short,
+                   and where they differ the two run different solves and (l)/(c) prices no launch.
+                   So a third leg, (p) the loop with the nominal plant alone (no noise or delay rows:
+                   k_loop_close and k_plan_set_init per shift, the plain exchange), runs the solves of
+                   (l): (l)/(p) prices the draws, k_loop_open and the stale exchange.
+                   For comparison the keys "noise" and "delay" of the same JSON are quoted as they
+                   stand (the one or two extra launches per step on an unclocked plan).  No ratio is
+                   fixed in advance.  Written under the key "loop" of the same JSON, the other keys kept.
+
 There is no CPU baseline on an equal footing (the C++ port of the local solver has no edge step);
 the edge launch is reported next to the local launch so the reader sees its share of an iterate.
 Writes one JSON (default profiles/obca_admm_bench.json) and prints it.
@@ -912,8 +931,79 @@ def delay_main(a):
     print(json.dumps(dict(delay=res)))
 
 
+def loop_main(a):
+    """--loop: (c) the clocked fleet against (l) the same with the loop under rows that draw zero."""
+    b = obca.OBCABatch(0)
+    n, K = a.scenarios, a.steps
+    specs, par = obca.overtaking_fleet(n, seed=0)
+    kw = dict(prob=[k % 2 for k in range(n)], t_step0=8, max_admm_iter=a.iterates - 1, specs=specs, clock=True, **par)
+    zero = dict(plant=None, noise=obca.noise_row(), delay=obca.delay_row(tau_max=0.0), seed=0, k0=0)
+    legs_at = dict(c_clocked=None, p_clocked_plant_only=dict(plant=None), l_clocked_zero_loop=zero)
+    warm = obca.OBCADevicePlanner(b, n, **kw)
+    state = warm.get("STATE")                          # the seeded state, so the later plans skip the host seeding
+    warm.close()
+    for loop in legs_at.values():
+        warm = obca.OBCADevicePlanner(b, n, state=state, loop=loop, **kw)
+        warm.step()
+        warm.close()
+    ms, traces, tau_any = {k: [] for k in legs_at}, {}, None
+    for _ in range(a.repeats):
+        for name, loop in legs_at.items():
+            dp = obca.OBCADevicePlanner(b, n, state=state, loop=loop, **kw)
+            t0 = time.perf_counter()
+            traces[name] = dp.run_traced(K, keep_lambda=False)
+            ms[name].append((time.perf_counter() - t0) * 1e3)
+            if loop is not None:
+                tau_any = bool(dp.loop_tau().any())
+            dp.close()
+    legs = {}
+    for name in legs_at:
+        tr = traces[name]
+        n_it, best = int(tr.iters.max(axis=1).sum()), min(ms[name])
+        legs[name] = dict(steps_run=int(tr.iters.shape[0]), admm_iterates=n_it, step_ms=best / max(tr.iters.shape[0], 1),
+                          total_ms_runs=ms[name], spread_max_over_min=max(ms[name]) / best,
+                          stop_iterate_histogram=np.bincount(tr.iters.ravel()).tolist())
+    tc, tp, tl = traces["c_clocked"], traces["p_clocked_plant_only"], traces["l_clocked_zero_loop"]
+    fields = ("states", "clearance", "iters", "status_mask", "primal", "dual")
+    same = {f: bool(np.array_equal(getattr(tc, f), getattr(tl, f))) for f in fields}
+    same_p = {f: bool(np.array_equal(getattr(tp, f), getattr(tl, f))) for f in fields}
+    ratio = min(ms["l_clocked_zero_loop"]) / min(ms["c_clocked"])
+    ratio_p = min(ms["l_clocked_zero_loop"]) / min(ms["p_clocked_plant_only"])
+    # the older attachments' lines of the same file, as they stand
+    quoted = {}
+    if os.path.exists(a.out):
+        with open(a.out) as f:
+            old = json.load(f)
+        for key, leg, over in (("noise", "z_zero_tape_zero_noise", "zero_noise_over_zero_tape"),
+                               ("delay", "d_zero_tape_zero_delay", "zero_delay_over_zero_tape")):
+            got = old.get(key, {})
+            quoted[key] = {over: got.get(over), "p_zero_tape_step_ms": got.get("legs", {}).get("p_zero_tape", {}).get("step_ms"),
+                           leg + "_step_ms": got.get("legs", {}).get(leg, {}).get("step_ms")}
+    res = dict(scenarios=n, steps=K, repeats=a.repeats, max_admm_iter=a.iterates - 1, legs=legs,
+               zero_loop_over_clocked=ratio, clocked_spread_max_over_min=legs["c_clocked"]["spread_max_over_min"],
+               ratio_exceeds_clocked_spread=bool(ratio > legs["c_clocked"]["spread_max_over_min"]),
+               extra_ms_per_step=(min(ms["l_clocked_zero_loop"]) - min(ms["c_clocked"])) / K,
+               records_equal=same, max_abs_state_difference=float(np.abs(tc.states - tl.states).max()),
+               zero_loop_over_plant_only=ratio_p, plant_only_spread_max_over_min=legs["p_clocked_plant_only"]["spread_max_over_min"],
+               ratio_exceeds_plant_only_spread=bool(ratio_p > legs["p_clocked_plant_only"]["spread_max_over_min"]),
+               extra_ms_per_step_over_plant_only=(min(ms["l_clocked_zero_loop"]) - min(ms["p_clocked_plant_only"])) / K,
+               records_equal_plant_only=same_p,
+               zero_loop_latencies_nonzero=tau_any, unclocked_attachments_quoted=quoted)
+    b.close()
+    out = {}
+    if os.path.exists(a.out):
+        with open(a.out) as f:
+            out = json.load(f)
+    out["loop"] = res
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+    print(json.dumps(dict(loop=res)))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--loop", action="store_true")
     ap.add_argument("--delay", action="store_true")
     ap.add_argument("--noise", action="store_true")
     ap.add_argument("--stats", action="store_true")
@@ -931,6 +1021,8 @@ def main():
     ap.add_argument("--iterates", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "obca_admm_bench.json"))
     a = ap.parse_args()
+    if a.loop:
+        return loop_main(a)
     if a.delay:
         return delay_main(a)
     if a.noise:
