@@ -1,7 +1,7 @@
 // piadmm_obca_plan.h -- what the units of the device-resident OBCA-ADMM consensus loop share
 // (internal, not installed): the layouts, the kernel-argument structs, the owners of device memory,
 // the plan and the small host helpers.  csrc/piadmm_obca_plan.hip holds the iterate and the shift and
-// describes the launch sequence; csrc/piadmm_obca_plan_{attach,trace,tenant,feedback,delay,loop}.hip hold
+// describes the launch sequence; csrc/piadmm_obca_plan_{attach,trace,tenant,feedback,delay,loop,ledger}.hip hold
 // the attachments.  Every kernel is defined in one unit; there is no relocatable device code, a unit
 // launches another unit's kernel through the declaration here.
 #pragma once
@@ -63,6 +63,13 @@ static_assert(Z_RESERVED + 1 == ZPAR, "noise row layout");
 constexpr int YPAR = PIADMM_OBCA_DELAY_PAR;
 constexpr int Y_AVG = 0, Y_STD = 2, Y_TMAX = 4, Y_TRUNC = 6, Y_RESERVED = 7;
 static_assert(Y_RESERVED + 1 == YPAR, "delay row layout");
+
+// a ledger record (include/piadmm.h): 22 words of 8 bytes
+constexpr int LREC = PIADMM_OBCA_LEDGER_REC / 8;
+constexpr int L_ID = 0, L_STREAM = 1, L_SLOT = 2, L_FIRST = 3, L_PLAIN = 4, L_TIGHT = 5, L_CMIN = 6, L_SUM = 7, L_MASK = 8,
+              L_PRIMAL = 9, L_DUAL = 10, L_TSTEP = 11, L_STATE = 12;
+static_assert(L_STATE + 10 == LREC && PIADMM_OBCA_LEDGER_REC % 8 == 0, "ledger record layout");
+constexpr int LVIEW = 11;            // the words of the statistics' view per record: summary 4, clear 2 x 2, iters 1, mask 2
 
 // dst[0 .. len) = src[0 .. len) by the 64 lanes of a wave in strided passes: 16 bytes a lane where
 // both ends sit on a 16-byte boundary and len is even, 8 bytes a lane otherwise.  The pointers are
@@ -305,6 +312,65 @@ __device__ __forceinline__ double delay_draw(uint32_t seed_lo, uint32_t seed_hi,
   return lo < tau_max ? lo : tau_max;
 }
 
+// The exact minimum distance between the two vehicles' rectangles (generate_vehicle_vertices,
+// util.py:34-42) at the state pair st[2][5], for two box sets at once: the plain boxes (centre x, y)
+// and the delay-tightened ones the planner constrains (compute_square_halfspaces_ca_prob,
+// util.py:70-101: each centre moved as halfspaces() above moves it; pr = 0 moves nothing, so both
+// results are the plain value).  The distance is 0 when no edge normal of either rectangle separates
+// them (SAT over the 4 axes), else the minimum of the 32 vertex-to-edge distances.  Lane = set * 32 +
+// dir * 16 + vertex * 4 + edge: a vertex of vehicle `dir` against an edge of the other vehicle, whose
+// normal (edge & 1: the lateral one) is the lane's SAT axis.  Every lane of the wave must be here (the
+// reductions are DPP scans over the whole wave) and st, pr are wave-uniform; plain and tight come back
+// uniform.  piadmm.obca.clearance is the same statements on the host; products and sums are kept
+// apart (no contraction).  The body of k_plan_clearance and of the ledger's k_ledger_open and
+// k_ledger_step: the same bits.
+__device__ __forceinline__ void clearance_pair(const double* st, int pr, double sigd, int lane, double& plain,
+                                               double& tight) {
+#pragma clang fp contract(off)
+  const int set = lane >> 5, dir = (lane >> 4) & 1, vi = (lane >> 2) & 3, ej = lane & 3;
+  constexpr double HL = LENGTH / 2, HW = WIDTH / 2;
+  // box a owns the lane's vertex, box o its edge
+  const double* sa = st + dir * 5;
+  const double* so = st + (1 - dir) * 5;
+  const double ca = cos(sa[3]), sna = sin(sa[3]), co = cos(so[3]), sno = sin(so[3]);
+  double ax = sa[0], ay = sa[1], ox = so[0], oy = so[1];
+  if (set == 1 && pr) {
+    const double va = sa[2], vo = so[2];
+    const double qax = VAR_DELAY * va * ca, qay = VAR_DELAY * va * sna;
+    const double qox = VAR_DELAY * vo * co, qoy = VAR_DELAY * vo * sno;
+    const double dax = AVG_DELAY * va * ca + sigd * (qax * qax), day = AVG_DELAY * va * sna + sigd * (qay * qay);
+    const double dox = AVG_DELAY * vo * co + sigd * (qox * qox), doy = AVG_DELAY * vo * sno + sigd * (qoy * qoy);
+    ax = ax + dax;  ay = ay + day;
+    ox = ox + dox;  oy = oy + doy;
+  }
+  // vertex i = centre + sl e + sw n: (+, +), (+, -), (-, -), (-, +)
+  const double pl = vi < 2 ? HL : -HL, pw = (vi == 0 || vi == 3) ? HW : -HW;
+  const double px = ax + pl * ca - pw * sna, py = ay + pl * sna + pw * ca;
+  const int e1 = (ej + 1) & 3;
+  const double al = ej < 2 ? HL : -HL, aw = (ej == 0 || ej == 3) ? HW : -HW;
+  const double bl = e1 < 2 ? HL : -HL, bw = (e1 == 0 || e1 == 3) ? HW : -HW;
+  const double e0x = ox + al * co - aw * sno, e0y = oy + al * sno + aw * co;
+  const double e1x = ox + bl * co - bw * sno, e1y = oy + bl * sno + bw * co;
+  const double abx = e1x - e0x, aby = e1y - e0y, apx = px - e0x, apy = py - e0y;
+  double t = (apx * abx + apy * aby) / (abx * abx + aby * aby);
+  t = fmin(fmax(t, 0.0), 1.0);
+  const double rx = apx - t * abx, ry = apy - t * aby;
+  const double dist = sqrt(rx * rx + ry * ry);
+  // SAT along the edge's normal: |centre distance| against the two half extents
+  const bool lateral = ej & 1;
+  const double ux = lateral ? -sno : co, uy = lateral ? co : sno;
+  const double cdx = ax - ox, cdy = ay - oy;
+  const double pc = fabs(cdx * ux + cdy * uy);
+  const double pe = fabs(ca * ux + sna * uy), pn = fabs(ca * uy - sna * ux);
+  const double gap = pc - ((lateral ? HW : HL) + (HL * pe + HW * pn));
+  // every lane is active here: the reductions are DPP scans over the whole wave
+  const double inf = __builtin_inf();
+  const double g0 = pd::wmax(set == 0 ? gap : -inf), g1 = pd::wmax(set == 1 ? gap : -inf);
+  const double d0 = pd::wmin(set == 0 ? dist : inf), d1 = pd::wmin(set == 1 ? dist : inf);
+  plain = g0 > 0.0 ? d0 : 0.0;
+  tight = g1 > 0.0 ? d1 : 0.0;
+}
+
 // The kernels launched from a unit other than their own (the comments are at the definitions).
 // csrc/piadmm_obca_plan.hip
 __global__ void __launch_bounds__(CT) k_plan_compact(const int* __restrict__ active, const int* __restrict__ keep,
@@ -443,6 +509,21 @@ struct piadmm_obca_plan_s {
     dbuf<double> plant, noise, delay, tau, next;
     dbuf<long long> streams;
   } lp;
+  // the tenant ledger (piadmm_obca_ledger_begin): rec = the appended records, cap x 22 words; run = the
+  // open record of every slot, n x 22; list / pos / ids = what an admission uploads for k_ledger_close and
+  // k_ledger_open, n each; view = the statistics' R = 1 view, grown on demand.  The host mirrors what
+  // decides a position: count, next_id and per slot the tenant's id (-1: none) and c_first
+  struct ledger_s {
+    bool on = false;
+    int cap = 0, count = 0;
+    long long next_id = 0;
+    dbuf<long long> rec, run, ids;
+    dbuf<int> list, pos;
+    dbuf<char> view;
+    size_t view_cap = 0;
+    std::vector<long long> id;
+    std::vector<int> c_first;
+  } lg;
   // the staging buffer of piadmm_obca_tenant_export / _import: the records, then the slot list; grown on demand
   struct stage_s {
     dbuf<char> buf;
@@ -584,5 +665,22 @@ int loop_set_init(piadmm_obca_t h, piadmm_obca_plan_s* p);
 int loop_open(piadmm_obca_t h, piadmm_obca_plan_s* p, int m);
 // csrc/piadmm_obca_plan_trace.hip
 int trace_append(piadmm_obca_t h, piadmm_obca_plan_s* p, int row);
+struct stats_out {
+  piadmm_obca_stats_t* stats;
+  int64_t* hist;
+  double* row_min;
+  int32_t *row_arg, *row_below, *worst;
+};
+int stats_args_check(piadmm_obca_t h, const std::string& who, int n, const double* edges, int B, int K,
+                     const stats_out& o);
+int stats_run(piadmm_obca_t h, int R, int n, const double* d_clear, const double* d_summary, const int* d_iters,
+              const int* d_mask, const double* edges, int B, int K, const stats_out& o);
+// csrc/piadmm_obca_plan_ledger.hip
+const char* ledger_refusal(const piadmm_obca_plan_s* p, int64_t steps);
+int ledger_step(piadmm_obca_t h, piadmm_obca_plan_s* p);
+void ledger_stepped(piadmm_obca_plan_s* p, const std::vector<int>& next);
+const char* ledger_replace_refusal(const piadmm_obca_plan_s* p, int m, const int32_t* slots, bool fresh_only);
+int ledger_close(piadmm_obca_t h, piadmm_obca_plan_s* p, int m, const int32_t* slots, int reason, bool fresh_only);
+int ledger_open(piadmm_obca_t h, piadmm_obca_plan_s* p, int m, const int32_t* slots);
 
 }  // namespace obca_plan

@@ -41,6 +41,10 @@
 // and with delay rows k_loop_open after the tick (the latencies of the alive scenarios at their new
 // clocks) and every iterate k_plan_exchange_stale in k_plan_exchange's place; without it none is
 // launched.
+// With a ledger attached (piadmm_obca_ledger_begin; a clocked plan only) piadmm_obca_plan_shift runs
+// k_ledger_step on the scenarios the step ran, after the shift (under the loop: after k_plan_set_init)
+// and before the tick: their open records take the step, and the ones the tick retires are appended;
+// an admission or an import runs k_ledger_close and k_ledger_open; without it none is launched.
 // The statistics of a run record (piadmm_obca_fleet_stats / _stats_trace: k_stats_fleet, k_stats_rows,
 // k_stats_worst and their merges) and k_trace_gather are launched by those calls alone and write
 // nothing of the plan or the trace.
@@ -56,7 +60,7 @@
 // min_dis, max_admm_iter) is a uniform load; the record parameters are loaded by the few lanes
 // that store them.
 //
-// The attachments' kernels and calls are in csrc/piadmm_obca_plan_{attach,trace,tenant,feedback,delay,loop}.hip;
+// The attachments' kernels and calls are in csrc/piadmm_obca_plan_{attach,trace,tenant,feedback,delay,loop,ledger}.hip;
 // the launches above that are theirs go through the declarations in csrc/piadmm_obca_plan.h.
 
 #include "piadmm_obca_plan.h"
@@ -477,7 +481,7 @@ int plan_open(piadmm_obca_t h, const piadmm_obca_plan_cfg_t* cfg, const int32_t*
 void piadmm_obca_plan_release(piadmm_obca_t h) {
   piadmm_obca_plan_s* p = h->plan;
   if (!p) return;
-  if (p->tr.on || p->du.on || p->ord.on || p->ck.on || p->fb.on || p->dl.on || p->lp.on) {
+  if (p->tr.on || p->du.on || p->ord.on || p->ck.on || p->fb.on || p->dl.on || p->lp.on || p->lg.on) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     p->tr = {};
@@ -488,6 +492,7 @@ void piadmm_obca_plan_release(piadmm_obca_t h) {
     p->nz = {};    // the noise counts its steps by the feedback's: it goes whenever the feedback goes
     p->dl = {};
     p->lp = {};
+    p->lg = {};
   }
   p->open = false;
 }
@@ -625,6 +630,7 @@ int32_t piadmm_obca_plan_shift(piadmm_obca_t h) {
   if (feedback_exhausted(p, 1)) return fail(h, PIADMM_E_STATE, "obca_plan_shift: disturbance tape exhausted");
   if (noise_exhausted(p, 1)) return fail(h, PIADMM_E_STATE, "obca_plan_shift: noise step index exhausted");
   if (loop_exhausted(p, 1)) return fail(h, PIADMM_E_STATE, "obca_plan_shift: loop step index exhausted");
+  if (const char* why = ledger_refusal(p, 1)) return fail(h, PIADMM_E_STATE, std::string("obca_plan_shift: ") + why);
   OWN_HIP(h, hipSetDevice(h->device));
   if (p->ck.on) return clock_shift(h, p);
   if (p->fb.on) {
@@ -703,6 +709,7 @@ int32_t piadmm_obca_plan_step(piadmm_obca_t h, int32_t* iters_out) {
   if (noise_exhausted(p, 1)) return fail(h, PIADMM_E_STATE, "obca_plan_step: noise step index exhausted");
   if (loop_exhausted(p, 1)) return fail(h, PIADMM_E_STATE, "obca_plan_step: loop step index exhausted");
   if (const char* why = delay_refusal(p, 1)) return fail(h, PIADMM_E_STATE, std::string("obca_plan_step: ") + why);
+  if (const char* why = ledger_refusal(p, 1)) return fail(h, PIADMM_E_STATE, std::string("obca_plan_step: ") + why);
   // i_iter > max_admm_iter stops a scenario: at most the largest max_admm_iter + 1 iterates in a step
   while (p->n_act > 0 && p->i_iter <= p->max_iter_all) {
     if (int rc = piadmm_obca_plan_iterate(h, nullptr)) return rc;

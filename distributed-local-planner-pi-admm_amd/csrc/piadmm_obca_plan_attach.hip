@@ -335,6 +335,10 @@ int clock_shift(piadmm_obca_t h, piadmm_obca_plan_s* p) {
     // the state each scenario reached over init_state of both copies, before the tick rebuilds the list
     if (int rc = loop_set_init(h, p)) return rc;
   }
+  if (p->lg.on) {
+    // the open records take the step while ck.list and the clocks are still the closing step's
+    if (int rc = ledger_step(h, p)) return rc;
+  }
   // the mirror: the tick is deterministic, nothing is read back for it
   std::vector<int> next = c.host;
   int n_alive = 0;
@@ -353,6 +357,7 @@ int clock_shift(piadmm_obca_t h, piadmm_obca_plan_s* p) {
     if (int rc = trace_append(h, p, p->tr.rows + 1)) return rc;
   }
   OWN_HIP(h, hipStreamSynchronize(h->stream));
+  if (p->lg.on) ledger_stepped(p, next);
   c.host.swap(next);
   c.cur = 1 - c.cur;
   c.n_list = n_alive;
@@ -583,6 +588,8 @@ int32_t piadmm_obca_clock_plan(piadmm_obca_t h, int32_t mode, const int32_t* clo
     return fail(h, PIADMM_E_STATE, "obca_clock_plan: feedback is attached (obca_feedback_plan: the tape has no per-scenario clocks)");
   if (mode == 1 && p->dl.on)
     return fail(h, PIADMM_E_STATE, "obca_clock_plan: the delay is attached (obca_delay_plan: it counts the plan's steps, not per-scenario clocks)");
+  if (p->lg.on)
+    return fail(h, PIADMM_E_STATE, "obca_clock_plan: a ledger is attached (obca_ledger_begin: its records open and close by the clocks; end it first)");
   if (p->lp.on)
     return fail(h, PIADMM_E_STATE, "obca_clock_plan: the loop is attached (obca_loop_plan: its step index is the tenant's clock; detach it first)");
   if (p->i_iter != 0) return fail(h, PIADMM_E_STATE, "obca_clock_plan: only at a step boundary (an MPC step is open)");
@@ -659,8 +666,14 @@ int32_t piadmm_obca_clock_admit(piadmm_obca_t h, int32_t m, const int32_t* slots
     for (int k = 0; k < m; ++k)
       if ((int64_t)p->lp.k0 + clock[2 * (size_t)k] >= ((int64_t)1 << 31))
         return fail(h, PIADMM_E_STATE, "obca_clock_admit: row " + std::to_string(k) + ": loop step index exhausted");
+  if (const char* why = ledger_replace_refusal(p, m, slots, false))
+    return fail(h, PIADMM_E_STATE, std::string("obca_clock_admit: ") + why);
   OWN_HIP(h, hipSetDevice(h->device));
   OWN_HIP(h, hipStreamSynchronize(h->stream));
+  if (p->lg.on) {
+    // the tenants that leave: their records, before anything of their slots is overwritten
+    if (int rc = ledger_close(h, p, m, slots, 2, false)) return rc;
+  }
   const size_t D = sizeof(double), ref_one = (size_t)2 * n_ref * 5;
   for (int k = 0; k < m; ++k) {
     const size_t s = (size_t)slots[k], K = (size_t)k;
@@ -704,6 +717,10 @@ int32_t piadmm_obca_clock_admit(piadmm_obca_t h, int32_t m, const int32_t* slots
       return rc;
     }
     OWN_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  if (p->lg.on) {
+    // a fresh record for every admitted tenant, at its clock and entry state
+    if (int rc = ledger_open(h, p, m, slots)) return rc;
   }
   return 0;
 }

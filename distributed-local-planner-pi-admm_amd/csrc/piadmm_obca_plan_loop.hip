@@ -260,8 +260,14 @@ int32_t piadmm_obca_loop_admit(piadmm_obca_t h, int32_t m, const int32_t* slots,
   if (plant && l.plant_rows != n) return fail(h, PIADMM_E_STATE, "obca_loop_admit: plant needs a loop with a plant row per scenario");
   if (noise && l.noise_rows != n) return fail(h, PIADMM_E_STATE, "obca_loop_admit: noise needs a loop with a noise row per scenario");
   if (delay && l.delay_rows != n) return fail(h, PIADMM_E_STATE, "obca_loop_admit: delay needs a loop with a delay row per scenario");
+  if (const char* why = ledger_replace_refusal(p, m, slots, true)) return fail(h, PIADMM_E_STATE, who + ": " + why);
   OWN_HIP(h, hipSetDevice(h->device));
   OWN_HIP(h, hipStreamSynchronize(h->stream));
+  if (p->lg.on) {
+    // a tenant that has closed a step leaves under its old stream id; one that has not (the second half
+    // of an admission) keeps its record, opened again below under the new one
+    if (int rc = ledger_close(h, p, m, slots, 2, true)) return rc;
+  }
   const size_t D = sizeof(double);
   for (int k = 0; k < m; ++k) {
     const size_t s = (size_t)slots[k], K = (size_t)k;
@@ -276,6 +282,9 @@ int32_t piadmm_obca_loop_admit(piadmm_obca_t h, int32_t m, const int32_t* slots,
     return rc;
   }
   OWN_HIP(h, hipStreamSynchronize(h->stream));
+  if (p->lg.on) {
+    if (int rc = ledger_open(h, p, m, slots)) return rc;
+  }
   return 0;
 }
 

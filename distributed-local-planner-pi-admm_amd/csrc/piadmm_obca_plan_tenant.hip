@@ -330,6 +330,8 @@ int32_t piadmm_obca_tenant_import(piadmm_obca_t h, int32_t m, const int32_t* slo
   if (order != p->ord.on)
     return fail(h, PIADMM_E_STATE, order ? "obca_tenant_import: the blob carries the order's record, the plan has no order attached"
                                           : "obca_tenant_import: the plan has the order attached, the blob carries no record");
+  if (const char* why = ledger_replace_refusal(p, m, slots, false))
+    return fail(h, PIADMM_E_STATE, std::string("obca_tenant_import: ") + why);
   OWN_HIP(h, hipSetDevice(h->device));
   const bool gains_travel = law && p->du.rows == n;
   if (law && !gains_travel) {
@@ -364,6 +366,10 @@ int32_t piadmm_obca_tenant_import(piadmm_obca_t h, int32_t m, const int32_t* slo
     }
   }
   if (int rc = stage_ensure(h, p, (size_t)body, m)) return rc;
+  if (p->lg.on) {
+    // the tenants that leave: their records, before k_plan_import overwrites their slots
+    if (int rc = ledger_close(h, p, m, slots, 3, false)) return rc;
+  }
   int* d_list = reinterpret_cast<int*>(p->stg.buf + body);
   OWN_HIP(h, hipMemcpyAsync(p->stg.buf, in + PIADMM_OBCA_TENANT_HEADER, (size_t)body, hipMemcpyHostToDevice, h->stream));
   OWN_HIP(h, hipMemcpyAsync(d_list, slots, (size_t)m * sizeof(int), hipMemcpyHostToDevice, h->stream));
@@ -394,6 +400,10 @@ int32_t piadmm_obca_tenant_import(piadmm_obca_t h, int32_t m, const int32_t* slo
       return rc;
     }
     OWN_HIP(h, hipStreamSynchronize(h->stream));
+  }
+  if (p->lg.on) {
+    // an imported tenant starts a fresh record (the blob carries none); a retired one holds no tenant
+    if (int rc = ledger_open(h, p, m, slots)) return rc;
   }
   return 0;
 }

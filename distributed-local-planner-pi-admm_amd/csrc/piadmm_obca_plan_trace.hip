@@ -51,69 +51,19 @@ __global__ void __launch_bounds__(64 * PW) k_plan_trace(int n, int row, const do
   }
 }
 
-// One wave per scenario: the exact minimum distance between the two vehicles' rectangles
-// (generate_vehicle_vertices, util.py:34-42) at the state pair st[2][5] = states + s * stride, for
-// two box sets at once: the plain boxes (centre x, y) and the delay-tightened ones the planner
-// constrains (compute_square_halfspaces_ca_prob, util.py:70-101: each centre moved as halfspaces()
-// above moves it; prob = 0 moves nothing, so both outputs are the plain value).  The distance is 0
-// when no edge normal of either rectangle separates them (SAT over the 4 axes), else the minimum of
-// the 32 vertex-to-edge distances.  Lane = set * 32 + dir * 16 + vertex * 4 + edge: a vertex of
-// vehicle `dir` against an edge of the other vehicle, whose normal (edge & 1: the lateral one) is
-// the lane's SAT axis.  piadmm.obca.clearance is the same statements on the host; products and
-// sums are kept apart (no contraction).  With `summary`, lane 0 keeps the scenario's running
-// minima: row 0 starts them, a later row replaces the plain minimum only when it is smaller, so
-// the row kept is the first at which the minimum was reached.
+// One wave per scenario: clearance_pair (csrc/piadmm_obca_plan.h) at the state pair st[2][5] = states +
+// s * stride, the plain and the tightened clearance into out[s].  With `summary`, lane 0 keeps the
+// scenario's running minima: row 0 starts them, a later row replaces the plain minimum only when it
+// is smaller, so the row kept is the first at which the minimum was reached.
 __global__ void __launch_bounds__(64 * PW) k_plan_clearance(int n, const double* __restrict__ states, int stride,
                                                             const int* __restrict__ prob, double sigd, int row,
                                                             double* __restrict__ out,
                                                             double* __restrict__ summary) {
-#pragma clang fp contract(off)
   const int lane = threadIdx.x & 63;
   const int s = blockIdx.x * PW + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (s >= n) return;
-  const double* st = states + (size_t)s * stride;
-  const int pr = prob[s];
-  const int set = lane >> 5, dir = (lane >> 4) & 1, vi = (lane >> 2) & 3, ej = lane & 3;
-  constexpr double HL = LENGTH / 2, HW = WIDTH / 2;
-  // box a owns the lane's vertex, box o its edge
-  const double* sa = st + dir * 5;
-  const double* so = st + (1 - dir) * 5;
-  const double ca = cos(sa[3]), sna = sin(sa[3]), co = cos(so[3]), sno = sin(so[3]);
-  double ax = sa[0], ay = sa[1], ox = so[0], oy = so[1];
-  if (set == 1 && pr) {
-    const double va = sa[2], vo = so[2];
-    const double qax = VAR_DELAY * va * ca, qay = VAR_DELAY * va * sna;
-    const double qox = VAR_DELAY * vo * co, qoy = VAR_DELAY * vo * sno;
-    const double dax = AVG_DELAY * va * ca + sigd * (qax * qax), day = AVG_DELAY * va * sna + sigd * (qay * qay);
-    const double dox = AVG_DELAY * vo * co + sigd * (qox * qox), doy = AVG_DELAY * vo * sno + sigd * (qoy * qoy);
-    ax = ax + dax;  ay = ay + day;
-    ox = ox + dox;  oy = oy + doy;
-  }
-  // vertex i = centre + sl e + sw n: (+, +), (+, -), (-, -), (-, +)
-  const double pl = vi < 2 ? HL : -HL, pw = (vi == 0 || vi == 3) ? HW : -HW;
-  const double px = ax + pl * ca - pw * sna, py = ay + pl * sna + pw * ca;
-  const int e1 = (ej + 1) & 3;
-  const double al = ej < 2 ? HL : -HL, aw = (ej == 0 || ej == 3) ? HW : -HW;
-  const double bl = e1 < 2 ? HL : -HL, bw = (e1 == 0 || e1 == 3) ? HW : -HW;
-  const double e0x = ox + al * co - aw * sno, e0y = oy + al * sno + aw * co;
-  const double e1x = ox + bl * co - bw * sno, e1y = oy + bl * sno + bw * co;
-  const double abx = e1x - e0x, aby = e1y - e0y, apx = px - e0x, apy = py - e0y;
-  double t = (apx * abx + apy * aby) / (abx * abx + aby * aby);
-  t = fmin(fmax(t, 0.0), 1.0);
-  const double rx = apx - t * abx, ry = apy - t * aby;
-  const double dist = sqrt(rx * rx + ry * ry);
-  // SAT along the edge's normal: |centre distance| against the two half extents
-  const bool lateral = ej & 1;
-  const double ux = lateral ? -sno : co, uy = lateral ? co : sno;
-  const double cdx = ax - ox, cdy = ay - oy;
-  const double pc = fabs(cdx * ux + cdy * uy);
-  const double pe = fabs(ca * ux + sna * uy), pn = fabs(ca * uy - sna * ux);
-  const double gap = pc - ((lateral ? HW : HL) + (HL * pe + HW * pn));
-  // every lane is active here: the reductions are DPP scans over the whole wave
-  const double inf = __builtin_inf();
-  const double g0 = pd::wmax(set == 0 ? gap : -inf), g1 = pd::wmax(set == 1 ? gap : -inf);
-  const double d0 = pd::wmin(set == 0 ? dist : inf), d1 = pd::wmin(set == 1 ? dist : inf);
-  const double plain = g0 > 0.0 ? d0 : 0.0, tight = g1 > 0.0 ? d1 : 0.0;
+  double plain, tight;
+  clearance_pair(states + (size_t)s * stride, prob[s], sigd, lane, plain, tight);
   if (lane == 0) {
     out[(size_t)s * 2] = plain;
     out[(size_t)s * 2 + 1] = tight;
@@ -571,15 +521,10 @@ int trace_append(piadmm_obca_t h, piadmm_obca_plan_s* p, int row) {
 
 namespace {
 size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+}  // namespace
 
-struct stats_out {
-  piadmm_obca_stats_t* stats;
-  int64_t* hist;
-  double* row_min;
-  int32_t *row_arg, *row_below, *worst;
-};
-
-// what both statistics calls check of their arguments, before any device call
+namespace obca_plan {
+// what every statistics call checks of its arguments, before any device call
 int stats_args_check(piadmm_obca_t h, const std::string& who, int n, const double* edges, int B, int K,
                      const stats_out& o) {
   if (B < 1 || B > PIADMM_OBCA_STATS_EDGES) return fail(h, PIADMM_E_ARG, who + ": 1 <= B <= 64");
@@ -661,7 +606,9 @@ int stats_run(piadmm_obca_t h, int R, int n, const double* d_clear, const double
   std::memcpy(o.worst, back.data() + o_worst, Kz * 4);
   return 0;
 }
+}  // namespace obca_plan
 
+namespace {
 // the offsets of a gathered record's segments, in bytes (include/piadmm.h)
 struct gather_layout {
   int64_t states, clear, primal, dual, summary, iters, mask, lamb, bytes;
@@ -715,6 +662,7 @@ int32_t piadmm_obca_trace_begin(piadmm_obca_t h, int32_t cap_steps, int32_t flag
   if (int rc = open_plan(h, &p, "obca_trace_begin")) return rc;
   if (cap_steps < 1 || cap_steps > (1 << 20)) return fail(h, PIADMM_E_ARG, "obca_trace_begin: 1 <= cap_steps <= 2^20");
   if (flags & ~PIADMM_OBCA_TRACE_LAMBDA) return fail(h, PIADMM_E_ARG, "obca_trace_begin: unknown flag bits");
+  if (p->lg.on) return fail(h, PIADMM_E_STATE, "obca_trace_begin: a ledger is attached (obca_ledger_end: the two do not record together)");
   if (p->i_iter != 0) return fail(h, PIADMM_E_STATE, "obca_trace_begin: only at a step boundary (an MPC step is open)");
   OWN_HIP(h, hipSetDevice(h->device));
   OWN_HIP(h, hipStreamSynchronize(h->stream));

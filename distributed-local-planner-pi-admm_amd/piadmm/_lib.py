@@ -163,6 +163,11 @@ SYMBOLS = [
     ("piadmm_obca_loop_admit", c_i32, [_H, c_i32, _ip, _dp, _dp, _dp, _P(ctypes.c_int64)]),
     ("piadmm_obca_loop_draw", c_i32, [_H, c_i32, _ip, _dp, c_i32, _dp, c_i32, _P(ctypes.c_int64), ctypes.c_uint64, c_i32,
                                       _dp, _dp]),
+    ("piadmm_obca_ledger_begin", c_i32, [_H, c_i32, c_i32]),
+    ("piadmm_obca_ledger_get", c_i32, [_H, c_i32, ctypes.c_void_p, ctypes.c_int64]),
+    ("piadmm_obca_ledger_clear", c_i32, [_H]),
+    ("piadmm_obca_ledger_stats", c_i32, [_H, _dp, c_i32, c_i32, _P(ObcaStatsC), _P(ctypes.c_int64), _ip]),
+    ("piadmm_obca_ledger_end", c_i32, [_H]),
 ]
 
 # PIADMM_OBCA_FLEET_PAR: doubles per parameter row of piadmm_obca_fleet_begin
@@ -175,6 +180,9 @@ FEEDBACK_PAR = 16
 NOISE_PAR = 22
 # PIADMM_OBCA_DELAY_PAR: doubles per delay row of piadmm_obca_delay_plan / piadmm_obca_delay_tau
 DELAY_PAR = 8
+
+# PIADMM_OBCA_LEDGER_REC: bytes per record of piadmm_obca_ledger_get
+LEDGER_REC = 176
 
 # PIADMM_OBCA_STATS_EDGES / _WORST: the most edges and the most worst scenarios of the statistics calls
 STATS_EDGES = 64

@@ -24,6 +24,7 @@ from .feedback import *  # noqa: F401,F403
 from .stats import *  # noqa: F401,F403
 from .tenant import *  # noqa: F401,F403
 from .loop import *  # noqa: F401,F403
+from .ledger import *  # noqa: F401,F403
 from .batch import *  # noqa: F401,F403
 from .planner import *  # noqa: F401,F403
 from .device import *  # noqa: F401,F403

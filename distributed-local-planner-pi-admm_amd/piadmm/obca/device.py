@@ -8,6 +8,7 @@ from .._lib import DELAY_PAR, DUAL_PAR, FEEDBACK_PAR, FLEET_PAR, NOISE_PAR
 from .attach import clock_rows, clock_tick, dual_rows
 from .batch import OBCAEdgeResult, OBCAResult
 from .feedback import DELAY_GET, NOISE_GET, _draw_rows, delay_row, feedback_args, noise_row
+from .ledger import LEDGER_GET, LEDGER_REC, ledger_unpack
 from .loop import LOOP_GET
 from .model import (DT, EDGE_OUT, EDGE_REC, FLEET_ROW, N_HORZ, NT, NU, NX, OUT, REC, _spec, executed_path, ref_traj_gen,
                     seeded_bar_state)
@@ -82,7 +83,13 @@ class OBCADevicePlanner:
     open step, `loop_tau()`.  plant one row or n (None: the nominal plant), noise / delay one row or
     n (None: that kind is absent).  `set_loop` / `clear_loop` attach and detach it at a step boundary,
     `admit(..., loop=dict(plant=, noise=, delay=, streams=))` gives an admitted tenant its own rows and
-    stream; the tenant records, `compact`, `save` and `load` carry it."""
+    stream; the tenant records, `compact`, `save` and `load` carry it.
+
+    With clock= the tenant ledger records a service (piadmm_obca_ledger_begin; `OBCALedger` is the
+    statement): `ledger_begin(cap)` opens a record per alive tenant, every closed step updates it on the
+    device, and a tenant that retires or that `admit` / `import_tenants` replace is appended --
+    `ledger_records`, `ledger_running`, `ledger_stats`, `ledger_clear`, `ledger_end`.  Not together
+    with a trace; `admit` and `import_tenants` work under it."""
 
     def __init__(self, batch, n_scenarios, prob=1, t_step0=0, rho=1.0, min_dis=0.1, max_admm_iter=50,
                  primal_thres=0.01, dual_thres=0.01, round_decimals=4, start=1, update_lamb_ij=0, max_iter=60,
@@ -769,6 +776,50 @@ class OBCADevicePlanner:
         """(statistics, the gathered record of the K worst scenarios by plain minimum clearance)."""
         st = self.trace_stats(edges, worst=K)
         return st, self.trace_gather(st.worst)
+
+    # -- the tenant ledger (piadmm_obca_ledger_begin): a record per tenant that survives retirement and admission --
+    def ledger_begin(self, cap_tenants, flags=0):
+        """Attach a ledger of cap_tenants records (a clocked plan at a step boundary, without a trace):
+        every alive slot's tenant takes its slot number as its id, the id counter starts at n."""
+        self._check(self._lib.piadmm_obca_ledger_begin(self.batch._h, int(cap_tenants), int(flags)))
+
+    def _ledger_get(self, what, count):
+        code, dt = LEDGER_GET[what]
+        out = np.zeros(count, dt)
+        self._check(self._lib.piadmm_obca_ledger_get(self.batch._h, code, out.ctypes.data, out.nbytes))
+        return out
+
+    def ledger_count(self):
+        return int(self._ledger_get("COUNT", 1)[0])
+
+    def ledger_next_id(self):
+        return int(self._ledger_get("NEXT_ID", 1)[0])
+
+    def ledger_records(self):
+        """The appended records, in the order of appending (`ledger_unpack` of the RECORDS item)."""
+        return ledger_unpack(self._ledger_get("RECORDS", self.ledger_count() * LEDGER_REC))
+
+    def ledger_running(self):
+        """The open record of every slot (the RUNNING item): reason 0, id -1 where the slot holds no tenant."""
+        return ledger_unpack(self._ledger_get("RUNNING", self.n * LEDGER_REC))
+
+    def ledger_clear(self):
+        """count = 0, so that a service drains the records and goes on; ids keep counting."""
+        self._check(self._lib.piadmm_obca_ledger_clear(self.batch._h))
+
+    def ledger_stats(self, edges, worst=1) -> OBCAFleetStats:
+        """The statistics of the appended records, reduced on the device in place
+        (piadmm_obca_ledger_stats): `worst` holds positions in the ledger; the rows' results of the
+        R = 1 view are not brought back (row_min, row_arg, row_below stay zero).  `ledger_stats_host`
+        on `ledger_records()` is the same statement."""
+        def call(edges_p, B, K, st, hist, row_min, row_arg, row_below, worst_p):
+            return self._lib.piadmm_obca_ledger_stats(self.batch._h, edges_p, B, K, st, hist, worst_p)
+        rc, out = _stats_call(call, 0, 1, edges, worst)
+        self._check(rc)
+        return out
+
+    def ledger_end(self):
+        self._check(self._lib.piadmm_obca_ledger_end(self.batch._h))
 
     def trace(self, keep_lambda=True):
         """The attached trace as an OBCATrace."""

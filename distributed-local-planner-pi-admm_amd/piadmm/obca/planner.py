@@ -4,10 +4,12 @@ import numpy as np
 from .. import _lib
 from .attach import clock_rows, clock_tick, dual_rows, lambda_update_pi, shift_dual
 from .feedback import NOISE_K_MAX, delay_args, delay_tau, feedback_args, noise_args, noise_tape, propagate
+from .ledger import LEDGER_ADMITTED, LEDGER_IMPORTED, LEDGER_RETIRED, OBCALedger
 from .loop import loop_args, loop_draw
-from .model import (DT, EDGE_WRITES_ITERATE, N_HORZ, NT, NU, NX, _per_scenario, _spec, bar_state_update, check_converge,
+from .model import (DT, EDGE_WRITES_ITERATE, FLEET_ROW, N_HORZ, NT, NU, NX, _per_scenario, _spec, bar_state_update, check_converge,
                     edge_record, executed_path, iterate_next_state, local_record, ref_traj_gen, seeded_bar_state)
 from .stats import OBCARunRecord
+from .tenant import tenant_unpack, unpack_state
 
 
 def _scenario_refs(pl, specs, ref_traj):
@@ -119,13 +121,18 @@ class OBCAPlanner:
     closes, for the scenarios it ran, with init_state = propagate(the closing step's init_state, the
     first control, plant[s], the noise row of stream streams[s] at step index k0 + c); with delay rows
     the open step's latency of an alive scenario is `delay_tau`'s at k0 + c (`loop_tau`), a retired
-    one's stays.  OBCADevicePlanner takes the same argument (piadmm_obca_loop_plan)."""
+    one's stays.  OBCADevicePlanner takes the same argument (piadmm_obca_loop_plan).
+
+    ledger: with clock=, True keeps the tenant ledger of piadmm_obca_ledger_begin in NumPy (`ledger`, an
+    OBCALedger; `ledger_cap` bounds it): a record per tenant, opened at its clock and entry state, updated
+    by every step it closes, appended when its clock retires it (reason 1) or `admit` / `import_tenants`
+    replace it (2 / 3).  `set_ledger` / `clear_ledger` attach and detach it at a step boundary."""
 
     def __init__(self, batch, n_scenarios, prob=1, t_step0=0, rho=1.0, min_dis=0.1, max_admm_iter=50,
                  primal_thres=0.01, dual_thres=0.01, round_decimals=4, start=1, update_lamb_ij=0, max_iter=60,
                  conv_thres=0.1, on_stage=None, max_x=150.0, max_y=20.0, r=1e4, q=1e5, x_bound=1000.0,
                  mu_max=100000.0, g_max=1000.0, ref_traj=None, specs=None, dual=None, clock=None, feedback=None,
-                 noise=None, delay=None, loop=None):
+                 noise=None, delay=None, loop=None, ledger=False, ledger_cap=None):
         _, _, rows, t0 = _planner_init(
             self, batch, n_scenarios, prob, t_step0, primal_thres, dual_thres, update_lamb_ij,
             on_stage or (lambda name, inputs, outputs: None), specs, ref_traj, clock, rho=rho, min_dis=min_dis,
@@ -156,8 +163,111 @@ class OBCAPlanner:
         self.loop = None
         if loop is not None:
             self.set_loop(**loop)
+        self.ledger = None
+        if ledger:
+            self.set_ledger(ledger_cap)
         self.record = OBCARunRecord()
         self.record.state_record.append(np.stack(self.init_state))
+
+    def _stream(self, s):
+        return -1 if self.loop is None else int(self.loop["streams"][s])
+
+    def set_ledger(self, cap=None):
+        """Attach the ledger (see the class; a clock must be attached, as piadmm_obca_ledger_begin
+        refuses otherwise): every alive slot's tenant takes its slot number, the id counter starts at n."""
+        if self.clock is None:
+            err = _lib.PiadmmError("obca_ledger_begin: no clock attached")
+            err.code = _lib.E_STATE
+            raise err
+        self.ledger = OBCALedger(self.n, cap)
+        for s in range(self.n):
+            if self.clock[s, 2]:
+                self.ledger.open(s, s, int(self.clock[s, 0]), self.init_state[s], self.prob[s], self._stream(s))
+
+    def clear_ledger(self):
+        self.ledger = None
+
+    def _replace(self, slots, reason, fill):
+        """What an admission and an import share: the alive tenants of `slots` leave the ledger's open
+        records in the order of `slots`, `fill(k, s)` puts the new tenant into slot s, and every new alive
+        tenant takes the next id, in that order."""
+        slots = [int(s) for s in slots]
+        assert self.clock is not None and len(set(slots)) == len(slots)
+        if self.ledger is not None:
+            leaving = [s for s in slots if self.ledger.running[s]["id"] >= 0 and self.clock[s, 2]]
+            if self.ledger.cap is not None and self.ledger.count + len(leaving) > self.ledger.cap:
+                raise ValueError("ledger full")
+            for s in leaving:
+                self.ledger.close(s, reason, self.t_step, self._stream(s))
+        self.bar_prev, self.init_state, self.prob = list(self.bar_prev), list(self.init_state), list(self.prob)
+        if self.loop is not None:
+            self.loop = dict(self.loop, streams=self.loop["streams"].copy())      # the caller's array stays as it is
+        for k, s in enumerate(slots):
+            fill(k, s)
+        if self.loop is not None:
+            self._loop_open()
+        if self.ledger is not None:
+            for s in slots:
+                if self.clock[s, 2]:
+                    self.ledger.admit(s, int(self.clock[s, 0]), self.init_state[s], self.prob[s], self._stream(s))
+                else:
+                    self.ledger.running[s]["id"] = -1
+
+    def admit(self, slots, clock, specs=None, bar=None, init_state=None, ref=None, prob=None, streams=None):
+        """New tenants into `slots` of the clocked planner, as OBCADevicePlanner.admit: clock m x 2 rows
+        (c0, len); with specs= a missing ref is the spec's reference, a missing bar the state seeded at
+        the tenant's c0 and a missing init_state the executed path there; ref m x 2 x n_ref x 5, prob m,
+        streams m stream ids of the loop -- None keeps what the slot has."""
+        clock = np.asarray(clock, np.int32).reshape(len(slots), 2)
+        specs = None if specs is None else [_spec(sp) for sp in specs]
+        self.ref_traj_s = np.array(self.ref_traj_s)
+        self.ref_traj = None
+
+        def fill(k, s):
+            c0, sp = int(clock[k, 0]), None if specs is None else specs[k]
+            if prob is not None:
+                self.prob[s] = int(np.broadcast_to(prob, (len(slots),))[k])
+            if ref is not None or sp is not None:
+                self.ref_traj_s[s] = np.stack(ref_traj_gen(sp)) if ref is None else ref[k]
+            if bar is not None or sp is not None:
+                self.bar_prev[s] = seeded_bar_state(c0, self.prob[s], spec=sp) if bar is None else self._copy(bar[k])
+            if init_state is not None or sp is not None:
+                self.init_state[s] = (np.stack([executed_path(v, c0 * DT, sp) for v in (0, 1)]) if init_state is None
+                                      else np.array(init_state[k], np.float64))
+            if self.specs is not None and sp is not None:
+                self.specs[s] = sp
+            self.lamb_last[s] = np.zeros((2, NT, 9))
+            if self.dual_par is not None:
+                self.dual_S[s], self.dual_D[s] = self.bar_prev[s]["lamb_bar"].copy(), np.zeros((2, NT, 9))
+            if streams is not None:
+                self.loop["streams"][s] = int(streams[k])
+            self.clock[s] = (c0, int(clock[k, 1]), 1)
+        self._replace(slots, LEDGER_ADMITTED, fill)
+
+    def import_tenants(self, slots, tenants):
+        """The tenants of a blob of OBCADevicePlanner.export_tenants into `slots`: the state, the
+        reference, prob, the thresholds, the parameter row, the clock and, with the loop, the stream id
+        of each; a retired tenant stays retired.  The dual law's integrator and the loop's rows do not travel here."""
+        t = tenant_unpack(tenants)
+        assert t["m"] == len(slots) and t["n_ref"] == self.n_ref
+        self.ref_traj_s = np.array(self.ref_traj_s)
+        self.ref_traj = None
+
+        def fill(k, s):
+            self.bar_prev[s], self.init_state[s] = unpack_state(t["STATE"][k])
+            self.prob[s] = int(t["PROB"][k])
+            self.ref_traj_s[s] = t["REF"][k]
+            self.primal_thres[s], self.dual_thres[s] = t["PRIMAL_THRES"][k], t["DUAL_THRES"][k]
+            for j, name in enumerate(FLEET_ROW):
+                col = getattr(self, name + "_s").astype(np.float64)
+                col[s] = t["PAR"][k, j]
+                setattr(self, name + "_s", col)
+            self.lamb_last[s] = t["LAMBDA"][k].reshape(2, NT, 9).copy()
+            if self.loop is not None and t["loop"]:
+                self.loop["streams"][s] = int(t["LOOP_STREAMS"][k])
+            c, ln = int(t["CLOCK"][k, 0]), int(t["CLOCK"][k, 1])
+            self.clock[s] = (c, ln, 1 if c + N_HORZ <= ln else 0)
+        self._replace(slots, LEDGER_IMPORTED, fill)
 
     def set_loop(self, plant=None, noise=None, delay=None, streams=None, seed=0, k0=0):
         """Attach the loop (see the class; a clock must be attached and neither feedback nor delay, as
@@ -270,6 +380,11 @@ class OBCAPlanner:
             ran = [s for s in range(n) if self.clock[s, 2]]
             assert ran, "no scenario alive"
             t_of = [int(c) for c in self.clock[:, 0]]
+        if self.ledger is not None and self.ledger.cap is not None:
+            # before anything changes, as piadmm_obca_plan_step refuses: every tenant the tick retires needs a place
+            out = sum(1 for s in ran if self.clock[s, 0] + 1 + N_HORZ > self.clock[s, 1])
+            if self.ledger.count + out > self.ledger.cap:
+                raise ValueError("ledger full")
         tau = None if self.delay is None else self.delay_tau()
         if self.loop is not None:
             assert (self.loop["k0"] + self.clock[ran, 0] + 1 < NOISE_K_MAX).all(), "loop step index exhausted"
@@ -282,6 +397,7 @@ class OBCAPlanner:
         U0 = [None] * n
         iters = np.zeros(n, int)
         shift_in = [None] * n
+        masks, resid = np.zeros((n, 2), np.int64), np.zeros((n, 2))      # what the ledger keeps of the step
         active = list(ran)
         i_iter = 0
         while active:
@@ -358,8 +474,13 @@ class OBCAPlanner:
                           dict(primal=primal, dual=dual, stop=stop))
             nxt = []
             for k, s in enumerate(active):
+                for v in (0, 1):
+                    masks[s, 0] |= 1 << int(res.status[2 * k + v])
+                for c in np.asarray(eres.status[k]).reshape(-1):
+                    masks[s, 1] |= 1 << int(c)
                 if stop[k]:
                     iters[s] = i_iter
+                    resid[s] = primal[k], dual[k]
                     shift_in[s] = bar_prev[s]           # :87: the previous iterate's bar_state (B16)
                     if self.dual_par is not None:
                         self.dual_S[s], self.dual_D[s] = dual_before[s]
@@ -402,6 +523,14 @@ class OBCAPlanner:
         self.record.state_record.append(np.stack(self.init_state))
         self.record.iter_num_record.append(iters)
         self.record.lambda_record.append(np.stack(self.lamb_last))
+        if self.ledger is not None:
+            # the open records take the step at the clock of the new state; the tick's retirees leave, ascending
+            out = [s for s in ran if self.clock[s, 0] + 1 + N_HORZ > self.clock[s, 1]]
+            for s in ran:
+                self.ledger.step(s, int(self.clock[s, 0]) + 1, self.init_state[s], self.prob[s], iters[s], masks[s, 0],
+                                 masks[s, 1], resid[s, 0], resid[s, 1], self._stream(s))
+            for s in out:
+                self.ledger.close(s, LEDGER_RETIRED, self.t_step)
         if self.clock is not None:
             self.clock = clock_tick(self.clock, self.clock[:, 2])
         if self.loop is not None:

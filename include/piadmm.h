@@ -1203,6 +1203,94 @@ int32_t piadmm_obca_stats_trace(piadmm_obca_t h, const double* edges /* B */, in
 int32_t piadmm_obca_gather_trace_bytes(piadmm_obca_t h, int32_t m, int64_t* bytes);
 int32_t piadmm_obca_gather_trace(piadmm_obca_t h, int32_t m, const int32_t* slots /* m */, void* blob, int64_t bytes);
 
+/* ---- the tenant ledger: risk records that survive retirement and admission ----------------------
+ * A trace is indexed by plan step and slot: it costs O(steps x n) device memory, ends at cap_steps and
+ * would mix two tenants of one slot, so admission and import refuse it.  The ledger is the record a
+ * service keeps instead: one small record per tenant, kept on the device while the tenant runs,
+ * appended when the tenant leaves its slot, and reducible by the statistics above.  Opt-in, the fifth
+ * attachment of a clocked plan (with or without the loop, the dual law and the order): without it
+ * every call issues exactly the launches it issued before and computes the same bits.
+ *
+ * A record is PIADMM_OBCA_LEDGER_REC = 176 bytes, 22 words of 8 bytes; of two int32 in a word the
+ * first is the low half:
+ *   word 0        int64   the tenant's id
+ *   word 1        int64   the stream id of the loop it ran under (-1 without the loop)
+ *   word 2        int32   the slot; int32 the reason: 1 retired by its clock, 2 replaced by an admission,
+ *                         3 replaced by an import (0 in an open record)
+ *   word 3        int32   c_first, the tenant's clock when its record was opened; int32 steps closed since
+ *   word 4        fp64    the minimum plain clearance over the entry state and every state a closed step left
+ *   word 5        fp64    the minimum tightened clearance over the same states
+ *   word 6        int32   c_min, the tenant's clock at the state where the plain minimum was first reached
+ *                         (strict <, as the trace's summary); int32 the largest stop iterate
+ *   word 7        int64   the sum of the stop iterates
+ *   word 8        int32   the OR of the local status masks; int32 the OR of the edge status masks
+ *   words 9, 10   fp64    the primal and the dual residual of the last closed step's stopping iterate
+ *                         (0 with steps = 0)
+ *   word 11       int32   the plan's T_STEP (PIADMM_OBCA_PLAN_GET_T_STEP) when the call that appended the
+ *                         record was made (-1 in an open record); int32 0
+ *   words 12-21   fp64    init_state[2][5] after the last closed step (the entry state with steps = 0)
+ * The clearances are those of piadmm_obca_clearance at the plan's prob[slot] (clearance_pair,
+ * csrc/piadmm_obca_plan.h: the statements k_plan_clearance runs, the same bits).
+ *
+ * piadmm_obca_ledger_begin attaches a ledger of cap_tenants records; a second call replaces the first.
+ * PIADMM_E_ARG before any device call: 1 <= cap_tenants <= 2^20, flags = 0.  PIADMM_E_STATE: no open
+ * plan, no clock attached, a trace attached (piadmm_obca_trace_begin refuses a plan with a ledger
+ * likewise), an MPC step open.  It opens a record for every alive slot (k_ledger_open): id = the slot
+ * number, c_first = the slot's clock, the clearances of its init_state start the minima.  A slot that
+ * is not alive holds no tenant: id -1, never appended.  The id counter starts at n.  While attached:
+ *   closing a step   piadmm_obca_plan_shift (called directly, by piadmm_obca_plan_step or by a run)
+ *                    updates the open record of every scenario the step ran (k_ledger_step, one launch,
+ *                    after the shift -- under the loop after `next` has gone over init_state -- and
+ *                    before the tick): the new init_state, its two clearances, the stop iterate, both
+ *                    masks, the residuals, the stream id.  A scenario this shift retires is appended
+ *                    with reason 1; the retirees of one shift are appended ascending by slot at
+ *                    positions count, count + 1, ...: a position is the host's count plus the number of
+ *                    retirees before the scenario in the list the step ran, counted on the device as
+ *                    k_plan_order counts a rank.  No atomic decides a position and nothing is read back.
+ *   the limit        the host mirrors count from its mirror of the clocks; a shift, step or run that
+ *                    would take count above cap_tenants is PIADMM_E_STATE ("ledger full") before any launch
+ *   admission        piadmm_obca_clock_admit and piadmm_obca_tenant_import append, before a slot is
+ *                    overwritten, the open record of its alive tenant (k_ledger_close; reason 2 / 3,
+ *                    in the order of `slots`, with the stream id it ran under); a retired tenant was
+ *                    appended already.  Each new alive tenant then takes the next id, in the order of
+ *                    `slots`, and a fresh record opens at its clock and entry state (k_ledger_open); an
+ *                    imported tenant that is retired holds no record.  "ledger full" as above, before
+ *                    any device call.  piadmm_obca_loop_admit does the same to a tenant that has closed
+ *                    a step; one that has not -- the slot was just admitted -- keeps its id and its
+ *                    record is opened again under the new stream id.
+ * piadmm_obca_clock_plan (either mode) is PIADMM_E_STATE while a ledger is attached: end it first.
+ * piadmm_obca_tenant_export and a blob do not change: an imported tenant starts a fresh record.
+ *
+ * piadmm_obca_ledger_get copies one item; `bytes` must be exact:
+ *   PIADMM_OBCA_LEDGER_GET_COUNT     1 int32              the appended records
+ *   PIADMM_OBCA_LEDGER_GET_RECORDS   count x 176 bytes    the appended records, in the order of appending
+ *   PIADMM_OBCA_LEDGER_GET_RUNNING   n x 176 bytes        the open record of every slot: reason 0; a slot
+ *                                                         without a tenant has id -1
+ *   PIADMM_OBCA_LEDGER_GET_NEXT_ID   1 int64              the id the next admitted tenant takes
+ * piadmm_obca_ledger_clear sets count to 0, so that a service drains the records and goes on; ids
+ * keep counting.  piadmm_obca_ledger_end frees the ledger alone; whatever ends the plan frees it too.
+ *
+ * piadmm_obca_ledger_stats reduces the appended records on the device in place: k_ledger_view builds,
+ * in the ledger's own scratch, the view of a run record with R = 1 and n = count -- summary (min
+ * plain, c_min, min tight, the iterate sum), clearances (both rows the minima), iterates (the largest
+ * stop iterate), masks (the two ORs) -- and the kernels of piadmm_obca_stats_trace run on it.  stats,
+ * hist and worst are those of the statistics section with a record's position in the ledger as the
+ * scenario.  The checks of edges, B and K are those of piadmm_obca_fleet_stats with n = count;
+ * count = 0 is PIADMM_E_STATE.  piadmm.obca.ledger_stats_host is the same statement in NumPy.
+ * Out of scope: an open record inside a tenant blob, a record per step (the trace), quantiles, a
+ * ledger on a plan without a clock; piadmm_obca_feedback_measure does not enter a record. */
+#define PIADMM_OBCA_LEDGER_REC 176
+#define PIADMM_OBCA_LEDGER_GET_COUNT 0
+#define PIADMM_OBCA_LEDGER_GET_RECORDS 1
+#define PIADMM_OBCA_LEDGER_GET_RUNNING 2
+#define PIADMM_OBCA_LEDGER_GET_NEXT_ID 3
+int32_t piadmm_obca_ledger_begin(piadmm_obca_t h, int32_t cap_tenants, int32_t flags);
+int32_t piadmm_obca_ledger_get(piadmm_obca_t h, int32_t what, void* out, int64_t bytes);
+int32_t piadmm_obca_ledger_clear(piadmm_obca_t h);
+int32_t piadmm_obca_ledger_stats(piadmm_obca_t h, const double* edges /* B */, int32_t B, int32_t K,
+                                 piadmm_obca_stats_t* stats, int64_t* hist /* 2 x (B + 1) */, int32_t* worst /* K */);
+int32_t piadmm_obca_ledger_end(piadmm_obca_t h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -156,6 +156,20 @@
                    stand (the one or two extra launches per step on an unclocked plan).  No ratio is
                    fixed in advance.  Written under the key "loop" of the same JSON, the other keys kept.
 
+  --ledger         instead of the above, the --loop fleet (--scenarios clocked scenarios under the loop
+                   with rows that draw zero, every clock at step 8 over the whole reference) over --steps
+                   MPC steps of piadmm_obca_plan_step, the legs alternating after a warm-up step of each,
+                   best of --repeats: (a) without a ledger, (b) with one (piadmm_obca_ledger_begin:
+                   k_ledger_step per shift), (c) without one but with a download of STATE after every
+                   step and obca.clearance + NumPy minima on the host, which is what a user does
+                   without the ledger.  ms per MPC step, the max/min of each leg's repeats, the bytes
+                   brought to the host per step, (b)/(a) next to (a)'s own spread.  Two more legs price
+                   the append: the same fleet on references that end with the last step, so that all
+                   --scenarios tenants retire at the last shift, without (ar) and with (br) a ledger.
+                   Asserted: (a) and (b), and (ar) and (br), leave identical STATE and LAMBDA.  No
+                   threshold is fixed in advance.  Written under the key "ledger" of the same JSON, the
+                   other keys kept.
+
 There is no CPU baseline on an equal footing (the C++ port of the local solver has no edge step);
 the edge launch is reported next to the local launch so the reader sees its share of an iterate.
 Writes one JSON (default profiles/obca_admm_bench.json) and prints it.
@@ -1001,8 +1015,109 @@ def loop_main(a):
     print(json.dumps(dict(loop=res)))
 
 
+def ledger_main(a):
+    """--ledger: the --loop fleet (a) without a ledger, (b) with one, (c) with a STATE download per step."""
+    b = obca.OBCABatch(0)
+    n, K = a.scenarios, a.steps
+    specs, par = obca.overtaking_fleet(n, seed=0)
+    prob = [k % 2 for k in range(n)]
+    kw = dict(prob=prob, t_step0=8, max_admm_iter=a.iterates - 1, specs=specs, **par)
+    zero = dict(plant=None, noise=obca.noise_row(), delay=obca.delay_row(tau_max=0.0), seed=0, k0=0)
+    warm = obca.OBCADevicePlanner(b, n, clock=True, **kw)
+    n_ref = warm.n_ref
+    state = warm.get("STATE")                          # the seeded state, so the later plans skip the host seeding
+    warm.close()
+    # the service's clocks: everyone at step 8 over the whole reference; and, for the append, everyone
+    # at step 8 on a reference that ends with the K-th step, so that all n retire at the last shift
+    live = np.array([[8, n_ref]] * n, np.int32)
+    last = np.array([[8, 8 + 8 + K - 1]] * n, np.int32)
+    legs_at = dict(a_no_ledger=(live, False, False), b_ledger=(live, True, False), c_state_download=(live, False, True),
+                   ar_no_ledger_all_retire=(last, False, False), br_ledger_all_retire=(last, True, False))
+
+    def run(clock, ledger, download, steps):
+        """One leg: `steps` MPC steps through piadmm_obca_plan_step, timed without the attachment."""
+        dp = obca.OBCADevicePlanner(b, n, state=state, clock=clock, loop=zero, **kw)
+        begin_ms, mins, per_step = 0.0, None, []
+        if ledger:
+            t0 = time.perf_counter()
+            dp.ledger_begin(n)
+            begin_ms = (time.perf_counter() - t0) * 1e3
+        if download:
+            st = dp.get("STATE")[:, 546:].reshape(n, 2, 5)
+            mins = np.array([obca.clearance(st[s], prob[s]) for s in range(n)])
+        t_all = time.perf_counter()
+        for _ in range(steps):
+            t0 = time.perf_counter()
+            dp._check(dp._lib.piadmm_obca_plan_step(b._h, None))
+            if download:
+                # what a user does today: the states to the host, the clearances and the minima there
+                st = dp.get("STATE")[:, 546:].reshape(n, 2, 5)
+                mins = np.minimum(mins, np.array([obca.clearance(st[s], prob[s]) for s in range(n)]))
+            per_step.append((time.perf_counter() - t0) * 1e3)
+        total = (time.perf_counter() - t_all) * 1e3
+        out = dict(total_ms=total, per_step_ms=per_step, begin_ms=begin_ms, mins=mins, STATE=dp.get("STATE"),
+                   LAMBDA=dp.get("LAMBDA"))
+        if ledger:
+            out.update(count=dp.ledger_count(), running=dp.ledger_running(), records=dp.ledger_records())
+        dp.close()
+        return out
+
+    for clock, ledger, download in legs_at.values():
+        run(clock, ledger, download, 1)
+    ms, last_ms, got = {k: [] for k in legs_at}, {k: [] for k in legs_at}, {}
+    for _ in range(a.repeats):
+        for name, (clock, ledger, download) in legs_at.items():
+            got[name] = run(clock, ledger, download, K)
+            ms[name].append(got[name]["total_ms"])
+            last_ms[name].append(got[name]["per_step_ms"][-1])
+    # the ledger changes nothing of the plan: asserted, on the fleet that is measured
+    for x, y in (("a_no_ledger", "b_ledger"), ("ar_no_ledger_all_retire", "br_ledger_all_retire")):
+        for item in ("STATE", "LAMBDA"):
+            assert got[x][item].tobytes() == got[y][item].tobytes(), f"{item} of {y} differs from {x}"
+    assert got["b_ledger"]["count"] == 0 and (got["b_ledger"]["running"]["steps"] == K).all()
+    assert got["br_ledger_all_retire"]["count"] == n
+    assert got["br_ledger_all_retire"]["records"]["slot"].tolist() == list(range(n))
+    # bytes brought to the host per MPC step: the 4-byte active count of every iterate, which every leg
+    # reads; (c) adds the states; the ledger adds nothing per step (its records come once, at the end)
+    iterates = a.iterates
+    host_bytes = dict(a_no_ledger=4 * iterates, b_ledger=4 * iterates, c_state_download=4 * iterates + n * 556 * 8,
+                      ar_no_ledger_all_retire=4 * iterates, br_ledger_all_retire=4 * iterates)
+    legs = {}
+    for name in legs_at:
+        best = min(ms[name])
+        legs[name] = dict(step_ms=best / K, total_ms_runs=ms[name], spread_max_over_min=max(ms[name]) / best,
+                          last_step_ms=min(last_ms[name]), host_bytes_per_step_at_most=host_bytes[name],
+                          ledger_begin_ms=got[name]["begin_ms"])
+    run_b = got["b_ledger"]["running"]
+    dev = np.stack((run_b["min_clearance"], run_b["min_clearance_tight"]), axis=1)
+    res = dict(scenarios=n, steps=K, repeats=a.repeats, max_admm_iter=a.iterates - 1, legs=legs,
+               ledger_over_no_ledger=min(ms["b_ledger"]) / min(ms["a_no_ledger"]),
+               no_ledger_spread_max_over_min=legs["a_no_ledger"]["spread_max_over_min"],
+               ratio_exceeds_no_ledger_spread=bool(min(ms["b_ledger"]) / min(ms["a_no_ledger"])
+                                                   > legs["a_no_ledger"]["spread_max_over_min"]),
+               extra_ms_per_step=(min(ms["b_ledger"]) - min(ms["a_no_ledger"])) / K,
+               download_over_no_ledger=min(ms["c_state_download"]) / min(ms["a_no_ledger"]),
+               all_retire_ledger_over_no_ledger=min(ms["br_ledger_all_retire"]) / min(ms["ar_no_ledger_all_retire"]),
+               all_retire_last_step_extra_ms=min(last_ms["br_ledger_all_retire"]) - min(last_ms["ar_no_ledger_all_retire"]),
+               all_retire_no_ledger_spread_max_over_min=legs["ar_no_ledger_all_retire"]["spread_max_over_min"],
+               state_and_lambda_equal_with_and_without_ledger=True,
+               ledger_bytes_at_the_end=int(n * 176),
+               ledger_minima_max_abs_deviation_from_host_minima=float(np.abs(dev - got["c_state_download"]["mins"]).max()))
+    b.close()
+    out = {}
+    if os.path.exists(a.out):
+        with open(a.out) as f:
+            out = json.load(f)
+    out["ledger"] = res
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+    print(json.dumps(dict(ledger=res)))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--ledger", action="store_true")
     ap.add_argument("--loop", action="store_true")
     ap.add_argument("--delay", action="store_true")
     ap.add_argument("--noise", action="store_true")
@@ -1021,6 +1136,8 @@ def main():
     ap.add_argument("--iterates", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "obca_admm_bench.json"))
     a = ap.parse_args()
+    if a.ledger:
+        return ledger_main(a)
     if a.loop:
         return loop_main(a)
     if a.delay:
