@@ -2,8 +2,10 @@
 // (internal, not installed): the layouts, the kernel-argument structs, the owners of device memory,
 // the plan and the small host helpers.  csrc/piadmm_obca_plan.hip holds the iterate and the shift and
 // describes the launch sequence; csrc/piadmm_obca_plan_{attach,trace,tenant,feedback,delay,loop,ledger}.hip hold
-// the attachments.  Every kernel is defined in one unit; there is no relocatable device code, a unit
-// launches another unit's kernel through the declaration here.
+// the attachments.  csrc/piadmm_obca_plan_draw.h, included below, holds what the closed loop (feedback,
+// noise, delay, loop) shares: the plant step, the draws, their launch views and argument checks.
+// Every kernel is defined in one unit; there is no relocatable device code, a unit launches another
+// unit's kernel through the declaration here.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -28,6 +30,9 @@ namespace obca_plan {
 
 using namespace pd_obca;     // NT, the vehicle constants, the record layouts R_*, O_*, E_*, EO_*
 constexpr int PW = 4;                          // waves per workgroup
+inline int blocks_for(int waves) { return (waves + PW - 1) / PW; }
+// workgroups of 64 * PW lanes for a kernel that runs one lane per item
+inline int lane_blocks(int lanes) { return (lanes + 64 * PW - 1) / (64 * PW); }
 constexpr int STATE = PIADMM_OBCA_PLAN_STATE;
 constexpr int REC = PIADMM_OBCA_REC, OUT = PIADMM_OBCA_OUT;
 constexpr int EREC = PIADMM_OBCA_EDGE_REC, EOUT = PIADMM_OBCA_EDGE_OUT;
@@ -85,61 +90,6 @@ __device__ __forceinline__ void copy_seg(double* dst, const double* src, int len
   }
 }
 
-// where the arrays of one k_plan_propagate launch sit, all indexed by scenario: the strides in
-// doubles per scenario; the vehicle's state row at + v * 5, its controls a and omega at
-// ctrl + v * ctrl_v and + ctrl_w behind it, its plant row at + v * 8 (par_s = 0: one shared row),
-// its disturbance row at + v * 5 (w = nullptr: none), its result at out + s * 10 + v * 5
-struct plant_io {
-  const double *x0, *ctrl, *par, *w;
-  double* out;
-  long long x0_s, w_s;
-  int ctrl_s, ctrl_v, ctrl_w, par_s;
-};
-
-// where the arrays of one k_plan_noise launch sit, indexed by scenario: par the noise rows (par_s =
-// 0: one shared row), streams the stream ids (nullptr: the scenario's number), tape the rows added
-// in front (nullptr: none), out the result, raw the Philox words (nullptr: not kept); the strides
-// in elements per scenario, and per step index (blockIdx.y) 10 doubles of tape and out and 24 words
-// of raw; k = the step index of blockIdx.y = 0
-struct noise_io {
-  const double *par, *tape;
-  const long long* streams;
-  double* out;
-  uint32_t* raw;
-  long long tape_s, out_s, raw_s;
-  uint32_t seed_lo, seed_hi, k;
-  int par_s;
-};
-
-// where the arrays of one k_plan_delay launch sit, indexed by scenario: par the delay rows (par_s =
-// 0: one shared row), streams the stream ids (nullptr: the scenario's number), tape the recorded
-// latencies added in front (nullptr: none), out the latencies, raw the Philox words (nullptr: not
-// kept); the strides in elements per scenario, and per step index (blockIdx.y) 2 doubles of tape and
-// out and 8 words of raw; k = the step index of blockIdx.y = 0
-struct delay_io {
-  const double *par, *tape;
-  const long long* streams;
-  double* out;
-  uint32_t* raw;
-  long long tape_s, out_s, raw_s;
-  uint32_t seed_lo, seed_hi, k;
-  int par_s;
-};
-
-// where the arrays of the loop's launches sit (piadmm_obca_loop_plan), indexed by scenario: plant,
-// noise and delay the rows (a stride 0: one shared row; noise / delay nullptr: that kind is absent),
-// streams the stream ids (nullptr: the scenario's number), clk the clocks (c, len, alive; the step
-// index of scenario s is k0 + clk[3 s]), x0 and ctrl what k_plan_propagate reads of the plan, next
-// the closing states by list position (m x 10), tau the latencies (n x 2)
-struct loop_io {
-  const double *plant, *noise, *delay, *x0, *ctrl;
-  const long long* streams;
-  const int* clk;
-  double *next, *tau;
-  int plant_s, noise_s, delay_s;
-  uint32_t seed_lo, seed_hi, k0;
-};
-
 // (A, b) of a vehicle at `st` -- halfspaces (piadmm/obca.py) in the host's order of operations,
 // products and sums kept apart (no contraction) so the two stay within rounding of each other.
 __device__ __forceinline__ void halfspaces(const double* st, int prob, double sigd, double A[4][2], double b[4]) {
@@ -163,153 +113,6 @@ __device__ __forceinline__ void halfspaces(const double* st, int prob, double si
   const double b0[4] = {LENGTH / 2, WIDTH / 2, LENGTH / 2, WIDTH / 2};
 #pragma unroll
   for (int i = 0; i < 4; ++i) b[i] = b0[i] + (A[i][0] * px + A[i][1] * py);
-}
-
-// The state a vehicle's message describes when it arrives tau late: x1 = X[t + 1] is what the
-// vehicle plans for the slot, x0 = X[t] where it planned to be one step earlier.  tau == 0 is x1 bit
-// for bit; otherwise x1 + (tau / DT) (x0 - x1), all five entries, the heading linearly.
-// piadmm.obca.stale_states is the same statements on the host; products and sums are kept apart, and
-// every operation is exact IEEE arithmetic, so the two agree bit for bit.  The body of the plan's
-// stale exchange and of the stand-alone k_delay_exchange.
-__device__ __forceinline__ void stale_state(const double* x0, const double* x1, double tau, double st[5]) {
-#pragma clang fp contract(off)
-  if (tau == 0.0) {
-#pragma unroll
-    for (int j = 0; j < 5; ++j) st[j] = x1[j];
-  } else {
-    const double f = tau / PLANT_DT;
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-      const double a = x1[j];
-      st[j] = a + f * (x0[j] - a);
-    }
-  }
-}
-
-// Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11):
-// c the counter's four words, replaced by the result; (k0, k1) the key.  Ten rounds of two
-// 32 x 32 -> 64 products (the high halves by __umulhi), the key bumped between rounds.  All 32-bit.
-__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
-  constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(M0, c[0]), lo0 = M0 * c[0];
-    const uint32_t hi1 = __umulhi(M1, c[2]), lo1 = M1 * c[2];
-    c[0] = hi1 ^ c[1] ^ k0;
-    c[1] = lo1;
-    c[2] = hi0 ^ c[3] ^ k1;
-    c[3] = lo0;
-    k0 += W0;
-    k1 += W1;
-  }
-}
-
-// One plant step of one vehicle, all in registers: x (5) <- F(x, (a, om)) under the vehicle's row P
-// (8), without the disturbance.  n_sub substeps of DT / n_sub; a substep is 1 stage (Euler) or 4
-// (classical RK4) of the one right-hand side below, the stage loop kept rolled so that the libm
-// calls are inlined once; then delta is clipped.  n_sub is clamped to its range, so the loop is
-// bounded whatever the row holds.  piadmm.obca.propagate is the same statements on the host;
-// products and sums are kept apart (no contraction).  The body of
-// k_plan_propagate (the stand-alone call and the in-plan step) and of k_loop_close: the same bits.
-__device__ __forceinline__ void plant_step(double x[5], double a, double om, const double P[FV]) {
-#pragma clang fp contract(off)
-  const double lr = P[F_LR], lf = P[F_LF];
-  const double a_eff = fmin(P[F_AMAX], fmax(P[F_GA] * a, -P[F_AMAX]));
-  const double w_eff = fmin(P[F_WMAX], fmax(P[F_GW] * om, -P[F_WMAX]));
-  const int n_sub = min(max((int)P[F_NSUB], 1), F_NSUB_MAX);
-  const int n_stage = P[F_METHOD] != 0.0 ? 4 : 1;
-  const double hs = PLANT_DT / (double)n_sub;
-  const double scale = n_stage == 4 ? hs / 6.0 : hs;
-#pragma unroll 1
-  for (int sub = 0; sub < n_sub; ++sub) {
-    double xs[5], acc[5];
-#pragma unroll
-    for (int i = 0; i < 5; ++i) { xs[i] = x[i]; acc[i] = 0.0; }
-#pragma unroll 1
-    for (int st = 0; st < n_stage; ++st) {
-      const double beta = atan(lr * tan(xs[4]) / (lr + lf));
-      const double ph = xs[3] + beta;
-      const double f[5] = {xs[2] * cos(ph), xs[2] * sin(ph), a_eff, xs[2] / lr * sin(beta), w_eff};
-      const double wgt = (st == 1 || st == 2) ? 2.0 : 1.0;
-      const double c = st < 2 ? 0.5 * hs : hs;          // the next stage's point: x + c f
-#pragma unroll
-      for (int i = 0; i < 5; ++i) {
-        acc[i] = st == 0 ? f[i] : acc[i] + wgt * f[i];
-        xs[i] = x[i] + c * f[i];
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < 5; ++i) x[i] = x[i] + scale * acc[i];
-    x[4] = fmin(MAX_STEER, fmax(x[4], -MAX_STEER));
-  }
-}
-
-// The five disturbances of vehicle v of stream t at step k under the row's sigma S, bias B and
-// trunc: three Philox calls at counter (k, 4 v + j, t low, t high), each giving two uniforms in
-// (0, 1) on 52 bits and by Box-Muller two normals; the sixth normal is discarded.  raw (12 words,
-// or nullptr) receives the calls' words.  piadmm.obca.noise_tape is the same statements on the
-// host; products and sums are kept apart (no contraction), so sigma = 0 gives the bias bit for bit.
-// The body of k_plan_noise (the in-plan step and the stand-alone tape) and of k_loop_close and
-// k_loop_draw: the same bits.
-__device__ __forceinline__ void noise_draw(uint32_t seed_lo, uint32_t seed_hi, uint32_t t_lo, uint32_t t_hi,
-                                           uint32_t k, int v, const double S[5], const double B[5], double trunc,
-                                           double w[5], uint32_t* raw) {
-#pragma clang fp contract(off)
-  double z[6];
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    uint32_t c[4] = {k, (uint32_t)(4 * v + j), t_lo, t_hi};
-    philox4x32_10(c, seed_lo, seed_hi);
-    if (raw) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) raw[4 * j + q] = c[q];
-    }
-    const unsigned long long a = ((unsigned long long)c[0] << 32) | c[1];
-    const unsigned long long b = ((unsigned long long)c[2] << 32) | c[3];
-    const double u1 = ((double)(a >> 12) + 0.5) * 0x1p-52;
-    const double u2 = ((double)(b >> 12) + 0.5) * 0x1p-52;
-    const double rad = sqrt(-2.0 * log(u1));
-    const double ang = 6.283185307179586 * u2;
-    z[2 * j] = rad * cos(ang);
-    z[2 * j + 1] = rad * sin(ang);
-  }
-#pragma unroll
-  for (int i = 0; i < 5; ++i) {
-    double zi = z[i];
-    if (trunc != 0.0) zi = fmin(trunc, fmax(zi, -trunc));
-    w[i] = B[i] + S[i] * zi;
-  }
-}
-
-// The latency of vehicle v of stream t at step k under the row's avg, std, tau_max and trunc: one
-// Philox call at counter (k, 4 v + 3, t low, t high) -- the call index the noise leaves free -- two
-// uniforms in (0, 1) on 52 bits as noise_draw forms them, the first Box-Muller normal; the second is
-// discarded.  tape is the recorded latency added in front (0 without one).  raw (4 words, or
-// nullptr) receives the call's words.  piadmm.obca.delay_tau is the same statements on the host;
-// products and sums are kept apart (no contraction), so std = 0 gives min(tau_max, tape + avg) bit
-// for bit.  The body of k_plan_delay (the in-plan step and the stand-alone call), of k_loop_open and
-// of k_loop_draw: the same bits.
-__device__ __forceinline__ double delay_draw(uint32_t seed_lo, uint32_t seed_hi, uint32_t t_lo, uint32_t t_hi,
-                                             uint32_t k, int v, double avg, double sd, double tau_max, double trunc,
-                                             double tape, uint32_t* raw) {
-#pragma clang fp contract(off)
-  uint32_t c[4] = {k, (uint32_t)(4 * v + 3), t_lo, t_hi};
-  philox4x32_10(c, seed_lo, seed_hi);
-  if (raw) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) raw[q] = c[q];
-  }
-  const unsigned long long a = ((unsigned long long)c[0] << 32) | c[1];
-  const unsigned long long b = ((unsigned long long)c[2] << 32) | c[3];
-  const double u1 = ((double)(a >> 12) + 0.5) * 0x1p-52;
-  const double u2 = ((double)(b >> 12) + 0.5) * 0x1p-52;
-  const double rad = sqrt(-2.0 * log(u1));
-  const double ang = 6.283185307179586 * u2;
-  double z = rad * cos(ang);
-  if (trunc != 0.0) z = fmin(trunc, fmax(z, -trunc));
-  const double x = tape + (avg + sd * z);
-  const double lo = x > 0.0 ? x : 0.0;
-  return lo < tau_max ? lo : tau_max;
 }
 
 // The exact minimum distance between the two vehicles' rectangles (generate_vehicle_vertices,
@@ -370,41 +173,6 @@ __device__ __forceinline__ void clearance_pair(const double* st, int pr, double 
   plain = g0 > 0.0 ? d0 : 0.0;
   tight = g1 > 0.0 ? d1 : 0.0;
 }
-
-// The kernels launched from a unit other than their own (the comments are at the definitions).
-// csrc/piadmm_obca_plan.hip
-__global__ void __launch_bounds__(CT) k_plan_compact(const int* __restrict__ active, const int* __restrict__ keep,
-                                                     int n_act, int* __restrict__ next, int* __restrict__ count);
-__global__ void __launch_bounds__(64) k_plan_shift_list(const int* __restrict__ list, int m,
-                                                        double* __restrict__ bar, double* __restrict__ barp,
-                                                        const double* __restrict__ X, double* __restrict__ lamb,
-                                                        double* __restrict__ ctrlp);
-// csrc/piadmm_obca_plan_attach.hip
-__global__ void __launch_bounds__(64 * PW) k_plan_dual_pi(const int* __restrict__ active, int n_act,
-                                                          const double* __restrict__ erecs,
-                                                          double* __restrict__ eout, const int* __restrict__ eist,
-                                                          const double* __restrict__ gains, int g_stride,
-                                                          double* __restrict__ S, double* __restrict__ D,
-                                                          double* __restrict__ Sp, double* __restrict__ Dp);
-__global__ void __launch_bounds__(64) k_plan_dual_shift(int n, double* __restrict__ S, double* __restrict__ D,
-                                                        double* __restrict__ Sp, double* __restrict__ Dp);
-__global__ void __launch_bounds__(64 * PW) k_plan_work(const int* __restrict__ active, int n_act,
-                                                       const int* __restrict__ list, const int* __restrict__ eist,
-                                                       int* __restrict__ work);
-__global__ void __launch_bounds__(64 * PW) k_plan_order(const int* __restrict__ list_in,
-                                                        const int* __restrict__ count, int m,
-                                                        const int* __restrict__ work, int* __restrict__ list_out);
-// csrc/piadmm_obca_plan_feedback.hip
-__global__ void __launch_bounds__(64 * PW) k_plan_propagate(const int* __restrict__ list, int m, plant_io io);
-__global__ void __launch_bounds__(64 * PW) k_plan_set_init(const int* __restrict__ list, int m,
-                                                           const double* __restrict__ states,
-                                                           double* __restrict__ bar, double* __restrict__ barp);
-__global__ void __launch_bounds__(64 * PW) k_plan_noise(const int* __restrict__ list, int m, noise_io io);
-// csrc/piadmm_obca_plan_delay.hip
-__global__ void __launch_bounds__(64 * PW) k_plan_delay(const int* __restrict__ list, int m, delay_io io);
-// csrc/piadmm_obca_plan_loop.hip
-__global__ void __launch_bounds__(64 * PW) k_loop_close(const int* __restrict__ list, int m, loop_io io);
-__global__ void __launch_bounds__(64 * PW) k_loop_open(const int* __restrict__ list, int m, loop_io io);
 
 // ---------------------------------------------------------------------------------------------
 // The host side
@@ -474,25 +242,25 @@ struct piadmm_obca_plan_s {
     int rows = 0, stride = 0, cap = 0, steps = 0;
     dbuf<double> par, tape, next;
   } fb;
-  // the device-side noise on top of the feedback (piadmm_obca_noise_plan): rows = 1 with stride 0 or n
+  // the device-side noise on top of the feedback (piadmm_obca_noise_plan): rows = 1 (shared) or n
   // noise rows; streams = the stream id of every scenario; wbuf = the disturbance rows of the step
   // that closes, n x 10, which k_plan_noise writes and k_plan_propagate reads; the step index of a
   // shift is k0 + fb.steps
   struct noise_s {
     bool on = false;
-    int rows = 0, stride = 0, k0 = 0;
+    int rows = 0, k0 = 0;
     uint64_t seed = 0;
     dbuf<double> par, wbuf;
     dbuf<long long> streams;
   } nz;
-  // the communication delay of the exchange (piadmm_obca_delay_plan): rows = 1 with stride 0 or n
+  // the communication delay of the exchange (piadmm_obca_delay_plan): rows = 1 (shared) or n
   // delay rows; streams = the stream id of every scenario; tape = cap recorded latencies per scenario
   // (nullptr: none), n x cap x 2; steps = the shifts since the attachment; tau = the open step's
   // latencies, n x 2, which k_plan_delay writes at the attachment and after every shift and
   // k_plan_exchange_stale reads; the open step's index is k0 + steps
   struct delay_s {
     bool on = false;
-    int rows = 0, stride = 0, k0 = 0, cap = 0, steps = 0;
+    int rows = 0, k0 = 0, cap = 0, steps = 0;
     uint64_t seed = 0;
     dbuf<double> par, tape, tau;
     dbuf<long long> streams;
@@ -531,7 +299,45 @@ struct piadmm_obca_plan_s {
   } stg;
 };
 
+// what the closed loop shares: the plant step, the draws, their launch views and argument checks
+#include "piadmm_obca_plan_draw.h"
+
 namespace obca_plan {
+
+// The kernels launched from a unit other than their own (the comments are at the definitions).
+// csrc/piadmm_obca_plan.hip
+__global__ void __launch_bounds__(CT) k_plan_compact(const int* __restrict__ active, const int* __restrict__ keep,
+                                                     int n_act, int* __restrict__ next, int* __restrict__ count);
+__global__ void __launch_bounds__(64) k_plan_shift_list(const int* __restrict__ list, int m,
+                                                        double* __restrict__ bar, double* __restrict__ barp,
+                                                        const double* __restrict__ X, double* __restrict__ lamb,
+                                                        double* __restrict__ ctrlp);
+// csrc/piadmm_obca_plan_attach.hip
+__global__ void __launch_bounds__(64 * PW) k_plan_dual_pi(const int* __restrict__ active, int n_act,
+                                                          const double* __restrict__ erecs,
+                                                          double* __restrict__ eout, const int* __restrict__ eist,
+                                                          const double* __restrict__ gains, int g_stride,
+                                                          double* __restrict__ S, double* __restrict__ D,
+                                                          double* __restrict__ Sp, double* __restrict__ Dp);
+__global__ void __launch_bounds__(64) k_plan_dual_shift(int n, double* __restrict__ S, double* __restrict__ D,
+                                                        double* __restrict__ Sp, double* __restrict__ Dp);
+__global__ void __launch_bounds__(64 * PW) k_plan_work(const int* __restrict__ active, int n_act,
+                                                       const int* __restrict__ list, const int* __restrict__ eist,
+                                                       int* __restrict__ work);
+__global__ void __launch_bounds__(64 * PW) k_plan_order(const int* __restrict__ list_in,
+                                                        const int* __restrict__ count, int m,
+                                                        const int* __restrict__ work, int* __restrict__ list_out);
+// csrc/piadmm_obca_plan_feedback.hip
+__global__ void __launch_bounds__(64 * PW) k_plan_propagate(const int* __restrict__ list, int m, plant_io io);
+__global__ void __launch_bounds__(64 * PW) k_plan_set_init(const int* __restrict__ list, int m,
+                                                           const double* __restrict__ states,
+                                                           double* __restrict__ bar, double* __restrict__ barp);
+__global__ void __launch_bounds__(64 * PW) k_plan_noise(const int* __restrict__ list, int m, draw_io io);
+// csrc/piadmm_obca_plan_delay.hip
+__global__ void __launch_bounds__(64 * PW) k_plan_delay(const int* __restrict__ list, int m, draw_io io);
+// csrc/piadmm_obca_plan_loop.hip
+__global__ void __launch_bounds__(64 * PW) k_loop_close(const int* __restrict__ list, int m, loop_io io);
+__global__ void __launch_bounds__(64 * PW) k_loop_open(const int* __restrict__ list, int m, loop_io io);
 
 inline int open_plan(piadmm_obca_t h, piadmm_obca_plan_s** out, const char* who) {
   if (!h) return PIADMM_E_ARG;
@@ -550,16 +356,9 @@ inline std::vector<int> identity_list(size_t n) {      // 0 .. n - 1
   std::iota(v.begin(), v.end(), 0);
   return v;
 }
-inline int blocks_for(int waves) { return (waves + PW - 1) / PW; }
-// workgroups of 64 * PW lanes for a kernel that runs one lane per item
-inline int lane_blocks(int lanes) { return (lanes + 64 * PW - 1) / (64 * PW); }
 // true when the attached feedback has a tape and the next `steps` shifts do not fit what is left of it
 inline bool feedback_exhausted(const piadmm_obca_plan_s* p, int64_t steps) {
   return p->fb.on && p->fb.tape && (int64_t)p->fb.steps + steps > p->fb.cap;
-}
-// true when the attached noise would pass step index 2^31 - 1 within the next `steps` shifts
-inline bool noise_exhausted(const piadmm_obca_plan_s* p, int64_t steps) {
-  return p->nz.on && (int64_t)p->nz.k0 + p->fb.steps + steps > ((int64_t)1 << 31);
 }
 
 // What refuses the next `steps` MPC steps of a plan with the delay attached, or nullptr: step k since
@@ -571,22 +370,6 @@ inline const char* delay_refusal(const piadmm_obca_plan_s* p, int64_t steps) {
   return nullptr;
 }
 
-// the launch arguments of the loop `l` on the plan's own arrays
-inline loop_io loop_view(const piadmm_obca_plan_s* p, const piadmm_obca_plan_s::loop_s& l) {
-  loop_io io{};
-  io.plant = l.plant;  io.plant_s = l.plant_rows > 1 ? FPAR : 0;
-  io.noise = (l.flags & 2) ? l.noise.get() : nullptr;  io.noise_s = l.noise_rows > 1 ? ZPAR : 0;
-  io.delay = (l.flags & 4) ? l.delay.get() : nullptr;  io.delay_s = l.delay_rows > 1 ? YPAR : 0;
-  io.streams = l.streams;
-  io.clk = p->ck.clk;
-  io.x0 = p->bar + S_INIT;
-  io.ctrl = p->ctrl;
-  io.next = l.next;
-  io.tau = l.tau;
-  io.seed_lo = (uint32_t)l.seed;  io.seed_hi = (uint32_t)(l.seed >> 32);
-  io.k0 = (uint32_t)l.k0;
-  return io;
-}
 // true when, with the loop attached, the next `steps` MPC steps would take an alive tenant's step
 // index k0 + c to 2^31 (a tenant ticks at most until it retires)
 inline bool loop_exhausted(const piadmm_obca_plan_s* p, int64_t steps) {
@@ -620,10 +403,6 @@ inline int tenant_slots_check(piadmm_obca_t h, const piadmm_obca_plan_s* p, int 
 }
 inline int prob_check(piadmm_obca_t h, const std::string& who, const int32_t* prob, int k) {
   if (prob[k] != 0 && prob[k] != 1) return fail(h, PIADMM_E_ARG, who + ": prob[" + std::to_string(k) + "] must be 0 or 1");
-  return 0;
-}
-inline int rows_check(piadmm_obca_t h, const std::string& who, int rows, int n) {
-  if (rows != 1 && rows != n) return fail(h, PIADMM_E_ARG, who + ": rows must be 1 or n (" + std::to_string(n) + ")");
   return 0;
 }
 // The tail of a _get call: item `what` is `want` bytes at src, on the host (`host`) or on the device.
@@ -682,5 +461,21 @@ void ledger_stepped(piadmm_obca_plan_s* p, const std::vector<int>& next);
 const char* ledger_replace_refusal(const piadmm_obca_plan_s* p, int m, const int32_t* slots, bool fresh_only);
 int ledger_close(piadmm_obca_t h, piadmm_obca_plan_s* p, int m, const int32_t* slots, int reason, bool fresh_only);
 int ledger_open(piadmm_obca_t h, piadmm_obca_plan_s* p, int m, const int32_t* slots);
+
+// What refuses the next `steps` MPC steps of the plan, or nullptr: the trace's rows, the disturbance
+// tape's rows, the noise's step index k0 + fb.steps below 2^31, the loop's, the ledger's places.  The
+// delay's refusal (delay_refusal) stays each call's own: piadmm_obca_plan_shift names it first,
+// piadmm_obca_plan_step behind these.  It excludes the loop's and the ledger's (the delay refuses a
+// clock, both need one), not the first three.
+// TAPE_EXHAUSTED is the tape's refusal, one array for every unit: piadmm_obca_trace_run tells it by
+// its address.
+inline constexpr char TAPE_EXHAUSTED[] = "disturbance tape exhausted";
+inline const char* step_refusal(const piadmm_obca_plan_s* p, int64_t steps) {
+  if (p->tr.on && (int64_t)p->tr.rows + steps > p->tr.cap) return "trace full";
+  if (feedback_exhausted(p, steps)) return TAPE_EXHAUSTED;
+  if (p->nz.on && (int64_t)p->nz.k0 + p->fb.steps + steps > ((int64_t)1 << 31)) return "noise step index exhausted";
+  if (loop_exhausted(p, steps)) return "loop step index exhausted";
+  return ledger_refusal(p, steps);
+}
 
 }  // namespace obca_plan

@@ -626,33 +626,17 @@ int32_t piadmm_obca_plan_shift(piadmm_obca_t h) {
   if (const char* why = delay_refusal(p, 1)) return fail(h, PIADMM_E_STATE, std::string("obca_plan_shift: ") + why);
   if (p->n_act > 0) return fail(h, PIADMM_E_STATE, "obca_plan_shift: scenarios are still active");
   if (p->i_iter == 0) return fail(h, PIADMM_E_STATE, "obca_plan_shift: no iterate ran in this step");
-  if (p->tr.on && p->tr.rows >= p->tr.cap) return fail(h, PIADMM_E_STATE, "obca_plan_shift: trace full");
-  if (feedback_exhausted(p, 1)) return fail(h, PIADMM_E_STATE, "obca_plan_shift: disturbance tape exhausted");
-  if (noise_exhausted(p, 1)) return fail(h, PIADMM_E_STATE, "obca_plan_shift: noise step index exhausted");
-  if (loop_exhausted(p, 1)) return fail(h, PIADMM_E_STATE, "obca_plan_shift: loop step index exhausted");
-  if (const char* why = ledger_refusal(p, 1)) return fail(h, PIADMM_E_STATE, std::string("obca_plan_shift: ") + why);
+  if (const char* why = step_refusal(p, 1)) return fail(h, PIADMM_E_STATE, std::string("obca_plan_shift: ") + why);
   OWN_HIP(h, hipSetDevice(h->device));
   if (p->ck.on) return clock_shift(h, p);
   if (p->fb.on) {
     // the plant step first: it reads the closing step's init_state and the stopping solution's first
     // control (k_plan_exchange wrote ctrl and X from the same local output), which the shift overwrites
-    plant_io io{};
-    io.x0 = p->bar + S_INIT;  io.x0_s = STATE;
-    io.ctrl = p->ctrl;  io.ctrl_s = NCTRL;  io.ctrl_v = NCTRL / 2;  io.ctrl_w = NT;
-    io.par = p->fb.par;  io.par_s = p->fb.stride;
-    io.w = p->fb.tape ? p->fb.tape + (size_t)p->fb.steps * 10 : nullptr;  io.w_s = (long long)p->fb.cap * 10;
-    io.out = p->fb.next;
+    plant_io io = feedback_view(p, p->fb, p->fb.steps);
     if (p->nz.on) {
       // the step's disturbance rows first (the tape's row added in front), then read in the tape's place
-      noise_io zo{};
-      zo.par = p->nz.par;  zo.par_s = p->nz.stride;
-      zo.streams = p->nz.streams;
-      zo.tape = io.w;  zo.tape_s = io.w_s;
-      zo.out = p->nz.wbuf;  zo.out_s = 10;
-      zo.seed_lo = (uint32_t)p->nz.seed;  zo.seed_hi = (uint32_t)(p->nz.seed >> 32);
-      zo.k = (uint32_t)p->nz.k0 + (uint32_t)p->fb.steps;
       hipLaunchKernelGGL(k_plan_noise, dim3(lane_blocks(2 * p->n)), dim3(64 * PW), 0, h->stream, (const int*)nullptr,
-                         p->n, zo);
+                         p->n, noise_view(p->nz, p->fb, p->fb.steps));
       OWN_HIP(h, hipGetLastError());
       io.w = p->nz.wbuf;  io.w_s = 10;
     }
@@ -704,12 +688,8 @@ int32_t piadmm_obca_plan_step(piadmm_obca_t h, int32_t* iters_out) {
   if (int rc = open_plan(h, &p, "obca_plan_step")) return rc;
   if (p->ck.on && p->ck.n_list == 0) return fail(h, PIADMM_E_STATE, "obca_plan_step: no scenario alive");
   if (!p->ck.on && p->t_step + 8 > p->cfg.n_ref) return fail(h, PIADMM_E_STATE, "obca_plan_step: reference exhausted");
-  if (p->tr.on && p->tr.rows >= p->tr.cap) return fail(h, PIADMM_E_STATE, "obca_plan_step: trace full");
-  if (feedback_exhausted(p, 1)) return fail(h, PIADMM_E_STATE, "obca_plan_step: disturbance tape exhausted");
-  if (noise_exhausted(p, 1)) return fail(h, PIADMM_E_STATE, "obca_plan_step: noise step index exhausted");
-  if (loop_exhausted(p, 1)) return fail(h, PIADMM_E_STATE, "obca_plan_step: loop step index exhausted");
+  if (const char* why = step_refusal(p, 1)) return fail(h, PIADMM_E_STATE, std::string("obca_plan_step: ") + why);
   if (const char* why = delay_refusal(p, 1)) return fail(h, PIADMM_E_STATE, std::string("obca_plan_step: ") + why);
-  if (const char* why = ledger_refusal(p, 1)) return fail(h, PIADMM_E_STATE, std::string("obca_plan_step: ") + why);
   // i_iter > max_admm_iter stops a scenario: at most the largest max_admm_iter + 1 iterates in a step
   while (p->n_act > 0 && p->i_iter <= p->max_iter_all) {
     if (int rc = piadmm_obca_plan_iterate(h, nullptr)) return rc;

@@ -372,11 +372,7 @@ int clock_shift(piadmm_obca_t h, piadmm_obca_plan_s* p) {
 
 namespace {
 int dual_rows_check(piadmm_obca_t h, const double* gains, int rows, int n, const std::string& who) {
-  if (int rc = rows_check(h, who, rows, n)) return rc;
-  for (int k = 0; k < rows; ++k)
-    if (const char* why = dual_row_check(gains + (size_t)k * obca_plan::DPAR))
-      return fail(h, PIADMM_E_ARG, who + ": row " + std::to_string(k) + ": " + why);
-  return 0;
+  return rows_check(h, who, "", gains, rows, n, obca_plan::DPAR, dual_row_check);
 }
 
 // One clock row (c0, len) against the plan's n_ref: nullptr when it is good, else what is wrong.

@@ -6,8 +6,8 @@
 // piadmm_obca_plan_shift launches k_plan_delay last, one lane per vehicle: the latencies of the step
 // that opens; without it neither is launched.
 // k_plan_exchange_stale is defined next to k_plan_exchange; here are k_plan_delay, the stand-alone
-// k_delay_exchange (the same device functions, stale_state and halfspaces of csrc/piadmm_obca_plan.h,
-// on the caller's arrays) and the calls.
+// k_delay_exchange (the same device functions, stale_state of csrc/piadmm_obca_plan_draw.h and
+// halfspaces of csrc/piadmm_obca_plan.h, on the caller's arrays) and the calls.
 
 #include "piadmm_obca_plan.h"
 
@@ -19,19 +19,19 @@ namespace obca_plan {
 // the step index are kernel arguments, the arithmetic 32-bit integer and fp64 in registers.  The
 // lane's 4 parameters are 8-byte loads from the row; its result one 8-byte store, neighbouring lanes
 // to neighbouring addresses.
-__global__ void __launch_bounds__(64 * PW) k_plan_delay(const int* __restrict__ list, int m, delay_io io) {
+__global__ void __launch_bounds__(64 * PW) k_plan_delay(const int* __restrict__ list, int m, draw_io io) {
   const int g = blockIdx.x * (64 * PW) + threadIdx.x;
   if (g >= 2 * m) return;
   const int v = g & 1;
   const size_t s = (size_t)(list ? list[g >> 1] : (g >> 1));
   const size_t y = blockIdx.y;
   const double* P = io.par + s * io.par_s;
-  const unsigned long long t = io.streams ? (unsigned long long)io.streams[s] : (unsigned long long)s;
+  uint32_t t_lo, t_hi;
+  stream_words(io.streams, s, t_lo, t_hi);
   const double tape = io.tape ? io.tape[s * io.tape_s + y * 2 + v] : 0.0;
   uint32_t words[4];
-  io.out[s * io.out_s + y * 2 + v] =
-      delay_draw(io.seed_lo, io.seed_hi, (uint32_t)t, (uint32_t)(t >> 32), io.k + (uint32_t)y, v, P[Y_AVG + v],
-                 P[Y_STD + v], P[Y_TMAX + v], P[Y_TRUNC], tape, io.raw ? words : nullptr);
+  io.out[s * io.out_s + y * 2 + v] = delay_draw(io.seed_lo, io.seed_hi, t_lo, t_hi, io.k + (uint32_t)y, v, P[Y_AVG + v],
+                                                P[Y_STD + v], P[Y_TMAX + v], P[Y_TRUNC], tape, io.raw ? words : nullptr);
   if (io.raw) {
     uint32_t* r = io.raw + s * io.raw_s + y * 8 + v * 4;
 #pragma unroll
@@ -74,15 +74,8 @@ __global__ void __launch_bounds__(64 * PW) k_delay_exchange(int n, const double*
 int delay_next(piadmm_obca_t h, piadmm_obca_plan_s* p) {
   const int64_t next = (int64_t)p->dl.steps + 1;
   if ((p->dl.tape && next >= p->dl.cap) || (int64_t)p->dl.k0 + next >= ((int64_t)1 << 31)) return 0;
-  delay_io yo{};
-  yo.par = p->dl.par;  yo.par_s = p->dl.stride;
-  yo.streams = p->dl.streams;
-  yo.tape = p->dl.tape ? p->dl.tape + (size_t)next * 2 : nullptr;  yo.tape_s = (long long)p->dl.cap * 2;
-  yo.out = p->dl.tau;  yo.out_s = 2;
-  yo.seed_lo = (uint32_t)p->dl.seed;  yo.seed_hi = (uint32_t)(p->dl.seed >> 32);
-  yo.k = (uint32_t)p->dl.k0 + (uint32_t)next;
   hipLaunchKernelGGL(k_plan_delay, dim3(lane_blocks(2 * p->n)), dim3(64 * PW), 0, h->stream, (const int*)nullptr, p->n,
-                     yo);
+                     delay_view(p->dl, (int)next));
   OWN_HIP(h, hipGetLastError());
   return 0;
 }
@@ -112,23 +105,10 @@ namespace {
 int delay_args_check(piadmm_obca_t h, int n, const double* par, int rows, const int64_t* streams, int32_t k0,
                      int64_t steps, const double* tape, int cap, const std::string& who) {
   if (!par) return fail(h, PIADMM_E_ARG, who + ": null argument");
-  if (int rc = rows_check(h, who, rows, n)) return rc;
-  for (int k = 0; k < rows; ++k)
-    if (const char* why = delay_row_check(par + (size_t)k * YPAR))
-      return fail(h, PIADMM_E_ARG, who + ": row " + std::to_string(k) + ": " + why);
-  if (streams)
-    for (int k = 0; k < n; ++k)
-      if (streams[k] < 0) return fail(h, PIADMM_E_ARG, who + ": streams[" + std::to_string(k) + "] must be >= 0");
-  if (k0 < 0 || (int64_t)k0 + steps > ((int64_t)1 << 31))
-    return fail(h, PIADMM_E_ARG, who + ": k0 >= 0 and every step index below 2^31");
-  if (tape) {
-    const size_t T = (size_t)n * (size_t)cap * 2;
-    for (size_t i = 0; i < T; ++i)
-      if (!std::isfinite(tape[i]))
-        return fail(h, PIADMM_E_ARG, who + ": the tape of scenario " + std::to_string(i / ((size_t)cap * 2)) +
-                    " is not finite (step " + std::to_string(i / 2 % (size_t)cap) + ")");
-  }
-  return 0;
+  if (int rc = rows_check(h, who, "", par, rows, n, YPAR, delay_row_check)) return rc;
+  if (int rc = streams_check(h, who, streams, n)) return rc;
+  if (int rc = step_index_check(h, who, k0, steps)) return rc;
+  return tape_finite_check(h, who, tape, n, cap, 2);
 }
 }  // namespace
 
@@ -156,22 +136,9 @@ int32_t piadmm_obca_delay_tau(piadmm_obca_t h, int32_t n, int32_t cap, const dou
   OWN_HIP(h, hipMemcpyAsync(d_par, par, (size_t)rows * YPAR * B, hipMemcpyHostToDevice, h->stream));
   if (streams) OWN_HIP(h, hipMemcpyAsync(d_str, streams, N * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
   if (tape) OWN_HIP(h, hipMemcpyAsync(d_tape, tape, N * C * 2 * B, hipMemcpyHostToDevice, h->stream));
-  delay_io yo{};
-  yo.par = d_par;  yo.par_s = rows > 1 ? YPAR : 0;
-  yo.streams = d_str;
-  yo.tape_s = yo.out_s = (long long)C * 2;  yo.raw_s = (long long)C * 8;
-  yo.seed_lo = (uint32_t)seed;  yo.seed_hi = (uint32_t)(seed >> 32);
-  // one grid row per step index, at most 32768 rows a launch
-  for (int at = 0; at < cap; at += 32768) {
-    const int ny = std::min(cap - at, 32768);
-    yo.out = d_out + (size_t)at * 2;
-    yo.tape = d_tape ? d_tape + (size_t)at * 2 : nullptr;
-    yo.raw = d_raw ? d_raw + (size_t)at * 8 : nullptr;
-    yo.k = (uint32_t)k0 + (uint32_t)at;
-    hipLaunchKernelGGL(k_plan_delay, dim3(lane_blocks(2 * n), ny), dim3(64 * PW), 0, h->stream, (const int*)nullptr, n,
-                       yo);
-    OWN_HIP(h, hipGetLastError());
-  }
+  if (int rc = draw_launch(h, k_plan_delay, draw_view(d_par, rows, YPAR, d_str, seed), n, cap, k0, 2, 8, d_out, d_tape,
+                           d_raw))
+    return rc;
   OWN_HIP(h, hipMemcpyAsync(tau_out, d_out, N * C * 2 * B, hipMemcpyDeviceToHost, h->stream));
   if (raw_out)
     OWN_HIP(h, hipMemcpyAsync(raw_out, d_raw, N * C * 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
@@ -236,19 +203,14 @@ int32_t piadmm_obca_delay_plan(piadmm_obca_t h, int32_t mode, const double* par,
   }
   // the new attachment is complete, the open step's latencies included, before it replaces the earlier one
   piadmm_obca_plan_s::delay_s nd;
-  std::vector<long long> ident;
-  if (!streams) {
-    ident.resize(N);
-    for (size_t k = 0; k < N; ++k) ident[k] = (long long)k;
-  }
-  const void* src = streams ? static_cast<const void*>(streams) : static_cast<const void*>(ident.data());
+  const std::vector<long long> ids = stream_ids(streams, N);
   const size_t T = tape ? N * (size_t)cap * 2 : 0;
   hipError_t e = nd.par.make((size_t)rows * YPAR);
   if (e == hipSuccess) e = nd.tau.make(N * 2);
   if (e == hipSuccess) e = nd.streams.make(N);
   if (e == hipSuccess) e = hipMemset(nd.tau, 0, N * 2 * sizeof(double));
   if (e == hipSuccess) e = hipMemcpy(nd.par, par, (size_t)rows * YPAR * sizeof(double), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(nd.streams, src, N * sizeof(long long), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(nd.streams, ids.data(), N * sizeof(long long), hipMemcpyHostToDevice);
   if (e == hipSuccess && tape) {
     // a tape without rows still counts as one: every step is then refused
     e = nd.tape.make(std::max(T, (size_t)1));
@@ -256,15 +218,14 @@ int32_t piadmm_obca_delay_plan(piadmm_obca_t h, int32_t mode, const double* par,
   }
   // the fill and the copies went through the null stream, which the handle's stream does not wait for
   if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+  nd.rows = rows;
+  nd.seed = seed;
+  nd.k0 = k0;
+  nd.cap = tape ? cap : 0;
+  nd.steps = 0;
   if (e == hipSuccess && !(tape && cap == 0)) {
-    delay_io yo{};
-    yo.par = nd.par;  yo.par_s = rows > 1 ? YPAR : 0;
-    yo.streams = nd.streams;
-    yo.tape = nd.tape;  yo.tape_s = (long long)cap * 2;
-    yo.out = nd.tau;  yo.out_s = 2;
-    yo.seed_lo = (uint32_t)seed;  yo.seed_hi = (uint32_t)(seed >> 32);
-    yo.k = (uint32_t)k0;
-    hipLaunchKernelGGL(k_plan_delay, dim3(lane_blocks(2 * n)), dim3(64 * PW), 0, h->stream, (const int*)nullptr, n, yo);
+    hipLaunchKernelGGL(k_plan_delay, dim3(lane_blocks(2 * n)), dim3(64 * PW), 0, h->stream, (const int*)nullptr, n,
+                       delay_view(nd, 0));
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
   }
@@ -272,14 +233,8 @@ int32_t piadmm_obca_delay_plan(piadmm_obca_t h, int32_t mode, const double* par,
     (void)hipStreamSynchronize(h->stream);
     return fail(h, PIADMM_E_HIP, std::string("obca_delay_plan: ") + hipGetErrorString(e));
   }
+  nd.on = true;
   p->dl = std::move(nd);
-  p->dl.rows = rows;
-  p->dl.stride = rows > 1 ? YPAR : 0;
-  p->dl.seed = seed;
-  p->dl.k0 = k0;
-  p->dl.cap = tape ? cap : 0;
-  p->dl.steps = 0;
-  p->dl.on = true;
   return 0;
 }
 

@@ -31,14 +31,8 @@ __global__ void __launch_bounds__(64 * PW) k_plan_propagate(const int* __restric
   if (g >= 2 * m) return;
   const int v = g & 1;
   const size_t s = (size_t)(list ? list[g >> 1] : (g >> 1));
-  const double2* P2 = reinterpret_cast<const double2*>(io.par + s * io.par_s + v * FV);
   double P[FV];
-#pragma unroll
-  for (int i = 0; i < FV / 2; ++i) {
-    const double2 q = P2[i];
-    P[2 * i] = q.x;
-    P[2 * i + 1] = q.y;
-  }
+  plant_row_load(io.par + s * io.par_s + v * FV, P);
   const double* xin = io.x0 + s * io.x0_s + v * 5;
   const double* cu = io.ctrl + s * io.ctrl_s + v * io.ctrl_v;
   double x[5];
@@ -88,7 +82,7 @@ __global__ void __launch_bounds__(64 * PW) k_plan_set_init(const int* __restrict
 // 32-bit integer and fp64 in registers.  The lane's 11 parameters are 8-byte loads from the row;
 // its five results 8-byte stores, neighbouring lanes to neighbouring rows as in k_plan_propagate.
 // With a tape the written value is tape + w, the tape term first.
-__global__ void __launch_bounds__(64 * PW) k_plan_noise(const int* __restrict__ list, int m, noise_io io) {
+__global__ void __launch_bounds__(64 * PW) k_plan_noise(const int* __restrict__ list, int m, draw_io io) {
   const int g = blockIdx.x * (64 * PW) + threadIdx.x;
   if (g >= 2 * m) return;
   const int v = g & 1;
@@ -96,16 +90,12 @@ __global__ void __launch_bounds__(64 * PW) k_plan_noise(const int* __restrict__ 
   const size_t y = blockIdx.y;
   const double* P = io.par + s * io.par_s;
   double S[5], B[5];
-#pragma unroll
-  for (int i = 0; i < 5; ++i) {
-    S[i] = P[Z_SIGMA + v * 5 + i];
-    B[i] = P[Z_BIAS + v * 5 + i];
-  }
-  const unsigned long long t = io.streams ? (unsigned long long)io.streams[s] : (unsigned long long)s;
+  noise_row_load(P, v, S, B);
+  uint32_t t_lo, t_hi;
+  stream_words(io.streams, s, t_lo, t_hi);
   uint32_t words[12];
   double w[5];
-  noise_draw(io.seed_lo, io.seed_hi, (uint32_t)t, (uint32_t)(t >> 32), io.k + (uint32_t)y, v, S, B, P[Z_TRUNC], w,
-             io.raw ? words : nullptr);
+  noise_draw(io.seed_lo, io.seed_hi, t_lo, t_hi, io.k + (uint32_t)y, v, S, B, P[Z_TRUNC], w, io.raw ? words : nullptr);
   double* o = io.out + s * io.out_s + y * 10 + v * 5;
   if (io.tape) {
 #pragma clang fp contract(off)
@@ -177,9 +167,7 @@ int32_t piadmm_obca_propagate(piadmm_obca_t h, int32_t n, const double* states, 
     return fail(h, PIADMM_E_ARG, "obca_propagate: ctrl of scenario " + std::to_string(bad / 4) + " is not finite");
   if (w && (bad = first_not_finite(w, N * 10)) >= 0)
     return fail(h, PIADMM_E_ARG, "obca_propagate: w of scenario " + std::to_string(bad / 10) + " is not finite");
-  for (int k = 0; k < n; ++k)
-    if (const char* why = feedback_row_check(par + (size_t)k * FPAR))
-      return fail(h, PIADMM_E_ARG, "obca_propagate: row " + std::to_string(k) + ": " + why);
+  if (int rc = rows_check(h, "obca_propagate", "", par, n, n, FPAR, feedback_row_check)) return rc;
   OWN_HIP(h, hipSetDevice(h->device));
   const size_t B = sizeof(double);
   scratch a(h);
@@ -215,23 +203,13 @@ int32_t piadmm_obca_feedback_plan(piadmm_obca_t h, int32_t mode, const double* p
   double nominal[FPAR];
   feedback_row_nominal(nominal);
   if (mode == 1) {
-    if (par) {
-      if (int rc = rows_check(h, "obca_feedback_plan", rows, n)) return rc;
-      for (int k = 0; k < rows; ++k)
-        if (const char* why = feedback_row_check(par + (size_t)k * FPAR))
-          return fail(h, PIADMM_E_ARG, "obca_feedback_plan: row " + std::to_string(k) + ": " + why);
-    } else {
+    if (int rc = rows_check(h, "obca_feedback_plan", "", par, rows, n, FPAR, feedback_row_check)) return rc;
+    if (!par) {
       par = nominal;
       rows = 1;
     }
-    if (tape) {
-      if (cap < 0 || cap > (1 << 20)) return fail(h, PIADMM_E_ARG, "obca_feedback_plan: 0 <= cap <= 2^20");
-      const int64_t bad = first_not_finite(tape, N * (size_t)cap * 10);
-      if (bad >= 0)
-        return fail(h, PIADMM_E_ARG, "obca_feedback_plan: the tape of scenario " +
-                    std::to_string(bad / ((int64_t)cap * 10)) + " is not finite (step " +
-                    std::to_string(bad / 10 % cap) + ")");
-    }
+    if (tape && (cap < 0 || cap > (1 << 20))) return fail(h, PIADMM_E_ARG, "obca_feedback_plan: 0 <= cap <= 2^20");
+    if (int rc = tape_finite_check(h, "obca_feedback_plan", tape, n, cap, 10)) return rc;
     if (p->ck.on)
       return fail(h, PIADMM_E_STATE, "obca_feedback_plan: a clock is attached (obca_clock_plan: the tape has no per-scenario clocks)");
   }
@@ -319,16 +297,9 @@ namespace {
 int noise_args_check(piadmm_obca_t h, int n, const double* par, int rows, const int64_t* streams, int32_t k0,
                      int64_t steps, const std::string& who) {
   if (!par) return fail(h, PIADMM_E_ARG, who + ": null argument");
-  if (int rc = rows_check(h, who, rows, n)) return rc;
-  for (int k = 0; k < rows; ++k)
-    if (const char* why = noise_row_check(par + (size_t)k * obca_plan::ZPAR))
-      return fail(h, PIADMM_E_ARG, who + ": row " + std::to_string(k) + ": " + why);
-  if (streams)
-    for (int k = 0; k < n; ++k)
-      if (streams[k] < 0) return fail(h, PIADMM_E_ARG, who + ": streams[" + std::to_string(k) + "] must be >= 0");
-  if (k0 < 0 || (int64_t)k0 + steps > ((int64_t)1 << 31))
-    return fail(h, PIADMM_E_ARG, who + ": k0 >= 0 and every step index below 2^31");
-  return 0;
+  if (int rc = rows_check(h, who, "", par, rows, n, ZPAR, noise_row_check)) return rc;
+  if (int rc = streams_check(h, who, streams, n)) return rc;
+  return step_index_check(h, who, k0, steps);
 }
 }  // namespace
 
@@ -353,21 +324,9 @@ int32_t piadmm_obca_noise_tape(piadmm_obca_t h, int32_t n, int32_t cap, const do
   if (a.rc) return a.rc;
   OWN_HIP(h, hipMemcpyAsync(d_par, par, (size_t)rows * ZPAR * B, hipMemcpyHostToDevice, h->stream));
   if (streams) OWN_HIP(h, hipMemcpyAsync(d_str, streams, N * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-  noise_io zo{};
-  zo.par = d_par;  zo.par_s = rows > 1 ? ZPAR : 0;
-  zo.streams = d_str;
-  zo.out_s = (long long)C * 10;  zo.raw_s = (long long)C * 24;
-  zo.seed_lo = (uint32_t)seed;  zo.seed_hi = (uint32_t)(seed >> 32);
-  // one grid row per step index, at most 32768 rows a launch
-  for (int at = 0; at < cap; at += 32768) {
-    const int ny = std::min(cap - at, 32768);
-    zo.out = d_out + (size_t)at * 10;
-    zo.raw = d_raw ? d_raw + (size_t)at * 24 : nullptr;
-    zo.k = (uint32_t)k0 + (uint32_t)at;
-    hipLaunchKernelGGL(k_plan_noise, dim3(lane_blocks(2 * n), ny), dim3(64 * PW), 0, h->stream, (const int*)nullptr,
-                       n, zo);
-    OWN_HIP(h, hipGetLastError());
-  }
+  if (int rc = draw_launch(h, k_plan_noise, draw_view(d_par, rows, ZPAR, d_str, seed), n, cap, k0, 10, 24, d_out, nullptr,
+                           d_raw))
+    return rc;
   OWN_HIP(h, hipMemcpyAsync(tape_out, d_out, N * C * 10 * B, hipMemcpyDeviceToHost, h->stream));
   if (raw_out)
     OWN_HIP(h, hipMemcpyAsync(raw_out, d_raw, N * C * 24 * sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
@@ -395,22 +354,16 @@ int32_t piadmm_obca_noise_plan(piadmm_obca_t h, int32_t mode, const double* par,
   }
   // the new attachment is complete before it replaces the earlier one
   piadmm_obca_plan_s::noise_s nz;
-  std::vector<long long> ident;
-  if (!streams) {
-    ident.resize(N);
-    for (size_t k = 0; k < N; ++k) ident[k] = (long long)k;
-  }
-  const void* src = streams ? static_cast<const void*>(streams) : static_cast<const void*>(ident.data());
+  const std::vector<long long> ids = stream_ids(streams, N);
   hipError_t e = nz.par.make((size_t)rows * ZPAR);
   if (e == hipSuccess) e = nz.wbuf.make(N * 10);
   if (e == hipSuccess) e = nz.streams.make(N);
   if (e == hipSuccess) e = hipMemset(nz.wbuf, 0, N * 10 * sizeof(double));
   if (e == hipSuccess) e = hipMemcpy(nz.par, par, (size_t)rows * ZPAR * sizeof(double), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(nz.streams, src, N * sizeof(long long), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(nz.streams, ids.data(), N * sizeof(long long), hipMemcpyHostToDevice);
   if (e != hipSuccess) return fail(h, PIADMM_E_HIP, std::string("obca_noise_plan: ") + hipGetErrorString(e));
   p->nz = std::move(nz);
   p->nz.rows = rows;
-  p->nz.stride = rows > 1 ? ZPAR : 0;
   p->nz.seed = seed;
   p->nz.k0 = k0;
   p->nz.on = true;

@@ -6,7 +6,7 @@
 // step ran) and k_plan_set_init after it (the state each reached over init_state of both copies),
 // and with delay rows k_loop_open after the tick (the latencies of the alive scenarios at their new
 // clocks) and every iterate k_plan_exchange_stale in k_plan_exchange's place; without it none is
-// launched.  The arithmetic is plant_step, noise_draw and delay_draw of csrc/piadmm_obca_plan.h, the
+// launched.  The arithmetic is plant_step, noise_draw and delay_draw of csrc/piadmm_obca_plan_draw.h, the
 // functions k_plan_propagate, k_plan_noise and k_plan_delay call.
 
 #include "piadmm_obca_plan.h"
@@ -23,14 +23,8 @@ __global__ void __launch_bounds__(64 * PW) k_loop_close(const int* __restrict__ 
   if (g >= 2 * m) return;
   const int v = g & 1;
   const size_t s = (size_t)(list ? list[g >> 1] : (g >> 1));
-  const double2* P2 = reinterpret_cast<const double2*>(io.plant + s * io.plant_s + v * FV);
   double P[FV];
-#pragma unroll
-  for (int i = 0; i < FV / 2; ++i) {
-    const double2 q = P2[i];
-    P[2 * i] = q.x;
-    P[2 * i + 1] = q.y;
-  }
+  plant_row_load(io.plant + s * io.plant_s + v * FV, P);
   const double* xin = io.x0 + s * STATE + v * 5;
   const double* cu = io.ctrl + s * NCTRL + v * (NCTRL / 2);
   double x[5];
@@ -42,14 +36,10 @@ __global__ void __launch_bounds__(64 * PW) k_loop_close(const int* __restrict__ 
 #pragma clang fp contract(off)
     const double* Z = io.noise + s * io.noise_s;
     double S[5], B[5], w[5];
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-      S[i] = Z[Z_SIGMA + v * 5 + i];
-      B[i] = Z[Z_BIAS + v * 5 + i];
-    }
-    const unsigned long long t = io.streams ? (unsigned long long)io.streams[s] : (unsigned long long)s;
-    noise_draw(io.seed_lo, io.seed_hi, (uint32_t)t, (uint32_t)(t >> 32), io.k0 + (uint32_t)io.clk[3 * s], v, S, B,
-               Z[Z_TRUNC], w, nullptr);
+    noise_row_load(Z, v, S, B);
+    uint32_t t_lo, t_hi;
+    stream_words(io.streams, s, t_lo, t_hi);
+    noise_draw(io.seed_lo, io.seed_hi, t_lo, t_hi, io.k0 + (uint32_t)io.clk[3 * s], v, S, B, Z[Z_TRUNC], w, nullptr);
 #pragma unroll
     for (int i = 0; i < 5; ++i) o[i] = x[i] + w[i];
   } else {
@@ -66,10 +56,10 @@ __global__ void __launch_bounds__(64 * PW) k_loop_open(const int* __restrict__ l
   const int v = g & 1;
   const size_t s = (size_t)(list ? list[g >> 1] : (g >> 1));
   const double* Y = io.delay + s * io.delay_s;
-  const unsigned long long t = io.streams ? (unsigned long long)io.streams[s] : (unsigned long long)s;
-  io.tau[2 * s + v] = delay_draw(io.seed_lo, io.seed_hi, (uint32_t)t, (uint32_t)(t >> 32),
-                                 io.k0 + (uint32_t)io.clk[3 * s], v, Y[Y_AVG + v], Y[Y_STD + v], Y[Y_TMAX + v],
-                                 Y[Y_TRUNC], 0.0, nullptr);
+  uint32_t t_lo, t_hi;
+  stream_words(io.streams, s, t_lo, t_hi);
+  io.tau[2 * s + v] = delay_draw(io.seed_lo, io.seed_hi, t_lo, t_hi, io.k0 + (uint32_t)io.clk[3 * s], v, Y[Y_AVG + v],
+                                 Y[Y_STD + v], Y[Y_TMAX + v], Y[Y_TRUNC], 0.0, nullptr);
 }
 
 // The stand-alone draw (piadmm_obca_loop_draw): one lane per (scenario, vehicle) of the caller's
@@ -80,23 +70,20 @@ __global__ void __launch_bounds__(64 * PW) k_loop_draw(int n, loop_io io) {
   if (g >= 2 * n) return;
   const int v = g & 1;
   const size_t s = (size_t)(g >> 1);
-  const unsigned long long t = io.streams ? (unsigned long long)io.streams[s] : (unsigned long long)s;
+  uint32_t t_lo, t_hi;
+  stream_words(io.streams, s, t_lo, t_hi);
   const uint32_t k = io.k0 + (uint32_t)io.clk[3 * s];
   double w[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, tau = 0.0;
   if (io.noise) {
     const double* Z = io.noise + s * io.noise_s;
     double S[5], B[5];
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-      S[i] = Z[Z_SIGMA + v * 5 + i];
-      B[i] = Z[Z_BIAS + v * 5 + i];
-    }
-    noise_draw(io.seed_lo, io.seed_hi, (uint32_t)t, (uint32_t)(t >> 32), k, v, S, B, Z[Z_TRUNC], w, nullptr);
+    noise_row_load(Z, v, S, B);
+    noise_draw(io.seed_lo, io.seed_hi, t_lo, t_hi, k, v, S, B, Z[Z_TRUNC], w, nullptr);
   }
   if (io.delay) {
     const double* Y = io.delay + s * io.delay_s;
-    tau = delay_draw(io.seed_lo, io.seed_hi, (uint32_t)t, (uint32_t)(t >> 32), k, v, Y[Y_AVG + v], Y[Y_STD + v],
-                     Y[Y_TMAX + v], Y[Y_TRUNC], 0.0, nullptr);
+    tau = delay_draw(io.seed_lo, io.seed_hi, t_lo, t_hi, k, v, Y[Y_AVG + v], Y[Y_STD + v], Y[Y_TMAX + v], Y[Y_TRUNC], 0.0,
+                     nullptr);
   }
   double* o = io.next + s * 10 + v * 5;
 #pragma unroll
@@ -139,22 +126,13 @@ int loop_open(piadmm_obca_t h, piadmm_obca_plan_s* p, int m) {
 using namespace obca_plan;
 
 namespace {
-// rows x width of one kind: the count, then every row through the kind's own check
-int loop_rows_check(piadmm_obca_t h, const std::string& who, const char* kind, const double* par, int rows, int n,
-                    int width, const char* (*check)(const double*)) {
-  if (!par) return 0;
-  if (rows != 1 && rows != n)
-    return fail(h, PIADMM_E_ARG, who + ": " + kind + " rows must be 1 or n (" + std::to_string(n) + ")");
-  for (int k = 0; k < rows; ++k)
-    if (const char* why = check(par + (size_t)k * width))
-      return fail(h, PIADMM_E_ARG, who + ": " + kind + " row " + std::to_string(k) + ": " + why);
-  return 0;
-}
-int loop_streams_check(piadmm_obca_t h, const std::string& who, const int64_t* streams, int count) {
-  if (streams)
-    for (int k = 0; k < count; ++k)
-      if (streams[k] < 0) return fail(h, PIADMM_E_ARG, who + ": streams[" + std::to_string(k) + "] must be >= 0");
-  return 0;
+// the rows of the kinds a loop call takes (nullptr: the kind is absent) and its stream ids
+int loop_args_check(piadmm_obca_t h, const std::string& who, int n, const double* plant, int plant_rows,
+                    const double* noise, int noise_rows, const double* delay, int delay_rows, const int64_t* streams) {
+  if (int rc = rows_check(h, who, "plant", plant, plant_rows, n, FPAR, feedback_row_check)) return rc;
+  if (int rc = rows_check(h, who, "noise", noise, noise_rows, n, ZPAR, noise_row_check)) return rc;
+  if (int rc = rows_check(h, who, "delay", delay, delay_rows, n, YPAR, delay_row_check)) return rc;
+  return streams_check(h, who, streams, n);
 }
 }  // namespace
 
@@ -176,10 +154,7 @@ int32_t piadmm_obca_loop_plan(piadmm_obca_t h, int32_t mode, const double* plant
       plant = nominal;
       plant_rows = 1;
     }
-    if (int rc = loop_rows_check(h, who, "plant", plant, plant_rows, n, FPAR, feedback_row_check)) return rc;
-    if (int rc = loop_rows_check(h, who, "noise", noise, noise_rows, n, ZPAR, noise_row_check)) return rc;
-    if (int rc = loop_rows_check(h, who, "delay", delay, delay_rows, n, YPAR, delay_row_check)) return rc;
-    if (int rc = loop_streams_check(h, who, streams, n)) return rc;
+    if (int rc = loop_args_check(h, who, n, plant, plant_rows, noise, noise_rows, delay, delay_rows, streams)) return rc;
     if (k0 < 0) return fail(h, PIADMM_E_ARG, "obca_loop_plan: k0 >= 0");
     if (p->fb.on) return fail(h, PIADMM_E_STATE, "obca_loop_plan: feedback is attached (obca_feedback_plan: it counts the plan's steps; detach it)");
     if (p->dl.on) return fail(h, PIADMM_E_STATE, "obca_loop_plan: the delay is attached (obca_delay_plan: it counts the plan's steps; detach it)");
@@ -198,12 +173,7 @@ int32_t piadmm_obca_loop_plan(piadmm_obca_t h, int32_t mode, const double* plant
   }
   // the new attachment is complete, the open step's latencies included, before it replaces the earlier one
   piadmm_obca_plan_s::loop_s nl;
-  std::vector<long long> ident;
-  if (!streams) {
-    ident.resize(N);
-    for (size_t k = 0; k < N; ++k) ident[k] = (long long)k;
-  }
-  const void* src = streams ? static_cast<const void*>(streams) : static_cast<const void*>(ident.data());
+  const std::vector<long long> ids = stream_ids(streams, N);
   const size_t D = sizeof(double);
   hipError_t e = nl.plant.make((size_t)plant_rows * FPAR);
   if (e == hipSuccess) e = nl.tau.make(N * 2);
@@ -214,7 +184,7 @@ int32_t piadmm_obca_loop_plan(piadmm_obca_t h, int32_t mode, const double* plant
   if (e == hipSuccess) e = hipMemset(nl.tau, 0, N * 2 * D);
   if (e == hipSuccess) e = hipMemset(nl.next, 0, N * 10 * D);
   if (e == hipSuccess) e = hipMemcpy(nl.plant, plant, (size_t)plant_rows * FPAR * D, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(nl.streams, src, N * sizeof(long long), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(nl.streams, ids.data(), N * sizeof(long long), hipMemcpyHostToDevice);
   if (e == hipSuccess && noise) e = hipMemcpy(nl.noise, noise, (size_t)noise_rows * ZPAR * D, hipMemcpyHostToDevice);
   if (e == hipSuccess && delay) e = hipMemcpy(nl.delay, delay, (size_t)delay_rows * YPAR * D, hipMemcpyHostToDevice);
   // the fills and the copies went through the null stream, which the handle's stream does not wait for
@@ -249,10 +219,7 @@ int32_t piadmm_obca_loop_admit(piadmm_obca_t h, int32_t m, const int32_t* slots,
   if (m < 1 || m > n) return fail(h, PIADMM_E_ARG, "obca_loop_admit: 1 <= m <= n_scenarios");
   if (!slots) return fail(h, PIADMM_E_ARG, "obca_loop_admit: null argument (slots)");
   if (int rc = slots_check(h, who, "slots", slots, m, n)) return rc;
-  if (int rc = loop_rows_check(h, who, "plant", plant, m, m, FPAR, feedback_row_check)) return rc;
-  if (int rc = loop_rows_check(h, who, "noise", noise, m, m, ZPAR, noise_row_check)) return rc;
-  if (int rc = loop_rows_check(h, who, "delay", delay, m, m, YPAR, delay_row_check)) return rc;
-  if (int rc = loop_streams_check(h, who, streams, m)) return rc;
+  if (int rc = loop_args_check(h, who, m, plant, m, noise, m, delay, m, streams)) return rc;
   auto& l = p->lp;
   if (!l.on) return fail(h, PIADMM_E_STATE, "obca_loop_admit: no loop attached (obca_loop_plan)");
   if (p->tr.on) return fail(h, PIADMM_E_STATE, "obca_loop_admit: a trace is attached (its minima would mix two tenants)");
@@ -295,9 +262,7 @@ int32_t piadmm_obca_loop_draw(piadmm_obca_t h, int32_t n, const int32_t* clock, 
   const std::string who = "obca_loop_draw";
   if (n < 1 || n > (1 << 20)) return fail(h, PIADMM_E_ARG, "obca_loop_draw: 1 <= n <= 2^20");
   if (!clock || !w_out || !tau_out) return fail(h, PIADMM_E_ARG, "obca_loop_draw: null argument (clock, w_out, tau_out)");
-  if (int rc = loop_rows_check(h, who, "noise", noise, noise_rows, n, ZPAR, noise_row_check)) return rc;
-  if (int rc = loop_rows_check(h, who, "delay", delay, delay_rows, n, YPAR, delay_row_check)) return rc;
-  if (int rc = loop_streams_check(h, who, streams, n)) return rc;
+  if (int rc = loop_args_check(h, who, n, nullptr, 0, noise, noise_rows, delay, delay_rows, streams)) return rc;
   if (k0 < 0) return fail(h, PIADMM_E_ARG, "obca_loop_draw: k0 >= 0");
   for (int s = 0; s < n; ++s) {
     const int c = clock[3 * (size_t)s];

@@ -700,15 +700,15 @@ int32_t piadmm_obca_trace_run(piadmm_obca_t h, int32_t n_steps, int32_t* steps_d
   if ((int64_t)p->tr.rows + n_steps > p->tr.cap)
     return fail(h, PIADMM_E_STATE, "obca_trace_run: " + std::to_string(n_steps) + " steps do not fit the trace (" +
                 std::to_string(p->tr.rows) + " of " + std::to_string(p->tr.cap) + " rows used)");
-  if (feedback_exhausted(p, n_steps))
-    return fail(h, PIADMM_E_STATE, "obca_trace_run: disturbance tape exhausted before " + std::to_string(n_steps) +
-                " steps (" + std::to_string(p->fb.steps) + " of " + std::to_string(p->fb.cap) + " rows used)");
-  if (noise_exhausted(p, n_steps))
-    return fail(h, PIADMM_E_STATE, "obca_trace_run: noise step index exhausted before " + std::to_string(n_steps) + " steps");
-  if (const char* why = delay_refusal(p, n_steps))
-    return fail(h, PIADMM_E_STATE, std::string("obca_trace_run: ") + why + " before " + std::to_string(n_steps) + " steps");
-  if (loop_exhausted(p, n_steps))
-    return fail(h, PIADMM_E_STATE, "obca_trace_run: loop step index exhausted before " + std::to_string(n_steps) + " steps");
+  // the steps fit the trace (above) and a trace excludes a ledger, so step_refusal names the tape, the
+  // noise or the loop here; the delay excludes the loop, so its place behind them names what it named
+  const char* why = step_refusal(p, n_steps);
+  if (!why) why = delay_refusal(p, n_steps);
+  if (why)
+    return fail(h, PIADMM_E_STATE, std::string("obca_trace_run: ") + why + " before " + std::to_string(n_steps) + " steps" +
+                (why == TAPE_EXHAUSTED
+                     ? " (" + std::to_string(p->fb.steps) + " of " + std::to_string(p->fb.cap) + " rows used)"
+                     : std::string()));
   if (p->ck.on) {
     // the steps the longest-lived scenario has left
     int left = 0;

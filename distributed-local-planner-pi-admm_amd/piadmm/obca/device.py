@@ -1,5 +1,6 @@
 """The same loop, device-resident (csrc/piadmm_obca_plan.hip behind piadmm_obca_plan_*)."""
 import ctypes
+from collections import ChainMap
 
 import numpy as np
 
@@ -15,6 +16,24 @@ from .model import (DT, EDGE_OUT, EDGE_REC, FLEET_ROW, N_HORZ, NT, NU, NX, OUT, 
 from .planner import _planner_init, _spec_of
 from .stats import TRACE_GET, TRACE_LAMBDA, OBCAFleetStats, OBCARunRecord, OBCATrace, _stats_call, trace_gather_unpack
 from .tenant import PLAN_GET, PLAN_STATE, pack_state, tenant_unpack, unpack_state
+
+# every item of piadmm_obca_plan_get: name -> (code, dtype)
+_GET = ChainMap(LOOP_GET, DELAY_GET, NOISE_GET, PLAN_GET)
+
+
+def _loop_args(n, plant, noise, delay, streams, each=None):
+    """(plant, noise, delay, streams) as a loop call takes them, unchecked: the rows of each kind as
+    rows x width (None stays None; each: the rows a kind must have), streams as n int64 or None."""
+    def rows_of(par, width):
+        if par is None:
+            return None
+        par = _draw_rows(par, width, None, n)[0]
+        assert each is None or par.shape[0] == each, par.shape
+        return par
+    if streams is not None:
+        streams = np.ascontiguousarray(streams, np.int64).reshape(-1)
+        assert streams.shape == (n,), streams.shape
+    return rows_of(plant, FEEDBACK_PAR), rows_of(noise, NOISE_PAR), rows_of(delay, DELAY_PAR), streams
 
 
 class OBCADevicePlanner:
@@ -169,12 +188,7 @@ class OBCADevicePlanner:
         delay row or n (None: the plain exchange), streams n stream ids (None: 0 .. n-1), seed a
         uint64, k0 the step index of clock 0.  A second call replaces the first.  The library checks
         the arguments."""
-        def rows_of(par, width):
-            return None if par is None else np.ascontiguousarray(np.asarray(par, np.float64).reshape(-1, width))
-        plant, noise, delay = rows_of(plant, FEEDBACK_PAR), rows_of(noise, NOISE_PAR), rows_of(delay, DELAY_PAR)
-        if streams is not None:
-            streams = np.ascontiguousarray(streams, np.int64).reshape(-1)
-            assert streams.shape == (self.n,), streams.shape
+        plant, noise, delay, streams = _loop_args(self.n, plant, noise, delay, streams)
         self._check(self._lib.piadmm_obca_loop_plan(
             self.batch._h, 1, _lib.dptr(plant), 0 if plant is None else len(plant), _lib.dptr(noise),
             0 if noise is None else len(noise), _lib.dptr(delay), 0 if delay is None else len(delay),
@@ -324,52 +338,46 @@ class OBCADevicePlanner:
         self._check(self._lib.piadmm_obca_clock_admit(self.batch._h, m, _lib.iptr(slots), _lib.iptr(clock),
                                                       _lib.dptr(state), _lib.dptr(ref), _lib.dptr(par), _lib.iptr(prob),
                                                       _lib.dptr(primal_thres), _lib.dptr(dual_thres)))
-        # the host's copies of what the slots now hold
+        self._mirror(slots, clock, 1, state, ref, par, prob, primal_thres, dual_thres, specs)
+        if loop is not None:
+            # last: a refusal here leaves the slots admitted, on their earlier loop rows, and the copies true
+            self.loop_admit(slots, **loop)
+
+    def _mirror(self, slots, clock, alive, state, ref, par, prob, primal_thres, dual_thres, specs):
+        """The host's copies of what `slots` now hold: their clock rows (c, len) and alive flags, and
+        of the rest what is not None (None keeps the copy)."""
         self._clock[slots, :2] = clock
-        self._clock[slots, 2] = 1
+        self._clock[slots, 2] = alive
         if ref is not None:
             self.ref_traj_s = np.array(self.ref_traj_s)
             self.ref_traj_s[slots] = ref
             self.ref_traj = None
+        if par is not None:
+            self.par[slots] = par
+            for j, name in enumerate(FLEET_ROW):
+                col = getattr(self, name + "_s").astype(np.float64)
+                col[slots] = par[:, j]
+                setattr(self, name + "_s", col)
+        if primal_thres is not None:
+            self.primal_thres[slots] = primal_thres
+        if dual_thres is not None:
+            self.dual_thres[slots] = dual_thres
         for k, s in enumerate(slots):
             if state is not None:
                 self.init_state[s] = unpack_state(state[k])[1]
             if prob is not None:
                 self.prob[s] = int(prob[k])
-            if primal_thres is not None:
-                self.primal_thres[s] = primal_thres[k]
-            if dual_thres is not None:
-                self.dual_thres[s] = dual_thres[k]
-            if par is not None:
-                self.par[s] = par[k]
-                for j, name in enumerate(FLEET_ROW):
-                    col = getattr(self, name + "_s").astype(np.float64)
-                    col[s] = par[k, j]
-                    setattr(self, name + "_s", col)
             if specs is not None and self.specs is not None:
                 self.specs[s] = specs[k]
-        if loop is not None:
-            # last: a refusal here leaves the slots admitted, on their earlier loop rows, and the copies true
-            self.loop_admit(slots, **loop)
 
     def loop_admit(self, slots, plant=None, noise=None, delay=None, streams=None):
         """The loop rows and stream ids of `slots` (piadmm_obca_loop_admit; a step boundary, no trace):
         m rows of a kind the loop holds per scenario, m stream ids; None keeps what the slot has."""
         slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
         m = len(slots)
-
-        def rows_of(par, width):
-            if par is None:
-                return None
-            par = np.ascontiguousarray(np.asarray(par, np.float64).reshape(-1, width))
-            assert par.shape == (m, width), par.shape
-            return par
-        if streams is not None:
-            streams = np.ascontiguousarray(streams, np.int64).reshape(-1)
-            assert streams.shape == (m,), streams.shape
-        self._check(self._lib.piadmm_obca_loop_admit(
-            self.batch._h, m, _lib.iptr(slots), _lib.dptr(rows_of(plant, FEEDBACK_PAR)), _lib.dptr(rows_of(noise, NOISE_PAR)),
-            _lib.dptr(rows_of(delay, DELAY_PAR)), _lib.i64ptr(streams)))
+        plant, noise, delay, streams = _loop_args(m, plant, noise, delay, streams, each=m)
+        self._check(self._lib.piadmm_obca_loop_admit(self.batch._h, m, _lib.iptr(slots), _lib.dptr(plant), _lib.dptr(noise),
+                                                     _lib.dptr(delay), _lib.i64ptr(streams)))
 
     # -- running tenants: export, import, compaction, checkpoints (piadmm_obca_tenant_export / _import) --
     TENANT_ITEMS = ("STATE", "STATE_PREV", "CTRL", "CTRL_PREV", "X", "LAMBDA", "PRIMAL", "DUAL", "PRIMAL_THRES",
@@ -411,27 +419,12 @@ class OBCADevicePlanner:
             else np.ascontiguousarray(tenants, np.uint8)
         self._check(self._lib.piadmm_obca_tenant_import(self.batch._h, len(slots), _lib.iptr(slots), blob.ctypes.data,
                                                       blob.nbytes))
-        # the host's copies of what the slots now hold
+        # a retired tenant stays retired; the tenant's reference is its own, not a spec's
         t = tenant_unpack(blob)
-        self._clock[slots, :2] = t["CLOCK"][:, :2]
-        self._clock[slots, 2] = t["CLOCK"][:, 0] + N_HORZ <= t["CLOCK"][:, 1]
-        self.ref_traj_s = np.array(self.ref_traj_s)
-        self.ref_traj_s[slots] = t["REF"]
-        self.ref_traj = None
-        self.par[slots] = t["PAR"]
-        for j, name in enumerate(FLEET_ROW):
-            col = getattr(self, name + "_s").astype(np.float64)
-            col[slots] = t["PAR"][:, j]
-            setattr(self, name + "_s", col)
-        self.primal_thres[slots] = t["PRIMAL_THRES"]
-        self.dual_thres[slots] = t["DUAL_THRES"]
+        self._mirror(slots, t["CLOCK"][:, :2], t["CLOCK"][:, 0] + N_HORZ <= t["CLOCK"][:, 1], t["STATE"], t["REF"],
+                     t["PAR"], t["PROB"], t["PRIMAL_THRES"], t["DUAL_THRES"], [None] * len(slots))
         if self.dual_par is not None and len(self.dual_par) == self.n:
             self.dual_par[slots] = t["DUAL_PAR"]
-        for k, s in enumerate(slots):
-            self.prob[s] = int(t["PROB"][k])
-            self.init_state[s] = unpack_state(t["STATE"][k])[1]
-            if self.specs is not None:
-                self.specs[s] = None              # the tenant's reference is its own, not a spec's
 
     @classmethod
     def from_tenants(cls, batch, tenants, t_step=0, dual_par=None, on_stage=None):
@@ -559,47 +552,37 @@ class OBCADevicePlanner:
     def get(self, what):
         """One item of the resident plan (include/piadmm.h, piadmm_obca_plan_get), shaped: a name of
         PLAN_GET, of NOISE_GET, of DELAY_GET or of LOOP_GET."""
-        if what in LOOP_GET:
-            code, dt = LOOP_GET[what]
-            lp = self._loop or dict(plant=1, noise=1, delay=1)
-            shape = {"LOOP_PLANT": (lp["plant"], FEEDBACK_PAR), "LOOP_NOISE": (lp["noise"] or 1, NOISE_PAR),
-                     "LOOP_DELAY": (lp["delay"] or 1, DELAY_PAR), "LOOP_TAU": (self.n, 2), "LOOP_STREAMS": (self.n,),
-                     "LOOP_SEED": (3,)}[what]
-            out = np.zeros(shape, dt)
-            self._check(self._lib.piadmm_obca_plan_get(self.batch._h, code, out.ctypes.data, out.nbytes))
-            return out
-        if what in DELAY_GET:
-            code, dt = DELAY_GET[what]
-            shape = {"DELAY_PAR": (1 if self._delay is None else len(self._delay[0]), DELAY_PAR),
-                     "DELAY_TAU": (self.n, 2), "DELAY_STREAMS": (self.n,), "DELAY_SEED": (3,)}[what]
-            out = np.zeros(shape, dt)
-            self._check(self._lib.piadmm_obca_plan_get(self.batch._h, code, out.ctypes.data, out.nbytes))
-            return out
-        if what in NOISE_GET:
-            code, dt = NOISE_GET[what]
-            shape = {"NOISE_PAR": (1 if self._noise is None else len(self._noise[0]), NOISE_PAR),
-                     "NOISE_STREAMS": (self.n,), "NOISE_SEED": (2,)}[what]
-            out = np.zeros(shape, dt)
-            self._check(self._lib.piadmm_obca_plan_get(self.batch._h, code, out.ctypes.data, out.nbytes))
-            return out
-        code, dt = PLAN_GET[what]
-        n, m = self.n, (self.counts()[0] if what != "COUNTS" else 0)
-        rows = n if self.fleet else 1
-        shape = {"STATE": (n, PLAN_STATE), "STATE_PREV": (n, PLAN_STATE), "CTRL": (n, 2, NT * NU),
-                 "CTRL_PREV": (n, 2, NT * NU), "X": (n, 2, N_HORZ, NX), "ITERS": (n,), "ACTIVE": (m,),
-                 "PRIMAL": (n,), "DUAL": (n,), "STOP": (n,), "CONVERGE": (n,), "LOCAL_REC": (2 * m, REC),
-                 "LOCAL_OUT": (2 * m, OUT), "LOCAL_IST": (2 * m, 3), "EDGE_REC": (m, EDGE_REC),
-                 "EDGE_OUT": (m, EDGE_OUT), "EDGE_IST": (m, NT, 3), "T_STEP": (1,), "LAMBDA": (n, 2, NT, 9),
-                 "COUNTS": (3,), "STATUS_MASK": (n, 2), "REF": (rows, 2, self.n_ref, NX),
-                 "PAR": (rows, FLEET_PAR), "DUAL_S": (n, 2, NT, 9), "DUAL_D": (n, 2, NT, 9),
-                 "DUAL_PAR": (1 if self.dual_par is None else len(self.dual_par), DUAL_PAR), "WORK": (n, 2),
-                 "CLOCK": (n, 3), "WINDOW": (n, 2, N_HORZ, NX), "PRIMAL_THRES": (n,), "DUAL_THRES": (n,),
-                 "PROB": (n,), "DUAL_S_PREV": (n, 2, NT, 9), "DUAL_D_PREV": (n, 2, NT, 9),
-                 "FEEDBACK_PAR": (1 if self._feedback is None else len(self._feedback[0]), FEEDBACK_PAR),
-                 "FEEDBACK_STEPS": (1,)}[what]
-        out = np.zeros(shape, dt)
+        code, dt = _GET[what]
+        out = np.zeros(self._shape(what), dt)
         self._check(self._lib.piadmm_obca_plan_get(self.batch._h, code, out.ctypes.data, out.nbytes))
         return out
+
+    def _shape(self, what):
+        """The shape of item `what` of `get`: m = the scenarios of the last iterate (a PLAN_GET item
+        reads the counts first), rows of an attachment = what the planner handed it (1 without one)."""
+        n, m = self.n, (self.counts()[0] if what in PLAN_GET and what != "COUNTS" else 0)
+        rows = n if self.fleet else 1
+        lp = self._loop or dict(plant=1, noise=1, delay=1)
+
+        def held(attached):
+            return 1 if attached is None else len(attached[0])
+        return {"STATE": (n, PLAN_STATE), "STATE_PREV": (n, PLAN_STATE), "CTRL": (n, 2, NT * NU),
+                "CTRL_PREV": (n, 2, NT * NU), "X": (n, 2, N_HORZ, NX), "ITERS": (n,), "ACTIVE": (m,),
+                "PRIMAL": (n,), "DUAL": (n,), "STOP": (n,), "CONVERGE": (n,), "LOCAL_REC": (2 * m, REC),
+                "LOCAL_OUT": (2 * m, OUT), "LOCAL_IST": (2 * m, 3), "EDGE_REC": (m, EDGE_REC),
+                "EDGE_OUT": (m, EDGE_OUT), "EDGE_IST": (m, NT, 3), "T_STEP": (1,), "LAMBDA": (n, 2, NT, 9),
+                "COUNTS": (3,), "STATUS_MASK": (n, 2), "REF": (rows, 2, self.n_ref, NX),
+                "PAR": (rows, FLEET_PAR), "DUAL_S": (n, 2, NT, 9), "DUAL_D": (n, 2, NT, 9),
+                "DUAL_PAR": (1 if self.dual_par is None else len(self.dual_par), DUAL_PAR), "WORK": (n, 2),
+                "CLOCK": (n, 3), "WINDOW": (n, 2, N_HORZ, NX), "PRIMAL_THRES": (n,), "DUAL_THRES": (n,),
+                "PROB": (n,), "DUAL_S_PREV": (n, 2, NT, 9), "DUAL_D_PREV": (n, 2, NT, 9),
+                "FEEDBACK_PAR": (held(self._feedback), FEEDBACK_PAR), "FEEDBACK_STEPS": (1,),
+                "NOISE_PAR": (held(self._noise), NOISE_PAR), "NOISE_STREAMS": (n,), "NOISE_SEED": (2,),
+                "DELAY_PAR": (held(self._delay), DELAY_PAR), "DELAY_TAU": (n, 2), "DELAY_STREAMS": (n,),
+                "DELAY_SEED": (3,),
+                "LOOP_PLANT": (lp["plant"], FEEDBACK_PAR), "LOOP_NOISE": (lp["noise"] or 1, NOISE_PAR),
+                "LOOP_DELAY": (lp["delay"] or 1, DELAY_PAR), "LOOP_TAU": (n, 2), "LOOP_STREAMS": (n,),
+                "LOOP_SEED": (3,)}[what]
 
     def iterate(self):
         """One ADMM iterate of the open MPC step; the number of scenarios still active."""

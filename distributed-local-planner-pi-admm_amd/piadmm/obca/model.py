@@ -266,7 +266,7 @@ def stale_states(X, tau):
     """The states a vehicle's message describes when it arrives tau late: X (..., 8, 5) the local
     solve's states (X[0] is init_state), tau (...) the latency in [0, DT]; (..., 7, 5) with slot t =
     X[t+1] where tau == 0 (bit for bit) and X[t+1] + (tau / DT) (X[t] - X[t+1]) otherwise, all five
-    entries, theta linearly, no wrap.  The statements of stale_state (csrc/piadmm_obca_plan.h) in
+    entries, theta linearly, no wrap.  The statements of stale_state (csrc/piadmm_obca_plan_draw.h) in
     the same order; every operation is exact IEEE arithmetic, so the device gives the same bits."""
     X = np.asarray(X, np.float64)
     assert X.shape[-2:] == (N_HORZ, NX), X.shape

@@ -490,7 +490,7 @@ def test_refusals_and_items(batches, plain):
     _expect(-3, "obca_plan_iterate: latency tape exhausted", pl.iterate)
     _expect(-3, "obca_plan_shift: latency tape exhausted", pl.shift)
     pl.trace_begin(2)
-    _expect(-3, "obca_trace_run: latency tape exhausted", pl.trace_run, 1)
+    _expect(-3, "obca_trace_run: latency tape exhausted before 1 steps$", pl.trace_run, 1)
     assert pl.trace_rows() == 0
     pl.trace_end()
     assert pl.counts() == (0, N, 0) and pl.get("DELAY_SEED").tolist() == [0, 0, 1]
@@ -502,7 +502,7 @@ def test_refusals_and_items(batches, plain):
     # the step index ends at 2^31 - 1: refused before anything runs
     pl.set_delay(par=DPAR, k0=2 ** 31 - 1)
     pl.trace_begin(2)
-    _expect(-3, "obca_trace_run: delay step index exhausted", pl.trace_run, 2)
+    _expect(-3, "obca_trace_run: delay step index exhausted before 2 steps$", pl.trace_run, 2)
     assert pl.trace_rows() == 0 and pl.counts() == (0, N, 0) and pl.get("DELAY_SEED").tolist() == [0, 2 ** 31 - 1, 0]
     pl.trace_end()
     # and the plan is still the plain plan once the delay is gone
@@ -510,4 +510,29 @@ def test_refusals_and_items(batches, plain):
     pl.step()
     for key in ITEMS:
         _bits(pl.get(key), plain["after2"][key], f"{key} after the refusals")
+    pl.close()
+
+
+def test_refusal_texts_in_full(batches):
+    """The refusals the tests above match by a part, to their last word, and the step index limit as
+    piadmm_obca_plan_step, _iterate and _shift name it.  2 scenarios, one MPC step."""
+    b, _ = batches
+    _expect(-1, "obca_delay_tau: rows must be 1 or n \\(4\\)$", b.delay_tau, 4, 1, np.stack([C.UNIT_ROW, C.UNIT_ROW]))
+    _expect(-1, "obca_delay_tau: streams\\[1\\] must be >= 0$", b.delay_tau, 2, 1, C.UNIT_ROW, [0, -1])
+    _expect(-1, "obca_delay_tau: k0 >= 0 and every step index below 2\\^31$", b.delay_tau, 2, 1, C.UNIT_ROW, None, 0, -1)
+    _expect(-1, "obca_delay_tau: k0 >= 0 and every step index below 2\\^31$", b.delay_tau, 2, 2, C.UNIT_ROW, None, 0, 2 ** 31 - 1)
+    bad = np.zeros((2, 2, 2))
+    bad[1, 1, 0] = np.inf
+    _expect(-1, "obca_delay_tau: the tape of scenario 1 is not finite \\(step 1\\)$", b.delay_tau, 2, 2, C.UNIT_ROW, None, 0, 0, bad)
+    pl = obca.OBCADevicePlanner(b, **_kw(CASES[:2]))
+    _expect(-1, "obca_delay_plan: rows must be 1 or n \\(2\\)$", pl.set_delay, par=DPAR)
+    _expect(-1, "obca_delay_plan: streams\\[1\\] must be >= 0$", pl.set_delay, par=DPAR[:2], streams=[0, -1])
+    _expect(-1, "obca_delay_plan: k0 >= 0 and every step index below 2\\^31$", pl.set_delay, par=DPAR[:2], k0=-1)
+    _expect(-1, "obca_delay_plan: the tape of scenario 1 is not finite \\(step 1\\)$", pl.set_delay, par=DPAR[:2], tape=bad)
+    pl.set_delay(par=DPAR[:2], k0=2 ** 31 - 1)
+    pl.step()
+    _expect(-3, "obca_plan_step: delay step index exhausted$", pl.step)
+    _expect(-3, "obca_plan_iterate: delay step index exhausted$", pl.iterate)
+    _expect(-3, "obca_plan_shift: delay step index exhausted$", pl.shift)
+    assert pl.get("DELAY_SEED").tolist() == [0, 2 ** 31 - 1, 1]
     pl.close()

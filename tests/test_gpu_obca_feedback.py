@@ -284,7 +284,7 @@ def test_tape_exhausted(batches):
     pl = obca.OBCADevicePlanner(b, feedback=dict(tape=TAPE[:, :1]), **_kw())
     state = pl.get("STATE")
     pl.trace_begin(2)
-    _expect(-3, "obca_trace_run: disturbance tape exhausted", pl.trace_run, 2)
+    _expect(-3, "obca_trace_run: disturbance tape exhausted before 2 steps \\(0 of 1 rows used\\)$", pl.trace_run, 2)
     assert pl.trace_rows() == 0 and pl.counts() == (0, N, 0) and pl.feedback_steps() == 0
     _bits(pl.get("STATE"), state, "STATE")
     assert pl.trace_run(1) == 1 and pl.feedback_steps() == 1
@@ -414,3 +414,17 @@ def test_host_loop_and_device_plan_describe_the_same_loop(batches):
     _bits(np.stack(dp.init_state), np.stack(hp.init_state), "measured init_state")
     _bits(_init(dp.get("STATE")), meas, "measured STATE")
     dp.close()
+
+
+def test_refusal_texts_in_full(batches):
+    """piadmm_obca_feedback_plan's refusals of the row count and of a tape that is not finite, to their
+    last word.  2 scenarios, no MPC step."""
+    b, _ = batches
+    pl = obca.OBCADevicePlanner(b, **F.fleet_kwargs(CASES[:2], T0))
+    rc = b._lib.piadmm_obca_feedback_plan(b._h, 1, _lib.dptr(PAR), 3, None, 0)
+    assert rc == -1 and b._lib.piadmm_obca_last_error(b._h) == b"obca_feedback_plan: rows must be 1 or n (2)"
+    bad = np.zeros((2, 2, 2, 5))
+    bad[1, 1, 0, 3] = np.nan
+    _expect(-1, "obca_feedback_plan: the tape of scenario 1 is not finite \\(step 1\\)$", pl.set_feedback, par=PAR[:2], tape=bad)
+    _expect(-3, "obca_plan_get: no feedback attached", pl.get, "FEEDBACK_STEPS")
+    pl.close()

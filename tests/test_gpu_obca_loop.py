@@ -420,7 +420,7 @@ def test_refusals_leave_the_plan_alone(batches):
     pl = obca.OBCADevicePlanner(b, clock=True, loop=dict(LOOP, k0=2 ** 31 - 1), **_kw())
     _expect(-3, "obca_plan_step: loop step index exhausted", pl.step)
     pl.trace_begin(2)
-    _expect(-3, "obca_trace_run: loop step index exhausted", pl.trace_run, 1)
+    _expect(-3, "obca_trace_run: loop step index exhausted before 1 steps$", pl.trace_run, 1)
     pl.trace_end()
     # detaching gives the clocked plan without the loop: today's bits
     pl.clear_loop()
@@ -524,3 +524,32 @@ def test_loop_draw_refuses_n_out_of_range(batches):
     assert lib.piadmm_obca_loop_draw(h, 1, _lib.iptr(one), _lib.dptr(NOISE[1:2].copy()), 1, _lib.dptr(DELAY[1:2].copy()), 1, None,
                                      SEED, 0, _lib.dptr(w), _lib.dptr(tau)) == 0
     assert w.all() and tau.any()
+
+
+def test_refusal_texts_in_full(batches):
+    """The argument refusals of piadmm_obca_loop_draw and piadmm_obca_loop_admit, to their last word.
+    2 scenarios, no MPC step."""
+    b, _ = batches
+    clock = np.array([[0, N_REF, 1], [3, N_REF, 1]], np.int32)
+    late = DELAY[:2].copy()
+    late[1, 4] = 0.2
+    loud = NOISE[:2].copy()
+    loud[1, 3] = -1.0
+    _expect(-1, "obca_loop_draw: noise rows must be 1 or n \\(2\\)$", b.loop_draw, clock, NOISE[:3])
+    _expect(-1, "obca_loop_draw: delay rows must be 1 or n \\(2\\)$", b.loop_draw, clock, None, DELAY[:3])
+    _expect(-1, "obca_loop_draw: noise row 1: sigma >= 0$", b.loop_draw, clock, loud)
+    _expect(-1, "obca_loop_draw: delay row 1: 0 <= tau_max <= DT$", b.loop_draw, clock, None, late)
+    _expect(-1, "obca_loop_draw: streams\\[1\\] must be >= 0$", b.loop_draw, clock, NOISE[:2], DELAY[:2], [4, -1])
+    _expect(-1, "obca_loop_draw: row 1: c >= 0 and the step index k0 \\+ c below 2\\^31$", b.loop_draw, clock, NOISE[:2],
+            None, None, 0, 2 ** 31 - 3)
+    loop = dict(plant=PLANT[:2], noise=NOISE[:2], delay=DELAY[:2], streams=STREAMS[:2], seed=SEED, k0=K0)
+    pl = obca.OBCADevicePlanner(b, clock=True, loop=loop, **_kw(CASES[:2]))
+    before = _items(pl, LOOP_NAMES)
+    coarse = PLANT[:1].copy()
+    coarse[0, 1] = 65.0
+    _expect(-1, "obca_loop_admit: streams\\[0\\] must be >= 0$", pl.loop_admit, [1], streams=[-3])
+    _expect(-1, "obca_loop_admit: plant row 0: 1 <= n_sub <= 64, an integer$", pl.loop_admit, [1], plant=coarse)
+    _expect(-1, "obca_loop_admit: delay row 0: 0 <= tau_max <= DT$", pl.loop_admit, [0], delay=late[1:])
+    for k in LOOP_NAMES:
+        _bits(pl.get(k), before[k], f"{k} after the refusals")
+    pl.close()

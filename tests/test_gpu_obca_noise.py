@@ -376,7 +376,7 @@ def test_refusals_and_items(batches, fb_only):
     # the step index ends at 2^31 - 1: refused before anything runs
     pl.set_noise(par=ZPAR, k0=2 ** 31 - 1)
     pl.trace_begin(2)
-    _expect(-3, "obca_trace_run: noise step index exhausted", pl.trace_run, 2)
+    _expect(-3, "obca_trace_run: noise step index exhausted before 2 steps$", pl.trace_run, 2)
     assert pl.trace_rows() == 0 and pl.counts() == (0, N, 0) and pl.feedback_steps() == 0
     pl.trace_end()
     # and the plan is still the feedback-only plan once the noise is gone
@@ -384,4 +384,30 @@ def test_refusals_and_items(batches, fb_only):
     pl.step()
     for key in ITEMS:
         _bits(pl.get(key), fb_only["after1"][key], f"{key} after the refusals")
+    pl.close()
+
+
+def test_refusal_texts_in_full(batches):
+    """The refusals the tests above match by a part, to their last word, and the step index limit as
+    piadmm_obca_plan_step and piadmm_obca_plan_shift name it.  2 scenarios.  This runs more than one
+    MPC step, on purpose: k0 is at most 2^31 - 1, so the limit k0 + k < 2^31 is first missed at k = 1,
+    after one whole step, and piadmm_obca_plan_shift refuses only a step whose iterates have all run;
+    so one MPC step runs and then the iterates of the next (max_admm_iter <= 2)."""
+    b, _ = batches
+    unit = obca.noise_row(sigma=1.0)
+    _expect(-1, "obca_noise_tape: rows must be 1 or n \\(4\\)$", b.noise_tape, 4, 1, np.stack([unit, unit]))
+    _expect(-1, "obca_noise_tape: streams\\[1\\] must be >= 0$", b.noise_tape, 2, 1, unit, [0, -1])
+    _expect(-1, "obca_noise_tape: k0 >= 0 and every step index below 2\\^31$", b.noise_tape, 2, 1, unit, None, 0, -1)
+    _expect(-1, "obca_noise_tape: k0 >= 0 and every step index below 2\\^31$", b.noise_tape, 2, 2, unit, None, 0, 2 ** 31 - 1)
+    pl = obca.OBCADevicePlanner(b, feedback=dict(par=PAR[:2]), **_kw(CASES[:2]))
+    _expect(-1, "obca_noise_plan: rows must be 1 or n \\(2\\)$", pl.set_noise, par=ZPAR)
+    _expect(-1, "obca_noise_plan: streams\\[1\\] must be >= 0$", pl.set_noise, par=ZPAR[:2], streams=[0, -1])
+    _expect(-1, "obca_noise_plan: k0 >= 0 and every step index below 2\\^31$", pl.set_noise, par=ZPAR[:2], k0=-1)
+    pl.set_noise(par=ZPAR[:2], k0=2 ** 31 - 1)
+    pl.step()
+    _expect(-3, "obca_plan_step: noise step index exhausted$", pl.step)
+    while pl.iterate():
+        pass
+    _expect(-3, "obca_plan_shift: noise step index exhausted$", pl.shift)
+    assert pl.feedback_steps() == 1
     pl.close()

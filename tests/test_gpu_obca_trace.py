@@ -200,6 +200,7 @@ def test_error_paths(batches):
     _bits(pl.get("STATE"), before, "STATE")
     assert int(pl.get("T_STEP")[0]) == 13 and get_rows() == 1 and pl.counts() == counts
     assert lib.piadmm_obca_plan_step(h, None) == _lib.E_STATE and pl.counts() == counts
+    assert lib.piadmm_obca_last_error(h) == b"obca_plan_step: trace full"
     # the trace freed alone: the plan goes on
     assert lib.piadmm_obca_trace_end(h) == 0
     pl.shift()
